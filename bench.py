@@ -4,6 +4,15 @@
 reference's own GFLOP/s convention 2*(nnz+rows)/t (spmv-host.cpp:100,185) plus achieved HBM GB/s.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload set|powerlaw|dense|model] [--scaling weak|strong]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, preheats and warms up, times exactly K steps and prints the line.  Everything else it can measure or
+check -- the fp64 self-check of y, the rank breakdown, the per-matrix table, the sub-measurements (standin_uniform,
+strong_scaling, the model workload's host-call figures) and the CPU baseline -- runs only with --full.
+--per-matrix-reps N > 0 and --details without --full are errors.
+--dump-outputs DIR: after the timed steps, y of every matrix as computed by the last timed step, DIR/y_<matrix>.npy in
+float32, at most 64 MB in all (inputs are seeded: the same arguments give the same inputs in every run).  N > 1: every rank
+writes the rows it owns as DIR/rank<k>_y_<matrix>.npy.
 
 --gpus N > 1 from a plain `python bench.py`: this process starts `python -m torch.distributed.run` with N ranks as a
 CHILD (before touching any GPU), relays rank 0's JSON line and exits with the children's status.  Started by
@@ -27,7 +36,7 @@ the nnz prefix; --scaling strong: the six largest matrices (+ s
 nnz-split over the ranks (hispmv_amd/dist.py: shard_csr).  x is replicated; the partial sums of rows cut by a rank
 boundary are exchanged with one RCCL all_gather per step -- never an all-reduce of y.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with "roofline" and "cpu_baseline".
+Prints ONE JSON line on rank 0 with "roofline" (and, with --full, "cpu_baseline").
 """
 from __future__ import annotations
 
@@ -72,8 +81,8 @@ def parse_args():
     ap.add_argument("--no-verify", action="store_true", help="skip the fp64 self-check of one step's y (outside the timed region)")
     ap.add_argument("--no-extras", action="store_true", help="skip the standin_uniform and strong_scaling sub-measurements")
     ap.add_argument("--cpu-budget", type=float, default=5.0, help="seconds of timed CPU work per implementation and thread count")
-    ap.add_argument("--per-matrix-reps", type=int, default=10)
-    ap.add_argument("--details", type=str, default="", help="write the per-matrix table to this JSON file")
+    ap.add_argument("--per-matrix-reps", type=int, default=None, help="launches per matrix in the per-matrix table (--full; default 10)")
+    ap.add_argument("--details", type=str, default="", help="write the per-matrix table to this JSON file (--full)")
     ap.add_argument("--streams", type=int, default=4,
                     help="HIP streams the SpMVs of a step are spread over with --launch streams")
     ap.add_argument("--launch", choices=["batch", "streams"], default="batch",
@@ -81,7 +90,22 @@ def parse_args():
                          "grid); streams: one launch per matrix, spread over --streams HIP streams")
     ap.add_argument("--standin", choices=["structured", "uniform"], default="structured",
                     help="stand-in family of the mesh-origin matrices: structured FEM-like (default) or unstructured band")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the self-check, rank breakdown, per-matrix table, sub-measurements and CPU baseline "
+                         "(a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write y of every matrix from the last timed step to DIR/y_<matrix>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # what only --full measures is asked for explicitly: an error, never a line or a file without it
+        if args.per_matrix_reps or args.details:
+            ap.error("--per-matrix-reps N > 0 and --details need --full (the per-matrix table is not measured in a plain run)")
+        args.no_verify, args.no_extras, args.no_cpu_baseline, args.per_matrix_reps = True, True, True, 0
+    elif args.per_matrix_reps is None:
+        args.per_matrix_reps = 10
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -156,6 +180,30 @@ def summarize_ranks(per_rank):
     if "batch_us" in out and out["batch_us"]["mean"] > 0:
         out["batch_imbalance_max_over_mean"] = round(out["batch_us"]["max"] / out["batch_us"]["mean"], 4)
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir, budget_bytes=DUMP_BUDGET_BYTES):
+    """--dump-outputs: {name: 1-D array} -> out_dir/<name>.npy in float32.  When the arrays together exceed budget_bytes,
+    each keeps the same fraction of its entries, at indices drawn (sorted, without replacement) from a generator seeded by
+    its name: two runs with the same arguments write the same sample.  -> {name: entries written}."""
+    import re
+    import zlib
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {re.sub(r"[^A-Za-z0-9._-]", "_", k): np.asarray(v, dtype=np.float32).reshape(-1) for k, v in arrays.items()}
+    total = sum(4 * a.size for a in arrays.values())
+    keep = 1.0 if total <= budget_bytes else budget_bytes / total
+    written = {}
+    for name, a in arrays.items():
+        if keep < 1.0:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(out / f"{name}.npy", a)
+        written[name] = int(a.size)
+    return written
 
 
 def cpu_baseline(workload: str, names, budget_s: float):
@@ -286,6 +334,14 @@ def load_powerlaw():
     return out
 
 
+def step_vectors(idx, rows, cols):
+    """x and b of the matrix with handle index idx (handles are numbered in load order): seeded host tensors, float32."""
+    import torch
+    g = torch.Generator(device="cpu").manual_seed(1234 + idx)
+    x = torch.rand(cols, generator=g, dtype=torch.float32)
+    return x, torch.rand(rows, generator=g, dtype=torch.float32)
+
+
 class Runner:
     """One FpgaHandle, device vectors and a timing helper shared by the main measurement and the sub-measurements."""
 
@@ -327,9 +383,8 @@ class Runner:
                      prep_seconds=info["prep_seconds"], n_split=info["n_split_rows"], compact_slices=info["compact_slices"],
                      plan=f'{info["block_threads"]}t/{info["group_slices"]}s/{info["lds_bytes"] // 1024}KiB/{info["col_tiles"]}ct'
                           + (f'/{100 * info["compact_slices"] // max(1, info["n_slices"])}%c' if not info["is_dense"] else ""))
-            g = torch.Generator(device="cpu").manual_seed(1234 + m["idx"])
-            m["x"] = torch.rand(m["cols"], generator=g, dtype=torch.float32).to(self.dev)
-            m["b"] = torch.rand(m["rows"], generator=g, dtype=torch.float32).to(self.dev)
+            x, b = step_vectors(m["idx"], m["rows"], m["cols"])
+            m["x"], m["b"] = x.to(self.dev), b.to(self.dev)
             m["y"] = torch.zeros(m["rows"], dtype=torch.float32, device=self.dev)
             if m.get("shard") is not None and m["shard"].tail_open:
                 m["b"][-1] = 0.0        # the cut row belongs to the next rank: this rank only contributes alpha*partial
@@ -680,6 +735,16 @@ def main():
             main_call_info = fpga.batch_call_info()
         except Exception:
             main_call_info = None
+    if args.dump_outputs:
+        # what the caller of the timed path receives: every matrix's y, as the last timed step left it.  N > 1: each rank
+        # writes its own rows within its share of the budget; a row cut at the shard's tail belongs to the next rank (this
+        # rank holds only alpha times its partial sum there) and is left out
+        def owned(m):
+            y = m["y"].cpu().numpy()
+            sh = m.get("shard")
+            return y[:-1] if (sh is not None and sh.tail_open) else y
+        prefix = f"rank{rank}_" if world > 1 else ""
+        dump_outputs({f"{prefix}y_{m['name']}": owned(m) for m in mats}, args.dump_outputs, DUMP_BUDGET_BYTES // world)
     # self-check (outside the timed region): one more step, every rank's y against a host fp64 product of its shard
     y_err, y_rows, y_skipped = (R.verify(mats, step) if not args.no_verify else (None, 0, len(mats)))
     # True / False when rows were checked; None when nothing was checkable (--no-verify, or no host CSR for any matrix): skipped,
@@ -724,7 +789,7 @@ def main():
             allr = [mine]
         return summarize_ranks(allr)
 
-    breakdown = rank_breakdown(mats, exch) if args.launch == "batch" else None
+    breakdown = rank_breakdown(mats, exch) if (args.full and args.launch == "batch") else None
     passes_main = R.passes + (args.warmup + args.steps + 2 if args.launch == "streams" else 0)      # before the sub-measurements add theirs
 
     def alg_bytes(m):

@@ -7,6 +7,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,11 +15,12 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
-def test_two_rank_rehearsal_line(scaling):
+def test_two_rank_rehearsal_line(scaling, tmp_path):
     env = dict(os.environ, HISPMV_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("HISPMV_HOST_THREADS", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "0.01", "--no-cpu-baseline",
-           "--per-matrix-reps", "0", "--matrices", "crankseg_2,crystk03,trans5,ford2", "--scaling", scaling, "--strong-gb", ""]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--preheat", "0.01", "--full", "--no-cpu-baseline",
+           "--per-matrix-reps", "0", "--matrices", "crankseg_2,crystk03,trans5,ford2", "--scaling", scaling, "--strong-gb", "",
+           "--dump-outputs", str(tmp_path)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert p.returncode == 0, (p.stdout[-400:], p.stderr[-1200:])
     line = [q for q in p.stdout.splitlines() if q.startswith("{") and '"metric"' in q]
@@ -35,3 +37,11 @@ def test_two_rank_rehearsal_line(scaling):
     assert rb["batch_imbalance_max_over_mean"] >= 1.0
     # every rank boundary cuts through a row in both layouts: the exchange carried real partial sums
     assert sum(q["cut_heads"] for q in rb["per_rank"]) >= 1 and sum(q["cut_tails"] for q in rb["per_rank"]) >= 1
+    # --dump-outputs: every rank writes the rows it owns (a row cut at its tail belongs to the next rank), so over the ranks
+    # every row of the global matrix is written once: `world` stacked blocks (weak) or the matrix itself (strong)
+    from hispmv_amd import matrices as M
+    rows = {name: r for name, r, *_ in M.SUITESPARSE_SET}
+    for name in ("crankseg_2", "crystk03", "trans5", "ford2"):
+        parts = [np.load(tmp_path / f"rank{k}_y_{name}.npy") for k in range(2)]
+        assert all(q.dtype == np.float32 and np.isfinite(q).all() for q in parts)
+        assert sum(q.size for q in parts) == rows[name] * (2 if scaling == "weak" else 1)

@@ -5,8 +5,8 @@ set -u
 export TMPDIR=/tmp
 O=gpurun_out/exp_pokec; mkdir -p $O
 M="--matrices soc-Pokec,mouse_gene,PFlow_742 --no-cpu-baseline --launch streams --streams 1 --steps 10 --warmup 2"
-python3 bench.py $M --details $O/base.json > $O/base.log 2>&1 && \
-rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/tcc -- python3 bench.py --matrices soc-Pokec --no-cpu-baseline --streams 1 --steps 3 --warmup 1 --per-matrix-reps 0 > $O/tcc.log 2>&1
+python3 bench.py --full $M --details $O/base.json > $O/base.log 2>&1 && \
+rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/tcc -- python3 bench.py --full --matrices soc-Pokec --no-cpu-baseline --streams 1 --steps 3 --warmup 1 --per-matrix-reps 0 > $O/tcc.log 2>&1
 python3 - <<'PY'
 import json,glob,csv,collections
 for t in ("base",):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 3: the 1024 x 8192 d=0.25 layer of apps/model_test.py as a slice stream with its whole x (32 KiB) in one LDS window
 out=gpurun_out/r3zb; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --workload model --no-cpu-baseline --per-matrix-reps 5 --details $out/$tag.json > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --workload model --no-cpu-baseline --per-matrix-reps 5 --details $out/$tag.json > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")][-1]; d=json.loads(l)

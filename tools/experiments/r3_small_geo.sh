@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 3: the half-LDS tile geometry for the small tile streams only (their own launch), byte-weighted lanes
 out=gpurun_out/r3r; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-verify --no-extras --steps 300 --warmup 100 --per-matrix-reps 3 --details $out/$tag.json > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-verify --no-extras --steps 300 --warmup 100 --per-matrix-reps 3 --details $out/$tag.json > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"frac": [0-9.]*' $out/$tag.log | tr '\n' ' ')"
   python3 - <<PY
 import json

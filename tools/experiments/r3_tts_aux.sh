@@ -6,7 +6,7 @@ echo "$0: HISPMV_TTS_AUX is not read by libhispmv.so any more -- this experiment
 set -e
 out=gpurun_out/r3a; mkdir -p $out
 for a in 0 1 2 16 17 3 18 19; do
-  HISPMV_TTS_AUX=$a python3 bench.py --matrices soc-Pokec --no-cpu-baseline --no-extras --steps 50 --warmup 20 \
+  HISPMV_TTS_AUX=$a python3 bench.py --full --matrices soc-Pokec --no-cpu-baseline --no-extras --steps 50 --warmup 20 \
      --per-matrix-reps 10 --details $out/aux_$a.json > $out/aux_$a.log 2>&1
   python3 - <<PY
 import json

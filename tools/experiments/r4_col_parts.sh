@@ -3,7 +3,7 @@
 # with tables of 1 - 13 MB: a gather of 20.7 lines costs HALF when x is L2-resident) with tile shapes between the standard and
 # the tall geometry: HISPMV_TTS_GEOMETRY=tall HISPMV_TTS_TALL_SHAPE=rows,slots,tiles per part,zero fill[,parts]
 out=gpurun_out/r4v; mkdir -p $out
-one() { tag=$1; shift; env "$@" python3 bench.py --matrices soc-Pokec --no-cpu-baseline --no-extras --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
+one() { tag=$1; shift; env "$@" python3 bench.py --full --matrices soc-Pokec --no-cpu-baseline --no-extras --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 try:

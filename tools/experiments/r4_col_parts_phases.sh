@@ -2,7 +2,7 @@
 # round 4: the column-part tile shapes of r4_col_parts.sh split into phases (libraries built with -DHISPMV_TTS_EXPERIMENT=1: no x
 # gathers, =2: no row-order pass), with and without the XCD pinning of the parts
 out=gpurun_out/r4w; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --matrices soc-Pokec --no-cpu-baseline --no-extras --no-verify --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --matrices soc-Pokec --no-cpu-baseline --no-extras --no-verify --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 d=json.load(open("$out/$tag.json")); r=d["per_matrix"][0]

@@ -3,7 +3,7 @@
 # 512-thread two-per-CU plans (HISPMV_PLAN_CORESIDE_KIB), PFlow_742 / mouse_gene keep their 1024-thread plans; the tile streams take
 # the paired geometry (8-wavefront tiles, 78 KiB); three launch lanes so that the 512-thread slice grid starts next to the tiles.
 out=gpurun_out/r4c; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 3 --details $out/$tag.json > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 3 --details $out/$tag.json > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"frac": [0-9.]*\|"y_checked": [a-z]*' $out/$tag.log | tr '\n' ' ')"
   python3 - <<PY
 import json

@@ -3,7 +3,7 @@
 out=gpurun_out/r4ak; mkdir -p $out
 for v in base div; do
   if [ $v = div ]; then export HISPMV_PLAN_RESIDENT_DIV=2,40; else unset HISPMV_PLAN_RESIDENT_DIV; fi
-  python3 bench.py --workload model --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 10 --details $out/model_$v.json > $out/model_$v.log 2>&1
+  python3 bench.py --full --workload model --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 10 --details $out/model_$v.json > $out/model_$v.log 2>&1
   python3 - <<PY
 import json
 d=json.load(open("$out/model_$v.json"))

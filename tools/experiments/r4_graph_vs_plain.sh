@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4: the two-lane step replayed as a HIP graph against plain launches (HISPMV_BATCH_GRAPH=0), interleaved repeats on one box
 out=gpurun_out/r4ag; mkdir -p $out
-run() { tag=$1; shift; env "$1" python3 bench.py --no-cpu-baseline --no-extras --per-matrix-reps 0 "${@:2}" > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$1" python3 bench.py --full --no-cpu-baseline --no-extras --per-matrix-reps 0 "${@:2}" > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"y_checked": [a-z]*' $out/$tag.log | tr '\n' ' ')"; }
 for rep in 1 2 3; do
   run graph_$rep HISPMV_BATCH_GRAPH=1 --steps 300 --warmup 100

@@ -2,7 +2,7 @@
 # round 4: longer resident groups (HISPMV_PLAN_RESIDENT_DIV=d[,g]): every workgroup of a slice stream stages its x window before it
 # streams, and nothing hides that phase with one 1024-thread workgroup per CU -- in a batch call a matrix need not cover every CU
 out=gpurun_out/r4aa; mkdir -p $out
-run() { tag=$1; shift; env "$1" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 "${@:2}" > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$1" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 "${@:2}" > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"frac": [0-9.]*\|"y_checked": [a-z]*' $out/$tag.log | tr '\n' ' ')"; }
 run base X=1
 run div2 HISPMV_PLAN_RESIDENT_DIV=2

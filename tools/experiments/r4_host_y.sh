@@ -2,7 +2,7 @@
 # round 4: the host-vector path (run_kernel / linear from host buffers): y written straight into pinned memory against the copy back
 out=gpurun_out/r4ab; mkdir -p $out
 for v in direct copy direct copy; do
-  HISPMV_HOST_Y=$v python3 bench.py --workload model --no-cpu-baseline --steps 100 --warmup 50 --per-matrix-reps 0 > $out/model_$v.log 2>&1
+  HISPMV_HOST_Y=$v python3 bench.py --full --workload model --no-cpu-baseline --steps 100 --warmup 50 --per-matrix-reps 0 > $out/model_$v.log 2>&1
   python3 - $out/model_$v.log $v <<'PY'
 import json, sys
 for line in open(sys.argv[1]):

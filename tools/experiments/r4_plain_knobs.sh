@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4: the launch-order knobs again with plain launches as the default (they were last settled under graph replay), one box
 out=gpurun_out/r4ai; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --per-matrix-reps 0 --steps 300 --warmup 100 > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --per-matrix-reps 0 --steps 300 --warmup 100 > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"y_checked": [a-z]*' $out/$tag.log | tr '\n' ' ')"; }
 run base_1 X=1
 run lanes_rr HISPMV_BATCH_LANES=rr

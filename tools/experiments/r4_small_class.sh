@@ -2,7 +2,7 @@
 # round 4 (verdict item 7): knobs of the small-matrix class measured INSIDE the step of the set (the step is the sum of its
 # kernels' CU-time: r4_step_subsets.sh), not alone
 out=gpurun_out/r4r; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"y_checked": [a-z]*' $out/$tag.log | tr '\n' ' ')"; }
 run base X=1
 run lines48 HISPMV_TTS_MAX_LINES=48

@@ -2,7 +2,7 @@
 # round 4: the head of the step kernel's queue: cycles of t long tiles and s slice items (HISPMV_STEP_ORDER=<16*t+s>; default 1:1),
 # against longest first (all long tiles first) and 1:2 / 1:3 (alt2 / alt3)
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4: where the four-group items of the 256-thread plans sit in the step kernel's queue (their price per slice), on one box
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

@@ -2,7 +2,7 @@
 # round 4: even longer groups for the five short-group matrices (batch layout planned for n_cus / 4, 6, 8 workgroups)
 out=gpurun_out/r4step; mkdir -p $out
 timeout -k 10 300 python3 -m pytest tests/test_gpu_step_kernel.py -x -q > $out/div_pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $out/div_pytest.log
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

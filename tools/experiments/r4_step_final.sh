@@ -2,7 +2,7 @@
 # round 4: defaults after the step kernel (batch layout below 80 slices, up to four times as long): tests that touch it, then bench lines
 out=gpurun_out/r4step; mkdir -p $out
 timeout -k 10 400 python3 -m pytest tests/test_gpu_parity.py tests/test_gpu_step_kernel.py tests/test_gpu_bench_set.py -x -q > $out/final_pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $out/final_pytest.log
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

@@ -2,7 +2,7 @@
 # round 4: the tile floor of the small tile streams (HISPMV_TTS_FLOOR, elements per row tile) under the step kernel -- in round 3 smaller
 # tiles were faster alone and slower in the step of grids; then the per-CU occupancy of the final defaults, both families
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

@@ -2,7 +2,7 @@
 # round 4: longer slice groups under the step kernel (an item's start-up -- descriptor chain, first slice from HBM, window staging --
 # costs 3 - 4 us whatever its length): the batch layout for resident groups below 40 / 80 / 200 slices, planned for n_cus / 2, 3, 4 workgroups
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

@@ -2,7 +2,7 @@
 # round 4: the step kernel (one persistent workgroup per CU drawing slice groups and tiles from a queue) against the grids on two lanes,
 # and the queue orders; then the per-CU occupancy of both (tools/wg_timeline.py, diagnostic library).
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

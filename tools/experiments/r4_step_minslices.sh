@@ -2,7 +2,7 @@
 # round 4: should the SMALLEST slice matrices keep their short groups under the step kernel (many 5 - 8 us items to end the queue with)?
 # HISPMV_BATCH_MIN_SLICES: matrices with fewer slices get no long-group layout (nd6k 6.7 K, thread 4.3 K, crankseg_2 13.8 K, Si41Ge41H72 14.7 K, TSOPF 15.8 K)
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4: the powerlaw workload (two tile streams) under the step kernel against the tile-stream grid, on one box
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --workload powerlaw --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --workload powerlaw --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

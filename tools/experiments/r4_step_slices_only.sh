@@ -3,7 +3,7 @@
 # does not have)?  Five slice matrices alone, same groups (no batch layout), grids against the step kernel in grid order.
 out=gpurun_out/r4step; mkdir -p $out
 M=PFlow_742,mouse_gene,TSOPF_RS_b2383,Si41Ge41H72,crankseg_2
-run() { tag=$1; shift; env "$@" python3 bench.py --matrices $M --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --matrices $M --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

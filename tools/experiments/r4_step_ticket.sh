@@ -2,7 +2,7 @@
 # round 4: the next ticket drawn right behind the top-of-item barrier (its round trip under the descriptor loads) against drawn where it
 # is consumed; libraries of the two commits, interleaved on one box.  Then the per-CU occupancy of the grids and the step kernel on this box.
 out=gpurun_out/r4step; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 $EXTRA > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 l=[x for x in open("$out/$tag.log") if x.startswith("{")]

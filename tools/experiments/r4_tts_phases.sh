@@ -3,7 +3,7 @@
 # (2) no row-order pass (phase B), against the kernel -- libraries built with -DHISPMV_TTS_EXPERIMENT=1|2 (results are wrong, only the
 # time counts: --no-verify); also the tall and paired geometries.
 out=gpurun_out/r4d; mkdir -p $out
-run() { tag=$1; shift; env "$@" python3 bench.py --matrices soc-Pokec --no-cpu-baseline --no-extras --no-verify --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$@" python3 bench.py --full --matrices soc-Pokec --no-cpu-baseline --no-extras --no-verify --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 d=json.load(open("$out/$tag.json")); r=d["per_matrix"][0]

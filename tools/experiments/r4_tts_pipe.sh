@@ -3,7 +3,7 @@
 # round 4: the x gathers of a wavefront's first slice of block b+1 issued BEFORE its row-order pass of block b (HISPMV_TTS_PIPE, tile
 # stream kernel): libraries built with -DHISPMV_TTS_PIPE=1 -DHISPMV_TTS_B_UNROLL=4|1 and -DHISPMV_TTS_PIPE=0, same box
 out=gpurun_out/r4y; mkdir -p $out
-one() { tag=$1; shift; env "$@" python3 bench.py --matrices soc-Pokec --no-cpu-baseline --no-extras --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
+one() { tag=$1; shift; env "$@" python3 bench.py --full --matrices soc-Pokec --no-cpu-baseline --no-extras --steps 100 --warmup 50 --per-matrix-reps 10 --details $out/$tag.json > $out/$tag.log 2>&1
   python3 - <<PY
 import json
 try:
@@ -12,7 +12,7 @@ try:
 except Exception as e: print("$tag: failed", e)
 PY
 }
-run() { tag=$1; shift; env "$1" python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 "${@:2}" > $out/$tag.log 2>&1
+run() { tag=$1; shift; env "$1" python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 100 --per-matrix-reps 0 "${@:2}" > $out/$tag.log 2>&1
   echo "$tag: $(grep -o '"ms_per_step": [0-9.]*\|"frac": [0-9.]*\|"y_checked": [a-z]*' $out/$tag.log | tr '\n' ' ')"; }
 L=$PWD/hispmv_amd/lib
 timeout -k 10 300 python3 -m pytest tests/test_gpu_tts.py -m gpu -x -q > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $out/pytest.log

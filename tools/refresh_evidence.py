@@ -25,7 +25,7 @@ for w in ("dense", "model", "powerlaw"):
 if (out / "parity_report.json").exists():
     shutil.copy(out / "parity_report.json", prof / f"{tag}_parity_report.json")
 drv = out / f"{tag}m" / "bench_driver_style.log"
-if drv.exists():           # the line of `python bench.py --gpus 1 --steps 20 --warmup 5` (what the driver runs at round end)
+if drv.exists():           # the line of `python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the driver's arguments, with --full)
     dl = [q for q in drv.read_text().splitlines() if q.startswith("{")]
     if dl:
         json.loads(dl[-1])
@@ -46,11 +46,11 @@ hbm = traffic.get("hbm_bytes_per_step")
 drv_note = ""
 if (prof / f"{tag}_bench_line_driver_style.json").exists():
     dd = json.loads((prof / f"{tag}_bench_line_driver_style.json").read_text())
-    drv_note = (f" Driver-style (`--gpus 1 --steps 20 --warmup 5`, `profiles/{tag}_bench_line_driver_style.json`): {dd['value']} GFLOP/s, "
+    drv_note = (f" Driver-style (`--gpus 1 --steps 20 --warmup 5 --full`, `profiles/{tag}_bench_line_driver_style.json`): {dd['value']} GFLOP/s, "
                 f"{dd['ms_per_step']} ms per step, frac {dd['roofline']['frac']} (pessimistic family {dd['standin_uniform']['roofline_frac']}); "
                 f"both lines carry `y_checked: {str(dd['y_checked']).lower()}` (max backward error {dd['y_check']['max_backward_error']:.2e} over {dd['y_check']['rows_checked']} rows).")
 lines = [
-    f"`python bench.py` (defaults: {s['steps']} steps, {s['warmup']} warm-up; `profiles/{tag}_bench_line.json`, "
+    f"`python bench.py --full` (defaults: {s['steps']} steps, {s['warmup']} warm-up; `profiles/{tag}_bench_line.json`, "
     f"`profiles/{tag}_bench_details.json`): **{s['value']} GFLOP/s** over the set, {s['ms_per_step']} ms per step, "
     f"{s['hbm_gbs_algorithmic']} GB/s algorithmic = **{s['hbm_pct_of_peak']} % of the 8 TB/s peak**; `roofline.achieved` "
     f"{rf['achieved']} GB/s (HIP events), `frac` {rf['frac']}." + drv_note,
