@@ -72,6 +72,10 @@ SIGNATURES = {
     "hispmv_batch_graph_stats": (C.c_int, [_p, C.POINTER(C.c_int64)]),
     "hispmv_batch_call_info": (C.c_int, [_p, C.POINTER(C.c_int64)]),
     "hispmv_spmv_device_batch": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p, C.c_float, C.c_float, _p]),
+    "hispmv_set_value_updates": (C.c_int, [_p, C.c_int]),
+    "hispmv_update_values": (C.c_int, [_p, C.c_int, _p, C.c_int64]),
+    "hispmv_update_values_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p]),
+    "hispmv_value_update_info": (C.c_int, [_p, C.c_int, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),
     "hispmv_num_matrices": (C.c_int, [_p]),
@@ -91,6 +95,8 @@ SIGNATURES = {
     "hispmv_prep_device_array": (C.c_void_p, [_p, C.c_int]),
     "hispmv_prep_device_stream_on_device": (C.c_int, [_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hispmv_prep_frags": (_i32p, [_p]),
+    "hispmv_prep_value_layouts": (C.c_int, [C.POINTER(_p), _p, _p, _p, C.c_int64, C.c_int32, C.c_int32, C.c_int, _i64p]),
+    "hispmv_prep_value_array": (C.c_void_p, [_p, C.c_int]),
     "hispmv_prep_csr_row_ptr": (_i64p, [_p]),
     "hispmv_prep_csr_col": (_i32p, [_p]),
     "hispmv_prep_csr_val": (_f32p, [_p]),

@@ -47,7 +47,7 @@ void free_matrix_device(Matrix& m) {
     for (void*& p : m.allocs) dev_free(p);
     m.allocs.clear();
     for (auto& p : m.parts) p.dev = SpmvDeviceMatrix{};
-    m.d_dense = nullptr; m.d_ypart = nullptr; m.d_fix_of_row = nullptr;
+    m.d_dense = nullptr; m.d_ypart = nullptr; m.d_fix_of_row = nullptr; m.d_map = nullptr; m.d_upd_table = nullptr;
     m.loaded = false;
 }
 
@@ -61,10 +61,33 @@ int ensure_vec(hispmv_ctx* c, float** p, int64_t* cap, int64_t n) {
     return HISPMV_OK;
 }
 
+// Value updates: the layouts of an updatable handle are packed from these payloads instead of its values -- the bits of k + 1 for
+// input position k, so that every value slot names the entry it holds (fp32 denormals below 2^23: nothing on the way does
+// arithmetic on a value, and nothing is built with fast-math).  Capped below the bits of +inf.
+constexpr int64_t kMaxUpdatableEntries = 0x7F7FFFFFll;
+std::vector<float> index_payloads(int64_t n) {
+    std::vector<float> p((size_t)n);
+#pragma omp parallel for num_threads(host_threads()) schedule(static)
+    for (int64_t k = 0; k < n; ++k) {
+        const uint32_t b = (uint32_t)(k + 1);
+        std::memcpy(&p[(size_t)k], &b, 4);
+    }
+    return p;
+}
+
+// The switches DESIGN records as negative experiments change the tile stream's words beyond what value_chunks describes: refused.
+int check_updatable(hispmv_ctx* c, int64_t nnz) {
+    if (nnz > kMaxUpdatableEntries) return fail(c, HISPMV_EINVAL, "value updates: more entries than an index payload can name");
+    if (c->format_opts.tts_geometry != 0 || c->format_opts.tts_small)
+        return fail(c, HISPMV_EINVAL, "value updates: not supported with HISPMV_TTS_GEOMETRY other than standard or HISPMV_TTS_SMALL (experiments)");
+    return HISPMV_OK;
+}
+
 // Registers a prepared sparse matrix with the context (capacity check = the reference's
 // "offset + size > MAX_BUFFER_SIZE_BYTES -> return -1", fpga_handle.cpp:192-195).  The format and tiling decision itself is
 // host-only code: choose_format (hispmv_choose.cpp).
-int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = nullptr) {
+// real_values (updatable handles): the creation input's values in input order; csr then holds their index payloads.
+int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = nullptr, std::vector<float>* real_values = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     // HISPMV_PREP_TRACE=1: the phases of the host side of preprocessing on stderr (diagnostics)
     static const bool trace = std::getenv("HISPMV_PREP_TRACE") != nullptr;
@@ -99,6 +122,15 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
         }
     }
     if (m->parts.size() > 1) m->device_bytes += (int64_t)(m->parts.size() - 1) * kMaxBatch * m->rows * 4;   // partial vectors of parts t > 0
+    if (real_values) {          // the map and its chunk table count against the arena
+        m->updatable = true;
+        m->upd_n = (int64_t)real_values->size();
+        int64_t chunks = 0;
+        for (const HostPart& p : m->parts)
+            for (const ValueChunk& q : value_chunks(p)) { ++chunks; m->upd_written += kValueChunk * (q.off1 >= 0 ? 2 : 1); }
+        m->map_slots = chunks * kValueChunk;
+        m->device_bytes += m->map_slots * 4 + chunks * (int64_t)sizeof(ValueChunkDev);
+    }
     if (m->format == 1) {
         m->plan_threads = m->parts[0].tts.geometry.threads; m->plan_group = m->parts[0].tts.geometry.max_slots / kTtsChunk; m->plan_lds = 0;
     } else {
@@ -106,10 +138,56 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
     }
     m->prep_seconds = t_csr + std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (c->arena_used + m->device_bytes > c->arena_budget) return HISPMV_FULL;
+    if (real_values) m->upd_values = std::move(*real_values);
     c->arena_used += m->device_bytes;
     m->index = (int)c->mats.size();
     c->mats.push_back(std::move(m));
     return (int)c->mats.size() - 1;
+}
+
+// The load's part of value updates, once the layouts of `m` are on the device (packed with index payloads): the chunk table, the
+// map read out of the layouts, then the real values gathered in -- so the update kernel runs on every load of an updatable handle.
+// `chunks`: value_chunks of every part, taken before the loader released the host tables; `layout_bytes`: {first, batch} layout
+// sizes per part, every chunk is checked against them before anything is written.
+int load_value_map(hispmv_ctx* c, Matrix& m, const std::vector<std::vector<ValueChunk>>& chunks, const std::vector<std::pair<int64_t, int64_t>>& layout_bytes) {
+    std::vector<ValueChunkDev> tab;
+    int64_t written = 0;
+    for (size_t t = 0; t < m.parts.size(); ++t) {
+        Matrix::Part& p = m.parts[t];
+        uint8_t* base0 = p.is_tts ? (uint8_t*)p.tdev.words : (uint8_t*)p.dev.words;
+        uint8_t* base1 = (!p.is_tts && p.has_batch_dev) ? (uint8_t*)p.batch_dev.words : nullptr;
+        for (const ValueChunk& q : chunks[t]) {
+            if (q.off0 < 0 || q.off0 + kValueChunk * 4 > layout_bytes[t].first || (base1 && (q.off1 < 0 || q.off1 + kValueChunk * 4 > layout_bytes[t].second)))
+                return fail(c, HISPMV_EINVAL, "internal: value region outside its layout");
+            ValueChunkDev e;
+            e.map_off = (int64_t)tab.size() * kValueChunk;
+            e.dst0 = (float*)(base0 + q.off0);
+            e.dst1 = base1 ? (float*)(base1 + q.off1) : nullptr;
+            written += kValueChunk * (e.dst1 ? 2 : 1);
+            tab.push_back(e);
+        }
+    }
+    if ((int64_t)tab.size() * kValueChunk != m.map_slots) return fail(c, HISPMV_EINVAL, "internal: value map size changed between creation and load");
+    m.upd_written = written;
+    if (!tab.empty()) {
+        void* dm = nullptr; void* dt = nullptr;
+        HIP_TRY(c, hipMalloc(&dm, (size_t)m.map_slots * 4));
+        m.allocs.push_back(dm);
+        HIP_TRY(c, hipMalloc(&dt, tab.size() * sizeof(ValueChunkDev)));
+        m.allocs.push_back(dt);
+        m.d_map = (int32_t*)dm; m.d_upd_table = (ValueChunkDev*)dt;
+        HIP_TRY(c, hipMemcpyAsync(dt, tab.data(), tab.size() * sizeof(ValueChunkDev), hipMemcpyHostToDevice, c->stream));
+        hipError_t e = launch_build_value_map(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_build_value_map");
+        int rc;
+        if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, m.upd_n)) != HISPMV_OK) return rc;
+        if (m.upd_n > 0) HIP_TRY(c, hipMemcpyAsync(c->d_upd, m.upd_values.data(), (size_t)m.upd_n * 4, hipMemcpyHostToDevice, c->stream));
+        e = launch_update_values(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_update_values");
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`tab` and the values are host locals / released next)
+    }
+    m.upd_values = std::vector<float>();
+    return HISPMV_OK;
 }
 
 template <class T>
@@ -330,6 +408,8 @@ HISPMV_API void hispmv_destroy(hispmv_ctx* c) {
     dev_free(c->d_y);
     host_free(c->h_err);
     host_free(c->h_stage);
+    host_free(c->h_upd);
+    dev_free(c->d_upd);
     free_batch_plans(c);
     for (int i = 0; i < 2; ++i) { if (c->side[i]) (void)hipStreamDestroy(c->side[i]); if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -351,17 +431,26 @@ HISPMV_API int64_t hispmv_arena_bytes_used(const hispmv_ctx* c) { return c ? c->
 static int add_from_coo(hispmv_ctx* c, int32_t rows, int32_t cols, int64_t nnz, const int32_t* r, const int32_t* cl, const float* v) {
     auto t0 = std::chrono::steady_clock::now();
     const bool on_device = c->prep_mode == 1 || (c->prep_mode == 2 && nnz >= (2 << 20));
+    std::vector<float> real, payloads;
+    if (c->value_updates) {
+        const int rc = check_updatable(c, nnz);
+        if (rc != HISPMV_OK) return rc;
+        real.assign(v, v + nnz);
+        payloads = index_payloads(nnz);
+        v = payloads.data();
+    }
+    std::vector<float>* const real_values = c->value_updates ? &real : nullptr;
     if (on_device) {
         HIP_TRY(c, hipSetDevice(c->device));
         Csr csr; SliceStream st; std::string err;
         if (!prep_on_device(rows, cols, nnz, r, cl, v, csr, st, c->last_prep_times, err))
             return fail(c, err.find("outside") != std::string::npos || err.find("dimension") != std::string::npos ? HISPMV_EINVAL : HISPMV_EDEVICE, err);
         double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return add_sparse(c, std::move(csr), t, &st);
+        return add_sparse(c, std::move(csr), t, &st, real_values);
     }
     Csr csr = coo_to_csr(rows, cols, nnz, r, cl, v);
     double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return add_sparse(c, std::move(csr), t);
+    return add_sparse(c, std::move(csr), t, nullptr, real_values);
 }
 
 HISPMV_API int hispmv_create_sparse_handle(hispmv_ctx* c, const int32_t* r, const int32_t* cl, const float* v,
@@ -380,6 +469,8 @@ HISPMV_API int hispmv_create_sparse_handle_from_mtx(hispmv_ctx* c, const char* p
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     if (!path || (flavor != 0 && flavor != 1)) return fail(c, HISPMV_EINVAL, "bad arguments");
+    // the reader drops zeros and mirrors symmetric entries: there is no input order an update could follow
+    if (c->value_updates) return fail(c, HISPMV_EINVAL, "value updates: a MatrixMarket handle cannot be updated (create it from COO or CSR)");
     try {
         auto t0 = std::chrono::steady_clock::now();
         Coo coo = read_mtx(path, (MtxFlavor)flavor);
@@ -406,11 +497,18 @@ HISPMV_API int hispmv_create_sparse_handle_from_csr(hispmv_ctx* c, const int32_t
         if (rp[0] != 0 || nnz < 0) return fail(c, HISPMV_EINVAL, "row_ptr must start at 0");
         for (int32_t i = 0; i < rows; ++i) if (rp[i + 1] < rp[i]) return fail(c, HISPMV_EINVAL, "row_ptr must be non-decreasing");
         if (nnz > 0 && (!ci || !va)) return fail(c, HISPMV_EINVAL, "col_idx / values are NULL");
-        csr.col.assign(ci, ci + nnz); csr.val.assign(va, va + nnz);
+        std::vector<float> real;
+        if (c->value_updates) {
+            const int rc = check_updatable(c, nnz);
+            if (rc != HISPMV_OK) return rc;
+        }
+        csr.col.assign(ci, ci + nnz);
+        if (c->value_updates) { real.assign(va, va + nnz); const std::vector<float> pl = index_payloads(nnz); csr.val.assign(pl.begin(), pl.end()); }   // input order: before the per-row sort
+        else csr.val.assign(va, va + nnz);
         for (int64_t k = 0; k < nnz; ++k) if (ci[k] < 0 || ci[k] >= cols) return fail(c, HISPMV_EINVAL, "CSR column outside matrix");
         sort_rows_by_column(csr);     // rows with unsorted columns (scipy: has_sorted_indices == False) are sorted, stably
         double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return add_sparse(c, std::move(csr), t);
+        return add_sparse(c, std::move(csr), t, nullptr, c->value_updates ? &real : nullptr);
     } catch (const std::bad_alloc&) { return fail(c, HISPMV_ENOMEM, "host out of memory");
     } catch (const std::exception& ex) { return fail(c, HISPMV_EINVAL, ex.what()); }
 }
@@ -428,6 +526,7 @@ HISPMV_API int hispmv_create_dense_handle(hispmv_ctx* c, const float* vals, int3
         m->device_bytes = m->nnz * 4;
         if (c->arena_used + m->device_bytes > c->arena_budget) return HISPMV_FULL;
         m->dense_host.assign(vals, vals + m->nnz);
+        if (c->value_updates) { m->updatable = true; m->upd_n = m->nnz; m->upd_written = m->nnz; }    // an update is a copy into d_dense
         m->prep_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         c->arena_used += m->device_bytes;
         m->index = (int)c->mats.size();
@@ -447,6 +546,14 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
         // (scratch of the device layout -- the uploaded host words of the parts --, freed once the stream has drained, also on an error return)
         struct Scratch { std::vector<void*> v; void push_back(void* p) { v.push_back(p); } ~Scratch() { for (void* p : v) (void)hipFree(p); } } layout_scratch;
         std::vector<std::vector<int32_t>> tts_fix_rows;       // tile streams: the rows cut into pieces, per part (fix list order)
+        // value updates: the value regions of every part and the sizes of its layouts, while the host tables exist
+        std::vector<std::vector<ValueChunk>> value_regions;
+        std::vector<std::pair<int64_t, int64_t>> layout_bytes;
+        if (m.updatable && !m.dense)
+            for (const Matrix::Part& p : m.parts) {
+                value_regions.push_back(value_chunks(p));
+                layout_bytes.emplace_back(p.is_tts ? (int64_t)p.tts.words.size() : p.dstream.n_bytes, p.has_batch_layout ? p.batch_dstream.n_bytes : 0);
+            }
         if (m.dense) {
             const float* d = nullptr;
             if ((rc = upload(c, m, m.dense_host.data(), m.dense_host.size(), &d)) != HISPMV_OK) return rc;
@@ -675,6 +782,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                 m.d_fix_of_row = const_cast<int32_t*>(d_of);
             }
         }
+        if (m.updatable && !m.dense && (rc = load_value_map(c, m, value_regions, layout_bytes)) != HISPMV_OK) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         // host copies are no longer needed
         for (auto& p : m.parts) { p.st = SliceStream{}; p.fix_short = {}; p.fix_long = {}; p.plan.groups = {}; p.plan.frags = {}; p.dstream = DeviceStream{};
@@ -831,3 +939,77 @@ HISPMV_API int hispmv_get_matrix_info(const hispmv_ctx* c, int idx, hispmv_matri
     return HISPMV_OK;
 }
 
+// ---- in-place value updates (include/hispmv.h: hispmv_set_value_updates) ----------------------------------------------------
+HISPMV_API int hispmv_set_value_updates(hispmv_ctx* c, int enable) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->value_updates = enable != 0;
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_value_update_info(const hispmv_ctx* c, int idx, int64_t out[4]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
+    const Matrix& m = *c->mats[idx];
+    out[0] = m.updatable ? 1 : 0; out[1] = m.upd_n; out[2] = m.map_slots; out[3] = m.upd_written;
+    return HISPMV_OK;
+}
+
+namespace {
+
+// The checks both update entries share; on success *out is the handle.
+int update_target(hispmv_ctx* c, int idx, const float* values, int64_t n, Matrix** out) {
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[idx];
+    if (!m.updatable) return fail(c, HISPMV_ESTATE, "handle was not created with value updates on (hispmv_set_value_updates)");
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, "update_values called before load_matrices");
+    if (n != m.upd_n) return fail(c, HISPMV_EINVAL, "update_values: n is not the number of values the handle was created with");
+    if (n > 0 && !values) return fail(c, HISPMV_EINVAL, "update_values: values is NULL");
+    *out = &m;
+    return HISPMV_OK;
+}
+
+// d_values (device) into the layouts of m, asynchronous on s
+int issue_update(hispmv_ctx* c, Matrix& m, const float* d_values, hipStream_t s) {
+    if (m.upd_n == 0) return HISPMV_OK;
+    if (m.dense) {
+        HIP_TRY(c, hipMemcpyAsync(m.d_dense, d_values, (size_t)m.upd_n * 4, hipMemcpyDeviceToDevice, s));
+        return HISPMV_OK;
+    }
+    const hipError_t e = launch_update_values(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s);
+    return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_update_values");
+}
+
+}  // namespace
+
+HISPMV_API int hispmv_update_values(hispmv_ctx* c, int idx, const float* values, int64_t n) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    Matrix* m = nullptr;
+    int rc = update_target(c, idx, values, n, &m);
+    if (rc != HISPMV_OK || n == 0) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // pinned staging, ONE copy into the context's scratch, the kernel, a synchronise
+    if (n > c->cap_h_upd) {
+        host_free(c->h_upd);
+        c->cap_h_upd = 0;
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_upd, (size_t)n * sizeof(float), hipHostMallocDefault));
+        c->cap_h_upd = n;
+    }
+    if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, n)) != HISPMV_OK) return rc;
+    std::memcpy(c->h_upd, values, (size_t)n * sizeof(float));
+    HIP_TRY(c, hipMemcpyAsync(c->d_upd, c->h_upd, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = issue_update(c, *m, c->d_upd, c->stream)) != HISPMV_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_update_values_device(hispmv_ctx* c, int idx, const float* d_values, int64_t n, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    Matrix* m = nullptr;
+    const int rc = update_target(c, idx, d_values, n, &m);
+    if (rc != HISPMV_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (stream) c->user_stream = (hipStream_t)stream;
+    return issue_update(c, *m, d_values, stream ? (hipStream_t)stream : c->stream);
+}

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 
 namespace hispmv {
 
@@ -539,6 +540,35 @@ std::vector<std::pair<int, int>> order_step_queue(const std::vector<double>& sli
         out.emplace_back(k, idx[k][pos[k]]);
         ++pos[k];
     }
+    return out;
+}
+
+
+std::vector<ValueChunk> value_chunks(const HostPart& p) {
+    std::vector<ValueChunk> out;
+    if (p.is_tts) {
+        const int64_t n = (int64_t)p.tts.col_base.size();        // slices of 1024 words
+        out.reserve((size_t)n);
+        for (int64_t s = 0; s < n; ++s) out.push_back({s * (int64_t)kTtsChunk * 8, -1});   // values at words + slice*8192, metas behind
+        return out;
+    }
+    const int64_t n = p.st.n_slices;
+    // the byte offset of every slice in a device layout: groups of plan.group_slices slices, compact (6 KiB) or wide (8 KiB)
+    auto offsets = [n](const DeviceStream& d, const LaunchPlan& plan, std::vector<int64_t>& off) {
+        const int64_t G = plan.group_slices;
+        off.assign((size_t)n, -1);
+        for (int64_t s = 0; s < n; ++s) {
+            const int64_t g = s / G;
+            if ((size_t)g * 4 + 3 >= d.groups.size()) throw std::logic_error("value_chunks: group table shorter than the stream");
+            const int32_t* e = d.groups.data() + g * 4;
+            off[(size_t)s] = (int64_t)e[2] * kSliceUnit + (s - g * G) * (e[3] ? kCompactSliceBytes : kWideSliceBytes);
+        }
+    };
+    std::vector<int64_t> a, b;
+    offsets(p.dstream, p.plan, a);
+    if (p.has_batch_layout) offsets(p.batch_dstream, p.batch_plan, b);
+    out.reserve((size_t)n);
+    for (int64_t s = 0; s < n; ++s) out.push_back({a[(size_t)s], p.has_batch_layout ? b[(size_t)s] : -1});
     return out;
 }
 

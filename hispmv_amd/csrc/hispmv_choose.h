@@ -95,4 +95,14 @@ std::vector<uint8_t> window_membership(const Csr& csr, const LaunchPlan& plan);
 FormatChoice choose_format(Csr&& csr, SliceStream* prebuilt, int n_cus, const FormatOptions& opt,
                            const std::function<void(const char*)>& lap = {});
 
+// VALUE REGIONS of a part's device layouts (hispmv_set_value_updates): every value slot of every layout holds one entry of the
+// creation input, or 0 for a filler / padding slot, and the slots come in regions of kSliceElems fp32 -- the first 4096 B of every
+// slice of a slice stream (the batch layout has the same slices: its region of a slice is the same chunk's second destination), the
+// first 4096 B of every 8192-byte slice of a tile stream's words.  One chunk per region, in map order: {byte offset in the part's
+// layout (dstream / tts.words), byte offset in its batch layout or -1}.  Needs the host group tables (before the loader frees them).
+struct ValueChunk {
+    int64_t off0, off1;
+};
+std::vector<ValueChunk> value_chunks(const HostPart& p);
+
 }  // namespace hispmv

@@ -26,6 +26,7 @@
 #include "hispmv_prep.h"
 #include "hispmv_prep_device.h"
 #include "hispmv_tts.h"
+#include "hispmv_update.h"
 
 #define HISPMV_API extern "C" __attribute__((visibility("default")))
 
@@ -65,6 +66,15 @@ struct Matrix {
     // column parts: for every part the fix-list index of each row (or -1), parts x rows, so that the merge of the partial
     // vectors can apply the fix-ups of its rows itself (spmv_tail_multi_kernel); nullptr when a part has a long chain
     int32_t* d_fix_of_row = nullptr;
+    // In-place value updates (hispmv_set_value_updates on at creation): the layouts were packed with the payloads bits(k + 1) of the
+    // input positions k; at load the map is read out of them and the real values (kept until then) are gathered in (hispmv_update.h)
+    bool updatable = false;
+    int64_t upd_n = 0;                      // values an update takes (nnz of the input, rows * cols for a dense handle)
+    int64_t map_slots = 0;                  // kValueChunk per chunk
+    int64_t upd_written = 0;                // slots an update writes (a batch layout's chunks twice)
+    std::vector<float> upd_values;          // the creation input's values, until the load has written them
+    int32_t* d_map = nullptr;
+    ValueChunkDev* d_upd_table = nullptr;
     std::vector<void*> allocs;
 };
 
@@ -111,6 +121,13 @@ struct hispmv_ctx {
     float* h_stage = nullptr;
     float* d_stage = nullptr;            // the device address of the same pinned block (run_kernel / linear write y straight into it)
     int64_t cap_stage = 0;
+    // value updates: the switch handles are created under (hispmv_set_value_updates), the pinned staging block and the device
+    // buffer of hispmv_update_values (host values) and of the load's first update
+    bool value_updates = false;
+    float* h_upd = nullptr;
+    int64_t cap_h_upd = 0;
+    float* d_upd = nullptr;
+    int64_t cap_d_upd = 0;
     // hispmv_spmv_device_batch: the launches of one call signature (handles, vectors, beta == 0 or not) with their device
     // tables, built on the first call and replayed afterwards
     struct BatchLaunch {
@@ -184,6 +201,11 @@ struct hispmv_prep {
     hispmv::LaunchPlan plan;
     hispmv::TtsStream tts;
     hispmv::DeviceStream dstream;     // hispmv_prep_device_stream: the planned stream in its device layout
+    // hispmv_prep_value_layouts: every device layout of a handle packed with the real values and with the index payloads, the map
+    // read out of the latter and the chunks' byte offsets {first destination, second or -1}
+    std::vector<uint8_t> vl_real, vl_index;
+    std::vector<int32_t> vl_map;
+    std::vector<int64_t> vl_chunks;
 };
 
 

@@ -236,3 +236,71 @@ HISPMV_API const float* hispmv_prep_csr_val(const hispmv_prep* p) { return p->cs
 HISPMV_API const uint64_t* hispmv_prep_words(const hispmv_prep* p) { return p->st.words.data(); }
 HISPMV_API const int32_t* hispmv_prep_slice_hdr(const hispmv_prep* p) { return (const int32_t*)p->st.hdr.data(); }
 HISPMV_API const int32_t* hispmv_prep_fix(const hispmv_prep* p) { return (const int32_t*)p->st.fix.data(); }
+
+// Every device layout of the handle hispmv_create_sparse_handle would make from this COO input on a device with n_cus CUs, packed
+// twice by the same host path: with the real values, and -- as for a handle created with value updates on -- with the index
+// payloads bits(k + 1).  The map is read out of the payload layouts' value regions (value_chunks) exactly as the loader reads it on
+// the device.  For tests: gathering the values through the map must give the real layouts byte for byte.
+HISPMV_API int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* r, const int32_t* cl, const float* v, int64_t nnz, int32_t rows,
+                                         int32_t cols, int n_cus, int64_t counts[8]) {
+    if (!out) return HISPMV_EINVAL;
+    host_threads();
+    *out = nullptr;
+    if (rows <= 0 || cols <= 0 || nnz < 0 || n_cus <= 0 || !counts || (nnz > 0 && (!r || !cl || !v))) { g_prep_err = "bad sparse matrix arguments"; return HISPMV_EINVAL; }
+    if (nnz > 0x7F7FFFFFll) { g_prep_err = "more entries than an index payload can name"; return HISPMV_EINVAL; }
+    try {
+        FormatOptions opt = FormatOptions::from_env();
+        if (opt.tts_geometry != 0 || opt.tts_small) { g_prep_err = "value updates: experiment geometries are refused"; return HISPMV_EINVAL; }
+        opt.device_layout = false;             // (the bytes on the host; HISPMV_LAYOUT=device writes the same ones on the device)
+        auto p = std::make_unique<hispmv_prep>();
+        std::vector<float> payloads((size_t)nnz);
+        for (int64_t k = 0; k < nnz; ++k) { const uint32_t b = (uint32_t)(k + 1); std::memcpy(&payloads[(size_t)k], &b, 4); }
+        int64_t info[4] = {0, 0, 0, 0};
+        auto pack = [&](const float* vals, std::vector<uint8_t>& bytes, bool record) {
+            FormatChoice ch = choose_format(coo_to_csr(rows, cols, nnz, r, cl, vals), nullptr, n_cus, opt);
+            if (record) { info[0] = ch.format; info[1] = ch.parts.size() > 1 ? (ch.tile_kind ? ch.tile_kind : 1) : 0; info[2] = (int64_t)ch.parts.size(); }
+            for (const HostPart& q : ch.parts) {
+                const std::vector<ValueChunk> chunks = value_chunks(q);
+                const int64_t base0 = (int64_t)bytes.size();
+                if (q.is_tts) bytes.insert(bytes.end(), q.tts.words.begin(), q.tts.words.end());
+                else bytes.insert(bytes.end(), q.dstream.bytes.begin(), q.dstream.bytes.end());
+                const int64_t base1 = (int64_t)bytes.size();
+                if (!q.is_tts && q.has_batch_layout) { bytes.insert(bytes.end(), q.batch_dstream.bytes.begin(), q.batch_dstream.bytes.end()); info[3]++; }
+                if (!record) continue;
+                for (const ValueChunk& c : chunks) {
+                    p->vl_chunks.push_back(base0 + c.off0);
+                    p->vl_chunks.push_back(c.off1 >= 0 ? base1 + c.off1 : -1);
+                }
+            }
+        };
+        pack(v, p->vl_real, false);
+        pack(payloads.data(), p->vl_index, true);
+        const int64_t n_chunks = (int64_t)p->vl_chunks.size() / 2;
+        p->vl_map.resize((size_t)n_chunks * kValueChunk);
+        int64_t written = 0;
+        for (int64_t k = 0; k < n_chunks; ++k) {
+            const int64_t off = p->vl_chunks[(size_t)k * 2];
+            if (off < 0 || off + kValueChunk * 4 > (int64_t)p->vl_index.size()) { g_prep_err = "internal: value region outside its layout"; return HISPMV_EINVAL; }
+            std::memcpy(p->vl_map.data() + k * kValueChunk, p->vl_index.data() + off, kValueChunk * 4);
+            written += kValueChunk * (p->vl_chunks[(size_t)k * 2 + 1] >= 0 ? 2 : 1);
+        }
+        counts[0] = (int64_t)p->vl_index.size(); counts[1] = (int64_t)p->vl_map.size(); counts[2] = n_chunks; counts[3] = written;
+        counts[4] = info[0]; counts[5] = info[1]; counts[6] = info[2]; counts[7] = info[3];
+        if (p->vl_real.size() != p->vl_index.size()) { g_prep_err = "the layouts of the two packings differ in size"; return HISPMV_EINVAL; }
+        *out = p.release();
+        return HISPMV_OK;
+    } catch (const std::exception& ex) { g_prep_err = ex.what(); return HISPMV_EINVAL; }
+}
+
+// 0 = the layouts with the real values (counts[0] bytes), 1 = the same with the index payloads, 2 = the map (int32, counts[1]),
+// 3 = the chunks (counts[2] x int64 {byte offset of the first destination, of the second or -1}).
+HISPMV_API const void* hispmv_prep_value_array(const hispmv_prep* p, int which) {
+    if (!p) return nullptr;
+    switch (which) {
+        case 0: return p->vl_real.data();
+        case 1: return p->vl_index.data();
+        case 2: return p->vl_map.data();
+        case 3: return p->vl_chunks.data();
+        default: return nullptr;
+    }
+}

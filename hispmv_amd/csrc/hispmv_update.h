@@ -1,0 +1,29 @@
+// hispmv_update.h -- in-place value updates of loaded handles (hispmv_update_values*, include/hispmv.h): the device side.
+// A handle created with value updates on carries a MAP: for every value slot of its device layouts, in chunks of kValueChunk
+// slots, the position k + 1 of the creation input entry the slot holds (0 = filler / padding).  An update gathers the new values
+// through it into the layouts, in place (hispmv_update.hip).  Kept apart from hispmv_kernels.hip, whose step kernel sits at its
+// register ceiling.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+namespace hispmv {
+
+constexpr int kValueChunk = 1024;     // slots per chunk: one slice's values (slice stream) or one 1024-word slice (tile stream)
+
+// One chunk of the map: slots [map_off, map_off + kValueChunk) of the map go to dst0 and, when not NULL, to dst1 (the batch
+// layout's copy of the same slice).  Both 16-byte aligned.
+struct ValueChunkDev {
+    int64_t map_off;
+    float* dst0;
+    float* dst1;
+};
+
+// map[chunk] = the payloads the creation left in the chunk's first destination (bits of k + 1, or 0), for every chunk of the table.
+hipError_t launch_build_value_map(const ValueChunkDev* d_table, int64_t n_chunks, int32_t* d_map, hipStream_t s);
+// dst[slot] = map[slot] ? values[map[slot] - 1] : 0 for every chunk of the table (an index above n also writes 0).
+hipError_t launch_update_values(const ValueChunkDev* d_table, int64_t n_chunks, const int32_t* d_map, const float* d_values, int64_t n,
+                                hipStream_t s);
+
+}  // namespace hispmv

@@ -31,6 +31,9 @@ class Shard:
     values: np.ndarray
     head_open: bool        # local row 0 continues a row begun on an earlier rank
     tail_open: bool        # last local row continues on a later rank (this rank does not own it)
+    value_begin: int = -1  # shard_csr: the local values are global CSR values [value_begin, value_end) of global_nnz
+    value_end: int = -1
+    global_nnz: int = -1
 
     def local_bias(self, bias: np.ndarray) -> np.ndarray:
         """bias restricted to the local rows, zeroed where this rank is not the owner."""
@@ -38,6 +41,16 @@ class Shard:
         if self.tail_open and self.n_rows:
             b[-1] = 0.0
         return b
+
+    def local_values(self, global_csr_values) -> np.ndarray:
+        """The rank's share of a new global CSR value array (same pattern, same order as the values shard_csr was given): what
+        FpgaHandle.update_values takes for the handle created from this shard."""
+        if self.value_begin < 0:
+            raise ValueError("local_values: this shard was not cut by shard_csr")
+        v = np.asarray(global_csr_values).reshape(-1)
+        if v.size != self.global_nnz:
+            raise ValueError(f"local_values: {v.size} values, the global matrix has {self.global_nnz}")
+        return np.ascontiguousarray(v[self.value_begin:self.value_end], dtype=np.float32)
 
 
 def split_points(n_elems: int, world: int) -> np.ndarray:
@@ -59,7 +72,8 @@ def shard_csr(row_ptr, col_idx, values, world: int, rank: int) -> Shard:
     cuts = split_points(int(eoff[-1]), world)
     b, e = int(cuts[rank]), int(cuts[rank + 1])
     if e == b:
-        return Shard(rank, world, b, e, 0, 0, np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), False, False)
+        return Shard(rank, world, b, e, 0, 0, np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), False, False,
+                     0, 0, int(rp[-1]))
     r0 = int(np.searchsorted(eoff[1:], b, side="right"))                  # first row ending after b
     r1 = int(np.searchsorted(eoff[:-1], e, side="left"))                  # one past the last row starting before e
     # real (non-filler) elements of local row i: global rows r0+i, clipped to the element range
@@ -78,7 +92,7 @@ def shard_csr(row_ptr, col_idx, values, world: int, rank: int) -> Shard:
     else:
         idx = slice(0, 0)
     return Shard(rank, world, b, e, r0, r1 - r0, loc, np.asarray(col_idx)[idx].astype(np.int32),
-                 np.asarray(values)[idx].astype(np.float32), bool(eoff[r0] < b), bool(eoff[r1] > e))
+                 np.asarray(values)[idx].astype(np.float32), bool(eoff[r0] < b), bool(eoff[r1] > e), idx.start, idx.stop, int(rp[-1]))
 
 
 def shard_of_stacked_blocks(cur, nxt, rows: int, cols: int, rank: int, world: int) -> Shard:

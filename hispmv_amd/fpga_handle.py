@@ -149,6 +149,29 @@ class FpgaHandle:
         rc = lib.hispmv_create_sparse_handle_from_csr(self._ctx, _ptr(rp), _ptr(ci), _ptr(va), int(rows), int(cols))
         return rc if rc == _lib.HISPMV_FULL else self._check(rc)
 
+    def set_value_updates(self, enable: bool) -> None:
+        """Handles created from now on (until switched off) can have their values updated in place (hispmv_set_value_updates)."""
+        self._check(lib.hispmv_set_value_updates(self._ctx, int(bool(enable))))
+
+    def update_values(self, matrix_idx: int, values) -> None:
+        """New values for a loaded updatable handle, in the order of its creation input (COO arrays, CSR values before the per-row
+        sort, W row-major); returns when the device holds them."""
+        v = _as(values, np.float32).reshape(-1)
+        self._check(lib.hispmv_update_values(self._ctx, int(matrix_idx), _ptr(v), v.size))
+
+    def update_values_device(self, matrix_idx: int, d_values: int, n: int, stream: int = 0) -> None:
+        """The same from device memory (an int pointer, e.g. a torch tensor's ``data_ptr()``): asynchronous and ordered on `stream`
+        (0 = the context's stream); ordering against other streams is the caller's job."""
+        self._check(lib.hispmv_update_values_device(self._ctx, int(matrix_idx), C.c_void_p(d_values), int(n), C.c_void_p(stream)))
+
+    def value_update_info(self, matrix_idx: int) -> dict:
+        """{"updatable", "n", "map_slots", "written"} of a handle (hispmv_value_update_info)."""
+        out = (C.c_int64 * 4)()
+        rc = lib.hispmv_value_update_info(self._ctx, int(matrix_idx), out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range")
+        return {"updatable": bool(out[0]), "n": int(out[1]), "map_slots": int(out[2]), "written": int(out[3])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

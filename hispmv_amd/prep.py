@@ -233,3 +233,32 @@ def step_queue(slice_costs, tile_costs, n_wg: int = 256, mode: int = 0):
     if rc != HISPMV_OK:
         raise ValueError("hispmv_prep_step_queue: invalid argument")
     return cls, idx
+
+
+VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
+
+
+def value_layouts_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256) -> dict:
+    """Every device layout of the handle a COO input makes, packed twice on the host (hispmv_prep_value_layouts): `real` with the
+    values, `index` with the index payloads of a handle created with value updates on; `map` (int32, read out of `index`) and
+    `chunks` ([n, 2] byte offsets of each chunk's first and second destination, -1 = none), plus the VALUE_LAYOUT_FIELDS counts."""
+    r = np.ascontiguousarray(coo_rows, dtype=np.int32)
+    c = np.ascontiguousarray(coo_cols, dtype=np.int32)
+    v = np.ascontiguousarray(coo_values, dtype=np.float32)
+    p = C.c_void_p()
+    cnt = (C.c_int64 * 8)()
+    rc = lib.hispmv_prep_value_layouts(C.byref(p), C.c_void_p(r.ctypes.data), C.c_void_p(c.ctypes.data), C.c_void_p(v.ctypes.data), r.size,
+                                       int(rows), int(cols), int(n_cus), cnt)
+    if rc != HISPMV_OK:
+        raise ValueError(lib.hispmv_prep_last_error().decode())
+    try:
+        d = dict(zip(VALUE_LAYOUT_FIELDS, (int(x) for x in cnt)))
+
+        def arr(which, n, dt):
+            ptr = lib.hispmv_prep_value_array(p, which)
+            return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy() if (n and ptr) else np.zeros(0, dt)
+        d.update(real=arr(0, d["bytes"], np.uint8), index=arr(1, d["bytes"], np.uint8), map=arr(2, d["map_slots"], np.int32),
+                 chunks=arr(3, 2 * d["chunks"], np.int64).reshape(-1, 2))
+        return d
+    finally:
+        lib.hispmv_prep_free(p)

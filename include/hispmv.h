@@ -130,6 +130,29 @@ int hispmv_batch_call_info(hispmv_ctx* ctx, int64_t out[4]);
  * bit from hispmv_spmv_device on a matrix whose single launch uses the look-back variant.  Asynchronous on `stream`. */
 int hispmv_spmv_device_batch(hispmv_ctx* ctx, int32_t n, const int32_t* idx, const float* const* d_x,
                              const float* const* d_bias, float* const* d_y, float alpha, float beta, void* stream);
+/* One call of a signature in flight at a time: the step kernel's queue state belongs to the cached plan of a call signature
+ * (handles, vectors, beta), so the same signature must not run on two streams at once, nor from a caller-captured graph replayed
+ * concurrently.  Value updates (below) follow the same ordering rule: they are ordered on their stream only. */
+
+/* ---- in-place value updates (no reference counterpart; MKL mkl_sparse_?_update_values, hipSPARSE SpMatSetValues) ------------
+ * A handle keeps its sparsity pattern, plan and device addresses; only its values change, in place: cached batch plans, step-kernel
+ * queues and captured graphs stay valid.  Context-wide switch, default off: sparse and dense handles created while it is on carry
+ * a VALUE MAP (4 bytes per value slot of their device layouts, charged to the arena: HISPMV_FULL covers it); handles created
+ * while it is off are exactly as before.  Values come in the order of the creation input: the COO arrays of
+ * hispmv_create_sparse_handle (duplicates included), col_idx / values of _from_csr BEFORE its per-row sort, W row-major for a
+ * dense handle.  hispmv_create_sparse_handle_from_mtx refuses (HISPMV_EINVAL) while the switch is on: its reader drops zeros and
+ * mirrors symmetric entries.  So do the tile-stream experiments HISPMV_TTS_GEOMETRY (other than standard) and HISPMV_TTS_SMALL. */
+int hispmv_set_value_updates(hispmv_ctx* ctx, int enable);
+/* n = the number of values of the creation input.  HISPMV_ESTATE: the handle is not updatable or not loaded; HISPMV_EINVAL: wrong
+ * n, NULL values, bad index.  Host values: returns when the device layout holds them (pinned staging, one copy, one launch). */
+int hispmv_update_values(hispmv_ctx* ctx, int matrix_idx, const float* values, int64_t n);
+/* Device values: asynchronous and ordered on `stream` (NULL = the context's stream, as for hispmv_spmv_device): a later SpMV on the
+ * same stream sees the new values.  Ordering against work on OTHER streams (an SpMV still reading the old values, the producer of
+ * d_values) is the caller's job. */
+int hispmv_update_values_device(hispmv_ctx* ctx, int matrix_idx, const float* d_values, int64_t n, void* stream);
+/* out = {1 if the handle is updatable, n an update takes, map slots, slots written per update (more than the map slots where a
+ * batch layout holds a second copy of the slices)}; zeros for a handle that is not updatable. */
+int hispmv_value_update_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
 
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */
@@ -259,6 +282,16 @@ const void* hispmv_prep_device_array(const hispmv_prep* p, int which);
  * NULL when counts[4] == 0).  For tests (device == host, byte for byte); HISPMV_EDEVICE without a GPU. */
 int hispmv_prep_device_stream_on_device(hispmv_prep* p, int device_id, uint8_t* bytes_out, uint32_t* stray_cols_out);
 const int32_t* hispmv_prep_frags(const hispmv_prep* p);
+
+/* Every device layout of the handle hispmv_create_sparse_handle makes from this COO input on a device with n_cus CUs (the parts'
+ * slice layouts, each followed by its batch layout if any, or the tile streams' words), packed twice by the same host path: with the
+ * real values and -- as for a handle created with value updates on -- with the index payloads bits(k + 1) of the input positions.
+ * counts = {layout bytes, map slots, chunks, slots an update writes, format, tile kind, parts, batch layouts}; arrays of
+ * hispmv_prep_value_array: 0 real layouts, 1 payload layouts, 2 the map read out of 1 (int32; 0 = filler / padding), 3 per chunk of
+ * 1024 map slots the byte offsets {first destination, second destination or -1} (int64 x 2).  For tests, no device needed. */
+int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* coo_rows, const int32_t* coo_cols, const float* coo_values, int64_t nnz,
+                              int32_t rows, int32_t cols, int n_cus, int64_t counts[8]);
+const void* hispmv_prep_value_array(const hispmv_prep* p, int which);
 
 /* Number of device / pinned-memory frees the runtime rejected since the library was loaded (a pointer released twice
  * or never allocated); 0 in a correct run.  For tests. */
