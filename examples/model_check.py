@@ -5,7 +5,10 @@ batch 1, every layer called rp_time=100 times through `FpgaHandle.linear` with R
 (model.py:68-80), weights seeded with torch.manual_seed(0).  The reference compares against torch /
 sparse_dot_mkl and prints error histograms; here the comparison is against an fp64 evaluation.
 
-    python examples/model_check.py [--batch_size 1 --rp_time 100]
+    python examples/model_check.py [--batch_size 1 --rp_time 100] [--bf16]
+
+--bf16: the weights are stored as bfloat16 (FpgaHandle.set_value_storage("bf16"): rounded once at creation, fp32 accumulation); the
+fp64 truth is then computed from the rounded weights and the 1e-5 verdict stays.
 """
 import argparse
 import os
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--density1", type=float, default=0.1)
     ap.add_argument("--density2", type=float, default=0.25)
     ap.add_argument("--rp_time", type=int, default=100)
+    ap.add_argument("--bf16", action="store_true", help="store the weights as bfloat16 (bf16 value storage)")
     a = ap.parse_args()
     torch.manual_seed(0)
     fpga = FpgaHandle("builds/Dense-HI-SpMV-24-1-1/SpMV.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
@@ -43,6 +47,8 @@ def main():
         sw = sparse_weight(out_f, in_f, dens)
         layers.append(("sparse", sw, np.zeros(out_f, np.float32)))
     handles = []
+    if a.bf16:
+        fpga.set_value_storage("bf16")
     t = time.time()
     for kind, w, b in layers:                                      # fpga_layer_manager.py:15-52
         if kind == "sparse":
@@ -66,7 +72,10 @@ def main():
             y = fpga.linear(idx, h.reshape(-1), b)
         dt = (time.time() - t) / a.rp_time
         y = y.reshape(a.batch_size, -1)
-        wd = (w.to_dense().numpy() if kind == "sparse" else w).astype(np.float64)
+        wd = w.to_dense().numpy() if kind == "sparse" else w
+        if a.bf16:                                                  # what the handle holds: every weight rounded once
+            wd = torch.from_numpy(np.ascontiguousarray(wd, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
+        wd = wd.astype(np.float64)
         y64 = h.astype(np.float64) @ wd.T + b
         mag = np.abs(h.astype(np.float64)) @ np.abs(wd.T) + np.abs(b)
         err = float(np.max(np.abs(y - y64) / mag))

@@ -22,6 +22,10 @@ HISPMV_ENOTDENSE = -5
 HISPMV_EIO = -6
 HISPMV_ENOMEM = -7
 
+HISPMV_VALUES_FP32 = 0
+HISPMV_VALUES_BF16 = 1
+VALUE_STORAGES = {"fp32": HISPMV_VALUES_FP32, "bf16": HISPMV_VALUES_BF16}
+
 
 class MatrixInfo(C.Structure):
     _fields_ = [
@@ -76,6 +80,9 @@ SIGNATURES = {
     "hispmv_update_values": (C.c_int, [_p, C.c_int, _p, C.c_int64]),
     "hispmv_update_values_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p]),
     "hispmv_value_update_info": (C.c_int, [_p, C.c_int, _i64p]),
+    "hispmv_set_value_storage": (C.c_int, [_p, C.c_int]),
+    "hispmv_value_storage_info": (C.c_int, [_p, C.c_int, _i64p]),
+    "hispmv_prep_set_value_storage": (C.c_int, [_p, C.c_int]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),
     "hispmv_num_matrices": (C.c_int, [_p]),

@@ -83,6 +83,22 @@ int check_updatable(hispmv_ctx* c, int64_t nnz) {
     return HISPMV_OK;
 }
 
+// bf16 value storage (include/hispmv.h: hispmv_set_value_storage): R over n values, once, before any packer sees them.
+void round_values_to_bf16(const float* in, float* out, int64_t n) {
+#pragma omp parallel for num_threads(host_threads()) schedule(static)
+    for (int64_t k = 0; k < n; ++k) {
+        uint32_t u;
+        std::memcpy(&u, in + k, 4);
+        u = round_bits_to_bf16(u);
+        std::memcpy(out + k, &u, 4);
+    }
+}
+int check_storage_and_updates(hispmv_ctx* c) {
+    if (c->value_storage == HISPMV_VALUES_BF16 && c->value_updates)
+        return fail(c, HISPMV_EINVAL, "bf16 value storage and value updates are both on: the value map lives in 32-bit value slots (create the handle with one of the two switched off)");
+    return HISPMV_OK;
+}
+
 // Registers a prepared sparse matrix with the context (capacity check = the reference's
 // "offset + size > MAX_BUFFER_SIZE_BYTES -> return -1", fpga_handle.cpp:192-195).  The format and tiling decision itself is
 // host-only code: choose_format (hispmv_choose.cpp).
@@ -102,7 +118,10 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
                             c->last_prep_times.stream_device * 1e3, c->last_prep_times.download * 1e3);
     auto m = std::make_unique<Matrix>();
     m->rows = csr.rows; m->cols = csr.cols; m->nnz = csr.nnz();
-    FormatChoice ch = choose_format(std::move(csr), prebuilt, c->n_cus, c->format_opts, lap);
+    FormatOptions opts = c->format_opts;
+    opts.half_values = c->value_storage == HISPMV_VALUES_BF16;      // (the values are rounded already: add_from_coo, _from_csr)
+    m->value_storage = c->value_storage;
+    FormatChoice ch = choose_format(std::move(csr), prebuilt, c->n_cus, opts, lap);
     m->format = ch.format; m->tile_kind = ch.tile_kind; m->col_tile_width = ch.col_tile_width; m->col_tile_base = ch.col_tile_base;
     m->l2_tiles = ch.l2_tiles; m->tts_lines_per_gather = ch.tts_lines_per_gather;
     for (HostPart& hp : ch.parts) {
@@ -113,10 +132,19 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
         if (p.is_tts) {
             m->n_slices += (int64_t)p.tts.col_base.size(); m->n_elems += p.tts.nnz + p.tts.n_fillers; m->n_split += (int64_t)p.tts.fix.size() / 4;
             m->device_bytes += p.tts.bytes();
+            m->slots_4byte += (int64_t)p.tts.words.size() / 8;
         } else {
             m->n_slices += p.st.n_slices; m->n_elems += p.st.n_elems; m->n_split += (int64_t)p.st.fix.size();
             m->device_bytes += sparse_device_bytes(p.st, p.dstream) + (int64_t)p.dstream.groups.size() * 4 + (int64_t)p.plan.frags.size() * 16 + (p.dstream.any_stray ? p.st.n_slices * (int64_t)kStraySlots * 4 : 0);
             m->compact_slices += p.dstream.compact_slices;
+            // value slots by size: the slices of half groups hold bf16 values and are kSliceUnit bytes shorter than compact ones
+            for (const DeviceStream* ds : {&p.dstream, p.has_batch_layout ? &p.batch_dstream : nullptr}) {
+                if (!ds) continue;
+                const int64_t half = ds->half_values ? ds->compact_slices : 0;
+                m->slots_2byte += half * kSliceElems;
+                m->slots_4byte += (p.st.n_slices - half) * kSliceElems;
+                m->saved_bytes += half * (kCompactSliceBytes - kHalfSliceBytes);
+            }
             if (p.has_batch_layout) m->device_bytes += p.batch_dstream.n_bytes + (int64_t)p.st.hdr.size() * 16 + (int64_t)p.batch_dstream.groups.size() * 4 + (int64_t)p.batch_plan.frags.size() * 16 +
                                                        (p.batch_dstream.any_stray ? p.st.n_slices * (int64_t)kStraySlots * 4 : 0);
         }
@@ -211,7 +239,7 @@ int launch_matrix(hispmv_ctx* c, Matrix& m, const float* d_x, const float* d_bia
         return spmv_batch_locked(c, 1, &idx, &d_x, &d_bias, &d_y, alpha, beta, s);
     }
     if (m.dense) {
-        hipError_t e = launch_gemv(m.d_dense, m.rows, m.cols, d_x, d_bias, d_y, alpha, beta, s);
+        hipError_t e = launch_gemv(m.d_dense, m.rows, m.cols, d_x, d_bias, d_y, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
         if (e != hipSuccess) return hip_fail(c, e, "launch_gemv");
         return HISPMV_OK;
     }
@@ -240,7 +268,7 @@ int launch_matrix_vectors(hispmv_ctx* c, Matrix& m, int64_t vecs, const float* d
     // (`linear` always takes the fix-up carry variant: one vector or many, every vector gets the same bits)
     if (vecs == 1) return launch_matrix(c, m, d_x, d_bias, d_y, alpha, beta, s, fixup_only);
     if (m.dense) {
-        hipError_t e = launch_gemv_batched(m.d_dense, m.rows, m.cols, vecs, d_x, d_bias, d_y, alpha, beta, s);
+        hipError_t e = launch_gemv_batched(m.d_dense, m.rows, m.cols, vecs, d_x, d_bias, d_y, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
         if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_batched");
         return HISPMV_OK;
     }
@@ -431,7 +459,16 @@ HISPMV_API int64_t hispmv_arena_bytes_used(const hispmv_ctx* c) { return c ? c->
 static int add_from_coo(hispmv_ctx* c, int32_t rows, int32_t cols, int64_t nnz, const int32_t* r, const int32_t* cl, const float* v) {
     auto t0 = std::chrono::steady_clock::now();
     const bool on_device = c->prep_mode == 1 || (c->prep_mode == 2 && nnz >= (2 << 20));
-    std::vector<float> real, payloads;
+    std::vector<float> real, payloads, rounded;
+    {
+        const int rc = check_storage_and_updates(c);
+        if (rc != HISPMV_OK) return rc;
+    }
+    if (c->value_storage == HISPMV_VALUES_BF16) {      // rounded once, here: the host and the device preprocessor see R(v)
+        rounded.resize((size_t)nnz);
+        round_values_to_bf16(v, rounded.data(), nnz);
+        v = rounded.data();
+    }
     if (c->value_updates) {
         const int rc = check_updatable(c, nnz);
         if (rc != HISPMV_OK) return rc;
@@ -498,6 +535,10 @@ HISPMV_API int hispmv_create_sparse_handle_from_csr(hispmv_ctx* c, const int32_t
         for (int32_t i = 0; i < rows; ++i) if (rp[i + 1] < rp[i]) return fail(c, HISPMV_EINVAL, "row_ptr must be non-decreasing");
         if (nnz > 0 && (!ci || !va)) return fail(c, HISPMV_EINVAL, "col_idx / values are NULL");
         std::vector<float> real;
+        {
+            const int rc = check_storage_and_updates(c);
+            if (rc != HISPMV_OK) return rc;
+        }
         if (c->value_updates) {
             const int rc = check_updatable(c, nnz);
             if (rc != HISPMV_OK) return rc;
@@ -505,6 +546,7 @@ HISPMV_API int hispmv_create_sparse_handle_from_csr(hispmv_ctx* c, const int32_t
         csr.col.assign(ci, ci + nnz);
         if (c->value_updates) { real.assign(va, va + nnz); const std::vector<float> pl = index_payloads(nnz); csr.val.assign(pl.begin(), pl.end()); }   // input order: before the per-row sort
         else csr.val.assign(va, va + nnz);
+        if (c->value_storage == HISPMV_VALUES_BF16) round_values_to_bf16(csr.val.data(), csr.val.data(), nnz);
         for (int64_t k = 0; k < nnz; ++k) if (ci[k] < 0 || ci[k] >= cols) return fail(c, HISPMV_EINVAL, "CSR column outside matrix");
         sort_rows_by_column(csr);     // rows with unsorted columns (scipy: has_sorted_indices == False) are sorted, stably
         double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -523,8 +565,25 @@ HISPMV_API int hispmv_create_dense_handle(hispmv_ctx* c, const float* vals, int3
         auto t0 = std::chrono::steady_clock::now();
         auto m = std::make_unique<Matrix>();
         m->dense = true; m->rows = rows; m->cols = cols; m->nnz = (int64_t)rows * cols;   // spmv-helper.cpp:722
-        m->device_bytes = m->nnz * 4;
+        {
+            const int rc = check_storage_and_updates(c);
+            if (rc != HISPMV_OK) return rc;
+        }
+        m->value_storage = c->value_storage;
+        const bool bf16 = m->value_storage == HISPMV_VALUES_BF16;
+        m->device_bytes = m->nnz * (bf16 ? 2 : 4);
+        (bf16 ? m->slots_2byte : m->slots_4byte) = m->nnz;
+        m->saved_bytes = bf16 ? m->nnz * 2 : 0;
         if (c->arena_used + m->device_bytes > c->arena_budget) return HISPMV_FULL;
+        if (bf16) {           // W row-major as bf16: the upper halves of R(w)
+            m->dense_host16.resize((size_t)m->nnz);
+#pragma omp parallel for num_threads(host_threads()) schedule(static)
+            for (int64_t k = 0; k < m->nnz; ++k) {
+                uint32_t u;
+                std::memcpy(&u, vals + k, 4);
+                m->dense_host16[(size_t)k] = (uint16_t)(round_bits_to_bf16(u) >> 16);
+            }
+        } else
         m->dense_host.assign(vals, vals + m->nnz);
         if (c->value_updates) { m->updatable = true; m->upd_n = m->nnz; m->upd_written = m->nnz; }    // an update is a copy into d_dense
         m->prep_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -554,7 +613,11 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                 value_regions.push_back(value_chunks(p));
                 layout_bytes.emplace_back(p.is_tts ? (int64_t)p.tts.words.size() : p.dstream.n_bytes, p.has_batch_layout ? p.batch_dstream.n_bytes : 0);
             }
-        if (m.dense) {
+        if (m.dense && m.value_storage == HISPMV_VALUES_BF16) {
+            const uint16_t* d = nullptr;
+            if ((rc = upload(c, m, m.dense_host16.data(), m.dense_host16.size(), &d)) != HISPMV_OK) return rc;
+            m.d_dense = (float*)const_cast<uint16_t*>(d);      // (rows x cols bf16: every launch of this handle passes its storage along)
+        } else if (m.dense) {
             const float* d = nullptr;
             if ((rc = upload(c, m, m.dense_host.data(), m.dense_host.size(), &d)) != HISPMV_OK) return rc;
             m.d_dense = const_cast<float*>(d);
@@ -717,6 +780,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                 // stray slots: the packer placed every slice's strays by the slice's position in the ROTATED walk of the fix-up
                 // variant; the look-back variant walks its groups in slice order
                 d.has_strays = p.dstream.stray_floats > 0;
+                d.has_half = p.dstream.half_values && p.dstream.compact_slices > 0;
                 if (d.has_strays) { d.lookback = false; d.use_ticket = false; }
                 // the batch layout (hispmv_choose.h): its own group table, fragments, slice bytes and headers (the spill flags differ);
                 // rows, carries, fix lists and the error word are the part's
@@ -756,6 +820,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                     b.group_slices = p.batch_plan.group_slices; b.n_groups = (ns + p.batch_plan.group_slices - 1) / p.batch_plan.group_slices;
                     b.lds_floats = p.batch_plan.lds_floats + p.batch_dstream.stray_floats;
                     b.has_strays = p.batch_dstream.stray_floats > 0;
+                    b.has_half = p.batch_dstream.half_values && p.batch_dstream.compact_slices > 0;
                     b.lookback = false; b.use_ticket = false;
                     if ((size_t)(b.lds_floats + b.ytile_floats * (b.block_threads / 64)) * 4 <= 160 * 1024 - 256) { p.batch_dev = b; p.has_batch_dev = true; }
                 }
@@ -788,6 +853,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
         for (auto& p : m.parts) { p.st = SliceStream{}; p.fix_short = {}; p.fix_long = {}; p.plan.groups = {}; p.plan.frags = {}; p.dstream = DeviceStream{};
                                   p.batch_plan.groups = {}; p.batch_plan.frags = {}; p.batch_plan.slice_spills = {}; p.batch_dstream = DeviceStream{}; p.batch_words = WordVec(); }
         m.dense_host = {};
+        m.dense_host16 = {};
         m.loaded = true;
     }
     return HISPMV_OK;
@@ -936,6 +1002,21 @@ HISPMV_API int hispmv_get_matrix_info(const hispmv_ctx* c, int idx, hispmv_matri
     out->batch_group_slices = 0;
     if (m.parts.size() == 1 && !m.parts[0].is_tts)
         out->batch_group_slices = m.loaded ? (m.parts[0].has_batch_dev ? m.parts[0].batch_dev.group_slices : 0) : (m.parts[0].has_batch_layout ? m.parts[0].batch_plan.group_slices : 0);
+    return HISPMV_OK;
+}
+
+// ---- bf16 value storage (include/hispmv.h: hispmv_set_value_storage) ----------------------------------------------------------
+HISPMV_API int hispmv_set_value_storage(hispmv_ctx* c, int storage) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (storage != HISPMV_VALUES_FP32 && storage != HISPMV_VALUES_BF16) return fail(c, HISPMV_EINVAL, "unknown value storage (HISPMV_VALUES_FP32 or HISPMV_VALUES_BF16)");
+    c->value_storage = storage;
+    return HISPMV_OK;
+}
+HISPMV_API int hispmv_value_storage_info(const hispmv_ctx* c, int idx, int64_t out[4]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
+    const Matrix& m = *c->mats[(size_t)idx];
+    out[0] = m.value_storage; out[1] = m.slots_2byte; out[2] = m.slots_4byte; out[3] = m.saved_bytes;
     return HISPMV_OK;
 }
 

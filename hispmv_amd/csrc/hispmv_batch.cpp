@@ -84,7 +84,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
             for (size_t k = k0; k < std::min(dense.size(), k0 + (size_t)kMultiMax); ++k) {
                 const int i = dense[k];
                 const Matrix& m = *c->mats[idx[i]];
-                l.gemv.push_back(GemvEntry{m.d_dense, d_x[i], bias[i], d_y[i], m.rows, m.cols, beta, 0});
+                l.gemv.push_back(GemvEntry{m.d_dense, d_x[i], bias[i], d_y[i], m.rows, m.cols, beta, m.value_storage == HISPMV_VALUES_BF16 ? 1 : 0});
             }
             plan.launches.push_back(std::move(l));
             const int rc0 = upload_table0(plan.launches.back(), plan.launches.back().gemv.data(), plan.launches.back().gemv.size() * sizeof(GemvEntry));
@@ -224,6 +224,10 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                     const size_t one = ((size_t)d->lds_floats + (size_t)d->ytile_floats * (d->block_threads / 64)) * sizeof(float);
                     lds = std::max(lds, d->block_threads == 256 ? 4 * one : one);
                     strays = strays || d->has_strays;
+                    // a handle with half groups (bf16 value storage): the step kernel has no instantiation that reads them -- the call
+                    // runs as separate grids (what HISPMV_STEP_KERNEL=0 does; DESIGN.md 2.6: the candidate instantiation compiles to 128 VGPRs without
+                    // scratch, but was not measured)
+                    ok = ok && !d->has_half;
                 }
             }
             if (l.kind == 3) {
@@ -359,7 +363,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
         for (auto& l : plan.launches) {
             if (l.kind == 0) for (const SpmvDeviceMatrix* d : l.parts) l.weight += d->n_slices * (int64_t)kWideSliceBytes;
             // (a tile stream runs at ~2.5 TB/s against ~6.5 for a slice stream: its bytes count 2.5-fold; set when the entries were made)
-            if (l.kind == 4) for (const GemvEntry& e : l.gemv) l.weight += 4 * (int64_t)e.rows * e.cols;
+            if (l.kind == 4) for (const GemvEntry& e : l.gemv) l.weight += (e.bf16 ? 2 : 4) * (int64_t)e.rows * e.cols;
             mains.push_back(&l);
         }
         plan.lanes = std::max(1, std::min<int>(plan.lanes, (int)mains.size()));

@@ -113,8 +113,8 @@ void plan_part(HostPart& p, int n_cus) {
 }
 void pack_part(HostPart& p, const FormatOptions& opt) {
     if (opt.decide_only) return;
-    p.dstream = pack_device_stream(p.st, p.plan, !opt.device_layout);
-    if (!opt.device_layout) p.st.words = WordVec();   // the device layout replaces the host words (else the loader uploads them and lays them out there)
+    p.dstream = pack_device_stream(p.st, p.plan, !opt.device_layout, opt.half_values);
+    if (!opt.device_layout || opt.half_values) p.st.words = WordVec();   // the device layout replaces the host words (else the loader uploads them and lays them out there)
 }
 void finish_part(HostPart& p, int n_cus, const FormatOptions& opt) { plan_part(p, n_cus); pack_part(p, opt); }
 
@@ -137,8 +137,8 @@ void add_batch_layout(HostPart& p, int n_cus, const FormatOptions& opt) {
         if (!found) alt.words = unplanned_words(p.st, p.plan);      // (make_plan rewrote the column fields of the words it staged)
     }
     if (!found) return;
-    p.batch_dstream = pack_device_stream(alt, q, !opt.device_layout);
-    if (opt.device_layout) p.batch_words = std::move(alt.words);
+    p.batch_dstream = pack_device_stream(alt, q, !opt.device_layout, opt.half_values);
+    if (opt.device_layout && !opt.half_values) p.batch_words = std::move(alt.words);
     p.batch_plan = std::move(q);
     p.has_batch_layout = true;
 }

@@ -61,6 +61,8 @@ struct FormatOptions {
     bool batch_plan_search = false;   // HISPMV_BATCH_PLAN_SEARCH=1: the batch layout's plan from all six planner configurations (as until the end of round 4) instead of the resident one alone
     int64_t batch_min_slices = 512;   // HISPMV_BATCH_MIN_SLICES: matrices with fewer slices keep their first layout (many short items: the filler at the end of the step kernel's queue)
     int batch_group_below = kBatchGroupBelow;     // HISPMV_BATCH_GROUP_BELOW (experiments): resident groups shorter than this get the batch layout
+    bool half_values = false;     // bf16 value storage (hispmv_set_value_storage; not an environment switch): the compact groups of every slice layout are packed
+                                  //   as half slices, on the host whatever device_layout says.  The values are already rounded; plans and choices do not look at it
     bool decide_only = false;     // skip the device layouts the decision does not need (tests: the choice, not the bytes)
     static FormatOptions from_env();
 };

@@ -75,6 +75,12 @@ struct Matrix {
     std::vector<float> upd_values;          // the creation input's values, until the load has written them
     int32_t* d_map = nullptr;
     ValueChunkDev* d_upd_table = nullptr;
+    // bf16 value storage (hispmv_set_value_storage at creation): the values were rounded once (hispmv_format.h: round_bits_to_bf16); the
+    // compact groups of the slice layouts are half slices, a dense W is rows x cols bf16 (d_dense then points at uint16_t)
+    int value_storage = HISPMV_VALUES_FP32;
+    int64_t slots_2byte = 0, slots_4byte = 0;   // value slots of the device layouts by size (a batch layout's slices counted again)
+    int64_t saved_bytes = 0;                    // device bytes less than the same handle with fp32 storage
+    std::vector<uint16_t> dense_host16;
     std::vector<void*> allocs;
 };
 
@@ -124,6 +130,7 @@ struct hispmv_ctx {
     // value updates: the switch handles are created under (hispmv_set_value_updates), the pinned staging block and the device
     // buffer of hispmv_update_values (host values) and of the load's first update
     bool value_updates = false;
+    int value_storage = HISPMV_VALUES_FP32;     // hispmv_set_value_storage: what handles created from now on store their values as
     float* h_upd = nullptr;
     int64_t cap_h_upd = 0;
     float* d_upd = nullptr;
@@ -200,6 +207,7 @@ struct hispmv_prep {
     hispmv::SliceStream st;
     hispmv::LaunchPlan plan;
     hispmv::TtsStream tts;
+    bool half_values = false;         // hispmv_prep_set_value_storage(bf16): values rounded in place, compact groups packed as half slices
     hispmv::DeviceStream dstream;     // hispmv_prep_device_stream: the planned stream in its device layout
     // hispmv_prep_value_layouts: every device layout of a handle packed with the real values and with the index payloads, the map
     // read out of the latter and the chunks' byte offsets {first destination, second or -1}

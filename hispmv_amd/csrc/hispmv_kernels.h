@@ -11,7 +11,7 @@ struct SpmvDeviceMatrix {
     const int4* hdr = nullptr;          // n_slices x {row_base, chain_len, rows ending in the slice, 1 if elements lie outside the x window}
     const int4* fix_short = nullptr;    // {row, first_slice, len, 0}, len <= kFixShortMax
     const int4* fix_long = nullptr;     // same, len > kFixShortMax
-    const int4* groups = nullptr;       // n_groups x {frag_begin, frag_count, offset of the group's first slice / kSliceUnit, 1 = compact}
+    const int4* groups = nullptr;       // n_groups x {frag_begin, frag_count, offset of the group's first slice / kSliceUnit, 1 = compact | 2 = stray slots | 4 = half}
     const int4* frags = nullptr;        // {col_start, len, lds_off, 0}
     float* carry = nullptr;             // n_slices: partial sum each slice hands to the next
     int64_t n_groups = 0;
@@ -19,6 +19,7 @@ struct SpmvDeviceMatrix {
     int32_t block_threads = 256;        // workgroup size (64 * wavefronts)
     int32_t lds_floats = 0;             // dynamic LDS (floats) for the x window (+ the wavefronts' stray areas behind it); 0 = gather x from L2
     bool has_strays = false;            // some groups use stray slots (hispmv_plan.h): the columns of every slice's strays follow the headers
+    bool has_half = false;              // some groups are HALF (bf16 values, hispmv_format.h): launches take the kernels that read them
     int32_t ytile_floats = 1024;        // LDS floats per wavefront for the row totals of one slice (>= max rows ending in a slice)
     // single-launch carry hand-off between slices (look-back); when false the fix-up kernels run instead
     bool lookback = true;
@@ -62,9 +63,9 @@ struct TtsEntry {                       // multi-matrix launch: one per matrix
 };
 
 struct GemvEntry {                      // multi-matrix launch of the dense overlay: one per matrix
-    const float* W; const float* x; const float* bias; float* y;
+    const float* W; const float* x; const float* bias; float* y;      // bf16 != 0: W points at rows x cols bfloat16
     int32_t rows, cols;
-    float beta; int32_t pad;
+    float beta; int32_t bf16;
 };
 
 struct LookbackArgs {
@@ -176,14 +177,15 @@ hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_t
 size_t tts_tile_lds_bytes(const TtsDeviceMatrix& m);
 
 // Dense overlay: y = alpha*W*x + beta*bias, W row-major rows x cols.
+// bf16: W is rows x cols bfloat16 (bf16 value storage): fp32 x, products and sums; 16-byte loads of W when cols % 8 == 0.
 hipError_t launch_gemv(const float* W, int32_t rows, int32_t cols, const float* x, const float* bias,
-                       float* y, float alpha, float beta, hipStream_t stream);
+                       float* y, float alpha, float beta, hipStream_t stream, bool bf16 = false);
 // the row blocks of `n` (<= kMultiMax) dense matrices in one grid (d_table: device copy of the entries); per matrix
-// bitwise equal to launch_gemv
+// bitwise equal to launch_gemv (entries with bf16 storage ride in the same grid: the launch then takes the kernel that knows both)
 hipError_t launch_gemv_multi(const GemvEntry* entries, int n, const GemvEntry* d_table, float alpha, hipStream_t stream);
 // `vecs` vectors (x + v*cols -> y + v*rows, shared bias), 8/4/2/1 per pass over W; per vector bitwise equal to launch_gemv.
 hipError_t launch_gemv_batched(const float* W, int32_t rows, int32_t cols, int64_t vecs, const float* x, const float* bias,
-                               float* y, float alpha, float beta, hipStream_t stream);
+                               float* y, float alpha, float beta, hipStream_t stream, bool bf16 = false);
 
 // Patches alpha into every kernel node of an instantiated batch-call graph (`graph`: the captured graph it came from).
 hipError_t graph_set_alpha(hipGraphExec_t exec, hipGraph_t graph, float alpha);

@@ -217,11 +217,18 @@ __device__ __forceinline__ int2 load_int2(const int2* p) {
 }
 
 // A slice as it arrives: per step 4 values and 4 metas per lane (compact: 4 x u16 in a uint2; wide: 4 x u32).
-template <bool COMPACT> struct SliceRaw;
+// HALF (bf16 value storage, hispmv_format.h): per step ONE 16-byte piece per lane, {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16}.
+template <bool COMPACT, bool HALF = false> struct SliceRaw;
 template <> struct SliceRaw<true>  { uint4 v[kSliceSteps]; uint2 m[kSliceSteps]; };
 template <> struct SliceRaw<false> { uint4 v[kSliceSteps]; uint4 m[kSliceSteps]; };
-template <bool COMPACT>
-__device__ __forceinline__ void request_slice(SliceRaw<COMPACT>& s, const char* base, int lane) {
+template <> struct SliceRaw<true, true> { uint4 q[kSliceSteps]; };
+template <bool COMPACT, bool HALF = false>
+__device__ __forceinline__ void request_slice(SliceRaw<COMPACT, HALF>& s, const char* base, int lane) {
+    if constexpr (HALF) {
+        const uint4* pq = (const uint4*)base + lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.q[j] = load_words(pq + j * 64);
+    } else {
     const uint4* pv = (const uint4*)base + lane;
 #pragma unroll
     for (int j = 0; j < kSliceSteps; ++j) s.v[j] = load_words(pv + j * 64);
@@ -234,14 +241,26 @@ __device__ __forceinline__ void request_slice(SliceRaw<COMPACT>& s, const char* 
 #pragma unroll
         for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
     }
+    }
+}
+// the fp32 bits of the four values of step j: as stored, or -- half slice -- the bf16 halves of a dword widened (one VALU operation each)
+template <bool COMPACT, bool HALF>
+__device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, int j, float (&v)[kLaneElems]) {
+    if constexpr (HALF) {
+        v[0] = i2f((int)(s.q[j].x << 16)); v[1] = i2f((int)(s.q[j].x & 0xffff0000u));
+        v[2] = i2f((int)(s.q[j].y << 16)); v[3] = i2f((int)(s.q[j].y & 0xffff0000u));
+    } else {
+        v[0] = i2f((int)s.v[j].x); v[1] = i2f((int)s.v[j].y); v[2] = i2f((int)s.v[j].z); v[3] = i2f((int)s.v[j].w);
+    }
 }
 // -> metas in wide form (rowEnd<<31 | window index or column), c[4*j + k] = element k of the lane in step j
-template <bool COMPACT>
-__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
+template <bool COMPACT, bool HALF = false>
+__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
     if constexpr (COMPACT) {
 #pragma unroll
         for (int j = 0; j < kSliceSteps; ++j) {
-            const unsigned a = s.m[j].x, b = s.m[j].y;
+            unsigned a, b;
+            if constexpr (HALF) { a = s.q[j].z; b = s.q[j].w; } else { a = s.m[j].x; b = s.m[j].y; }
             c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
             c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
             c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
@@ -339,7 +358,9 @@ struct SubBlock {
 
 // The work of one workgroup on group `group` of a matrix (the body of the slice kernels below), for a group stored
 // COMPACT (6 B per element) or wide (8 B): two instantiations, chosen per group by slices_body.
-template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool COMPACT, bool STRAYS = false>
+// HALF (with COMPACT): the compact slice with bf16 values, 4 B per element (hispmv_format.h) -- like STRAYS a template parameter that
+// only the instantiations of launches with such a group carry (spmv_slices_half_kernel and its siblings below).
+template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool COMPACT, bool STRAYS = false, bool HALF = false>
 __device__ __forceinline__ void slices_group(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
     const int4* __restrict__ frags,
@@ -368,7 +389,7 @@ __device__ __forceinline__ void slices_group(
     const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;   // exclusive
     // where the group's slices lie in the stream: the group table says so for staged plans; a plan without windows is
     // all wide, slice after slice
-    constexpr int slice_bytes = COMPACT ? kCompactSliceBytes : kWideSliceBytes;
+    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
     const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit
                                                 : (size_t)first * kWideSliceBytes);
 
@@ -383,7 +404,7 @@ __device__ __forceinline__ void slices_group(
     const int rot = (LOOKBACK || n_here == 0) ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
     int k_slice = wave;                                         // position in the group's rotated order
     int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
-    SliceRaw<COMPACT> w;
+    SliceRaw<COMPACT, HALF> w;
     int4 h = int4{0, 0, 0, 0};
     // STRAY SLOTS (hispmv_plan.h): a compact group whose slices have a few elements outside the window.  The columns of a slice's
     // strays (<= 64, one per lane, 0xffffffff = none) live behind the headers; their x values are gathered ONE SLICE AHEAD and
@@ -410,7 +431,7 @@ __device__ __forceinline__ void slices_group(
         // once -- a write-after-write hazard with the load in flight, and waiting for the YOUNGEST load waits for the
         // whole prefetch: s_waitcnt vmcnt(0) right behind the request, seen in the compact loop)
         h = load_int4(hdr + first + local);
-        request_slice<COMPACT>(w, gbase + (size_t)local * slice_bytes, lane);
+        request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
     }
 
     if (LOOKBACK) {
@@ -458,7 +479,7 @@ __device__ __forceinline__ void slices_group(
         // Compute_C operand: the slice's rows are consecutive, so bias is read with coalesced loads that leave
         // together with the x gathers (first 128 rows here, the rest in the epilogue loop).
         unsigned c[kE];
-        decode_metas<COMPACT>(w, c);
+        decode_metas<COMPACT, HALF>(w, c);
         if (!LOOKBACK) {
             asm volatile("" : "+v"(c[0]), "+v"(c[kE - 1]) :: "memory");      // behind the wait for this slice
             __builtin_amdgcn_raw_buffer_store_b32((unsigned)f2i(HAS_BETA ? alpha * out_t0 + beta * out_b0 : alpha * out_t0), ry, out_d0, 0, 0);
@@ -525,10 +546,17 @@ __device__ __forceinline__ void slices_group(
         float p[kE];
 #pragma unroll
         for (int j = 0; j < kSliceSteps; ++j) {
+            if constexpr (HALF) {
+                float vj[kLaneElems];
+                slice_values(w, j, vj);
+                p[4 * j + 0] = vj[0] * xv[4 * j + 0]; p[4 * j + 1] = vj[1] * xv[4 * j + 1];
+                p[4 * j + 2] = vj[2] * xv[4 * j + 2]; p[4 * j + 3] = vj[3] * xv[4 * j + 3];
+            } else {
             p[4 * j + 0] = i2f((int)w.v[j].x) * xv[4 * j + 0];
             p[4 * j + 1] = i2f((int)w.v[j].y) * xv[4 * j + 1];
             p[4 * j + 2] = i2f((int)w.v[j].z) * xv[4 * j + 2];
             p[4 * j + 3] = i2f((int)w.v[j].w) * xv[4 * j + 3];
+            }
         }
         // hipcc would hoist the prefetch above the products (its results land in fresh registers); the waits for the
         // gathers, placed after the point where the three gather paths merge, then count conservatively and wait for
@@ -551,7 +579,7 @@ __device__ __forceinline__ void slices_group(
         }
         if (local < n_here) {
             h = load_int4(hdr + first + local);       // header first: see the prologue
-            request_slice<COMPACT>(w, gbase + (size_t)local * slice_bytes, lane);
+            request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
         }
 
         // PreAccumulator + row distribution network: lane-local combine + segmented scan per 256-element step
@@ -678,7 +706,9 @@ __device__ __forceinline__ void slices_group(
     }
 }
 
-template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false>
+// HALF: 0 = no half groups in the launch; 1 = half, compact and wide groups (a multi-matrix grid with a bf16 handle in it);
+// 2 = half and wide groups only (ONE bf16 handle: it has no compact group that is not half, the compact body stays out)
+template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false, int HALF = 0>
 __device__ __forceinline__ void slices_body(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
     const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
@@ -702,6 +732,18 @@ __device__ __forceinline__ void slices_body(
     if constexpr (USE_LDS) {
         // (a sub-block of the step kernel past the matrix's last group: an empty group -- it only joins the barrier)
         const int4 g = group * group_slices < n_slices ? load_int4(groups + group) : int4{0, 0, 0, 0};     // {first fragment, fragments, offset of the group's slices, compact}
+        if constexpr (HALF != 0) {      // (a launch with a half group: fp32 handles of the same grid keep their compact and wide groups)
+            if ((__builtin_amdgcn_readfirstlane(g.w) & kGroupHalf) != 0) {
+                slices_group<HAS_BETA, true, LOOKBACK, true, STRAYS, true>(stream, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
+                                                                           lds_floats, ytile_floats, cols, rows, lb, group, g, sb);
+                return;
+            }
+        }
+        if constexpr (HALF == 2) {
+            slices_group<HAS_BETA, true, LOOKBACK, false>(stream, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
+                                                          lds_floats, ytile_floats, cols, rows, lb, group, g, sb);
+            return;
+        }
         if (__builtin_amdgcn_readfirstlane(g.w) != 0)
             slices_group<HAS_BETA, true, LOOKBACK, true, STRAYS>(stream, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
                                                          lds_floats, ytile_floats, cols, rows, lb, group, g, sb);
@@ -713,13 +755,15 @@ __device__ __forceinline__ void slices_body(
                                                        lds_floats, ytile_floats, cols, rows, lb, group, int4{0, 0, 0, 0}, sb);
     }
 }
-template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false>
+// HALF: 0 = no half groups in the launch; 1 = half, compact and wide groups (a multi-matrix grid with a bf16 handle in it);
+// 2 = half and wide groups only (ONE bf16 handle: it has no compact group that is not half, the compact body stays out)
+template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false, int HALF = 0>
 __device__ __forceinline__ void slices_body(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
     const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
     float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
     int lds_floats, int ytile_floats, int cols, int rows, const LookbackArgs& lb, long long group) {
-    slices_body<HAS_BETA, USE_LDS, LOOKBACK, STRAYS>(stream, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
+    slices_body<HAS_BETA, USE_LDS, LOOKBACK, STRAYS, HALF>(stream, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
                                                      lds_floats, ytile_floats, cols, rows, lb, group, SubBlock::whole());
 }
 
@@ -731,6 +775,18 @@ __global__ __launch_bounds__(1024) void spmv_slices_kernel(
     int lds_floats, int ytile_floats, int cols, int rows, LookbackArgs lb) {
     slices_body<HAS_BETA, USE_LDS, LOOKBACK, STRAYS>(words, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
                                              lds_floats, ytile_floats, cols, rows, lb, (long long)blockIdx.x);
+}
+
+// The same for a handle with HALF groups (bf16 value storage): a kernel of its own, so that handles without them run exactly the
+// instantiations above.  Half groups are compact groups: such a plan always has a window (USE_LDS).
+template <bool HAS_BETA, bool LOOKBACK, bool STRAYS>
+__global__ __launch_bounds__(1024) void spmv_slices_half_kernel(
+    const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups,
+    const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
+    float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
+    int lds_floats, int ytile_floats, int cols, int rows, LookbackArgs lb) {
+    slices_body<HAS_BETA, true, LOOKBACK, STRAYS, 2>(words, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
+                                                        lds_floats, ytile_floats, cols, rows, lb, (long long)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -767,7 +823,35 @@ __global__ __launch_bounds__(1024) void spmv_slices_multi_kernel(const MultiEntr
                                         t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
     WGT_END(blockDim.x == 1024 ? 1 : 2, e, group);
 }
-
+// ... when a part of the launch has half groups (bf16 value storage).  The same text with the HALF bodies -- a kernel of its own and not a
+// shared body function: called through one, spmv_slices_multi_kernel<false> came out with 93 VGPRs instead of 91.
+template <bool STRAYS>
+__global__ __launch_bounds__(1024) void spmv_slices_multi_half_kernel(const MultiEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
+    int k = 0;
+#pragma unroll 1
+    while (k + 1 < prefix.n && (long long)blockIdx.x >= prefix.begin[k + 1]) ++k;
+    long long group = (long long)blockIdx.x - prefix.begin[k];
+    int e = prefix.first[k];
+    const int tiles = prefix.tiles[k];
+    if (tiles > 1) {              // XCD-pinned column tiles (hispmv_kernels.h): tile from the block's index mod 8
+        const int per = 8 / tiles, res = (int)(group & 7);
+        e += res / per;
+        group = (group >> 3) * per + (res % per);
+    }
+    const MultiEntry t = table[e];
+    if (group * t.group_slices >= t.n_slices) return;      // (a pinned tile with fewer groups than its siblings)
+    WGT_BEGIN();
+    const LookbackArgs lb{};
+    // beta is per entry: the first column tile of a matrix applies beta*bias, its other tiles write alpha*A_t*x into the
+    // handle's partial vectors (no bias read) -- both kinds share the grid, a workgroup runs one of the two bodies
+    if (t.beta != 0.0f)
+        slices_body<true, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, alpha, t.beta,
+                                       t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
+    else
+        slices_body<false, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, alpha, 0.0f,
+                                        t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
+    WGT_END(blockDim.x == 1024 ? 1 : 2, e, group);
+}
 // Fix-up of all matrices of a multi launch: thread blocks are concatenated the same way.
 __global__ __launch_bounds__(256) void spmv_fixup_multi_kernel(const MultiFixEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
     int e = 0;
@@ -862,7 +946,7 @@ __global__ __launch_bounds__(256) void spmv_tail_multi_kernel(const MultiFixEntr
 // slice is requested after the last vector's products.  The x windows of the NV vectors sit side by side in LDS.
 // Host guarantees: cols % 4 == 0 when USE_LDS, cols*NV < 2^30, rows*NV < 2^30, NV*lds_floats + tiles fit LDS.
 // ---------------------------------------------------------------------------
-template <bool HAS_BETA, bool USE_LDS, int NV, bool COMPACT>
+template <bool HAS_BETA, bool USE_LDS, int NV, bool COMPACT, bool HALF = false>
 __device__ __forceinline__ void batched_group(
     const char* __restrict__ stream, const int4* __restrict__ hdr,
     const int4* __restrict__ frags,
@@ -881,7 +965,7 @@ __device__ __forceinline__ void batched_group(
     const long long group = blockIdx.x;
     const long long first = group * group_slices;
     const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;   // exclusive
-    constexpr int slice_bytes = COMPACT ? kCompactSliceBytes : kWideSliceBytes;
+    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
     const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit
                                                 : (size_t)first * kWideSliceBytes);
 
@@ -896,12 +980,12 @@ __device__ __forceinline__ void batched_group(
     const bool strays = COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & 2) != 0;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
     unsigned sc = 0xffffffffu;
-    SliceRaw<COMPACT> w;
+    SliceRaw<COMPACT, HALF> w;
     int4 h = int4{0, 0, 0, 0};
     if (slice < last) {
         if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(slice * kStraySlots + lane) << 2, 0, 0);
         h = load_int4(hdr + slice);
-        request_slice<COMPACT>(w, gbase + (size_t)(slice - first) * slice_bytes, lane);
+        request_slice<COMPACT, HALF>(w, gbase + (size_t)(slice - first) * slice_bytes, lane);
     }
     bool in_lds = false;
     if (USE_LDS) {
@@ -919,12 +1003,19 @@ __device__ __forceinline__ void batched_group(
         const int n_rows = __builtin_amdgcn_readfirstlane(h.z);
         const bool spills = USE_LDS && __builtin_amdgcn_readfirstlane(h.w) != 0;
         unsigned c[kE];
-        decode_metas<COMPACT>(w, c);
-        float val[kE];
+        decode_metas<COMPACT, HALF>(w, c);
+        float val[HALF ? 1 : kE];
+        // (half slice: the values stay PACKED across the vectors -- 8 registers instead of 16 -- and are widened per product: kept
+        // widened, the NV = 4 instantiation with a bias spilled 3 - 4 VGPRs to scratch)
+        unsigned hv[HALF ? 2 * kSliceSteps : 1];
 #pragma unroll
         for (int j = 0; j < kSliceSteps; ++j) {
+            if constexpr (HALF) {
+                hv[2 * j] = w.q[j].x; hv[2 * j + 1] = w.q[j].y;
+            } else {
             val[4 * j + 0] = i2f((int)w.v[j].x); val[4 * j + 1] = i2f((int)w.v[j].y);
             val[4 * j + 2] = i2f((int)w.v[j].z); val[4 * j + 3] = i2f((int)w.v[j].w);
+            }
         }
         int r0[kSliceSteps];
         // (Round 4: taking each vector's row-end masks through an opaque copy, so that the 4 x 7 scan flag words are recomputed per
@@ -992,14 +1083,20 @@ __device__ __forceinline__ void batched_group(
                 if (slice < last) {
                     if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(slice * kStraySlots + lane) << 2, 0, 0);
                     h = load_int4(hdr + slice);
-                    request_slice<COMPACT>(w, gbase + (size_t)(slice - first) * slice_bytes, lane);
+                    request_slice<COMPACT, HALF>(w, gbase + (size_t)(slice - first) * slice_bytes, lane);
                 }
             }
             float t[kE];
             float carry_step = 0.0f;
 #pragma unroll
             for (int j = 0; j < kSliceSteps; ++j) {
-                const float pj[kLaneElems] = {val[4 * j] * xg[4 * j], val[4 * j + 1] * xg[4 * j + 1], val[4 * j + 2] * xg[4 * j + 2], val[4 * j + 3] * xg[4 * j + 3]};
+                float pj[kLaneElems];
+                if constexpr (HALF) {
+                    pj[0] = i2f((int)(hv[2 * j] << 16)) * xg[4 * j]; pj[1] = i2f((int)(hv[2 * j] & 0xffff0000u)) * xg[4 * j + 1];
+                    pj[2] = i2f((int)(hv[2 * j + 1] << 16)) * xg[4 * j + 2]; pj[3] = i2f((int)(hv[2 * j + 1] & 0xffff0000u)) * xg[4 * j + 3];
+                } else {
+                    pj[0] = val[4 * j] * xg[4 * j]; pj[1] = val[4 * j + 1] * xg[4 * j + 1]; pj[2] = val[4 * j + 2] * xg[4 * j + 2]; pj[3] = val[4 * j + 3] * xg[4 * j + 3];
+                }
                 float tj[kLaneElems];
                 scan_step(pj, ends[4 * j], ends[4 * j + 1], ends[4 * j + 2], ends[4 * j + 3], carry_step, tj);
                 t[4 * j] = tj[0]; t[4 * j + 1] = tj[1]; t[4 * j + 2] = tj[2]; t[4 * j + 3] = tj[3];
@@ -1048,6 +1145,23 @@ __global__ __launch_bounds__(1024) void spmv_slices_batched_kernel(
     }
 }
 
+// ... of a handle with half groups (bf16 value storage)
+template <bool HAS_BETA, int NV>
+__global__ __launch_bounds__(1024) void spmv_slices_batched_half_kernel(
+    const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
+    const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
+    float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
+    int lds_floats, int ytile_floats, int cols, int rows, int bias_stride) {
+    const int4 g = load_int4(groups + blockIdx.x);
+    const int kind = __builtin_amdgcn_readfirstlane(g.w);
+    if ((kind & kGroupHalf) != 0)
+        batched_group<HAS_BETA, true, NV, true, true>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
+                                                      ytile_floats, cols, rows, bias_stride, g);
+    else      // (a bf16 handle has no compact group that is not half: two bodies, not three)
+        batched_group<HAS_BETA, true, NV, false>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
+                                                 ytile_floats, cols, rows, bias_stride, g);
+}
+
 // Fix-up for rows shared between slices: y[row] += alpha * (carry[first] + ... + carry[first+len-1]),
 // summed in slice order.  One thread per entry (short chains) ...
 __global__ __launch_bounds__(256) void spmv_fixup_short_kernel(const int4* __restrict__ fix, int n,
@@ -1085,6 +1199,19 @@ static void launch_slices(const SpmvDeviceMatrix& m, const LookbackArgs& lb, con
                           float alpha, float beta, hipStream_t stream) {
     const size_t lds = ((USE_LDS ? (size_t)m.lds_floats : 0) + (size_t)m.ytile_floats * (m.block_threads / 64)) * sizeof(float) +
                        (LOOKBACK ? (size_t)m.group_slices * 8 : 0);
+    if constexpr (USE_LDS) {
+        if (m.has_half) {      // (bf16 value storage: the kernel that reads half groups, with the stray code only where the handle has stray slots)
+            if (!LOOKBACK && m.has_strays)
+                hipLaunchKernelGGL((spmv_slices_half_kernel<HAS_BETA, false, true>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
+                                   (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
+                                   (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, lb);
+            else
+                hipLaunchKernelGGL((spmv_slices_half_kernel<HAS_BETA, LOOKBACK, false>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
+                                   (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
+                                   (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, lb);
+            return;
+        }
+    }
     if (USE_LDS && !LOOKBACK && m.has_strays)       // (stray slots: the instantiation that fetches them; never with look-back, hispmv_abi.cpp)
         hipLaunchKernelGGL((spmv_slices_kernel<HAS_BETA, USE_LDS && !LOOKBACK, false, USE_LDS && !LOOKBACK>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
                            (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
@@ -1116,6 +1243,12 @@ hipError_t prepare_spmv_kernels() {
     if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -1157,6 +1290,21 @@ template <bool HAS_BETA, bool USE_LDS, int NV>
 static hipError_t launch_batched(const SpmvDeviceMatrix& m, const float* x, const float* bias, int bias_stride, float* y,
                                  float alpha, float beta, hipStream_t stream) {
     const size_t lds = ((USE_LDS ? (size_t)m.lds_floats * NV : 0) + (size_t)m.ytile_floats * (m.block_threads / 64)) * sizeof(float);
+    if constexpr (USE_LDS) {
+        if (m.has_half) {      // (bf16 value storage)
+            static bool raised_half = false;
+            if (!raised_half) {
+                hipError_t e = hipFuncSetAttribute((const void*)spmv_slices_batched_half_kernel<HAS_BETA, NV>,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+                if (e != hipSuccess) return e;
+                raised_half = true;
+            }
+            hipLaunchKernelGGL((spmv_slices_batched_half_kernel<HAS_BETA, NV>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
+                               (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
+                               (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, bias_stride);
+            return hipGetLastError();
+        }
+    }
     static bool raised = false;      // per instantiation
     if (!raised) {
         hipError_t e = hipFuncSetAttribute((const void*)spmv_slices_batched_kernel<HAS_BETA, USE_LDS, NV>,
@@ -1247,11 +1395,17 @@ hipError_t launch_spmv_multi(const SpmvDeviceMatrix* const* parts, int n, const 
         hipError_t err;
         if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
         if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
+        if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_half_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
+        if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_half_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
         raised = true;
     }
     bool strays = false;          // (a launch with a stray-slot part takes the instantiation that fetches them; hispmv_batch.cpp keeps such parts in grids of their own)
     for (int i = 0; i < n; ++i) strays = strays || parts[i]->has_strays;
-    if (g > 0 && strays) hipLaunchKernelGGL(spmv_slices_multi_kernel<true>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
+    bool half = false;            // (... and one with a half group -- bf16 value storage -- the kernel that reads them)
+    for (int i = 0; i < n; ++i) half = half || parts[i]->has_half;
+    if (g > 0 && half && strays) hipLaunchKernelGGL(spmv_slices_multi_half_kernel<true>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
+    else if (g > 0 && half) hipLaunchKernelGGL(spmv_slices_multi_half_kernel<false>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
+    else if (g > 0 && strays) hipLaunchKernelGGL(spmv_slices_multi_kernel<true>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
     else if (g > 0) hipLaunchKernelGGL(spmv_slices_multi_kernel<false>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
     return hipGetLastError();
 }
@@ -2004,6 +2158,97 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const float* __restrict_
     gemv_rows_body<R, HAS_BETA, NV>(W, x, bias, y, rows, cols, alpha, beta, (int)blockIdx.x);
 }
 
+// bf16 value storage: W is rows x cols bfloat16 (2 bytes per element), everything else as above -- fp32 x, products and sums.  With
+// cols % 8 == 0 a lane takes 8 consecutive columns per step: ONE 16-byte load of W per row (rows are 16-byte aligned) against two
+// float4 of x per vector; with cols % 4 == 0 four columns (8-byte loads of W); otherwise element by element.  bf16 -> fp32: `bits << 16` / `bits & 0xffff0000`.  The lane-to-column
+// assignment differs from the fp32 body's (8 columns per lane instead of 4), so the bits differ from an fp32 handle of R(W); every
+// (row, vector) pair again accumulates in the order of this body's single-vector instantiation.
+template <int R, bool HAS_BETA, int NV>
+__device__ __forceinline__ void gemv_rows_bf16_body(const uint16_t* __restrict__ W, const float* __restrict__ x,
+                                                    const float* __restrict__ bias, float* __restrict__ y,
+                                                    int rows, int cols, float alpha, float beta, int block) {
+    __shared__ float part16[4][R][NV];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int row0 = block * R;
+    float acc[R][NV];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) acc[r][v] = 0.0f;
+
+    if ((cols & 7) == 0) {
+        const int n8 = cols >> 3, n4 = cols >> 2;
+        const float4* x4 = (const float4*)x;
+        for (int c = threadIdx.x; c < n8; c += 256) {
+            float4 xa[NV], xb[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) { xa[v] = x4[(size_t)v * n4 + 2 * c]; xb[v] = x4[(size_t)v * n4 + 2 * c + 1]; }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int row = min(row0 + r, rows - 1);
+                const uint4 q = ((const uint4*)(W + (size_t)row * cols))[c];
+                const float a0 = i2f((int)(q.x << 16)), a1 = i2f((int)(q.x & 0xffff0000u)), a2 = i2f((int)(q.y << 16)), a3 = i2f((int)(q.y & 0xffff0000u));
+                const float a4 = i2f((int)(q.z << 16)), a5 = i2f((int)(q.z & 0xffff0000u)), a6 = i2f((int)(q.w << 16)), a7 = i2f((int)(q.w & 0xffff0000u));
+#pragma unroll
+                for (int v = 0; v < NV; ++v)
+                    acc[r][v] += (a0 * xa[v].x + a1 * xa[v].y + a2 * xa[v].z + a3 * xa[v].w) + (a4 * xb[v].x + a5 * xb[v].y + a6 * xb[v].z + a7 * xb[v].w);
+            }
+        }
+    } else if ((cols & 3) == 0) {   // rows are 8-byte aligned: 4 columns per lane, one 8-byte load of W against one float4 of x
+        const int n4 = cols >> 2;
+        const float4* x4 = (const float4*)x;
+        for (int c = threadIdx.x; c < n4; c += 256) {
+            float4 xa[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) xa[v] = x4[(size_t)v * n4 + c];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int row = min(row0 + r, rows - 1);
+                const uint2 q = ((const uint2*)(W + (size_t)row * cols))[c];
+                const float a0 = i2f((int)(q.x << 16)), a1 = i2f((int)(q.x & 0xffff0000u)), a2 = i2f((int)(q.y << 16)), a3 = i2f((int)(q.y & 0xffff0000u));
+#pragma unroll
+                for (int v = 0; v < NV; ++v) acc[r][v] += a0 * xa[v].x + a1 * xa[v].y + a2 * xa[v].z + a3 * xa[v].w;
+            }
+        }
+    } else {   // element path
+        for (int c = threadIdx.x; c < cols; c += 256) {
+            float xv[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) xv[v] = x[(size_t)v * cols + c];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int row = min(row0 + r, rows - 1);
+                const float a = i2f((int)((unsigned)W[(size_t)row * cols + c] << 16));
+#pragma unroll
+                for (int v = 0; v < NV; ++v) acc[r][v] += a * xv[v];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const float s = wave_sum(acc[r][v]);
+            if (lane == 0) part16[wv][r][v] = s;
+        }
+    __syncthreads();
+    if (threadIdx.x < R * NV) {
+        const int r = threadIdx.x / NV, v = threadIdx.x % NV;
+        const int row = row0 + r;
+        if (row < rows) {
+            const float s = (part16[0][r][v] + part16[1][r][v]) + (part16[2][r][v] + part16[3][r][v]);
+            y[(size_t)v * rows + row] = HAS_BETA ? alpha * s + beta * bias[row] : alpha * s;
+        }
+    }
+}
+
+template <int R, bool HAS_BETA, int NV>
+__global__ __launch_bounds__(256) void gemv_rows_bf16_kernel(const uint16_t* __restrict__ W, const float* __restrict__ x,
+                                                             const float* __restrict__ bias, float* __restrict__ y,
+                                                             int rows, int cols, float alpha, float beta) {
+    gemv_rows_bf16_body<R, HAS_BETA, NV>(W, x, bias, y, rows, cols, alpha, beta, (int)blockIdx.x);
+}
+
 // The dense handles of a batch call in one grid: block ranges per matrix (prefix.begin), largest matrix first so that the
 // small ones fill the tail.
 __global__ __launch_bounds__(256) void gemv_rows_multi_kernel(const GemvEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
@@ -2016,11 +2261,34 @@ __global__ __launch_bounds__(256) void gemv_rows_multi_kernel(const GemvEntry* _
     else gemv_rows_body<4, false, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
 }
 
+// ... with bf16 entries among them (GemvEntry::bf16): the kernel that knows both bodies; a launch without one takes the kernel above
+__global__ __launch_bounds__(256) void gemv_rows_multi_mixed_kernel(const GemvEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
+    int k = 0;
+#pragma unroll 1
+    while (k + 1 < prefix.n && (long long)blockIdx.x >= prefix.begin[k + 1]) ++k;
+    const GemvEntry e = table[k];
+    const int block = (int)((long long)blockIdx.x - prefix.begin[k]);
+    if (e.bf16) {
+        if (e.beta != 0.0f) gemv_rows_bf16_body<4, true, 1>((const uint16_t*)e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
+        else gemv_rows_bf16_body<4, false, 1>((const uint16_t*)e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
+    } else {
+        if (e.beta != 0.0f) gemv_rows_body<4, true, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
+        else gemv_rows_body<4, false, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
+    }
+}
+
 template <int NV>
 static void launch_gemv_nv(const float* W, int32_t rows, int32_t cols, const float* x, const float* bias,
-                           float* y, float alpha, float beta, hipStream_t stream) {
+                           float* y, float alpha, float beta, hipStream_t stream, bool bf16 = false) {
     constexpr int R = 4;
     const unsigned blocks = (unsigned)((rows + R - 1) / R);
+    if (bf16) {
+        if (beta != 0.0f)
+            hipLaunchKernelGGL((gemv_rows_bf16_kernel<R, true, NV>), dim3(blocks), dim3(256), 0, stream, (const uint16_t*)W, x, bias, y, rows, cols, alpha, beta);
+        else
+            hipLaunchKernelGGL((gemv_rows_bf16_kernel<R, false, NV>), dim3(blocks), dim3(256), 0, stream, (const uint16_t*)W, x, bias, y, rows, cols, alpha, beta);
+        return;
+    }
     if (beta != 0.0f)
         hipLaunchKernelGGL((gemv_rows_kernel<R, true, NV>), dim3(blocks), dim3(256), 0, stream, W, x, bias, y, rows, cols, alpha, beta);
     else
@@ -2028,10 +2296,10 @@ static void launch_gemv_nv(const float* W, int32_t rows, int32_t cols, const flo
 }
 
 hipError_t launch_gemv(const float* W, int32_t rows, int32_t cols, const float* x, const float* bias,
-                       float* y, float alpha, float beta, hipStream_t stream) {
+                       float* y, float alpha, float beta, hipStream_t stream, bool bf16) {
     (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
     if (rows <= 0) return hipSuccess;
-    launch_gemv_nv<1>(W, rows, cols, x, bias, y, alpha, beta, stream);
+    launch_gemv_nv<1>(W, rows, cols, x, bias, y, alpha, beta, stream, bf16);
     return hipGetLastError();
 }
 
@@ -2045,22 +2313,26 @@ hipError_t launch_gemv_multi(const GemvEntry* entries, int n, const GemvEntry* d
     for (int i = 0; i < n; ++i) { prefix.begin[i] = total; total += (entries[i].rows + 3) / 4; }
     prefix.begin[n] = total;
     if (total <= 0) return hipSuccess;
+    bool bf16 = false;
+    for (int i = 0; i < n; ++i) bf16 = bf16 || entries[i].bf16 != 0;
+    if (bf16) hipLaunchKernelGGL(gemv_rows_multi_mixed_kernel, dim3((unsigned)total), dim3(256), 0, stream, d_table, prefix, alpha);
+    else
     hipLaunchKernelGGL(gemv_rows_multi_kernel, dim3((unsigned)total), dim3(256), 0, stream, d_table, prefix, alpha);
     return hipGetLastError();
 }
 
 hipError_t launch_gemv_batched(const float* W, int32_t rows, int32_t cols, int64_t vecs, const float* x, const float* bias,
-                               float* y, float alpha, float beta, hipStream_t stream) {
+                               float* y, float alpha, float beta, hipStream_t stream, bool bf16) {
     (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
     if (rows <= 0) return hipSuccess;
     int64_t k = 0;
     while (k < vecs) {      // 8, 4, 2, 1 vectors per pass over W
         const float* xk = x + (size_t)k * cols;
         float* yk = y + (size_t)k * rows;
-        if (vecs - k >= 8) { launch_gemv_nv<8>(W, rows, cols, xk, bias, yk, alpha, beta, stream); k += 8; }
-        else if (vecs - k >= 4) { launch_gemv_nv<4>(W, rows, cols, xk, bias, yk, alpha, beta, stream); k += 4; }
-        else if (vecs - k >= 2) { launch_gemv_nv<2>(W, rows, cols, xk, bias, yk, alpha, beta, stream); k += 2; }
-        else { launch_gemv_nv<1>(W, rows, cols, xk, bias, yk, alpha, beta, stream); k += 1; }
+        if (vecs - k >= 8) { launch_gemv_nv<8>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 8; }
+        else if (vecs - k >= 4) { launch_gemv_nv<4>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 4; }
+        else if (vecs - k >= 2) { launch_gemv_nv<2>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 2; }
+        else { launch_gemv_nv<1>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 1; }
     }
     return hipGetLastError();
 }
@@ -2085,7 +2357,8 @@ hipError_t graph_set_alpha(hipGraphExec_t exec, hipGraph_t graph, float alpha) {
         hipKernelNodeParams p{};
         if ((e = hipGraphKernelNodeGetParams(nodes[i], &p)) != hipSuccess) return e;
         int idx, n_args;
-        if (p.func == (void*)spmv_slices_multi_kernel<false> || p.func == (void*)spmv_slices_multi_kernel<true> || p.func == (void*)spmv_tts_multi_kernel<false> || p.func == (void*)spmv_tts_multi_kernel<true> ||
+        if (p.func == (void*)spmv_slices_multi_kernel<false> || p.func == (void*)spmv_slices_multi_kernel<true> ||
+            p.func == (void*)spmv_slices_multi_half_kernel<false> || p.func == (void*)spmv_slices_multi_half_kernel<true> || p.func == (void*)gemv_rows_multi_mixed_kernel || p.func == (void*)spmv_tts_multi_kernel<false> || p.func == (void*)spmv_tts_multi_kernel<true> ||
             p.func == (void*)spmv_tts_multi_kernel<false, true> || p.func == (void*)spmv_tts_multi_kernel<false, false, true> ||
             p.func == (void*)gemv_rows_multi_kernel ||
             p.func == (void*)spmv_fixup_multi_kernel) { idx = 2; n_args = 3; }

@@ -308,14 +308,17 @@ double stray_slot_coverage(const SliceStream& st, const LaunchPlan& plan) {
     return all > 0 ? (double)covered / (double)all : 0.0;
 }
 
-DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, bool materialize) {
+DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, bool materialize, bool half_values) {
     DeviceStream d;
+    d.half_values = half_values;
+    if (half_values) materialize = true;      // (the device layout kernel does not know the half slice)
     const int64_t n = st.n_slices, G = plan.group_slices;
     const int64_t ng = std::max<int64_t>((n + G - 1) / G, 1);
     const int n_waves = plan.block_threads / 64;
     d.groups.assign((size_t)ng * 4, 0);
     std::vector<int64_t> off((size_t)ng + 1, 0);
-    std::vector<uint8_t> compact((size_t)ng, 0);       // 1 compact, 3 compact with stray slots
+    std::vector<uint8_t> compact((size_t)ng, 0);       // 1 compact, 3 compact with stray slots (| kGroupHalf in the group table when half_values)
+    const int64_t compact_bytes = half_values ? kHalfSliceBytes : kCompactSliceBytes;
     const bool stray_possible = stray_slots_possible(plan);
     bool any_stray = false;
     for (int64_t g = 0; g < ng; ++g) {
@@ -323,9 +326,9 @@ DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, b
         const int64_t s0 = g * G, s1 = std::min(n, s0 + G);
         compact[(size_t)g] = gd.frag_count > 0 && gd.n_global == 0 && gd.lds_floats <= kCompactMaxIndex;
         if (!compact[(size_t)g] && stray_possible && (size_t)g < plan.groups.size() && stray_group_ok(plan, g, n)) { compact[(size_t)g] = 3; any_stray = true; }
-        off[(size_t)g + 1] = off[(size_t)g] + std::max<int64_t>(s1 - s0, 0) * (compact[(size_t)g] ? kCompactSliceBytes : kWideSliceBytes);
+        off[(size_t)g + 1] = off[(size_t)g] + std::max<int64_t>(s1 - s0, 0) * (compact[(size_t)g] ? compact_bytes : (int64_t)kWideSliceBytes);
         d.groups[(size_t)g * 4 + 0] = gd.frag_begin; d.groups[(size_t)g * 4 + 1] = gd.frag_count;
-        d.groups[(size_t)g * 4 + 2] = (int32_t)(off[(size_t)g] / kSliceUnit); d.groups[(size_t)g * 4 + 3] = compact[(size_t)g];
+        d.groups[(size_t)g * 4 + 2] = (int32_t)(off[(size_t)g] / kSliceUnit); d.groups[(size_t)g * 4 + 3] = compact[(size_t)g] | (half_values && compact[(size_t)g] ? kGroupHalf : 0);
         if (compact[(size_t)g]) d.compact_slices += std::max<int64_t>(s1 - s0, 0);
         if (compact[(size_t)g] == 3) d.stray_slices += std::max<int64_t>(s1 - s0, 0);
     }
@@ -343,11 +346,13 @@ DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, b
         const int64_t rot = n_here > 0 ? (int64_t)(((unsigned long long)g * 29ull) % (unsigned long long)n_here) : 0;   // the kernel's walk (slices_group)
         for (int64_t sl = s0; sl < s1; ++sl) {
             const uint64_t* w = st.words.data() + sl * kSliceElems;
-            uint8_t* base = d.bytes.data() + off[(size_t)g] + (sl - s0) * (compact[(size_t)g] ? kCompactSliceBytes : kWideSliceBytes);
+            uint8_t* base = d.bytes.data() + off[(size_t)g] + (sl - s0) * (compact[(size_t)g] ? compact_bytes : (int64_t)kWideSliceBytes);
+            const bool half = half_values && compact[(size_t)g];
             uint32_t* vals = (uint32_t*)base;
-            for (int i = 0; i < kSliceElems; ++i) vals[i] = (uint32_t)w[i];
+            if (!half) for (int i = 0; i < kSliceElems; ++i) vals[i] = (uint32_t)w[i];
+            uint16_t half_meta[kSliceElems];
             if (compact[(size_t)g]) {
-                uint16_t* meta = (uint16_t*)(base + kSliceElems * 4);
+                uint16_t* meta = half ? half_meta : (uint16_t*)(base + kSliceElems * 4);
                 // position of the slice in its workgroup's walk -> the wavefront that takes it -> that wavefront's stray area
                 const int64_t pos = ((sl - s0) - rot + n_here) % n_here;
                 const uint32_t area = (uint32_t)plan.lds_floats + (uint32_t)(pos % n_waves) * kStraySlots;
@@ -360,6 +365,16 @@ DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, b
                         idx = area + k++;
                     }
                     meta[i] = (uint16_t)(idx | ((m & kRowEndBit) ? kCompactEndBit : 0u));
+                }
+                if (half) {
+                    // half slice (hispmv_format.h): per lane and step one 16-byte piece {v0 v1, v2 v3, m0 m1, m2 m3}; the values
+                    // are exact in bf16 (rounded when the handle was created), so their upper 16 bits are the whole value
+                    uint16_t* q = (uint16_t*)base;
+                    for (int i = 0; i < kSliceElems; i += kLaneElems)
+                        for (int k = 0; k < kLaneElems; ++k) {
+                            q[2 * i + k] = (uint16_t)((uint32_t)w[i + k] >> 16);
+                            q[2 * i + kLaneElems + k] = half_meta[i + k];
+                        }
                 }
             } else {
                 uint32_t* meta = (uint32_t*)(base + kSliceElems * 4);

@@ -71,16 +71,19 @@ int ytile_floats_for(const SliceStream& st);
 // of the roofline when 2 % of its entries are re-drawn at random columns (profiles/r4_standin_sweep*.json).
 struct DeviceStream {
     std::vector<uint8_t, DefaultInitAllocator<uint8_t>> bytes;   // the slices, group after group (uninitialised until the packing loop writes them)
-    std::vector<int32_t> groups;         // n_groups x {frag_begin, frag_count, offset of the group's first slice in kSliceUnit, 1 = compact | 2 = has stray slots}
+    std::vector<int32_t> groups;         // n_groups x {frag_begin, frag_count, offset of the group's first slice in kSliceUnit, 1 = compact | 2 = has stray slots | 4 = half}
     std::vector<uint32_t> stray_cols;    // n_slices x kStraySlots columns (0xffffffff = unused), empty when no group uses stray slots
     int stray_floats = 0;                // LDS floats of the stray areas (wavefronts x kStraySlots) behind the window, 0 = none
     int64_t compact_slices = 0, stray_slices = 0;
     int64_t n_bytes = 0;                 // size of `bytes`, also when they are left to the device (materialize = false)
+    bool half_values = false;            // bf16 value storage: every compact group is packed as HALF slices (hispmv_format.h), 4 B per element
     bool any_stray = false;              // some group uses stray slots (stray_cols has n_slices x kStraySlots entries once materialized)
 };
 // materialize = false: the group table, sizes and flags only -- the loader then runs layout_on_device (hispmv_prep_device.h) over the
 // uploaded host words, which writes the same bytes and stray columns.
-DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, bool materialize = true);
+// half_values (bf16 value storage, hispmv_set_value_storage): the compact groups become half groups; the values must already be
+// exact in bf16 (round_values_to_bf16 below ran over the CSR before the stream was built).  Always materialized on the host.
+DeviceStream pack_device_stream(const SliceStream& st, const LaunchPlan& plan, bool materialize = true, bool half_values = false);
 // Share of the plan's elements outside their windows that stray slots will serve (groups whose slices have <= kStraySlots each).
 double stray_slot_coverage(const SliceStream& st, const LaunchPlan& plan);
 

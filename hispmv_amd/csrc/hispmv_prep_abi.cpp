@@ -141,12 +141,22 @@ HISPMV_API int hispmv_prep_apply_plan(hispmv_prep* p, int n_cus, int64_t counts[
     counts[0] = (int64_t)p->plan.groups.size(); counts[1] = (int64_t)p->plan.frags.size();
     return HISPMV_OK;
 }
+// Host-only counterpart of hispmv_set_value_storage: bf16 rounds the prepared values once, in place -- the CSR and the value halves of
+// the stream words (fillers and padding are zeros: unchanged) -- and selects the half slice for hispmv_prep_device_stream.
+HISPMV_API int hispmv_prep_set_value_storage(hispmv_prep* p, int storage) {
+    if (!p || (storage != HISPMV_VALUES_FP32 && storage != HISPMV_VALUES_BF16)) { g_prep_err = "bad value storage arguments"; return HISPMV_EINVAL; }
+    p->half_values = storage == HISPMV_VALUES_BF16;
+    if (!p->half_values) return HISPMV_OK;
+    for (float& v : p->csr.val) { uint32_t u; std::memcpy(&u, &v, 4); u = round_bits_to_bf16(u); std::memcpy(&v, &u, 4); }
+    for (uint64_t& w : p->st.words) w = (w & 0xffffffff00000000ull) | round_bits_to_bf16((uint32_t)w);
+    return HISPMV_OK;
+}
 // The device layout of the stream under the plan hispmv_prep_apply_plan computed (call that first): counts = {bytes, groups,
 // compact slices, slices with stray slots, stray-area floats, window floats of the plan}; arrays through hispmv_prep_device_array.
 HISPMV_API int hispmv_prep_device_stream(hispmv_prep* p, int64_t counts[6]) {
     if (!p || !counts) return HISPMV_EINVAL;
     try {
-        p->dstream = pack_device_stream(p->st, p->plan);
+        p->dstream = pack_device_stream(p->st, p->plan, true, p->half_values);
         counts[0] = (int64_t)p->dstream.bytes.size(); counts[1] = (int64_t)p->dstream.groups.size() / 4; counts[2] = p->dstream.compact_slices;
         counts[3] = p->dstream.stray_slices; counts[4] = p->dstream.stray_floats; counts[5] = p->plan.lds_floats;
         return HISPMV_OK;

@@ -172,6 +172,22 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range")
         return {"updatable": bool(out[0]), "n": int(out[1]), "map_slots": int(out[2]), "written": int(out[3])}
 
+    def set_value_storage(self, storage: str) -> None:
+        """"fp32" (default) or "bf16": how handles created from now on store their values (hispmv_set_value_storage).  A bf16 handle
+        rounds its values once, at creation, and computes with fp32 x, products and sums; compact slice groups and dense W shrink."""
+        if storage not in _lib.VALUE_STORAGES:
+            raise ValueError('value storage must be "fp32" or "bf16"')
+        self._check(lib.hispmv_set_value_storage(self._ctx, _lib.VALUE_STORAGES[storage]))
+
+    def value_storage_info(self, matrix_idx: int) -> dict:
+        """{"storage", "slots_2byte", "slots_4byte", "saved_bytes"} of a handle (hispmv_value_storage_info)."""
+        out = (C.c_int64 * 4)()
+        rc = lib.hispmv_value_storage_info(self._ctx, int(matrix_idx), out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range")
+        return {"storage": "bf16" if out[0] == _lib.HISPMV_VALUES_BF16 else "fp32", "slots_2byte": int(out[1]), "slots_4byte": int(out[2]),
+                "saved_bytes": int(out[3])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import lib, HISPMV_OK
+from ._lib import lib, HISPMV_OK, VALUE_STORAGES
 
 
 @dataclass
@@ -95,8 +95,18 @@ def _collect(p, tts=None) -> Prepared:
     return out
 
 
-def prep_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, tts=None) -> Prepared:
-    """tts: None, or the target elements per row tile of the transposed tile stream to pack as well (0 = loader's choice),
+def _set_storage(p, value_storage: str) -> None:
+    if value_storage not in VALUE_STORAGES:
+        lib.hispmv_prep_free(p)
+        raise ValueError('value_storage must be "fp32" or "bf16"')
+    if lib.hispmv_prep_set_value_storage(p, VALUE_STORAGES[value_storage]) != HISPMV_OK:
+        lib.hispmv_prep_free(p)
+        raise ValueError(lib.hispmv_prep_last_error().decode())
+
+
+def prep_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, tts=None, value_storage: str = "fp32") -> Prepared:
+    """value_storage "bf16": the prepared values (CSR, words, tile stream) are rounded to bfloat16 (hispmv_prep_set_value_storage).
+    tts: None, or the target elements per row tile of the transposed tile stream to pack as well (0 = loader's choice),
     or (target, geometry) with geometry 0 standard / 1 small / "tall" (Prepared.tts is then the list of the two column
     parts) -- see hispmv_prep_build_tts."""
     r = np.ascontiguousarray(coo_rows, dtype=np.int32)
@@ -107,6 +117,7 @@ def prep_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, tts=None
                                   C.c_void_p(v.ctypes.data), r.size, rows, cols)
     if rc != HISPMV_OK:
         raise ValueError(lib.hispmv_prep_last_error().decode())
+    _set_storage(p, value_storage)
     return _collect(p, tts)
 
 
@@ -175,9 +186,10 @@ def window_membership(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cu
     return inside, np.lexsort((np.arange(r.size), c, r))     # stable: duplicates keep their input order, as in coo_to_csr
 
 
-def device_layout_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256, on_device: int = -1) -> dict:
+def device_layout_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256, on_device: int = -1,
+                           value_storage: str = "fp32") -> dict:
     """The stream of a matrix as the device gets it (hispmv_prep_device_stream), host-only: -> dict with the host words before
-    planning (`words`), the plan (`threads`, `group_slices`, `window_floats`, `stray_floats`, `groups`, `frags`) and the device
+    planning (`words`; value_storage "bf16": with the rounded values, and the compact groups of `bytes` packed as half slices), the plan (`threads`, `group_slices`, `window_floats`, `stray_floats`, `groups`, `frags`) and the device
     arrays (`bytes` u8, `dgroups` [n,4], `stray_cols` [n_slices,64] or empty)."""
     r = np.ascontiguousarray(coo_rows, dtype=np.int32)
     c = np.ascontiguousarray(coo_cols, dtype=np.int32)
@@ -185,6 +197,7 @@ def device_layout_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int,
     p = C.c_void_p()
     if lib.hispmv_prep_from_coo(C.byref(p), C.c_void_p(r.ctypes.data), C.c_void_p(c.ctypes.data), C.c_void_p(v.ctypes.data), r.size, rows, cols) != HISPMV_OK:
         raise ValueError(lib.hispmv_prep_last_error().decode())
+    _set_storage(p, value_storage)
     try:
         d = (C.c_int64 * 8)()
         lib.hispmv_prep_dims(p, d)

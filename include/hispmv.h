@@ -154,6 +154,23 @@ int hispmv_update_values_device(hispmv_ctx* ctx, int matrix_idx, const float* d_
  * batch layout holds a second copy of the slices)}; zeros for a handle that is not updatable. */
 int hispmv_value_update_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
 
+/* ---- bf16 value storage (no reference counterpart; the 16-bit value types of rocSPARSE / hipBLASLt are the analogue) -------------
+ * Context-wide switch, default HISPMV_VALUES_FP32, may be flipped between creations: a sparse or dense handle created (COO, CSR or
+ * MatrixMarket) while it is HISPMV_VALUES_BF16 computes  y = alpha * R(A) * x + beta * bias,  where R rounds every stored value of A
+ * ONCE, at creation, to bfloat16 (nearest, ties to even; +-Inf stay, a finite value above the largest bf16 becomes Inf, NaN stays a
+ * quiet NaN; duplicated COO entries are rounded one by one).  x, bias, y, alpha, beta, every product and every sum stay fp32, in the
+ * order of an fp32 handle: the result equals, bit for bit, that of an fp32 handle created from the pre-rounded values.  Format choice
+ * and launch plan do not depend on the storage.  Where a layout has a kernel that reads 16-bit values its bytes shrink -- compact
+ * slice groups (6 -> 4 bytes per element, stray-slot groups included), dense W (4 -> 2) --; wide groups, plans without a window and
+ * the tile stream keep 32-bit slots that hold R(v).  Unknown storage or NULL context -> HISPMV_EINVAL.  Creating a handle while
+ * value updates AND bf16 storage are both on -> HISPMV_EINVAL (the value map lives in 32-bit slots). */
+#define HISPMV_VALUES_FP32 0
+#define HISPMV_VALUES_BF16 1
+int hispmv_set_value_storage(hispmv_ctx* ctx, int storage);
+/* out = {storage of the handle, value slots held in 2 bytes, value slots held in 4 bytes, device bytes the handle saves against
+ * fp32 storage}; the slices of a batch layout count again (as in hispmv_value_update_info). */
+int hispmv_value_storage_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
+
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */
 float hispmv_time_device(hispmv_ctx* ctx, int matrix_idx, const float* d_x, const float* d_bias, float* d_y,
@@ -270,10 +287,16 @@ int hispmv_prep_window_membership(const hispmv_prep* p, int n_cus, uint8_t* insi
  * outside the window}, frags = m x {col_start, len, lds_off, 0}.  counts[0..1] = n, m. */
 int hispmv_prep_apply_plan(hispmv_prep* p, int n_cus, int64_t counts[2]);
 const int32_t* hispmv_prep_groups(const hispmv_prep* p);
+/* Host-only counterpart of hispmv_set_value_storage: HISPMV_VALUES_BF16 rounds the prepared values in place (CSR and stream words;
+ * call it before hispmv_prep_apply_plan) and makes hispmv_prep_device_stream pack every compact group as HALF slices -- 1024 x 16-byte
+ * pieces {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16} of four consecutive elements (bf16 values, the compact metas),
+ * 4096 B per slice, groups[].w |= 4; hispmv_prep_build_tts then carries the rounded values.  Back to HISPMV_VALUES_FP32 restores the
+ * layout, not the values. */
+int hispmv_prep_set_value_storage(hispmv_prep* p, int storage);
 /* The planned stream in its DEVICE LAYOUT (hispmv_amd/csrc/hispmv_format.h; call hispmv_prep_apply_plan first): counts = {bytes, groups,
  * compact slices, slices of groups with stray slots, LDS floats of the wavefronts' stray areas, LDS floats of the x window}.  Arrays:
  * 0 = the slices, group after group (compact: 1024 x fp32 then 1024 x u16 {rowEnd:1 | LDS index:15}; wide: 1024 x u32 metas);
- * 1 = groups x {frag_begin, frag_count, offset of the group's first slice / 2048, 1 = compact | 2 = stray slots}; 2 = slices x 64 stray
+ * 1 = groups x {frag_begin, frag_count, offset of the group's first slice / 2048, 1 = compact | 2 = stray slots | 4 = half}; 2 = slices x 64 stray
  * columns (0xffffffff = unused; empty when no group has stray slots).  For tests: the packer without a device. */
 int hispmv_prep_device_stream(hispmv_prep* p, int64_t counts[6]);
 const void* hispmv_prep_device_array(const hispmv_prep* p, int which);

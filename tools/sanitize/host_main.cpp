@@ -72,6 +72,15 @@ int main(int argc, char** argv) {
             std::vector<int32_t> rh, ch2; std::vector<float> vh;
             for (int i = 0; i < rows; ++i) for (int k = 0; k < per / 2; ++k) { rh.push_back(i); ch2.push_back((i + (k * 37) % 3000) % rows); vh.push_back(1.f); }
             Csr mc = coo_to_csr(rows, rows, (long)rh.size(), rh.data(), ch2.data(), vh.data());
+            {   // bf16 value storage: the same decision, every compact group packed as half slices (first and batch layout)
+                Csr mh = mc;
+                FormatOptions oh;
+                oh.half_values = true;
+                FormatChoice chh = choose_format(std::move(mh), nullptr, 256, oh);
+                const DeviceStream& dh = chh.parts[0].dstream;
+                if (!dh.half_values || dh.compact_slices == 0 || (long long)dh.bytes.size() != dh.n_bytes) { std::puts("half slices: not packed"); return 1; }
+                std::printf("stencil with half slices: %lld compact slices, %lld bytes\n", (long long)dh.compact_slices, (long long)dh.n_bytes);
+            }
             FormatOptions o;
             FormatChoice ch = choose_format(std::move(mc), nullptr, 256, o);
             std::printf("stencil through choose_format: %d threads, %d slices per workgroup, batch layout %s (%d slices per workgroup)\n", ch.parts[0].plan.block_threads,
