@@ -376,7 +376,6 @@ HISPMV_API int hispmv_create(hispmv_ctx** out, const char* xclbin_path, int devi
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(nullptr, HISPMV_EDEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(nullptr, e, "hipSetDevice");
-    if ((e = prepare_spmv_kernels()) != hipSuccess) return hip_fail(nullptr, e, "hipFuncSetAttribute(max dynamic LDS)");
 
     auto c = std::make_unique<hispmv_ctx>();
     c->device = device_id;
@@ -667,7 +666,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
             // apps/model_test.py: 16.7 against 15.1 us alone, 8 vectors 74 against 58 us: that layer's tiles are latency chains
             // of 8 K elements, not gather-bound)
             d.xlds_floats = (m.cols <= kTtsXldsMax && std::getenv("HISPMV_TTS_XLDS")) ? ((m.cols + 63) & ~63) : 0;
-            if (((size_t)d.acc_floats + (size_t)d.staging_floats + 64) * 4 > 160 * 1024 - 256) return fail(c, HISPMV_EINVAL, "internal: tile stream exceeds the LDS of a CU");
+            if (tts_tile_lds_bytes(d) > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: tile stream exceeds the LDS of a CU");
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             p.tts = TtsStream{};
           }
@@ -754,15 +753,15 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                 d.group_slices = p.plan.group_slices; d.block_threads = p.plan.block_threads;
                 d.lds_floats = p.plan.lds_floats + p.dstream.stray_floats;        // the x window + the wavefronts' stray areas behind it
                 d.ytile_floats = std::min(kSliceElems, (max_rows + 63) & ~63);
-                const size_t lds_plain = (size_t)(d.lds_floats + d.ytile_floats * (d.block_threads / 64)) * 4;
-                if (lds_plain > 160 * 1024 - 256) return fail(c, HISPMV_EINVAL, "internal: launch plan exceeds the LDS of a CU");
-                const bool mailbox_fits = lds_plain + (size_t)d.group_slices * 8 <= 160 * 1024 - 256;   // look-back: 8 B per slice of a group
+                const size_t lds_plain = slice_lds_bytes(d);
+                if (lds_plain > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: launch plan exceeds the LDS of a CU");
+                const bool mailbox_fits = slice_lds_bytes(d, 1, true) <= kDynLdsMax;
                 d.n_fix_short = (int32_t)p.fix_short.size(); d.n_fix_long = (int32_t)p.fix_long.size();
                 d.rows = m.rows; d.cols = m.cols;
                 // co-residency of the whole grid: workgroups per CU by LDS and waves (conservative: <= 4 blocks,
                 // <= 16 waves per CU; MI355X_MICROARCH.md "Residency")
                 const int lds_b = std::max(1, (int)lds_plain + 64);
-                const int per_cu = std::max(1, std::min({4, (160 * 1024) / lds_b, 16 / (d.block_threads / 64)}));
+                const int per_cu = std::max(1, std::min({4, kLdsPerCu / lds_b, 16 / (d.block_threads / 64)}));
                 const bool resident = d.n_groups <= (int64_t)c->n_cus * per_cu;
                 const bool one_round = d.group_slices <= d.block_threads / 64;
                 // carry_mode: 0 fix-up launch; 1 look-back for every plan, workgroups in blockIdx order (relies on the
@@ -822,7 +821,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                     b.has_strays = p.batch_dstream.stray_floats > 0;
                     b.has_half = p.batch_dstream.half_values && p.batch_dstream.compact_slices > 0;
                     b.lookback = false; b.use_ticket = false;
-                    if ((size_t)(b.lds_floats + b.ytile_floats * (b.block_threads / 64)) * 4 <= 160 * 1024 - 256) { p.batch_dev = b; p.has_batch_dev = true; }
+                    if (slice_lds_bytes(b) <= kDynLdsMax) { p.batch_dev = b; p.has_batch_dev = true; }
                 }
             }
         }

@@ -221,7 +221,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                 for (uint8_t t : l.item_tiles) ok = ok && t == 1;
                 for (const SpmvDeviceMatrix* d : l.parts) {
                     ok = ok && (d->block_threads == 1024 || d->block_threads == 256);
-                    const size_t one = ((size_t)d->lds_floats + (size_t)d->ytile_floats * (d->block_threads / 64)) * sizeof(float);
+                    const size_t one = slice_lds_bytes(*d);
                     lds = std::max(lds, d->block_threads == 256 ? 4 * one : one);
                     strays = strays || d->has_strays;
                     // a handle with half groups (bf16 value storage): the step kernel has no instantiation that reads them -- the call
@@ -238,7 +238,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                 }
             }
         }
-        ok = ok && lds <= 160 * 1024 - 256;
+        ok = ok && lds <= kDynLdsMax;
         if (ok) {
             struct QItem { uint32_t a, b; double cost; int cls; };      // cls 0 = slice items, 1 = tiles
             std::vector<QItem> q[2];

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
+#include <cstddef>
 #include <cstdint>
 
 namespace hispmv {
@@ -114,8 +115,17 @@ struct MultiPrefix {
 
 constexpr int kMaxBatch = 4;                // vectors one pass of the batched slice kernel takes (carry holds kMaxBatch * n_slices)
 
-// Once per process/device before the first launch (raises the dynamic-LDS limit of the slice kernels).
-hipError_t prepare_spmv_kernels();
+// The LDS of a CU, and the dynamic LDS a launch may ask for: the rest is a reserve for the few bytes of static LDS the
+// kernels hold.  (The launchers raise every kernel's limit to it on the kernel's first launch.)  The step kernel alone may
+// take all of it: its ticket word is the last 4 bytes of its dynamic LDS.
+constexpr int kLdsPerCu = 160 * 1024;
+constexpr int kDynLdsMax = kLdsPerCu - 256;
+// Dynamic LDS of a slice launch: the x window of `nv` vectors (+ the wavefronts' stray areas behind it), the row-total tile of
+// every wavefront and -- look-back -- the mailbox of a group, 8 B per slice; of a tile-stream launch: accumulators, staging, 64 tails.
+inline size_t slice_lds_bytes(const SpmvDeviceMatrix& m, int nv = 1, bool mailbox = false) {
+    return ((size_t)m.lds_floats * nv + (size_t)m.ytile_floats * (m.block_threads / 64)) * sizeof(float) + (mailbox ? (size_t)m.group_slices * 8 : 0);
+}
+inline size_t tts_tile_lds_bytes(const TtsDeviceMatrix& m) { return ((size_t)m.acc_floats + (size_t)m.staging_floats + 64) * sizeof(float); }
 
 // y = alpha*A*x + beta*bias.  Two launches on `stream`: the slice kernel, then (if any row is
 // shared between slices) the carry fix-up.  Returns the first HIP error.
@@ -174,7 +184,6 @@ hipError_t launch_tts_multi(const TtsEntry* entries, int n, const uint8_t* item_
 struct StepArgs { const MultiEntry* slice_table; const TtsEntry* tts_table; const int2* items; unsigned* sync; unsigned n_items; float alpha; int pad, ticket_word; };
 hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_tts_table, const void* d_items, unsigned n_items,
                             unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, float alpha, hipStream_t stream);
-size_t tts_tile_lds_bytes(const TtsDeviceMatrix& m);
 
 // Dense overlay: y = alpha*W*x + beta*bias, W row-major rows x cols.
 // bf16: W is rows x cols bfloat16 (bf16 value storage): fp32 x, products and sums; 16-byte loads of W when cols % 8 == 0.

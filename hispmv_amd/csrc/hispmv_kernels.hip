@@ -22,6 +22,8 @@
 #include "hispmv_kernels.h"
 #include <algorithm>
 #include <cstdlib>
+#include <mutex>
+#include <type_traits>
 #include <vector>
 
 #ifndef HISPMV_TTS_EXPERIMENT
@@ -1194,73 +1196,146 @@ __global__ __launch_bounds__(256) void spmv_fixup_long_kernel(const int4* __rest
     if (lane == 0) y[f.x] += alpha * s;
 }
 
-template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK>
-static void launch_slices(const SpmvDeviceMatrix& m, const LookbackArgs& lb, const float* x, const float* bias, float* y,
-                          float alpha, float beta, hipStream_t stream) {
-    const size_t lds = ((USE_LDS ? (size_t)m.lds_floats : 0) + (size_t)m.ytile_floats * (m.block_threads / 64)) * sizeof(float) +
-                       (LOOKBACK ? (size_t)m.group_slices * 8 : 0);
-    if constexpr (USE_LDS) {
-        if (m.has_half) {      // (bf16 value storage: the kernel that reads half groups, with the stray code only where the handle has stray slots)
-            if (!LOOKBACK && m.has_strays)
-                hipLaunchKernelGGL((spmv_slices_half_kernel<HAS_BETA, false, true>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
-                                   (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
-                                   (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, lb);
-            else
-                hipLaunchKernelGGL((spmv_slices_half_kernel<HAS_BETA, LOOKBACK, false>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
-                                   (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
-                                   (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, lb);
-            return;
+// ---------------------------------------------------------------------------
+// The launch layer (host code from here on, between the kernel families): every launch of this file goes through
+// launch<Kernel>() or launch_in_graph<Kernel, ALPHA_AT>().  Per instantiation, on its first launch: the dynamic-LDS
+// limit is raised (LDS_LIMIT > 0) and -- launch_in_graph: kernels that can sit in a captured batch call -- the
+// kernel enters the registry graph_set_alpha() patches from, with the position of its alpha argument and its
+// argument count.  Every later launch costs the test of one flag.
+// ---------------------------------------------------------------------------
+constexpr int kNotInGraphs = -2;    // ALPHA_AT of plain launches: not registered, graph_set_alpha refuses the kernel
+constexpr int kNoAlpha = -1;        // registered, nothing to patch
+
+struct GraphKernel { const void* func; int alpha_at, n_args; };
+struct KernelRegistry { std::mutex mu; std::vector<GraphKernel> kernels; };
+static KernelRegistry& kernel_registry() { static KernelRegistry r; return r; }
+
+static bool find_graph_kernel(const void* func, GraphKernel& out) {
+    KernelRegistry& r = kernel_registry();
+    std::lock_guard<std::mutex> g(r.mu);
+    for (const GraphKernel& k : r.kernels) if (k.func == func) { out = k; return true; }
+    return false;
+}
+static void register_graph_kernel(const GraphKernel& k) {
+    GraphKernel known;
+    if (find_graph_kernel(k.func, known)) return;      // (two threads in the same first launch)
+    KernelRegistry& r = kernel_registry();
+    std::lock_guard<std::mutex> g(r.mu);
+    r.kernels.push_back(k);
+}
+
+// The status a launcher returns must be that of its own launches, not a stale one of the thread (e.g. PyTorch's pointer
+// queries): the public launchers start here, and every launch below reports its own status.
+static inline void clear_stale_error() { (void)hipGetLastError(); }
+
+template <auto Kernel, int LDS_LIMIT = 0, int ALPHA_AT = kNotInGraphs, class... Args>
+static hipError_t launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    if constexpr (LDS_LIMIT > 0 || ALPHA_AT != kNotInGraphs) {
+        static bool ready = false;      // per instantiation
+        if (!ready) {
+            if constexpr (LDS_LIMIT > 0) {
+                const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
+                if (e != hipSuccess) return e;
+            }
+            if constexpr (ALPHA_AT != kNotInGraphs) {
+                static_assert(ALPHA_AT < (int)sizeof...(Args), "alpha position outside the argument list");
+                register_graph_kernel({(const void*)Kernel, ALPHA_AT, (int)sizeof...(Args)});
+            }
+            ready = true;
         }
     }
-    if (USE_LDS && !LOOKBACK && m.has_strays)       // (stray slots: the instantiation that fetches them; never with look-back, hispmv_abi.cpp)
-        hipLaunchKernelGGL((spmv_slices_kernel<HAS_BETA, USE_LDS && !LOOKBACK, false, USE_LDS && !LOOKBACK>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
-                           (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
-                           (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, lb);
-    else
-    hipLaunchKernelGGL((spmv_slices_kernel<HAS_BETA, USE_LDS, LOOKBACK>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
-                       (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
-                       (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, lb);
+    Kernel<<<grid, block, lds_bytes, stream>>>(args...);
+    return hipGetLastError();
+}
+template <auto Kernel, int ALPHA_AT, int LDS_LIMIT = 0, class... Args>
+static hipError_t launch_in_graph(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    return launch<Kernel, LDS_LIMIT, ALPHA_AT>(grid, block, lds_bytes, stream, args...);
 }
 
-template <bool HAS_BETA, bool USE_LDS>
-static void launch_slices2(const SpmvDeviceMatrix& m, const LookbackArgs& lb, const float* x, const float* bias, float* y,
-                           float alpha, float beta, hipStream_t stream) {
-    if (m.lookback) launch_slices<HAS_BETA, USE_LDS, true>(m, lb, x, bias, y, alpha, beta, stream);
-    else launch_slices<HAS_BETA, USE_LDS, false>(m, lb, x, bias, y, alpha, beta, stream);
+// Runtime bools -> template arguments: f(std::bool_constant<b[0]>{}, std::bool_constant<b[1]>{}, ...).  A combination
+// that has no kernel is ruled out inside f with `if constexpr`, so that it is never instantiated.
+template <size_t I = 0, size_t N, class F, class... C>
+static hipError_t with_bools(const bool (&b)[N], F&& f, C... c) {
+    if constexpr (I == N) return f(c...);
+    else return b[I] ? with_bools<I + 1>(b, f, c..., std::true_type{}) : with_bools<I + 1>(b, f, c..., std::false_type{});
+}
+// ... and a vector count out of the listed ones: f(std::integral_constant<int, nv>{}); any other count is an error.
+template <int... NV, class F>
+static hipError_t with_nv(int nv, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((nv == NV && ((e = f(std::integral_constant<int, NV>{})), true)) || ...);
+    return e;
 }
 
-hipError_t prepare_spmv_kernels() {
-    // the x window may use (almost) the whole 160 KiB LDS of a CU
-    hipError_t e;
-    const int max_lds = 160 * 1024 - 256;   // the kernels also hold a few bytes of static LDS
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)spmv_slices_half_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    return hipSuccess;
+// Where each entry's workgroups begin in the grid of a multi-matrix launch; both return the grid size.
+template <class F>
+static long long plain_prefix(MultiPrefix& px, int n, F&& workgroups) {
+    px.n = n;
+    long long g = 0;
+    for (int i = 0; i < n; ++i) { px.begin[i] = g; g += workgroups(i); }
+    px.begin[n] = g;
+    return g;
+}
+// ... with ITEMS of 1, 2, 4 .. max_tiles consecutive entries (hispmv_kernels.h: MultiPrefix): a set of several is pinned to
+// XCDs -- it starts at a multiple of 8 and takes as many rounds of 8 workgroups as its largest member needs.  -1: malformed items.
+template <class F>
+static long long pinned_prefix(MultiPrefix& px, int n, const uint8_t* item_tiles, int n_items, int max_tiles, F&& workgroups) {
+    if (!item_tiles) n_items = n;
+    px.n = n_items;
+    long long g = 0;
+    int e = 0;
+    for (int k = 0; k < n_items; ++k) {
+        const int tiles = item_tiles ? item_tiles[k] : 1;
+        if (tiles < 1 || tiles > max_tiles || (tiles & (tiles - 1)) != 0 || e + tiles > n) return -1;
+        if (tiles > 1) g = (g + 7) & ~7LL;
+        px.begin[k] = g; px.first[k] = (uint8_t)e; px.tiles[k] = (uint8_t)tiles;
+        long long most = 0;
+        for (int q = 0; q < tiles; ++q, ++e) most = std::max<long long>(most, workgroups(e));
+        const int per = 8 / tiles;
+        g += tiles == 1 ? most : 8 * ((most + per - 1) / per);
+    }
+    if (e != n) return -1;
+    px.begin[n_items] = g;
+    return g;
+}
+// Every multi-matrix kernel takes (table, prefix, alpha).
+template <auto Kernel, int LDS_LIMIT = 0, class Entry>
+static hipError_t launch_multi(long long grid, int threads, size_t lds_bytes, hipStream_t stream, const Entry* d_table, const MultiPrefix& px, float alpha) {
+    if (grid <= 0) return hipSuccess;
+    return launch_in_graph<Kernel, 2, LDS_LIMIT>(dim3((unsigned)grid), dim3(threads), lds_bytes, stream, d_table, px, alpha);
+}
+
+// The two fix-up launches: y[row] += alpha * chain, for `nv` vectors (grid.y) whose carries / rows lie the strides apart.
+static hipError_t launch_short_chains(const int4* fix, int n, const float* carry, float* y, float alpha, hipStream_t stream,
+                                     int nv = 1, long long carry_stride = 0, long long y_stride = 0) {
+    if (n <= 0) return hipSuccess;
+    return launch<spmv_fixup_short_kernel>(dim3((n + 255) / 256, nv), dim3(256), 0, stream, fix, n, carry, y, alpha, carry_stride, y_stride);
+}
+static hipError_t launch_long_chains(const int4* fix, int n, const float* carry, float* y, float alpha, hipStream_t stream,
+                                    int nv = 1, long long carry_stride = 0, long long y_stride = 0) {
+    if (n <= 0) return hipSuccess;
+    return launch_in_graph<spmv_fixup_long_kernel, 4>(dim3((n + 3) / 4, nv), dim3(256), 0, stream, fix, n, carry, y, alpha, carry_stride, y_stride);
+}
+
+// One slice grid of a single matrix: `last` is the look-back block or the bias stride of the batched kernels.
+template <auto Kernel, class Last>
+static hipError_t launch_slice_grid(const SpmvDeviceMatrix& m, size_t lds_bytes, const float* x, const float* bias, float* y,
+                                    float alpha, float beta, hipStream_t stream, const Last& last) {
+    return launch<Kernel, kDynLdsMax>(dim3((unsigned)m.n_groups), dim3(m.block_threads), lds_bytes, stream,
+                                      (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
+                                      (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, last);
 }
 
 hipError_t launch_spmv(SpmvDeviceMatrix& m_in, const float* x, const float* bias, float* y,
                        float alpha, float beta, hipStream_t stream, bool fixup_only) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     // fixup_only (FpgaHandle::linear): the carry hand-off through the fix-up launch even where a single launch would merge
     // the cut rows in-kernel -- the summation order of the batched kernels, so that every vector of a `linear` call has
     // the same bits whatever the number of vectors in the call
     SpmvDeviceMatrix forced;
     if (fixup_only && m_in.lookback) { forced = m_in; forced.lookback = false; }
     SpmvDeviceMatrix& m = (fixup_only && m_in.lookback) ? forced : m_in;
+    hipError_t e;
     if (m.n_slices > 0) {
         if (m.n_groups <= 0 || m.n_groups > 0x7fffffffLL) return hipErrorInvalidValue;
         LookbackArgs lb{};
@@ -1272,50 +1347,20 @@ hipError_t launch_spmv(SpmvDeviceMatrix& m_in, const float* x, const float* bias
             lb.epoch = (unsigned)(m.launches % 0xffffffffull) + 1u;   // never 0: tag 0 means "never written"
             m.launches++;
         }
-        const bool lds = m.lds_floats > 0;
-        if (beta != 0.0f) { if (lds) launch_slices2<true, true>(m, lb, x, bias, y, alpha, beta, stream); else launch_slices2<true, false>(m, lb, x, bias, y, alpha, beta, stream); }
-        else              { if (lds) launch_slices2<false, true>(m, lb, x, bias, y, alpha, beta, stream); else launch_slices2<false, false>(m, lb, x, bias, y, alpha, beta, stream); }
-        if (m.lookback) return hipGetLastError();
+        // stray slots and half groups (bf16 value storage) exist only in plans with a window, stray slots never with
+        // look-back (hispmv_abi.cpp); a handle with half groups takes the kernel of its own that reads them
+        const bool window = m.lds_floats > 0;
+        e = with_bools({beta != 0.0f, window, m.lookback, window && !m.lookback && m.has_strays, window && m.has_half},
+                       [&](auto HAS_BETA, auto USE_LDS, auto LOOKBACK, auto STRAYS, auto HALF) {
+            const size_t lds = slice_lds_bytes(m, 1, LOOKBACK());
+            if constexpr ((STRAYS() && (LOOKBACK() || !USE_LDS())) || (HALF() && !USE_LDS())) return hipErrorInvalidValue;
+            else if constexpr (HALF()) return launch_slice_grid<spmv_slices_half_kernel<HAS_BETA(), LOOKBACK(), STRAYS()>>(m, lds, x, bias, y, alpha, beta, stream, lb);
+            else return launch_slice_grid<spmv_slices_kernel<HAS_BETA(), USE_LDS(), LOOKBACK(), STRAYS()>>(m, lds, x, bias, y, alpha, beta, stream, lb);
+        });
+        if (e != hipSuccess || m.lookback) return e;
     }
-    if (m.n_fix_short > 0)
-        hipLaunchKernelGGL(spmv_fixup_short_kernel, dim3((m.n_fix_short + 255) / 256), dim3(256), 0, stream,
-                           m.fix_short, m.n_fix_short, m.carry, y, alpha, 0LL, 0LL);
-    if (m.n_fix_long > 0)
-        hipLaunchKernelGGL(spmv_fixup_long_kernel, dim3((m.n_fix_long + 3) / 4), dim3(256), 0, stream,
-                           m.fix_long, m.n_fix_long, m.carry, y, alpha, 0LL, 0LL);
-    return hipGetLastError();
-}
-
-template <bool HAS_BETA, bool USE_LDS, int NV>
-static hipError_t launch_batched(const SpmvDeviceMatrix& m, const float* x, const float* bias, int bias_stride, float* y,
-                                 float alpha, float beta, hipStream_t stream) {
-    const size_t lds = ((USE_LDS ? (size_t)m.lds_floats * NV : 0) + (size_t)m.ytile_floats * (m.block_threads / 64)) * sizeof(float);
-    if constexpr (USE_LDS) {
-        if (m.has_half) {      // (bf16 value storage)
-            static bool raised_half = false;
-            if (!raised_half) {
-                hipError_t e = hipFuncSetAttribute((const void*)spmv_slices_batched_half_kernel<HAS_BETA, NV>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-                if (e != hipSuccess) return e;
-                raised_half = true;
-            }
-            hipLaunchKernelGGL((spmv_slices_batched_half_kernel<HAS_BETA, NV>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
-                               (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
-                               (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, bias_stride);
-            return hipGetLastError();
-        }
-    }
-    static bool raised = false;      // per instantiation
-    if (!raised) {
-        hipError_t e = hipFuncSetAttribute((const void*)spmv_slices_batched_kernel<HAS_BETA, USE_LDS, NV>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        if (e != hipSuccess) return e;
-        raised = true;
-    }
-    hipLaunchKernelGGL((spmv_slices_batched_kernel<HAS_BETA, USE_LDS, NV>), dim3((unsigned)m.n_groups), dim3(m.block_threads), lds, stream,
-                       (const char*)m.words, m.hdr, m.groups, m.frags, x, bias, y, m.carry, alpha, beta,
-                       (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows, bias_stride);
-    return hipGetLastError();
+    if ((e = launch_short_chains(m.fix_short, m.n_fix_short, m.carry, y, alpha, stream)) != hipSuccess) return e;
+    return launch_long_chains(m.fix_long, m.n_fix_long, m.carry, y, alpha, stream);
 }
 
 int spmv_batch_width(const SpmvDeviceMatrix& m, int64_t vecs) {
@@ -1324,155 +1369,107 @@ int spmv_batch_width(const SpmvDeviceMatrix& m, int64_t vecs) {
     for (int nv = kMaxBatch; nv >= 2; nv >>= 1) {
         if (nv > vecs) continue;
         if ((int64_t)m.cols * nv >= (1 << 30) || (int64_t)m.rows * nv >= (1 << 30)) continue;
-        const size_t lds = ((size_t)m.lds_floats * nv + (size_t)m.ytile_floats * (m.block_threads / 64)) * sizeof(float);
-        if (lds <= 160 * 1024 - 256) return nv;
+        if (slice_lds_bytes(m, nv) <= kDynLdsMax) return nv;
     }
     return 1;
 }
 
 hipError_t launch_spmv_batched(SpmvDeviceMatrix& m, int nv, const float* x, const float* bias, int bias_stride, float* y,
                                float alpha, float beta, hipStream_t stream) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     if (nv != 2 && nv != 4) return hipErrorInvalidValue;
+    if (beta == 0.0f) bias = y;      // never read; keeps the buffer descriptor well-formed
+    hipError_t e;
     if (m.n_slices > 0) {
         if (m.n_groups <= 0 || m.n_groups > 0x7fffffffLL) return hipErrorInvalidValue;
-        const bool lds = m.lds_floats > 0;
-        hipError_t e;
-        const bool hb = beta != 0.0f;
-        if (!hb) bias = y;      // never read; keeps the buffer descriptor well-formed
-        if (nv == 4) e = hb ? (lds ? launch_batched<true, true, 4>(m, x, bias, bias_stride, y, alpha, beta, stream)
-                                   : launch_batched<true, false, 4>(m, x, bias, bias_stride, y, alpha, beta, stream))
-                            : (lds ? launch_batched<false, true, 4>(m, x, bias, bias_stride, y, alpha, beta, stream)
-                                   : launch_batched<false, false, 4>(m, x, bias, bias_stride, y, alpha, beta, stream));
-        else         e = hb ? (lds ? launch_batched<true, true, 2>(m, x, bias, bias_stride, y, alpha, beta, stream)
-                                   : launch_batched<true, false, 2>(m, x, bias, bias_stride, y, alpha, beta, stream))
-                            : (lds ? launch_batched<false, true, 2>(m, x, bias, bias_stride, y, alpha, beta, stream)
-                                   : launch_batched<false, false, 2>(m, x, bias, bias_stride, y, alpha, beta, stream));
+        const bool window = m.lds_floats > 0;
+        e = with_nv<2, 4>(nv, [&](auto NV_) {
+            constexpr int NV = NV_();
+            return with_bools({beta != 0.0f, window, window && m.has_half}, [&](auto HAS_BETA, auto USE_LDS, auto HALF) {
+                const size_t lds = slice_lds_bytes(m, NV);
+                if constexpr (HALF() && !USE_LDS()) return hipErrorInvalidValue;
+                else if constexpr (HALF()) return launch_slice_grid<spmv_slices_batched_half_kernel<HAS_BETA(), NV>>(m, lds, x, bias, y, alpha, beta, stream, bias_stride);
+                else return launch_slice_grid<spmv_slices_batched_kernel<HAS_BETA(), USE_LDS(), NV>>(m, lds, x, bias, y, alpha, beta, stream, bias_stride);
+            });
+        });
         if (e != hipSuccess) return e;
     }
-    if (m.n_fix_short > 0)     // one fix-up launch for all vectors of the pass (grid.y = vector)
-        hipLaunchKernelGGL(spmv_fixup_short_kernel, dim3((m.n_fix_short + 255) / 256, nv), dim3(256), 0, stream,
-                           m.fix_short, m.n_fix_short, m.carry, y, alpha, (long long)m.n_slices, (long long)m.rows);
-    if (m.n_fix_long > 0)
-        hipLaunchKernelGGL(spmv_fixup_long_kernel, dim3((m.n_fix_long + 3) / 4, nv), dim3(256), 0, stream,
-                           m.fix_long, m.n_fix_long, m.carry, y, alpha, (long long)m.n_slices, (long long)m.rows);
-    return hipGetLastError();
+    // one fix-up launch for all vectors of the pass (grid.y = vector)
+    if ((e = launch_short_chains(m.fix_short, m.n_fix_short, m.carry, y, alpha, stream, nv, m.n_slices, m.rows)) != hipSuccess) return e;
+    return launch_long_chains(m.fix_long, m.n_fix_long, m.carry, y, alpha, stream, nv, m.n_slices, m.rows);
 }
 
 hipError_t launch_spmv_multi(const SpmvDeviceMatrix* const* parts, int n, const uint8_t* item_tiles, int n_items,
                              const MultiEntry* d_table, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     if (n <= 0) return hipSuccess;
     if (n > kMultiMax) return hipErrorInvalidValue;
-    if (!item_tiles) n_items = n;
-    MultiPrefix px{};
-    px.n = n_items;
-    long long g = 0;
-    size_t lds = 0;
     const int threads = parts[0]->block_threads;
-    int e = 0;
-    for (int k = 0; k < n_items; ++k) {
-        const int tiles = item_tiles ? item_tiles[k] : 1;
-        if (tiles != 1 && tiles != 2 && tiles != 4 && tiles != 8) return hipErrorInvalidValue;
-        if (e + tiles > n) return hipErrorInvalidValue;
-        if (tiles > 1) g = (g + 7) & ~7LL;                 // a pinned set starts at a multiple of 8
-        px.begin[k] = g; px.first[k] = (uint8_t)e; px.tiles[k] = (uint8_t)tiles;
-        long long most = 0;
-        for (int q = 0; q < tiles; ++q, ++e) {
-            const SpmvDeviceMatrix& m = *parts[e];
-            if (m.block_threads != threads || m.n_groups < 0) return hipErrorInvalidValue;
-            most = std::max<long long>(most, m.n_slices > 0 ? m.n_groups : 0);
-            lds = std::max(lds, ((size_t)m.lds_floats + (size_t)m.ytile_floats * (threads / 64)) * sizeof(float));
-        }
-        if (tiles == 1) g += most;
-        else { const int per = 8 / tiles; g += 8 * ((most + per - 1) / per); }
-    }
-    if (e != n) return hipErrorInvalidValue;
-    px.begin[n_items] = g;
-    if (g > 0x7fffffffLL) return hipErrorInvalidValue;
-    static bool raised = false;
-    if (!raised) {
-        hipError_t err;
-        if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
-        if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
-        if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_half_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
-        if ((err = hipFuncSetAttribute((const void*)spmv_slices_multi_half_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return err;
-        raised = true;
-    }
+    size_t lds = 0;
     bool strays = false;          // (a launch with a stray-slot part takes the instantiation that fetches them; hispmv_batch.cpp keeps such parts in grids of their own)
-    for (int i = 0; i < n; ++i) strays = strays || parts[i]->has_strays;
     bool half = false;            // (... and one with a half group -- bf16 value storage -- the kernel that reads them)
-    for (int i = 0; i < n; ++i) half = half || parts[i]->has_half;
-    if (g > 0 && half && strays) hipLaunchKernelGGL(spmv_slices_multi_half_kernel<true>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
-    else if (g > 0 && half) hipLaunchKernelGGL(spmv_slices_multi_half_kernel<false>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
-    else if (g > 0 && strays) hipLaunchKernelGGL(spmv_slices_multi_kernel<true>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
-    else if (g > 0) hipLaunchKernelGGL(spmv_slices_multi_kernel<false>, dim3((unsigned)g), dim3(threads), lds, stream, d_table, px, alpha);
-    return hipGetLastError();
+    for (int i = 0; i < n; ++i) {
+        const SpmvDeviceMatrix& m = *parts[i];
+        if (m.block_threads != threads || m.n_groups < 0) return hipErrorInvalidValue;
+        lds = std::max(lds, slice_lds_bytes(m));
+        strays = strays || m.has_strays;
+        half = half || m.has_half;
+    }
+    MultiPrefix px{};
+    const long long g = pinned_prefix(px, n, item_tiles, n_items, 8, [&](int e) { return parts[e]->n_slices > 0 ? (long long)parts[e]->n_groups : 0LL; });
+    if (g < 0 || g > 0x7fffffffLL) return hipErrorInvalidValue;
+    return with_bools({half, strays}, [&](auto HALF, auto STRAYS) {
+        if constexpr (HALF()) return launch_multi<spmv_slices_multi_half_kernel<STRAYS()>, kDynLdsMax>(g, threads, lds, stream, d_table, px, alpha);
+        else return launch_multi<spmv_slices_multi_kernel<STRAYS()>, kDynLdsMax>(g, threads, lds, stream, d_table, px, alpha);
+    });
 }
 
 hipError_t launch_merge_parts(float* y, const float* parts, int n_parts, int64_t part_stride, int32_t rows, int nv,
                               int64_t y_stride, int64_t vec_stride, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n_parts <= 0 || rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(spmv_merge_parts_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)nv), dim3(256), 0, stream,
-                       y, parts, n_parts, (long long)part_stride, rows, (long long)y_stride, (long long)vec_stride);
-    return hipGetLastError();
+    return launch<spmv_merge_parts_kernel>(dim3((unsigned)((rows + 255) / 256), (unsigned)nv), dim3(256), 0, stream,
+                                           y, parts, n_parts, (long long)part_stride, rows, (long long)y_stride, (long long)vec_stride);
 }
 
 hipError_t launch_merge_multi(const int32_t* rows, int n, const MultiMergeEntry* d_table, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n <= 0) return hipSuccess;
     if (n > kMultiMax) return hipErrorInvalidValue;
     MultiPrefix px{};
-    px.n = n;
-    long long b = 0;
-    for (int i = 0; i < n; ++i) { px.begin[i] = b; b += (rows[i] + 255) / 256; }
-    px.begin[n] = b;
-    if (b > 0) hipLaunchKernelGGL(spmv_merge_multi_kernel, dim3((unsigned)b), dim3(256), 0, stream, d_table, px);
-    return hipGetLastError();
+    const long long b = plain_prefix(px, n, [&](int i) { return (rows[i] + 255) / 256; });
+    if (b <= 0) return hipSuccess;
+    return launch_in_graph<spmv_merge_multi_kernel, kNoAlpha>(dim3((unsigned)b), dim3(256), 0, stream, d_table, px);
 }
 
 hipError_t launch_fixup_long(const SpmvDeviceMatrix& m, float* y, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (m.n_fix_long > 0)
-        hipLaunchKernelGGL(spmv_fixup_long_kernel, dim3((m.n_fix_long + 3) / 4), dim3(256), 0, stream, m.fix_long, m.n_fix_long, m.carry, y, alpha, 0LL, 0LL);
-    return hipGetLastError();
+    clear_stale_error();
+    return launch_long_chains(m.fix_long, m.n_fix_long, m.carry, y, alpha, stream);
 }
 
 hipError_t launch_tail_multi(const int32_t* fix_counts, int n_fix, const MultiFixEntry* d_fix_table, const int32_t* merge_rows, int n_merge,
                              const TailMergeEntry* d_merge_table, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n_fix > kMultiMax || n_merge > kMultiMax) return hipErrorInvalidValue;
     MultiPrefix fx{}, mx{};
-    fx.n = n_fix; mx.n = n_merge;
-    long long fb = 0, mb = 0;
-    for (int i = 0; i < n_fix; ++i) { fx.begin[i] = fb; fb += (fix_counts[i] + 255) / 256; }
-    fx.begin[n_fix] = fb;
-    for (int i = 0; i < n_merge; ++i) { mx.begin[i] = mb; mb += (merge_rows[i] + 255) / 256; }
-    mx.begin[n_merge] = mb;
+    const long long fb = plain_prefix(fx, n_fix, [&](int i) { return (fix_counts[i] + 255) / 256; });
+    const long long mb = plain_prefix(mx, n_merge, [&](int i) { return (merge_rows[i] + 255) / 256; });
     if (fb + mb > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (fb + mb > 0) hipLaunchKernelGGL(spmv_tail_multi_kernel, dim3((unsigned)(fb + mb)), dim3(256), 0, stream, d_fix_table, fx, d_merge_table, mx, alpha);
-    return hipGetLastError();
+    if (fb + mb <= 0) return hipSuccess;
+    return launch_in_graph<spmv_tail_multi_kernel, 4>(dim3((unsigned)(fb + mb)), dim3(256), 0, stream, d_fix_table, fx, d_merge_table, mx, alpha);
 }
 
 hipError_t launch_fixup_multi(const SpmvDeviceMatrix* const* parts, float* const* ys, int n, const MultiFixEntry* d_fix_table,
                               float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n <= 0) return hipSuccess;
     if (n > kMultiMax) return hipErrorInvalidValue;
     MultiPrefix fx{};
-    fx.n = n;
-    long long fb = 0;
-    for (int i = 0; i < n; ++i) { fx.begin[i] = fb; fb += (parts[i]->n_fix_short + 255) / 256; }
-    fx.begin[n] = fb;
-    if (fb > 0) hipLaunchKernelGGL(spmv_fixup_multi_kernel, dim3((unsigned)fb), dim3(256), 0, stream, d_fix_table, fx, alpha);
-    for (int i = 0; i < n; ++i) {
-        const SpmvDeviceMatrix& m = *parts[i];
-        if (m.n_fix_long > 0)
-            hipLaunchKernelGGL(spmv_fixup_long_kernel, dim3((m.n_fix_long + 3) / 4), dim3(256), 0, stream,
-                               m.fix_long, m.n_fix_long, m.carry, ys[i], alpha, 0LL, 0LL);
-    }
-    return hipGetLastError();
+    const long long fb = plain_prefix(fx, n, [&](int i) { return (parts[i]->n_fix_short + 255) / 256; });
+    hipError_t e = launch_multi<spmv_fixup_multi_kernel>(fb, 256, 0, stream, d_fix_table, fx, alpha);
+    for (int i = 0; e == hipSuccess && i < n; ++i)
+        e = launch_long_chains(parts[i]->fix_long, parts[i]->n_fix_long, parts[i]->carry, ys[i], alpha, stream);
+    return e;
 }
 
 // ---------------------------------------------------------------------------
@@ -1919,41 +1916,13 @@ __global__ __launch_bounds__(1024) void spmv_step_kernel(StepArgs args) {
     }
 }
 
-template <int NV, bool XLDS>
-static hipError_t launch_tts_nv2(const TtsDeviceMatrix& m, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream);
-
-static size_t tts_lds_bytes(const TtsDeviceMatrix& m) { return ((size_t)m.acc_floats + (size_t)m.staging_floats + 64) * sizeof(float); }
-
-hipError_t launch_tts(const TtsDeviceMatrix& m, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (m.n_tiles <= 0) return hipSuccess;
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        raised = true;
-    }
-    const size_t lds = tts_lds_bytes(m);
-    if (lds > 160 * 1024 - 256 || m.zero_fill) return hipErrorInvalidValue;      // (zero-fill geometries have column parts: launch_tts_multi)
-    if (tts_x_in_lds(m, 1)) {           // a short x: gathered from the LDS
-        hipError_t e = launch_tts_nv2<1, true>(m, x, bias, y, alpha, beta, stream);
-        if (e != hipSuccess) return e;
-    } else
-    if (beta != 0.0f) hipLaunchKernelGGL(spmv_tts_kernel<true>, dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, bias, y, alpha, beta);
-    else hipLaunchKernelGGL(spmv_tts_kernel<false>, dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, y, y, alpha, beta);
-    if (m.n_fix > 0)
-        hipLaunchKernelGGL(spmv_fixup_short_kernel, dim3((m.n_fix + 255) / 256), dim3(256), 0, stream, m.fix, m.n_fix, m.carry, y, alpha, 0LL, 0LL);
-    return hipGetLastError();
-}
-
 // LDS of the NV-vector / x-in-LDS kernels: per vector the accumulators, one staging area (largest block of the matrix), 64
 // tails and -- xlds -- a copy of x
 static size_t tts_nv_lds_bytes(const TtsDeviceMatrix& m, int nv, bool xlds) {
     return ((size_t)m.acc_floats + (size_t)m.batch_stage_floats + 64 + (xlds ? (size_t)m.xlds_floats : 0)) * nv * sizeof(float);
 }
 bool tts_x_in_lds(const TtsDeviceMatrix& m, int nv) {
-    return !m.zero_fill && m.xlds_floats > 0 && m.batch_stage_floats > 0 && tts_nv_lds_bytes(m, nv, true) <= 160 * 1024 - 256;
+    return !m.zero_fill && m.xlds_floats > 0 && m.batch_stage_floats > 0 && tts_nv_lds_bytes(m, nv, true) <= kDynLdsMax;
 }
 int tts_batch_width(const TtsDeviceMatrix& m, int64_t vecs) {
     if (vecs < 2 || m.zero_fill || m.batch_stage_floats <= 0) return 1;
@@ -1962,127 +1931,94 @@ int tts_batch_width(const TtsDeviceMatrix& m, int64_t vecs) {
     for (int nv = 4; nv >= 2; nv >>= 1) {
         if (nv > vecs) continue;
         if ((int64_t)m.cols * nv >= (1 << 30) || (int64_t)m.rows * nv >= (1 << 30)) continue;
-        if (tts_nv_lds_bytes(m, nv, false) <= 160 * 1024 - 256) return nv;
+        if (tts_nv_lds_bytes(m, nv, false) <= kDynLdsMax) return nv;
     }
     return 1;
 }
 
-template <bool HAS_BETA, int NV, bool XLDS>
-static hipError_t launch_tts_nv(const TtsDeviceMatrix& m, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream) {
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e = hipFuncSetAttribute((const void*)spmv_tts_nv_kernel<HAS_BETA, NV, XLDS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        if (e != hipSuccess) return e;
-        raised = true;
-    }
-    const size_t lds = tts_nv_lds_bytes(m, NV, XLDS);
-    hipLaunchKernelGGL((spmv_tts_nv_kernel<HAS_BETA, NV, XLDS>), dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, HAS_BETA ? bias : y, y, alpha, beta);
-    return hipGetLastError();
+// NV vectors per pass, x through the cache or from the LDS (one vector: from the LDS only -- spmv_tts_kernel is the other case)
+template <int NV>
+static hipError_t launch_tts_nv(const TtsDeviceMatrix& m, bool xlds, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream) {
+    return with_bools({beta != 0.0f, xlds}, [&](auto HAS_BETA, auto XLDS) {
+        if constexpr (NV == 1 && !XLDS()) return hipErrorInvalidValue;
+        else return launch<spmv_tts_nv_kernel<HAS_BETA(), NV, XLDS()>, kDynLdsMax>(dim3((unsigned)m.n_tiles), dim3(m.threads), tts_nv_lds_bytes(m, NV, XLDS()), stream,
+                                                                                  m, x, bias, y, alpha, beta);
+    });
 }
-template <int NV, bool XLDS>
-static hipError_t launch_tts_nv2(const TtsDeviceMatrix& m, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream) {
-    return beta != 0.0f ? launch_tts_nv<true, NV, XLDS>(m, x, bias, y, alpha, beta, stream) : launch_tts_nv<false, NV, XLDS>(m, x, bias, y, alpha, beta, stream);
+
+hipError_t launch_tts(const TtsDeviceMatrix& m, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream) {
+    clear_stale_error();
+    if (m.n_tiles <= 0) return hipSuccess;
+    const size_t lds = tts_tile_lds_bytes(m);
+    if (lds > kDynLdsMax || m.zero_fill) return hipErrorInvalidValue;      // (zero-fill geometries have column parts: launch_tts_multi)
+    if (beta == 0.0f) bias = y;      // never read; keeps the buffer descriptor well-formed
+    const hipError_t e = tts_x_in_lds(m, 1)           // a short x: gathered from the LDS
+        ? launch_tts_nv<1>(m, true, x, bias, y, alpha, beta, stream)
+        : with_bools({beta != 0.0f}, [&](auto HAS_BETA) {
+              return launch<spmv_tts_kernel<HAS_BETA()>, kDynLdsMax>(dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, bias, y, alpha, beta);
+          });
+    if (e != hipSuccess) return e;
+    return launch_short_chains(m.fix, m.n_fix, m.carry, y, alpha, stream);
 }
 
 hipError_t launch_tts_batched(const TtsDeviceMatrix& m, int nv, const float* x, const float* bias, float* y, float alpha, float beta, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (nv < 2 || nv > kTtsMaxVectors || m.zero_fill) return hipErrorInvalidValue;
     if (m.n_tiles <= 0) return hipSuccess;
+    if (beta == 0.0f) bias = y;      // never read; keeps the buffer descriptor well-formed
+    hipError_t e;
     if ((nv == 2 || nv == 4) && tts_batch_width(m, nv) == nv) {        // the vectors share every pass over the words
-        const bool xl = tts_x_in_lds(m, nv);
-        hipError_t e = nv == 4 ? (xl ? launch_tts_nv2<4, true>(m, x, bias, y, alpha, beta, stream) : launch_tts_nv2<4, false>(m, x, bias, y, alpha, beta, stream))
-                               : (xl ? launch_tts_nv2<2, true>(m, x, bias, y, alpha, beta, stream) : launch_tts_nv2<2, false>(m, x, bias, y, alpha, beta, stream));
-        if (e != hipSuccess) return e;
-        if (m.n_fix > 0)
-            hipLaunchKernelGGL(spmv_fixup_short_kernel, dim3((m.n_fix + 255) / 256, nv), dim3(256), 0, stream, m.fix, m.n_fix, m.carry, y, alpha,
-                               (long long)m.n_carry, (long long)m.rows);
-        return hipGetLastError();
+        e = with_nv<2, 4>(nv, [&](auto NV) { return launch_tts_nv<NV()>(m, tts_x_in_lds(m, nv), x, bias, y, alpha, beta, stream); });
+    } else {                                                           // ... or the workgroup takes its tile through them one after the other
+        const size_t lds = tts_tile_lds_bytes(m);
+        if (lds > kDynLdsMax) return hipErrorInvalidValue;
+        e = with_bools({beta != 0.0f}, [&](auto HAS_BETA) {
+            return launch<spmv_tts_batched_kernel<HAS_BETA()>, kDynLdsMax>(dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, bias, y, alpha, beta, nv);
+        });
     }
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_batched_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_batched_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        raised = true;
-    }
-    const size_t lds = tts_lds_bytes(m);
-    if (lds > 160 * 1024 - 256) return hipErrorInvalidValue;
-    if (beta != 0.0f) hipLaunchKernelGGL(spmv_tts_batched_kernel<true>, dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, bias, y, alpha, beta, nv);
-    else hipLaunchKernelGGL(spmv_tts_batched_kernel<false>, dim3((unsigned)m.n_tiles), dim3(m.threads), lds, stream, m, x, y, y, alpha, beta, nv);
-    if (m.n_fix > 0)      // rows cut into pieces: one fix-up launch for all vectors (grid.y = vector)
-        hipLaunchKernelGGL(spmv_fixup_short_kernel, dim3((m.n_fix + 255) / 256, nv), dim3(256), 0, stream, m.fix, m.n_fix, m.carry, y, alpha,
-                           (long long)m.n_carry, (long long)m.rows);
-    return hipGetLastError();
+    if (e != hipSuccess) return e;
+    // rows cut into pieces: one fix-up launch for all vectors (grid.y = vector)
+    return launch_short_chains(m.fix, m.n_fix, m.carry, y, alpha, stream, nv, m.n_carry, m.rows);
 }
 
 hipError_t launch_tts_multi(const TtsEntry* entries, int n, const uint8_t* item_parts, int n_items, const TtsEntry* d_table, float alpha,
                             hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n <= 0) return hipSuccess;
     if (n > kMultiMax) return hipErrorInvalidValue;
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_multi_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_multi_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_multi_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_tts_multi_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)) != hipSuccess) return e;
-        raised = true;
-    }
-    if (!item_parts) n_items = n;
-    const bool xlds = tts_x_in_lds(entries[0].m, 1);       // the launch's matrices gather x from the LDS (a class of their own)
-    MultiPrefix px{};
-    px.n = n_items;
-    long long g = 0;
+    const TtsDeviceMatrix& m0 = entries[0].m;
+    const bool xlds = tts_x_in_lds(m0, 1);       // the launch's matrices gather x from the LDS (a class of their own)
     size_t lds = 0;
-    int e = 0;
-    for (int k = 0; k < n_items; ++k) {
-        const int parts = item_parts ? item_parts[k] : 1;
-        if ((parts != 1 && parts != 2 && parts != 4) || e + parts > n) return hipErrorInvalidValue;
-        if (parts > 1) g = (g + 7) & ~7LL;                 // a pinned set starts at a multiple of 8
-        px.begin[k] = g; px.first[k] = (uint8_t)e; px.tiles[k] = (uint8_t)parts;
-        long long most = 0;
-        for (int q = 0; q < parts; ++q, ++e) {
-            most = std::max<long long>(most, entries[e].m.n_tiles);
-            lds = std::max(lds, xlds ? tts_nv_lds_bytes(entries[e].m, 1, true) : tts_lds_bytes(entries[e].m));
-            if (tts_x_in_lds(entries[e].m, 1) != xlds) return hipErrorInvalidValue;      // (one class per launch: hispmv_abi.cpp)
-        }
-        if (parts == 1) g += most;
-        else { const int per = 8 / parts; g += 8 * ((most + per - 1) / per); }
+    for (int i = 0; i < n; ++i) {
+        const TtsDeviceMatrix& m = entries[i].m;
+        if (tts_x_in_lds(m, 1) != xlds) return hipErrorInvalidValue;      // (one class per launch: hispmv_abi.cpp)
+        if (m.zero_fill != m0.zero_fill || m.threads != m0.threads) return hipErrorInvalidValue;
+        lds = std::max(lds, xlds ? tts_nv_lds_bytes(m, 1, true) : tts_tile_lds_bytes(m));
     }
-    if (e != n) return hipErrorInvalidValue;
-    px.begin[n_items] = g;
-    if (g > 0x7fffffffLL || lds > 160 * 1024 - 256) return hipErrorInvalidValue;
-    for (int i = 1; i < n; ++i) if (entries[i].m.zero_fill != entries[0].m.zero_fill || entries[i].m.threads != entries[0].m.threads) return hipErrorInvalidValue;
-    if (g > 0 && xlds) hipLaunchKernelGGL((spmv_tts_multi_kernel<false, true>), dim3((unsigned)g), dim3(entries[0].m.threads), lds, stream, d_table, px, alpha);
-    else if (g > 0 && entries[0].m.zero_fill == 2) hipLaunchKernelGGL((spmv_tts_multi_kernel<false, false, true>), dim3((unsigned)g), dim3(entries[0].m.threads), lds, stream, d_table, px, alpha);
-    else if (g > 0 && entries[0].m.zero_fill) hipLaunchKernelGGL(spmv_tts_multi_kernel<true>, dim3((unsigned)g), dim3(entries[0].m.threads), lds, stream, d_table, px, alpha);
-    else if (g > 0) hipLaunchKernelGGL(spmv_tts_multi_kernel<false>, dim3((unsigned)g), dim3(entries[0].m.threads), lds, stream, d_table, px, alpha);
-    return hipGetLastError();
+    MultiPrefix px{};
+    const long long g = pinned_prefix(px, n, item_parts, n_items, 4, [&](int e) { return (long long)entries[e].m.n_tiles; });
+    if (g < 0 || g > 0x7fffffffLL || lds > kDynLdsMax) return hipErrorInvalidValue;
+    // x in the LDS excludes the zero-fill (1) and gap-coded (2) geometries (tts_x_in_lds): at most one of the three holds
+    return with_bools({m0.zero_fill != 0 && m0.zero_fill != 2, xlds, m0.zero_fill == 2}, [&](auto ZERO_FILL, auto XLDS, auto GAP) {
+        if constexpr (ZERO_FILL() + XLDS() + GAP() > 1) return hipErrorInvalidValue;
+        else return launch_multi<spmv_tts_multi_kernel<ZERO_FILL(), XLDS(), GAP()>, kDynLdsMax>(g, m0.threads, lds, stream, d_table, px, alpha);
+    });
 }
 
 hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_tts_table, const void* d_items, unsigned n_items,
                             unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n_items == 0) return hipSuccess;
-    if (workgroups <= 0 || lds_bytes > 160 * 1024 - 256) return hipErrorInvalidValue;
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_step_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)spmv_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-        raised = true;
-    }
-    // (+ 16 bytes behind the items' LDS for the ticket word)
+    if (workgroups <= 0 || lds_bytes > kDynLdsMax) return hipErrorInvalidValue;
+    // (+ 16 bytes behind the items' LDS for the ticket word: the step kernel may take the CU's whole LDS)
     const size_t ticket_byte = (lds_bytes + 15) & ~(size_t)15;
     lds_bytes = ticket_byte + 16;
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    if (lds_bytes > kLdsPerCu) return hipErrorInvalidValue;
     const StepArgs a{d_slice_table, d_tts_table, (const int2*)d_items, d_sync, n_items, alpha, 0, (int)(ticket_byte / 4)};
-    if (strays) hipLaunchKernelGGL(spmv_step_kernel<true>, dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
-    else hipLaunchKernelGGL(spmv_step_kernel<false>, dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return with_bools({strays}, [&](auto STRAYS) {
+        return launch<spmv_step_kernel<STRAYS()>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
+    });
 }
-size_t tts_tile_lds_bytes(const TtsDeviceMatrix& m) { return tts_lds_bytes(m); }
 
 // ---------------------------------------------------------------------------
 // Dense overlay (reference: ComputeAB dense branch base_functions.cpp:188-226, packing
@@ -2277,64 +2213,52 @@ __global__ __launch_bounds__(256) void gemv_rows_multi_mixed_kernel(const GemvEn
     }
 }
 
-template <int NV>
-static void launch_gemv_nv(const float* W, int32_t rows, int32_t cols, const float* x, const float* bias,
-                           float* y, float alpha, float beta, hipStream_t stream, bool bf16 = false) {
-    constexpr int R = 4;
-    const unsigned blocks = (unsigned)((rows + R - 1) / R);
-    if (bf16) {
-        if (beta != 0.0f)
-            hipLaunchKernelGGL((gemv_rows_bf16_kernel<R, true, NV>), dim3(blocks), dim3(256), 0, stream, (const uint16_t*)W, x, bias, y, rows, cols, alpha, beta);
-        else
-            hipLaunchKernelGGL((gemv_rows_bf16_kernel<R, false, NV>), dim3(blocks), dim3(256), 0, stream, (const uint16_t*)W, x, bias, y, rows, cols, alpha, beta);
-        return;
-    }
-    if (beta != 0.0f)
-        hipLaunchKernelGGL((gemv_rows_kernel<R, true, NV>), dim3(blocks), dim3(256), 0, stream, W, x, bias, y, rows, cols, alpha, beta);
-    else
-        hipLaunchKernelGGL((gemv_rows_kernel<R, false, NV>), dim3(blocks), dim3(256), 0, stream, W, x, bias, y, rows, cols, alpha, beta);
+template <auto Kernel, class WT>
+static hipError_t launch_gemv_rows(const WT* W, int32_t rows, int32_t cols, const float* x, const float* bias,
+                                   float* y, float alpha, float beta, hipStream_t stream) {
+    return launch<Kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, W, x, bias, y, rows, cols, alpha, beta);
+}
+static hipError_t launch_gemv_nv(int nv, const float* W, int32_t rows, int32_t cols, const float* x, const float* bias,
+                                 float* y, float alpha, float beta, hipStream_t stream, bool bf16) {
+    return with_nv<1, 2, 4, 8>(nv, [&](auto NV_) {
+        constexpr int NV = NV_();
+        return with_bools({bf16, beta != 0.0f}, [&](auto BF16, auto HAS_BETA) {
+            if constexpr (BF16()) return launch_gemv_rows<gemv_rows_bf16_kernel<4, HAS_BETA(), NV>>((const uint16_t*)W, rows, cols, x, bias, y, alpha, beta, stream);
+            else return launch_gemv_rows<gemv_rows_kernel<4, HAS_BETA(), NV>>(W, rows, cols, x, bias, y, alpha, beta, stream);
+        });
+    });
 }
 
 hipError_t launch_gemv(const float* W, int32_t rows, int32_t cols, const float* x, const float* bias,
                        float* y, float alpha, float beta, hipStream_t stream, bool bf16) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     if (rows <= 0) return hipSuccess;
-    launch_gemv_nv<1>(W, rows, cols, x, bias, y, alpha, beta, stream, bf16);
-    return hipGetLastError();
+    return launch_gemv_nv(1, W, rows, cols, x, bias, y, alpha, beta, stream, bf16);
 }
 
 hipError_t launch_gemv_multi(const GemvEntry* entries, int n, const GemvEntry* d_table, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
+    clear_stale_error();
     if (n <= 0) return hipSuccess;
     if (n > kMultiMax) return hipErrorInvalidValue;
     MultiPrefix prefix{};
-    prefix.n = n;
-    long long total = 0;
-    for (int i = 0; i < n; ++i) { prefix.begin[i] = total; total += (entries[i].rows + 3) / 4; }
-    prefix.begin[n] = total;
-    if (total <= 0) return hipSuccess;
-    bool bf16 = false;
+    const long long total = plain_prefix(prefix, n, [&](int i) { return (entries[i].rows + 3) / 4; });
+    bool bf16 = false;      // (entries with bf16 storage: the kernel that knows both)
     for (int i = 0; i < n; ++i) bf16 = bf16 || entries[i].bf16 != 0;
-    if (bf16) hipLaunchKernelGGL(gemv_rows_multi_mixed_kernel, dim3((unsigned)total), dim3(256), 0, stream, d_table, prefix, alpha);
-    else
-    hipLaunchKernelGGL(gemv_rows_multi_kernel, dim3((unsigned)total), dim3(256), 0, stream, d_table, prefix, alpha);
-    return hipGetLastError();
+    if (bf16) return launch_multi<gemv_rows_multi_mixed_kernel>(total, 256, 0, stream, d_table, prefix, alpha);
+    return launch_multi<gemv_rows_multi_kernel>(total, 256, 0, stream, d_table, prefix, alpha);
 }
 
 hipError_t launch_gemv_batched(const float* W, int32_t rows, int32_t cols, int64_t vecs, const float* x, const float* bias,
                                float* y, float alpha, float beta, hipStream_t stream, bool bf16) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     if (rows <= 0) return hipSuccess;
-    int64_t k = 0;
-    while (k < vecs) {      // 8, 4, 2, 1 vectors per pass over W
-        const float* xk = x + (size_t)k * cols;
-        float* yk = y + (size_t)k * rows;
-        if (vecs - k >= 8) { launch_gemv_nv<8>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 8; }
-        else if (vecs - k >= 4) { launch_gemv_nv<4>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 4; }
-        else if (vecs - k >= 2) { launch_gemv_nv<2>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 2; }
-        else { launch_gemv_nv<1>(W, rows, cols, xk, bias, yk, alpha, beta, stream, bf16); k += 1; }
+    hipError_t e = hipSuccess;
+    for (int64_t k = 0; e == hipSuccess && k < vecs;) {      // 8, 4, 2, 1 vectors per pass over W
+        const int nv = vecs - k >= 8 ? 8 : vecs - k >= 4 ? 4 : vecs - k >= 2 ? 2 : 1;
+        e = launch_gemv_nv(nv, W, rows, cols, x + (size_t)k * cols, bias, y + (size_t)k * rows, alpha, beta, stream, bf16);
+        k += nv;
     }
-    return hipGetLastError();
+    return e;
 }
 
 // ---------------------------------------------------------------------------
@@ -2356,22 +2280,15 @@ hipError_t graph_set_alpha(hipGraphExec_t exec, hipGraph_t graph, float alpha) {
         if (type != hipGraphNodeTypeKernel) continue;
         hipKernelNodeParams p{};
         if ((e = hipGraphKernelNodeGetParams(nodes[i], &p)) != hipSuccess) return e;
-        int idx, n_args;
-        if (p.func == (void*)spmv_slices_multi_kernel<false> || p.func == (void*)spmv_slices_multi_kernel<true> ||
-            p.func == (void*)spmv_slices_multi_half_kernel<false> || p.func == (void*)spmv_slices_multi_half_kernel<true> || p.func == (void*)gemv_rows_multi_mixed_kernel || p.func == (void*)spmv_tts_multi_kernel<false> || p.func == (void*)spmv_tts_multi_kernel<true> ||
-            p.func == (void*)spmv_tts_multi_kernel<false, true> || p.func == (void*)spmv_tts_multi_kernel<false, false, true> ||
-            p.func == (void*)gemv_rows_multi_kernel ||
-            p.func == (void*)spmv_fixup_multi_kernel) { idx = 2; n_args = 3; }
-        else if (p.func == (void*)spmv_fixup_long_kernel) { idx = 4; n_args = 7; }
-        else if (p.func == (void*)spmv_tail_multi_kernel) { idx = 4; n_args = 5; }
-        else if (p.func == (void*)spmv_merge_multi_kernel) continue;          // no alpha
-        else return hipErrorInvalidValue;                                      // a kernel this function does not know: do not guess
+        // every kernel node of a batch-call graph was launched through launch_in_graph() while it was captured
+        GraphKernel k;
+        if (!find_graph_kernel(p.func, k)) return hipErrorInvalidValue;        // a kernel the registry does not know: do not guess
+        if (k.alpha_at < 0) continue;                                          // no alpha
         if (!p.kernelParams) return hipErrorInvalidValue;
-        void* args[8];
-        for (int k = 0; k < n_args; ++k) args[k] = p.kernelParams[k];
+        std::vector<void*> args(p.kernelParams, p.kernelParams + k.n_args);
         float a = alpha;
-        args[idx] = &a;
-        p.kernelParams = args;
+        args[k.alpha_at] = &a;
+        p.kernelParams = args.data();
         p.extra = nullptr;
         if ((e = hipGraphExecKernelNodeSetParams(exec, nodes[i], &p)) != hipSuccess) return e;
     }
@@ -2405,23 +2322,20 @@ __global__ __launch_bounds__(256) void fetch_vectors_kernel(const float4* __rest
 hipError_t launch_fetch_vectors(const float* src, float* dst, int64_t n_floats, hipStream_t stream) {
     const int n4 = (int)((n_floats + 3) / 4);
     if (n4 <= 0) return hipSuccess;
-    hipLaunchKernelGGL(fetch_vectors_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const float4*)src, (float4*)dst, n4);
-    return hipGetLastError();
+    return launch<fetch_vectors_kernel>(dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const float4*)src, (float4*)dst, n4);
 }
 
 hipError_t launch_boundary_pack(const float* const* last, const float* mask, float* send, int n, hipStream_t stream) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(boundary_pack_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, last, mask, send, n);
-    return hipGetLastError();
+    return launch<boundary_pack_kernel>(dim3((n + 63) / 64), dim3(64), 0, stream, last, mask, send, n);
 }
 
 hipError_t launch_boundary_apply(float* const* first, const float* recv, const float* weights, int n, int world,
                                  hipStream_t stream) {
-    (void)hipGetLastError();   // the status returned below must be this launch's, not a stale one of the thread (e.g. PyTorch's pointer queries)
+    clear_stale_error();
     if (n <= 0 || world <= 0) return hipSuccess;
-    hipLaunchKernelGGL(boundary_apply_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, first, recv, weights, n, world);
-    return hipGetLastError();
+    return launch<boundary_apply_kernel>(dim3((n + 63) / 64), dim3(64), 0, stream, first, recv, weights, n, world);
 }
 
 }  // namespace hispmv
