@@ -13,6 +13,9 @@ SLICES = {"HISPMV_FORMAT": "slices"}
 AUTO = {"HISPMV_FORMAT": "auto", "HISPMV_TTS_MIN_NNZ": "20000"}
 COLTILES = {"HISPMV_FORMAT": "slices", "HISPMV_COL_TILE_BYTES": "65536"}
 NOSPLIT = {"HISPMV_FORMAT": "slices", "HISPMV_STRAY_SPLIT": "0"}
+TTS = {"HISPMV_FORMAT": "tts"}                                   # every candidate of >= 64 K entries becomes a tile stream, the rest stay slice streams
+TTS_XLDS = {"HISPMV_FORMAT": "tts", "HISPMV_TTS_XLDS": "1"}      # ... and x of <= 16 K floats is kept in the LDS
+TTS_SMALL = {"HISPMV_FORMAT": "tts", "HISPMV_TTS_SMALL": "1"}    # ... in the 13 K-slot geometry where a gather touches <= 8 lines
 
 
 @contextmanager
@@ -113,6 +116,106 @@ def case_c():
     return [big_band(), tile_stream(), tile_stream_cut_row(), a[3], a[5], a[6], a[7]]
 
 
+# ---- tile streams whose x fits the LDS (HISPMV_TTS_XLDS=1), the small geometry, a chain of more than 32 slices --------------------------
+TTS_XLDS_MAX = 16 * 1024           # kTtsXldsMax (hispmv_kernels.h): the longest x the kernels keep in the LDS
+DYN_LDS_MAX = 160 * 1024 - 256     # kDynLdsMax
+
+
+def tts_nv_lds_bytes(tts, cols, nv, xlds):
+    """tts_nv_lds_bytes (hispmv_kernels.hip) from the packer's arrays: per vector the accumulators, a staging area of the largest
+    block in whole chunks + the dummy slot, 64 tails and -- xlds -- x rounded up to 64 floats."""
+    acc = (tts["max_rows"] + 63) & ~63
+    stage = -(-tts["max_slots"] // 1024) * 1024 + 64
+    return (acc + stage + 64 + (((cols + 63) & ~63) if xlds else 0)) * nv * 4
+
+
+def x_in_lds(tts, cols, nv=1):
+    """tts_x_in_lds under HISPMV_TTS_XLDS=1: a one-part stream with stream words for every row, x short enough, the LDS large enough."""
+    return (not isinstance(tts, (list, tuple)) and not tts["zero_fill"] and tts["flags_hi"] is None and cols <= TTS_XLDS_MAX
+            and tts_nv_lds_bytes(tts, cols, nv, True) <= DYN_LDS_MAX)
+
+
+def tts_widths(tts, cols):
+    """-> (from the LDS, through the cache): the most vectors (4, 2, 1; 0 = none) that share a pass over the words with x in the LDS,
+    and with x gathered through the cache -- what tts_batch_width returns for a call of >= 4 vectors with and without the switch."""
+    lds = next((nv for nv in (4, 2, 1) if x_in_lds(tts, cols, nv)), 0)
+    cache = next((nv for nv in (4, 2) if tts_nv_lds_bytes(tts, cols, nv, False) <= DYN_LDS_MAX), 1)
+    return lds, cache
+
+
+def linear_passes(tts, cols, vecs, xlds_on):
+    """The passes of a `linear` call of `vecs` vectors (launch_matrix_vectors + tts_batch_width): [(vectors, x in the LDS)]."""
+    out, k = [], 0
+    while k < vecs:
+        left, nv, lds = vecs - k, 1, False
+        if left >= 2:
+            nv = next((n for n in (4, 2) if n <= left and xlds_on and x_in_lds(tts, cols, n)), 0)
+            lds = nv > 0
+            if not nv:
+                nv = next((n for n in (4, 2) if n <= left and tts_nv_lds_bytes(tts, cols, n, False) <= DYN_LDS_MAX), 1)
+            if nv < 2:
+                nv, lds = min(left, 8), False                      # (one after the other inside one launch: kTtsMaxVectors)
+        if nv == 1:
+            lds = xlds_on and x_in_lds(tts, cols, 1)
+        out.append((nv, lds))
+        k += nv
+    return out
+
+
+def xlds_cases():
+    """Uniform random columns, every column count but D's odd.  name -> matrix; expect["widths"] = tts_widths of its packed stream.
+    A has 72 000 entries, not 60 000: under HISPMV_FORMAT=tts the loader keeps a matrix of fewer than 64 K entries a slice stream
+    (hispmv_choose.cpp), so the smaller one never reaches a tile-stream kernel; shape, heavy row and share are unchanged."""
+    return dict(
+        A=uniform(2000, 2047, 72000, 301, dict(format=1, group=28, cut_rows=True, widths=(4, 4), xlds=True), heavy_row=(7, 1.0 / 3), name="xlds_A"),
+        B=uniform(3000, 8191, 120000, 302, dict(format=1, group=28, widths=(2, 4), xlds=True), name="xlds_B"),
+        C=uniform(3000, 16383, 120000, 303, dict(format=1, group=28, cut_rows=True, widths=(1, 4), xlds=True), heavy_row=(7, 1.0 / 3), name="xlds_C"),
+        D=uniform(300, 16384, 70000, 304, dict(format=1, group=28, xlds=True), name="xlds_D"),
+        E=uniform(300, 16385, 70000, 305, dict(format=1, group=28, xlds=False), name="xlds_E"))
+
+
+def small_band(seed=306):
+    """6 entries per row within +-100 columns of the row: 1.4 lines of x per gather, so HISPMV_TTS_SMALL=1 packs it in 13 K-slot blocks."""
+    rng = np.random.default_rng(seed)
+    n = 20000
+    r = np.repeat(np.arange(n, dtype=np.int64), 6)
+    c = np.clip(r + rng.integers(-100, 101, r.size), 0, n - 1)
+    return _finish("small_band", n, n, r, c, seed, dict(format=1, group=13))
+
+
+def single_row_long(seed=95):
+    """One row of 40 000 entries: a chain of more than 32 slices (kFixShortMax), finished by a launch of its own behind the tail."""
+    rng = np.random.default_rng(seed)
+    return _finish("single_row_long", 1, 4096, np.zeros(40000, np.int64), rng.integers(0, 4096, 40000), seed,
+                   dict(format=0, threads=256, cut_rows=True, long_chain=True))
+
+
+def tall(m, geometry):
+    """The tile stream under HISPMV_TTS_GEOMETRY=tall / tallgap: two column parts of 16 K-row tiles, part 1 through a partial vector."""
+    return dict(m, name=f'{m["name"]}_{geometry}', expect=dict(format=1, group=23, parts=2, tile_kind=1, geometry=geometry))
+
+
+def tall_env(geometry):
+    return dict(TTS, HISPMV_TTS_GEOMETRY=geometry)
+
+
+def as_slices(m, **expect):
+    """The same matrix where the context's switches keep it a slice stream (HISPMV_FORMAT=tts: fewer than 64 K entries)."""
+    return dict(m, expect=dict(format=0, **expect))
+
+
+def bf16_exact(a):
+    """fp32 values rounded to bfloat16 once (round to nearest even), kept as fp32: a bf16 handle stores exactly these."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
+    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32).reshape(np.shape(a))
+
+
+def as_bf16(m):
+    """The matrix with bf16-exact values, to be created under set_value_storage("bf16"): the CPU models apply unchanged."""
+    key = "W" if m.get("dense") else "v"
+    return dict(m, name=m["name"] + "_bf16", storage="bf16", **{key: bf16_exact(m[key])})
+
+
 # ---- case D -----------------------------------------------------------------------------------------------------------------------
 def stray_split_band():
     return band(20000, 200, 41, dict(format=0, tile_kind=3, parts=2), redraw=0.02)
@@ -190,6 +293,9 @@ def packed(m, info):
     from hispmv_amd.prep import prep_from_coo
     from util import prepared_tiles
     if info["format"] == 1:
+        if info["group_slices"] == 23:                                                    # the two column parts of the tall geometries
+            assert info["col_tiles"] == 2 and m["expect"]["geometry"] in ("tall", "tallgap"), info
+            return prep_from_coo(m["r"], m["c"], m["v"], m["rows"], m["cols"], tts=(0, m["expect"]["geometry"]))
         assert info["col_tiles"] == 1 and info["group_slices"] in (28, 13), info          # the standard or the small geometry
         return prep_from_coo(m["r"], m["c"], m["v"], m["rows"], m["cols"], tts=(0, {28: 0, 13: 1}[info["group_slices"]]))
     return prepared_tiles(info, m["r"], m["c"], m["v"], m["rows"], m["cols"])
@@ -214,7 +320,7 @@ def queue_items(info, pk, shared_chip=True):
     """Queue items of the matrix in a step-kernel call, counted without the library: a group of a 1024-thread part is an item,
     four groups of a 256-thread part share one, a tile of a tile stream is one."""
     if info["format"] == 1:
-        return int(pk.tts["n_tiles"])
+        return sum(int(t["n_tiles"]) for t in _tts_parts(pk))
     n = 0
     for P, (threads, gs) in zip(pk, part_plans(info, pk, shared_chip)):
         assert threads in (256, 1024), (info, threads)
@@ -223,9 +329,13 @@ def queue_items(info, pk, shared_chip=True):
     return n
 
 
+def _tts_parts(pk):
+    return pk.tts if isinstance(pk.tts, (list, tuple)) else [pk.tts]
+
+
 def cut_rows(info, pk):
     """Per part: the number of rows the packer cut between slices (or, in a tile stream, into pieces)."""
-    return [int(pk.tts["fix"].shape[0])] if info["format"] == 1 else [int(P.fix.shape[0]) for P in pk]
+    return [int(t["fix"].shape[0]) for t in _tts_parts(pk)] if info["format"] == 1 else [int(P.fix.shape[0]) for P in pk]
 
 
 def check_expect(m, info, pk):
@@ -251,6 +361,12 @@ def check_expect(m, info, pk):
         assert bool(info["l2_tiles"]) == e["l2_tiles"], tag
     if "compact" in e and "compact_slices" in info:
         assert info["compact_slices"] == e["compact"], tag
+    if "widths" in e:
+        assert tts_widths(pk.tts, m["cols"]) == e["widths"], (tag, tts_widths(pk.tts, m["cols"]))
+    if "xlds" in e:
+        assert x_in_lds(pk.tts, m["cols"]) == e["xlds"], tag
+    if e.get("long_chain"):
+        assert int(pk[0].fix[:, 2].max()) > 32, (tag, pk[0].fix)                          # more slices than kFixShortMax: a fix_long entry
 
 
 def stray_layout(m):
@@ -264,9 +380,10 @@ PAIRS = ((0.85, -2.06), (1.0, 0.0))               # (ALPHA, BETA) of tests/conft
 MORE_PAIRS = ((0.0, 1.0), (-1.5, 0.5))
 
 
-def reference(m, info, pk, alpha, beta):
+def reference(m, info, pk, alpha, beta, mode=0):
     """-> (ye, y64, mag): the CPU model of the matrix's format on the packer's arrays (a batch call always uses the fix-up carry
-    variant of the slice stream, mode 0) and the fp64 accumulation with the magnitude sum of its terms."""
+    variant of the slice stream, mode 0; 1 = the look-back variant of a single launch) and the fp64 accumulation with the magnitude
+    sum of its terms."""
     import oracle
     from util import csr_truth, emulate_tiles
     if m.get("dense"):
@@ -276,6 +393,6 @@ def reference(m, info, pk, alpha, beta):
     if info["format"] == 1:
         ye = oracle.emu_tts(pk.tts, m["x"], m["b"], alpha, beta, m["rows"])
     else:
-        ye = emulate_tiles(pk, m["x"], m["b"], alpha, beta, m["rows"], 0)
+        ye = emulate_tiles(pk, m["x"], m["b"], alpha, beta, m["rows"], mode)
     y64, mag = csr_truth(m["r"], m["c"], m["v"], m["rows"], m["x"], m["b"], alpha, beta)
     return ye, y64, mag

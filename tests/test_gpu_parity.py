@@ -67,11 +67,12 @@ def test_golden_matrices_vs_mkl_and_emulator(name, golden, fpga):
     assert info["nnz"] == g["ref_col_idx"].size and info["loaded"] == 1 and not info["is_dense"]
 
 
-@pytest.mark.parametrize("carry,mode", [("lookback", 1), ("fixup", 0), ("resident", None), ("auto", None)])
+@pytest.mark.parametrize("carry,mode", [("lookback", 1), ("fixup", 0), ("resident", None), ("auto", None), ("ticket", 1)])
 def test_both_carry_variants_match_their_wavefront_model(pyhispmv_mod, monkeypatch, carry, mode):
     """Rows shared between slices: the two-launch fix-up variant (default) and the single-launch
     look-back (HISPMV_CARRY=lookback) each reproduce their CPU model bit for bit, on a matrix with
-    short chains, a 100-slice chain and empty rows."""
+    short chains, a 100-slice chain and empty rows.  "ticket": the look-back with groups handed out in start order; launch k
+    draws the tickets [k * n_groups, (k + 1) * n_groups), so the fourth launch runs on a base three launches deep."""
     from hispmv_amd.prep import prep_from_coo
     monkeypatch.setenv("HISPMV_CARRY", carry)
     rng = np.random.default_rng(3)
@@ -93,7 +94,7 @@ def test_both_carry_variants_match_their_wavefront_model(pyhispmv_mod, monkeypat
         assert info["carry_lookback"] == mode
     y64, mag = oracle.spmv_f64(P.row_ptr.astype(np.int32), P.col_idx, P.values, x, b, ALPHA, BETA)
     ye = emulate_device(info, r, c, v, rows, cols, x, b, ALPHA, BETA)
-    for _ in range(3):                      # repeated launches reuse the granules with a new launch tag
+    for _ in range(4):                      # repeated launches reuse the granules with a new launch tag (ticket: a new ticket base)
         y = np.full(rows, np.nan, np.float32)
         h.run_kernel(x, b, y, ALPHA, BETA)
         assert bwd_err(y, y64, mag) < TOL

@@ -30,6 +30,10 @@ def make(case, rng):
         rows, cols, nnz = 300, 6000, 500000
         r = rng.integers(0, rows, nnz); r[:200000] = 7
         c = rng.integers(0, cols, nnz)
+    elif case == "narrow_band":               # 1.4 lines of x per gather: with HISPMV_TTS_SMALL=1 the 13 K-slot blocks and 4 K-row tiles
+        rows = cols = 20000
+        r = np.repeat(np.arange(rows), 6); nnz = r.size
+        c = np.clip(r + rng.integers(-100, 101, nnz), 0, cols - 1)
     elif case == "banded_jitter":
         rows = cols = 150000
         r = np.repeat(np.arange(rows), 6); nnz = r.size
@@ -42,18 +46,24 @@ def make(case, rng):
 
 
 CASES = [(c, "standard") for c in ("uniform_short_rows", "empty_and_heavy_rows", "wide_columns_few_rows", "banded_jitter", "duplicates", "short_wide_layer")] + \
-        [(c, g) for g in ("tall", "paired", "zerofill", "tallgap") for c in ("uniform_short_rows", "empty_and_heavy_rows", "duplicates")]
+        [(c, g) for g in ("tall", "paired", "zerofill", "tallgap") for c in ("uniform_short_rows", "empty_and_heavy_rows", "duplicates")] + \
+        [("narrow_band", "small")]
 
 
 @pytest.mark.parametrize("case,geometry", CASES)
 def test_tile_stream_matches_its_model_and_the_fp64_truth(case, geometry, monkeypatch):
     """geometry "tall": two column parts of 16 K-row tiles whose absent rows have no stream word (zero-filled staging),
-    part 1 through a partial vector and the merge launch, both parts pinned to XCD subsets in one grid."""
+    part 1 through a partial vector and the merge launch, both parts pinned to XCD subsets in one grid.
+    geometry "small": HISPMV_TTS_SMALL=1 with HISPMV_TTS_GEOMETRY unset -- 13 K-slot blocks, 4 K-row tiles, two workgroups per CU."""
     import pyhispmv
     import torch
     from hispmv_amd.prep import prep_from_coo
     monkeypatch.setenv("HISPMV_FORMAT", "tts")
-    monkeypatch.setenv("HISPMV_TTS_GEOMETRY", geometry)
+    if geometry == "small":
+        monkeypatch.delenv("HISPMV_TTS_GEOMETRY", raising=False)
+        monkeypatch.setenv("HISPMV_TTS_SMALL", "1")
+    else:
+        monkeypatch.setenv("HISPMV_TTS_GEOMETRY", geometry)
     rng = np.random.default_rng(abs(hash(case)) % 997)
     rows, cols, r, c, v = make(case, rng)
     x = rng.random(cols, dtype=np.float32) - np.float32(0.3)
@@ -62,9 +72,9 @@ def test_tile_stream_matches_its_model_and_the_fp64_truth(case, geometry, monkey
     idx = h.create_sparse_handle(r, c, v, rows, cols)
     h.load_matrices()
     info = h.matrix_info(idx)
-    assert info["format"] == 1 and info["group_slices"] == {"standard": 28, "tall": 23, "paired": 11, "zerofill": 28, "tallgap": 23}[geometry]
-    assert info["col_tiles"] == (1 if geometry in ("standard", "zerofill") else 2)
-    if geometry in ("standard", "zerofill"):
+    assert info["format"] == 1 and info["group_slices"] == {"standard": 28, "tall": 23, "paired": 11, "zerofill": 28, "tallgap": 23, "small": 13}[geometry]
+    assert info["col_tiles"] == (1 if geometry in ("standard", "zerofill", "small") else 2)
+    if geometry in ("standard", "zerofill", "small"):
         assert info["n_split_rows"] == {"empty_and_heavy_rows": 2, "short_wide_layer": 1}.get(case, 0)      # rows cut into pieces (carry tiles + fix-up)
     P = prep_from_coo(r, c, v, rows, cols, tts=(0, geometry if geometry in ("zerofill", "tallgap") else {13: 1, 28: 0, 23: "tall", 11: "paired"}[info["group_slices"]]))     # the geometry the loader chose
     rp = P.row_ptr.astype(np.int32)
