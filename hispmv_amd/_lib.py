@@ -21,6 +21,7 @@ HISPMV_ESTATE = -4
 HISPMV_ENOTDENSE = -5
 HISPMV_EIO = -6
 HISPMV_ENOMEM = -7
+HISPMV_ENOTSUP = -8
 
 HISPMV_VALUES_FP32 = 0
 HISPMV_VALUES_BF16 = 1
@@ -83,6 +84,9 @@ SIGNATURES = {
     "hispmv_set_value_storage": (C.c_int, [_p, C.c_int]),
     "hispmv_value_storage_info": (C.c_int, [_p, C.c_int, _i64p]),
     "hispmv_prep_set_value_storage": (C.c_int, [_p, C.c_int]),
+    "hispmv_spmv_device_t": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, _p]),
+    "hispmv_set_transposable": (C.c_int, [_p, C.c_int]),
+    "hispmv_transpose_info": (C.c_int, [_p, C.c_int, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),
     "hispmv_num_matrices": (C.c_int, [_p]),

@@ -120,6 +120,7 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
     m->rows = csr.rows; m->cols = csr.cols; m->nnz = csr.nnz();
     FormatOptions opts = c->format_opts;
     opts.half_values = c->value_storage == HISPMV_VALUES_BF16;      // (the values are rounded already: add_from_coo, _from_csr)
+    if (c->transposable) opts.format_mode = 0;                      // hispmv_set_transposable: keep the slice stream, as HISPMV_FORMAT=slices does
     m->value_storage = c->value_storage;
     FormatChoice ch = choose_format(std::move(csr), prebuilt, c->n_cus, opts, lap);
     m->format = ch.format; m->tile_kind = ch.tile_kind; m->col_tile_width = ch.col_tile_width; m->col_tile_base = ch.col_tile_base;
@@ -228,6 +229,36 @@ int upload(hispmv_ctx* c, Matrix& m, const T* host, size_t count, const T** dev_
     HIP_TRY(c, hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
     *dev_out = (const T*)d;
     return HISPMV_OK;
+}
+
+// What one transposed call (hispmv_spmv_device_t) costs on slice part `p` of `m`, added to the handle's counts while the host
+// tables of the plan exist: one launch; the window flush of every staged group (its fragments, clipped to `cols`); one float per
+// stray of a stray-slot group; one float per element that adds to y directly -- the elements outside the window of a wide group,
+// and every stored slot (fillers included, tail padding not) of a group without fragments or of a plan without a window.
+void transpose_costs(Matrix& m, const HostPart& p, const SpmvDeviceMatrix& d) {
+    if (d.n_groups <= 0) return;
+    m.t_launches += 1;
+    const int64_t G = d.group_slices, ns = d.n_slices;
+    const int64_t padding = std::max<int64_t>(0, ns * kSliceElems - p.st.n_elems);
+    int64_t flushed = 0, strays = 0, direct = 0;
+    for (int64_t g = 0; g < d.n_groups; ++g) {
+        const GroupDesc gd = (size_t)g < p.plan.groups.size() ? p.plan.groups[(size_t)g] : GroupDesc{0, 0, 0, 0};
+        const int32_t gw = (size_t)g * 4 + 3 < p.dstream.groups.size() ? p.dstream.groups[(size_t)g * 4 + 3] : 0;
+        const int64_t s0 = g * G, s1 = std::min(ns, s0 + G);
+        if (p.plan.lds_floats > 0 && gd.frag_count > 0) {
+            for (int32_t f = gd.frag_begin; f < gd.frag_begin + gd.frag_count && (size_t)f < p.plan.frags.size(); ++f)
+                flushed += std::max<int64_t>(0, std::min<int64_t>(p.plan.frags[(size_t)f].len, (int64_t)m.cols - p.plan.frags[(size_t)f].col_start));
+            if (gw & kGroupStrays) {
+                for (int64_t sl = s0; sl < s1 && (size_t)sl < p.plan.slice_spills.size(); ++sl) strays += p.plan.slice_spills[(size_t)sl];
+            } else if (!(gw & kGroupCompact)) {
+                direct += gd.n_global;
+            }
+        } else {
+            direct += (s1 - s0) * kSliceElems - (s1 == ns ? padding : 0);
+        }
+    }
+    m.t_direct += direct;
+    m.t_atomic_bytes += 4 * (flushed + strays + direct);
 }
 
 int launch_matrix(hispmv_ctx* c, Matrix& m, const float* d_x, const float* d_bias, float* d_y,
@@ -781,6 +812,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                 d.has_strays = p.dstream.stray_floats > 0;
                 d.has_half = p.dstream.half_values && p.dstream.compact_slices > 0;
                 if (d.has_strays) { d.lookback = false; d.use_ticket = false; }
+                transpose_costs(m, p, d);
                 // the batch layout (hispmv_choose.h): its own group table, fragments, slice bytes and headers (the spill flags differ);
                 // rows, carries, fix lists and the error word are the part's
                 if (p.has_batch_layout) {
@@ -853,6 +885,12 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                                   p.batch_plan.groups = {}; p.batch_plan.frags = {}; p.batch_plan.slice_spills = {}; p.batch_dstream = DeviceStream{}; p.batch_words = WordVec(); }
         m.dense_host = {};
         m.dense_host16 = {};
+        if (m.dense) {          // transposed product of a dense handle: the row blocks add their column sums to y (plain stores when there is one)
+            const int nb = gemv_t_row_blocks(m.rows, m.cols);
+            m.t_launches = nb > 0 ? 1 : 0;
+            m.t_atomic_bytes = nb > 1 ? (int64_t)nb * m.cols * 4 : 0;
+        }
+        if (m.dense || m.format == 0) m.t_launches += 1;      // the prologue y = beta * bias
         m.loaded = true;
     }
     return HISPMV_OK;
@@ -950,6 +988,53 @@ HISPMV_API int hispmv_spmv_device(hispmv_ctx* c, int idx, const float* d_x, cons
     HIP_TRY(c, hipSetDevice(c->device));
     if (stream) c->user_stream = (hipStream_t)stream;
     return launch_matrix(c, m, d_x, d_bias, d_y, alpha, beta, stream ? (hipStream_t)stream : c->stream);
+}
+
+// ---- transposed product (include/hispmv.h: hispmv_spmv_device_t; kernels: hispmv_transpose.hip) ---------------------------------
+HISPMV_API int hispmv_set_transposable(hispmv_ctx* c, int enable) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->transposable = enable != 0;
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_transpose_info(const hispmv_ctx* c, int idx, int64_t out[4]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
+    const Matrix& m = *c->mats[(size_t)idx];
+    const bool ok = m.loaded && (m.dense || m.format == 0);
+    out[0] = ok ? 1 : 0; out[1] = ok ? m.t_launches : 0; out[2] = ok ? m.t_atomic_bytes : 0; out[3] = ok ? m.t_direct : 0;
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_spmv_device_t(hispmv_ctx* c, int idx, const float* d_x, const float* d_bias, float* d_y,
+                                    float alpha, float beta, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[idx];
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device_t called before load_matrices");
+    if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
+    if (d_x == d_y) return fail(c, HISPMV_EINVAL, "spmv_device_t: x and y must not be the same vector");
+    if (!m.dense && m.format != 0)
+        return fail(c, HISPMV_ENOTSUP, "spmv_device_t: this handle is a transposed tile stream, which has no transposed product; create it after "
+                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (stream) c->user_stream = (hipStream_t)stream;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    // y = beta * bias first, then every part of the matrix adds alpha * A_t^T * x into it: no partial vectors, no merge
+    hipError_t e = launch_transpose_prologue(d_bias, d_y, m.cols, beta, s);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
+    if (alpha == 0.0f) return HISPMV_OK;          // y is exactly beta * bias
+    if (m.dense) {
+        e = launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, d_x, d_y, alpha, s);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_t");
+        return HISPMV_OK;
+    }
+    for (auto& p : m.parts) {
+        e = launch_spmv_t(p.dev, d_x, d_y, alpha, s);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_t");
+    }
+    return HISPMV_OK;
 }
 
 HISPMV_API int hispmv_synchronize(hispmv_ctx* c) {

@@ -25,6 +25,7 @@
 #include "hispmv_plan.h"
 #include "hispmv_prep.h"
 #include "hispmv_prep_device.h"
+#include "hispmv_transpose.h"
 #include "hispmv_tts.h"
 #include "hispmv_update.h"
 
@@ -81,6 +82,9 @@ struct Matrix {
     int64_t slots_2byte = 0, slots_4byte = 0;   // value slots of the device layouts by size (a batch layout's slices counted again)
     int64_t saved_bytes = 0;                    // device bytes less than the same handle with fp32 storage
     std::vector<uint16_t> dense_host16;
+    // transposed product (hispmv_spmv_device_t; hispmv_transpose.h): what one call of it costs on this handle, counted at load from
+    // the plan tables before they are released -- {launches, bytes of float atomic adds to y, stream elements that add to y directly}
+    int64_t t_launches = 0, t_atomic_bytes = 0, t_direct = 0;
     std::vector<void*> allocs;
 };
 
@@ -131,6 +135,7 @@ struct hispmv_ctx {
     // buffer of hispmv_update_values (host values) and of the load's first update
     bool value_updates = false;
     int value_storage = HISPMV_VALUES_FP32;     // hispmv_set_value_storage: what handles created from now on store their values as
+    bool transposable = false;                  // hispmv_set_transposable: sparse handles created from now on keep the slice stream (format_mode 0)
     float* h_upd = nullptr;
     int64_t cap_h_upd = 0;
     float* d_upd = nullptr;

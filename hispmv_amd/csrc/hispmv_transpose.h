@@ -1,0 +1,29 @@
+// hispmv_transpose.h -- launchers of the transposed product y[cols] = alpha * A^T * x[rows] + beta * bias[cols] on the layouts a loaded
+// handle already holds (hispmv_transpose.hip; include/hispmv.h: hispmv_spmv_device_t).  Nothing is stored for it: the row of a slice
+// element is its slice's row_base plus the row ends before it, its column is the meta (through the group's fragment table where the
+// meta is a window index), and the LDS window that holds x in the forward kernel holds the accumulators of y here.  Sums into one
+// y[col] arrive through float atomics, in no fixed order.  A stored slot whose value is +-0 adds nothing, whatever x holds.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+#include "hispmv_kernels.h"
+
+namespace hispmv {
+
+// y[i] = beta * bias[i] (0 when beta == 0: bias is not read), i < n.  Elementwise, so bias may be y.
+hipError_t launch_transpose_prologue(const float* bias, float* y, int32_t n, float beta, hipStream_t stream);
+
+// y += alpha * A^T * x for one slice stream (one part of a handle): one workgroup per group of the part's plan, the same workgroup
+// size and LDS as the forward launch.  x has m.rows floats, y has m.cols.
+hipError_t launch_spmv_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream);
+
+// y += alpha * W^T * x, W row-major rows x cols (fp32, or bfloat16 when bf16).  The rows are split over gemv_t_row_blocks() workgroups
+// per block of kGemvTCols columns; their column sums meet in y through one contiguous atomic per 64 columns (plain read-add-write when
+// one row block suffices).
+constexpr int kGemvTCols = 1024;
+int gemv_t_row_blocks(int32_t rows, int32_t cols);
+hipError_t launch_gemv_t(const void* W, int32_t rows, int32_t cols, bool bf16, const float* x, float* y, float alpha, hipStream_t stream);
+
+}  // namespace hispmv

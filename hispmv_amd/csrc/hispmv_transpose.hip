@@ -1,0 +1,403 @@
+// hispmv_transpose.hip -- the kernels of the transposed product (hispmv_transpose.h): y[cols] = alpha * A^T * x[rows] + beta * bias[cols]
+// on the slice streams and dense layouts of loaded handles.  Stands on its own like hispmv_update.hip: the few decode helpers of the
+// slice format it needs (the slice request, decode_metas, the bf16 widening) are its own copies, so that hispmv_kernels.hip -- and with
+// it every forward kernel -- is untouched by this file.
+//
+// Roles, against the forward slice kernel (hispmv_kernels.hip: slices_group):
+//   forward                                           transposed
+//   x window of the group in the LDS (staged)         the same floats ZEROED: accumulators of y, flushed per fragment at the end
+//   row-total tile of a wavefront (one slice's y)     x[row_first .. row_first + n_rows] of the slice (its rows are consecutive)
+//   stray area of a wavefront (x of <= 64 strays)     accumulators of the slice's strays, flushed per slice to the stray columns
+//   gather through L2 (wide metas, no-window plans)   one global float atomic per element (the expensive shape: 64 lanes, 64 lines)
+// A stored slot whose value is +-0 adds nothing, whatever x holds (fillers of empty rows, row extensions, tail padding, explicit zeros).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+
+#include "hispmv_format.h"
+#include "hispmv_transpose.h"
+
+namespace hispmv {
+
+namespace {
+
+#define HISPMV_T_GLOBAL __attribute__((address_space(1)))
+__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
+__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
+__device__ __forceinline__ uint4 load_words(const uint4* p) {
+    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+    const u4v v = __builtin_nontemporal_load((const HISPMV_T_GLOBAL u4v*)p);
+    return uint4{v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ uint2 load_words2(const uint2* p) {
+    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+    const u2v v = __builtin_nontemporal_load((const HISPMV_T_GLOBAL u2v*)p);
+    return uint2{v.x, v.y};
+}
+__device__ __forceinline__ int4 load_int4(const int4* p) {
+    typedef int i4v __attribute__((ext_vector_type(4)));
+    const i4v v = *(const HISPMV_T_GLOBAL i4v*)p;
+    return int4{v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+// The float adds: ds_add_f32 into the LDS, global_atomic_add_f32 (no return value) into y.
+__device__ __forceinline__ void lds_add(float* p, float v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void y_add(float* y, unsigned col, float v) { (void)atomicAdd(y + col, v); }
+
+// A slice as it arrives (hispmv_format.h; the forward kernel's SliceRaw): per step 4 values and 4 metas per lane, or -- HALF -- one
+// 16-byte piece {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16}.
+template <bool COMPACT, bool HALF = false> struct SliceRaw;
+template <> struct SliceRaw<true>  { uint4 v[kSliceSteps]; uint2 m[kSliceSteps]; };
+template <> struct SliceRaw<false> { uint4 v[kSliceSteps]; uint4 m[kSliceSteps]; };
+template <> struct SliceRaw<true, true> { uint4 q[kSliceSteps]; };
+template <bool COMPACT, bool HALF>
+__device__ __forceinline__ void request_slice(SliceRaw<COMPACT, HALF>& s, const char* base, int lane) {
+    if constexpr (HALF) {
+        const uint4* pq = (const uint4*)base + lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.q[j] = load_words(pq + j * 64);
+    } else {
+        const uint4* pv = (const uint4*)base + lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.v[j] = load_words(pv + j * 64);
+        if constexpr (COMPACT) {
+            const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
+#pragma unroll
+            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
+        } else {
+            const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
+#pragma unroll
+            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
+        }
+    }
+}
+// the fp32 bits of the lane's 16 values: as stored, or the bf16 halves of a dword widened
+template <bool COMPACT, bool HALF>
+__device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, float (&v)[kSliceSteps * kLaneElems]) {
+#pragma unroll
+    for (int j = 0; j < kSliceSteps; ++j) {
+        if constexpr (HALF) {
+            v[4 * j + 0] = i2f((int)(s.q[j].x << 16)); v[4 * j + 1] = i2f((int)(s.q[j].x & 0xffff0000u));
+            v[4 * j + 2] = i2f((int)(s.q[j].y << 16)); v[4 * j + 3] = i2f((int)(s.q[j].y & 0xffff0000u));
+        } else {
+            v[4 * j + 0] = i2f((int)s.v[j].x); v[4 * j + 1] = i2f((int)s.v[j].y); v[4 * j + 2] = i2f((int)s.v[j].z); v[4 * j + 3] = i2f((int)s.v[j].w);
+        }
+    }
+}
+// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j
+template <bool COMPACT, bool HALF>
+__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
+    if constexpr (COMPACT) {
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) {
+            unsigned a, b;
+            if constexpr (HALF) { a = s.q[j].z; b = s.q[j].w; } else { a = s.m[j].x; b = s.m[j].y; }
+            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
+            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
+            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
+            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
+    }
+}
+
+// y = beta * bias, 4 consecutive floats per thread.  Each thread reads what it writes: bias may be y.
+__global__ __launch_bounds__(256) void transpose_prologue_kernel(const float* bias, float* y, int n, float beta, int vec) {
+    const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    if (vec && i0 + 3 < n) {
+        float4 b = float4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (beta != 0.0f) { b = *(const float4*)(bias + i0); b.x *= beta; b.y *= beta; b.z *= beta; b.w *= beta; }
+        *(float4*)(y + i0) = b;
+    } else {
+        for (long long i = i0; i < i0 + 4 && i < n; ++i) y[i] = beta != 0.0f ? beta * bias[i] : 0.0f;
+    }
+}
+
+// The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
+// STRAYS: the plan has stray areas behind the window (m.has_strays); whether THIS group uses them is bit 2 of its group word.
+// LDS as in the forward launch: [window: lds_floats (the wavefronts' stray areas are its last floats)][ytile_floats per wavefront].
+template <bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
+__device__ __forceinline__ void slices_group_t(
+    const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const float* __restrict__ x, float* y,
+    float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows, long long group, int4 g) {
+    extern __shared__ float xs[];
+    constexpr unsigned kNoAccess = 0xffffffffu;
+    constexpr int kE = kSliceSteps * kLaneElems;
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
+    // x is reached through a buffer descriptor over `rows` floats: a row past the end (the open row behind the last slice) reads as 0
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
+    float* const xtile = xs + (USE_LDS ? lds_floats : 0) + wave * ytile_floats;
+    const long long first = group * group_slices;
+    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
+    const int n_here = (int)(last > first ? last - first : 0);
+    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
+    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
+    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;      // 0 fragments: the metas of this group are plain columns
+    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
+    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
+    float* const stray_area = xs + win_floats + wave * kStraySlots;
+    // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
+
+    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the window is zeroed
+    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
+    int k_slice = wave;
+    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
+    SliceRaw<COMPACT, HALF> w;
+    int4 h = int4{0, 0, 0, 0};
+    if (local < n_here) {
+        h = load_int4(hdr + first + local);
+        request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    }
+    if (USE_LDS) {
+        for (int i = (int)threadIdx.x; i < lds_floats; i += (int)blockDim.x) xs[i] = 0.0f;
+        __syncthreads();
+    }
+
+    while (local < n_here) {
+        const int row_first = __builtin_amdgcn_readfirstlane(h.x);      // first row that ends in this slice
+        const int n_rows = __builtin_amdgcn_readfirstlane(h.z);         // rows that end in it; its elements lie in rows row_first .. row_first + n_rows
+        const long long cur = first + local;
+        unsigned c[kE];
+        float v[kE];
+        decode_metas<COMPACT, HALF>(w, c);
+        slice_values<COMPACT, HALF>(w, v);
+        // x of the slice's rows -> this wavefront's tile, coalesced; the open last row has no place in a full tile and is kept in a register
+        for (int i = lane; i <= n_rows && i < ytile_floats; i += 64)
+            xtile[i] = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + i) << 2, 0, 0));
+        const float x_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+        unsigned sc = kNoAccess;
+        if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(cur * kStraySlots + lane) << 2, 0, 0);
+        // local row of every element = row ends before it in the slice (the forward kernel's ballots, plus the lane's own ends)
+        int lr[kE];
+        int row = 0;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) {
+            int below = 0, total = 0;
+#pragma unroll
+            for (int k = 0; k < kLaneElems; ++k) {
+                const unsigned long long m = __builtin_amdgcn_ballot_w64((c[4 * j + k] & kRowEndBit) != 0);
+                below += lanes_below(m);
+                total += __builtin_popcountll(m);
+            }
+            int r = row + below;
+#pragma unroll
+            for (int k = 0; k < kLaneElems; ++k) {
+                lr[4 * j + k] = r;
+                r += (c[4 * j + k] & kRowEndBit) ? 1 : 0;
+            }
+            row += total;
+        }
+        // the next slice of this wavefront, into the registers the copies above have left
+        k_slice += n_waves;
+        local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
+        if (local < n_here) {
+            h = load_int4(hdr + first + local);
+            request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+        }
+        __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order: the tile is complete for every lane)
+#pragma unroll
+        for (int i = 0; i < kE; ++i) {
+            const int li = lr[i] < ytile_floats ? lr[i] : ytile_floats - 1;
+            const float xt = xtile[li];
+            const float xr = lr[i] < ytile_floats ? xt : x_open;
+            if ((f2i(v[i]) & 0x7fffffff) == 0) continue;          // a +-0 slot adds nothing, whatever x holds
+            const float p = v[i] * xr;
+            if constexpr (COMPACT) {
+                const int idx = (int)(c[i] & 0x7fffu);
+                if (STRAYS && strays && idx >= win_floats) lds_add(stray_area + ((idx - win_floats) & (kStraySlots - 1)), p);
+                else lds_add(xs + idx, p);
+            } else {
+                const unsigned ci = c[i] & ~kRowEndBit;
+                if (USE_LDS && in_lds && !(ci & kGlobalColBit)) {
+                    if (ci < (unsigned)win_floats) lds_add(xs + ci, p);
+                } else {
+                    const unsigned col = ci & ~kGlobalColBit;
+                    if (col < (unsigned)cols) y_add(y, col, alpha * p);
+                }
+            }
+        }
+        if (STRAYS && strays) {       // the slice's strays leave for their columns; the area is zero again for the wavefront's next slice
+            __builtin_amdgcn_wave_barrier();
+            const float a = stray_area[lane];
+            stray_area[lane] = 0.0f;
+            if (sc != kNoAccess && sc < (unsigned)cols) y_add(y, sc, alpha * a);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (USE_LDS) {
+        __syncthreads();
+        // the flush: per fragment {col_start, len, lds_off} one wave-instruction per 64 consecutive floats of y
+        const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
+        for (int f = wave; f < nf; f += n_waves) {
+            const int4 fr = load_int4(frags + f0 + f);
+            const int col0 = __builtin_amdgcn_readfirstlane(fr.x), len = __builtin_amdgcn_readfirstlane(fr.y), off = __builtin_amdgcn_readfirstlane(fr.z);
+            for (int i = lane; i < len; i += 64)
+                if (col0 + i < cols && off + i < win_floats) y_add(y, (unsigned)(col0 + i), alpha * xs[off + i]);
+        }
+    }
+}
+
+// HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
+template <bool USE_LDS, bool STRAYS, bool HALF>
+__global__ __launch_bounds__(1024) void spmv_slices_t_kernel(
+    const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
+    const float* __restrict__ x, float* y, float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows) {
+    const long long group = (long long)blockIdx.x;
+    if constexpr (USE_LDS) {
+        const int4 g = load_int4(groups + group);
+        const int gw = __builtin_amdgcn_readfirstlane(g.w);
+        if constexpr (HALF) {
+            if (gw & kGroupHalf) {
+                slices_group_t<true, true, STRAYS, true>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+                return;
+            }
+        }
+        // (a compact group that is not half does not exist in a bf16 handle today; should a packer ever make one, it is decoded as what
+        // its group word says it is)
+        if (gw & kGroupCompact)
+            slices_group_t<true, true, STRAYS, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+        else
+            slices_group_t<true, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+    } else {
+        slices_group_t<false, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, int4{0, 0, 0, 0});
+    }
+}
+
+// Dense: a workgroup of 256 threads takes rows [r0, r1) x kGemvTCols columns.  A thread owns 4 consecutive columns (one 16-byte load of
+// fp32 W per row, 8 bytes of bf16 W) and sums over the rows in registers, x[row] wave-uniform; the sums cross the LDS so that every
+// wave-instruction of the output covers 64 consecutive floats of y.  VEC: cols % 4 == 0 and W aligned; otherwise element loads (odd
+// cols, where a row of W starts at any 4-byte -- bf16: 2-byte -- boundary).
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(256) void gemv_t_kernel(const void* __restrict__ Wv, int rows, int cols, const float* __restrict__ x, float* y,
+                                                    float alpha, int rows_per_block, int atomic) {
+    __shared__ float out[kGemvTCols];
+    const int tid = (int)threadIdx.x;
+    const int cb = (int)blockIdx.x * kGemvTCols;
+    const int c0 = cb + tid * 4;
+    const int r0 = (int)blockIdx.y * rows_per_block;
+    const int r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    if (c0 < cols) {
+#pragma unroll 4
+        for (int r = r0; r < r1; ++r) {
+            const float xr = x[r];
+            const size_t at = (size_t)r * (size_t)cols + (size_t)c0;
+            float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
+            if constexpr (BF16) {
+                const uint16_t* W = (const uint16_t*)Wv;
+                if constexpr (VEC) {
+                    const uint2 q = *(const uint2*)(W + at);
+                    w0 = i2f((int)(q.x << 16)); w1 = i2f((int)(q.x & 0xffff0000u)); w2 = i2f((int)(q.y << 16)); w3 = i2f((int)(q.y & 0xffff0000u));
+                } else {
+                    w0 = i2f((int)((unsigned)W[at] << 16));
+                    if (c0 + 1 < cols) w1 = i2f((int)((unsigned)W[at + 1] << 16));
+                    if (c0 + 2 < cols) w2 = i2f((int)((unsigned)W[at + 2] << 16));
+                    if (c0 + 3 < cols) w3 = i2f((int)((unsigned)W[at + 3] << 16));
+                }
+            } else {
+                const float* W = (const float*)Wv;
+                if constexpr (VEC) {
+                    const float4 q = *(const float4*)(W + at);
+                    w0 = q.x; w1 = q.y; w2 = q.z; w3 = q.w;
+                } else {
+                    w0 = W[at];
+                    if (c0 + 1 < cols) w1 = W[at + 1];
+                    if (c0 + 2 < cols) w2 = W[at + 2];
+                    if (c0 + 3 < cols) w3 = W[at + 3];
+                }
+            }
+            a0 += w0 * xr; a1 += w1 * xr; a2 += w2 * xr; a3 += w3 * xr;
+        }
+    }
+    out[tid * 4 + 0] = a0; out[tid * 4 + 1] = a1; out[tid * 4 + 2] = a2; out[tid * 4 + 3] = a3;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int col = cb + tid + 256 * k;
+        if (col >= cols) continue;
+        const float s = alpha * out[tid + 256 * k];
+        if (atomic) y_add(y, (unsigned)col, s);
+        else y[col] = y[col] + s;            // one row block: this thread is the only writer of the column
+    }
+}
+
+template <auto Kernel>
+hipError_t raise_lds_limit() {
+    static std::once_flag once;
+    static hipError_t status = hipSuccess;
+    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
+    return status;
+}
+
+template <bool USE_LDS, bool STRAYS, bool HALF>
+hipError_t launch_slices_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
+    constexpr auto kernel = spmv_slices_t_kernel<USE_LDS, STRAYS, HALF>;
+    const hipError_t e = raise_lds_limit<kernel>();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m), stream, (const char*)m.words, m.hdr,
+                       m.groups, m.frags, x, y, alpha, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_transpose_prologue(const float* bias, float* y, int32_t n, float beta, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (n <= 0) return hipSuccess;
+    const bool aligned = ((uintptr_t)y & 15) == 0 && (beta == 0.0f || ((uintptr_t)bias & 15) == 0);
+    hipLaunchKernelGGL(transpose_prologue_kernel, dim3((unsigned)(((int64_t)n + 1023) / 1024)), dim3(256), 0, stream, bias, y, (int)n, beta, aligned ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_spmv_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
+    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || slice_lds_bytes(m) > (size_t)kDynLdsMax)
+        return hipErrorInvalidValue;
+    // stray slots and half groups exist only in plans with a window (hispmv_abi.cpp)
+    const bool window = m.lds_floats > 0;
+    if (!window) return (m.has_strays || m.has_half) ? hipErrorInvalidValue : launch_slices_t<false, false, false>(m, x, y, alpha, stream);
+    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
+    if (m.has_strays) return m.has_half ? launch_slices_t<true, true, true>(m, x, y, alpha, stream) : launch_slices_t<true, true, false>(m, x, y, alpha, stream);
+    return m.has_half ? launch_slices_t<true, false, true>(m, x, y, alpha, stream) : launch_slices_t<true, false, false>(m, x, y, alpha, stream);
+}
+
+// Row blocks per column block: enough workgroups to fill the chip twice over (1024 in all) while a block keeps at least 16 rows,
+// so that a small layer still spreads over the CUs and the atomic bytes stay a small multiple of y.
+int gemv_t_row_blocks(int32_t rows, int32_t cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    const int64_t col_blocks = ((int64_t)cols + kGemvTCols - 1) / kGemvTCols;
+    const int64_t want = std::max<int64_t>(1, (1024 + col_blocks - 1) / col_blocks);
+    const int64_t most = ((int64_t)rows + 15) / 16;
+    const int64_t nb = std::min(want, most);
+    const int64_t per = ((int64_t)rows + nb - 1) / nb;
+    return (int)(((int64_t)rows + per - 1) / per);
+}
+
+hipError_t launch_gemv_t(const void* W, int32_t rows, int32_t cols, bool bf16, const float* x, float* y, float alpha, hipStream_t stream) {
+    (void)hipGetLastError();
+    const int nb = gemv_t_row_blocks(rows, cols);
+    if (nb <= 0) return hipSuccess;
+    const int per = (rows + nb - 1) / nb;
+    const dim3 grid((unsigned)(((int64_t)cols + kGemvTCols - 1) / kGemvTCols), (unsigned)nb);
+    const bool vec = (cols & 3) == 0 && ((uintptr_t)W & (bf16 ? 7 : 15)) == 0;
+    const int atomic = nb > 1 ? 1 : 0;
+    if (bf16) {
+        if (vec) hipLaunchKernelGGL((gemv_t_kernel<true, true>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+        else hipLaunchKernelGGL((gemv_t_kernel<true, false>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+    } else {
+        if (vec) hipLaunchKernelGGL((gemv_t_kernel<false, true>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+        else hipLaunchKernelGGL((gemv_t_kernel<false, false>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace hispmv

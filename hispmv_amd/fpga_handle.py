@@ -78,6 +78,8 @@ class FpgaHandle:
             raise OSError(msg)
         if rc == _lib.HISPMV_ENOMEM:
             raise MemoryError(msg)
+        if rc == _lib.HISPMV_ENOTSUP:
+            raise NotImplementedError(msg)
         raise RuntimeError(msg)
 
     # -- reference API (bindings :15-38) --------------------------------------------------------
@@ -187,6 +189,27 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range")
         return {"storage": "bf16" if out[0] == _lib.HISPMV_VALUES_BF16 else "fp32", "slots_2byte": int(out[1]), "slots_4byte": int(out[2]),
                 "saved_bytes": int(out[3])}
+
+    def set_transposable(self, enable: bool) -> None:
+        """Sparse handles created from now on (until switched off) keep the slice stream, so that spmv_device_t accepts them
+        (hispmv_set_transposable)."""
+        self._check(lib.hispmv_set_transposable(self._ctx, int(bool(enable))))
+
+    def spmv_device_t(self, matrix_idx: int, d_x: int, d_bias: int, d_y: int, alpha: float, beta: float,
+                      stream: int = 0) -> None:
+        """y[cols] = alpha * A^T x[rows] + beta * bias[cols] on device pointers (ints), asynchronous on `stream` (hispmv_spmv_device_t).
+        Sums arrive through float atomics: the last bits may differ from run to run.  d_y must be ordinary device memory (not fine-grained
+        or host-pinned).  A tile-stream handle raises NotImplementedError."""
+        self._check(lib.hispmv_spmv_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_x), C.c_void_p(d_bias),
+                                             C.c_void_p(d_y), float(alpha), float(beta), C.c_void_p(stream)))
+
+    def transpose_info(self, matrix_idx: int) -> dict:
+        """{"transposable", "launches", "atomic_bytes", "direct_elems"} of a handle (hispmv_transpose_info)."""
+        out = (C.c_int64 * 4)()
+        rc = lib.hispmv_transpose_info(self._ctx, int(matrix_idx), out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range")
+        return {"transposable": bool(out[0]), "launches": int(out[1]), "atomic_bytes": int(out[2]), "direct_elems": int(out[3])}
 
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))

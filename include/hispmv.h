@@ -30,6 +30,7 @@ extern "C" {
 #define HISPMV_ENOTDENSE  -5   /* dense handle requested on a context created without dense_overlay (spmv-helper.cpp:718) */
 #define HISPMV_EIO        -6   /* MatrixMarket file unreadable / malformed */
 #define HISPMV_ENOMEM     -7
+#define HISPMV_ENOTSUP    -8   /* the handle's device format has no kernel for the operation (hispmv_spmv_device_t on a tile stream) */
 
 typedef struct hispmv_ctx hispmv_ctx;
 
@@ -170,6 +171,45 @@ int hispmv_set_value_storage(hispmv_ctx* ctx, int storage);
 /* out = {storage of the handle, value slots held in 2 bytes, value slots held in 4 bytes, device bytes the handle saves against
  * fp32 storage}; the slices of a batch layout count again (as in hispmv_value_update_info). */
 int hispmv_value_storage_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
+
+/* ---- transposed product (no reference counterpart; MKL SPARSE_OPERATION_TRANSPOSE, hipSPARSE HIPSPARSE_OPERATION_TRANSPOSE) ----------
+ *   y[cols] = alpha * A^T * x[rows] + beta * bias[cols]
+ * on a loaded handle: hispmv_spmv_device with the roles of the two dimensions exchanged -- d_x holds `rows` floats, d_bias and d_y
+ * `cols`.  Device pointers, asynchronous on `stream` (the stream rule above: NULL = the context's stream).  Nothing is stored for it:
+ * the kernels read the layout the forward product reads (the row of a slice element is its slice's row base plus the row ends before
+ * it, its column is the meta), so a value update is seen by both products and the handle uses no extra arena bytes.
+ *  - beta == 0: bias is not read and may be NULL, y is overwritten.  alpha == 0: y is exactly beta * bias.
+ *  - d_bias == d_y is allowed.  d_x == d_y, a NULL d_x or d_y, a NULL d_bias with beta != 0 -> HISPMV_EINVAL; before
+ *    hispmv_load_matrices -> HISPMV_ESTATE.  The argument checks come before any device call.
+ *  - d_y must be ordinary device memory (hipMalloc, a torch tensor: coarse-grained).  The adds into y are hardware float atomics
+ *    without a compare-and-swap fall-back; on fine-grained or host-pinned memory they are not guaranteed to land.  The forward
+ *    entries store plainly and have no such precondition; d_x and d_bias are only read and may live anywhere the device can read.
+ *  - A bf16 handle multiplies with its stored (rounded) values.
+ *  - ZERO SLOTS: a stored slot whose value is +-0 contributes nothing, whatever x holds.  That covers the zero-valued fillers of empty
+ *    rows, the row extensions of aligned slices, tail padding and explicit zeros of the input: an Inf or NaN in x[empty row] does not
+ *    reach any y[col] (0 * Inf would), and neither does one in x[r] through an explicit zero a_rc.
+ *  - ORDER: the sums into one y[col] arrive through float atomic adds, in no fixed order.  The result may differ in the last bits
+ *    from run to run and from the forward product of a handle created from the swapped COO; this entry does not keep the bit-for-bit
+ *    promises of the forward entries.  The handle's own state (carries, tickets, cached batch plans) is not touched.
+ *  - A sparse handle whose device format is the transposed tile stream (hispmv_matrix_info.format == 1) has no transposed kernel:
+ *    HISPMV_ENOTSUP, and the message names the remedy, hispmv_set_transposable.  Every slice-stream handle (all its parts: column
+ *    tiles, band tiles, stray split) and every dense handle is accepted.
+ * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, several vectors per pass, host-pointer entries,
+ * sharding over devices, a tile-stream kernel. */
+int hispmv_spmv_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, const float* d_bias, float* d_y,
+                         float alpha, float beta, void* stream);
+/* Context-wide switch, default off, may be flipped between creations (like hispmv_set_value_storage): a sparse handle created while
+ * it is on keeps the slice stream -- the format choice of that creation is the one HISPMV_FORMAT=slices makes for a whole process --
+ * and is therefore accepted by hispmv_spmv_device_t.  Nothing else about the handle changes.  A handle created while the switch is
+ * off that happens to be a slice stream is transposable all the same, and so is every dense handle. */
+int hispmv_set_transposable(hispmv_ctx* ctx, int enable);
+/* out = {1 if hispmv_spmv_device_t accepts the (loaded) handle; launches of one call with alpha != 0 (the prologue y = beta * bias +
+ * one per part); bytes of float atomic adds to y per call (window flushes + stray flushes + direct adds); stream elements that add
+ * to y directly, one atomic each (elements outside their group's window, every stored slot -- fillers included, which add nothing
+ * at run time -- of a group or plan without a window)}.  The flushes are 256 contiguous bytes per wave-instruction, the cheap shape;
+ * the direct adds scatter over up to 64 lines per wave-instruction, the expensive one.  Zeros for a handle that is not transposable
+ * or not loaded. */
+int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
 
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */
