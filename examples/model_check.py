@@ -5,10 +5,12 @@ batch 1, every layer called rp_time=100 times through `FpgaHandle.linear` with R
 (model.py:68-80), weights seeded with torch.manual_seed(0).  The reference compares against torch /
 sparse_dot_mkl and prints error histograms; here the comparison is against an fp64 evaluation.
 
-    python examples/model_check.py [--batch_size 1 --rp_time 100] [--bf16]
+    python examples/model_check.py [--batch_size 1 --rp_time 100] [--bf16] [--device-linear]
 
 --bf16: the weights are stored as bfloat16 (FpgaHandle.set_value_storage("bf16"): rounded once at creation, fp32 accumulation); the
 fp64 truth is then computed from the rounded weights and the 1e-5 verdict stays.
+--device-linear: the layers run through hispmv_amd.torch_ops.sparse_linear on device tensors (the activations cross PCIe once in and
+once out per layer for the check, not once per call); the verdicts are the same.
 """
 import argparse
 import os
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--density2", type=float, default=0.25)
     ap.add_argument("--rp_time", type=int, default=100)
     ap.add_argument("--bf16", action="store_true", help="store the weights as bfloat16 (bf16 value storage)")
+    ap.add_argument("--device-linear", action="store_true", help="run the layers through torch_ops.sparse_linear on device tensors")
     a = ap.parse_args()
     torch.manual_seed(0)
     fpga = FpgaHandle("builds/Dense-HI-SpMV-24-1-1/SpMV.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
@@ -68,8 +71,16 @@ def main():
     worst = 0.0
     for (kind, w, b), idx in zip(layers, handles):
         t = time.time()
-        for _ in range(a.rp_time):
-            y = fpga.linear(idx, h.reshape(-1), b)
+        if a.device_linear:
+            from hispmv_amd.torch_ops import sparse_linear
+            dh, db = torch.from_numpy(np.ascontiguousarray(h, np.float32)).cuda(), torch.from_numpy(np.ascontiguousarray(b, np.float32)).cuda()
+            for _ in range(a.rp_time):
+                dy = sparse_linear(fpga, idx, dh, db)
+            torch.cuda.synchronize()
+            y = dy.cpu().numpy()
+        else:
+            for _ in range(a.rp_time):
+                y = fpga.linear(idx, h.reshape(-1), b)
         dt = (time.time() - t) / a.rp_time
         y = y.reshape(a.batch_size, -1)
         wd = w.to_dense().numpy() if kind == "sparse" else w
@@ -80,8 +91,11 @@ def main():
         mag = np.abs(h.astype(np.float64)) @ np.abs(wd.T) + np.abs(b)
         err = float(np.max(np.abs(y - y64) / mag))
         worst = max(worst, err)
-        print(f"layer {idx} ({kind} {wd.shape[0]}x{wd.shape[1]}): {dt * 1e6:.1f} us per linear() call incl. PCIe, "
-              f"device {fpga.last_kernel_ms() * 1e3:.1f} us, backward error {err:.2e}")
+        if a.device_linear:
+            print(f"layer {idx} ({kind} {wd.shape[0]}x{wd.shape[1]}): {dt * 1e6:.1f} us per sparse_linear() call on device tensors, backward error {err:.2e}")
+        else:
+            print(f"layer {idx} ({kind} {wd.shape[0]}x{wd.shape[1]}): {dt * 1e6:.1f} us per linear() call incl. PCIe, "
+                  f"device {fpga.last_kernel_ms() * 1e3:.1f} us, backward error {err:.2e}")
         h = np.maximum(y, 0).astype(np.float32)
     fpga.close()
     print("model check", "passed" if worst < 1e-5 else "FAILED", f"(worst backward error {worst:.2e})")

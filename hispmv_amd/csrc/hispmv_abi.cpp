@@ -1037,6 +1037,137 @@ HISPMV_API int hispmv_spmv_device_t(hispmv_ctx* c, int idx, const float* d_x, co
     return HISPMV_OK;
 }
 
+// ---- several vectors on device pointers (include/hispmv.h: hispmv_linear_device, hispmv_linear_device_t) ---------------------------
+namespace {
+
+// The checks both entries share, all before any device call; on success *out is the handle.  in_len / out_len: floats per vector.
+int linear_device_target(hispmv_ctx* c, int idx, const float* d_x, int64_t num_vecs, const float* d_bias, const float* d_y, float beta,
+                         const char* who, Matrix** out) {
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[idx];
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, std::string(who) + " called before load_matrices");
+    if (num_vecs < 1) return fail(c, HISPMV_EINVAL, std::string(who) + ": num_vecs must be at least 1");
+    if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
+    if (d_x == d_y) return fail(c, HISPMV_EINVAL, std::string(who) + ": x and y must not be the same vectors");
+    if ((int64_t)m.rows * num_vecs >= (1LL << 30) || (int64_t)m.cols * num_vecs >= (1LL << 30))
+        return fail(c, HISPMV_EINVAL, std::string(who) + ": rows * num_vecs and cols * num_vecs must stay below 2^30 floats; split the batch");
+    *out = &m;
+    return HISPMV_OK;
+}
+
+// The passes of a forward call with beta != 0: widest pass and number of passes.  A COPY of the width choices of
+// launch_matrix_vectors (above) and launch_gemv_batched (hispmv_kernels.hip), which launch as they choose and report nothing: whoever
+// changes a width there changes it here.  (The transposed side has one function, transposed_width, for launch loop and report.)
+void forward_passes(const Matrix& m, int64_t vecs, int64_t& widest, int64_t& passes) {
+    widest = 0; passes = 0;
+    for (int64_t k = 0; k < vecs;) {
+        int64_t nv = 1;
+        if (vecs == 1) nv = 1;
+        else if (m.dense) nv = vecs - k >= 8 ? 8 : vecs - k >= 4 ? 4 : vecs - k >= 2 ? 2 : 1;
+        else if (m.format == 1) {
+            if (m.parts.size() == 1 && !m.parts[0].tdev.zero_fill) {
+                nv = tts_batch_width(m.parts[0].tdev, vecs - k);
+                if (nv < 2) nv = std::min<int64_t>(vecs - k, kTtsMaxVectors);
+            }
+        } else {
+            nv = kMaxBatch;
+            for (auto& p : m.parts) nv = std::min<int64_t>(nv, spmv_batch_width(p.dev, vecs - k));
+        }
+        widest = std::max(widest, nv); passes += 1; k += nv;
+    }
+}
+int transposed_width(const Matrix& m, int64_t left) {
+    if (m.dense) return gemv_t_width(left);
+    int nv = kMaxBatch;
+    for (auto& p : m.parts) nv = std::min(nv, spmv_t_width(p.dev, left));
+    return nv;
+}
+
+}  // namespace
+
+HISPMV_API int hispmv_linear_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t out[5]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size() || num_vecs < 1) return HISPMV_EINVAL;
+    const Matrix& m = *c->mats[(size_t)idx];
+    for (int i = 0; i < 5; ++i) out[i] = 0;
+    if (!m.loaded) return HISPMV_OK;
+    forward_passes(m, num_vecs, out[0], out[1]);
+    if (!m.dense && m.format != 0) return HISPMV_OK;
+    int64_t launches = 1;           // the prologue
+    for (int64_t k = 0; k < num_vecs;) {
+        const int nv = transposed_width(m, num_vecs - k);
+        out[2] = std::max<int64_t>(out[2], nv); out[3] += 1; k += nv;
+        if (m.dense) launches += 1;
+        else for (auto& p : m.parts) launches += p.dev.n_groups > 0 ? 1 : 0;
+    }
+    out[4] = launches;
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_linear_device(hispmv_ctx* c, int idx, const float* d_x, int64_t num_vecs, const float* d_bias, float* d_y,
+                                    float alpha, float beta, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    Matrix* mp = nullptr;
+    const int rc = linear_device_target(c, idx, d_x, num_vecs, d_bias, d_y, beta, "linear_device", &mp);
+    if (rc != HISPMV_OK) return rc;
+    Matrix& m = *mp;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (stream) c->user_stream = (hipStream_t)stream;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    // A d_x off the 16-byte alignment takes one vector per pass (the same bits): the launches hispmv_spmv_device makes for such a
+    // pointer.  Single- and multi-vector kernels alike stage x with 16-byte global loads (stage_fragments, the dense and tile-stream
+    // bodies), so this does not align those loads -- the hardware executes them at any 4-byte address --; it keeps an unusual
+    // pointer off the batched passes, whose only stated condition is on cols (spmv_batch_width).
+    if (((uintptr_t)d_x & 15) != 0 && num_vecs > 1) {
+        for (int64_t k = 0; k < num_vecs; ++k) {
+            const int r1 = launch_matrix_vectors(c, m, 1, d_x + k * m.cols, d_bias, d_y + k * m.rows, alpha, beta, s, true);
+            if (r1 != HISPMV_OK) return r1;
+        }
+        return HISPMV_OK;
+    }
+    return launch_matrix_vectors(c, m, num_vecs, d_x, d_bias, d_y, alpha, beta, s, true);
+}
+
+HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, int64_t num_vecs, const float* d_bias, int64_t bias_stride,
+                                      float* d_y, float alpha, float beta, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    Matrix* mp = nullptr;
+    const int rc = linear_device_target(c, idx, d_x, num_vecs, d_bias, d_y, beta, "linear_device_t", &mp);
+    if (rc != HISPMV_OK) return rc;
+    Matrix& m = *mp;
+    if (bias_stride != 0 && bias_stride != m.cols) return fail(c, HISPMV_EINVAL, "linear_device_t: bias_stride must be 0 (one bias for all vectors) or cols");
+    if (beta != 0.0f && d_bias == d_y && bias_stride == 0 && num_vecs > 1)
+        return fail(c, HISPMV_EINVAL, "linear_device_t: d_bias == d_y needs bias_stride = cols (a shared bias would be overwritten by vector 0)");
+    if (!m.dense && m.format != 0)
+        return fail(c, HISPMV_ENOTSUP, "spmv_device_t: this handle is a transposed tile stream, which has no transposed product; create it after "
+                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (stream) c->user_stream = (hipStream_t)stream;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    // ONE prologue for all vectors, then passes of the widest width that fits (4, 2, 1; dense 8, 4, 2, 1)
+    hipError_t e = launch_transpose_prologue(d_bias, d_y, m.cols, beta, s, num_vecs, bias_stride);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
+    if (alpha == 0.0f) return HISPMV_OK;          // y is exactly beta * bias, per vector
+    for (int64_t k = 0; k < num_vecs;) {
+        const int nv = transposed_width(m, num_vecs - k);
+        const float* xk = d_x + k * m.rows;
+        float* yk = d_y + k * m.cols;
+        if (m.dense) {
+            e = nv == 1 ? launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, xk, yk, alpha, s)
+                        : launch_gemv_t_nv(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, nv, xk, yk, alpha, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_t");
+        } else {
+            for (auto& p : m.parts) {
+                e = nv == 1 ? launch_spmv_t(p.dev, xk, yk, alpha, s) : launch_spmv_t_nv(p.dev, nv, xk, yk, alpha, s);
+                if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_t");
+            }
+        }
+        k += nv;
+    }
+    return HISPMV_OK;
+}
+
 HISPMV_API int hispmv_synchronize(hispmv_ctx* c) {
     if (!c) return HISPMV_EINVAL;
     HIP_TRY(c, hipSetDevice(c->device));

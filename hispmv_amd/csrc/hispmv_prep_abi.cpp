@@ -135,6 +135,22 @@ HISPMV_API int hispmv_prep_plan(const hispmv_prep* p, int n_cus, int64_t plan[6]
     return HISPMV_OK;
 }
 
+// The widths hispmv_linear_device / hispmv_linear_device_t take for this stream as a single-part handle: the plan's workgroup, its
+// window with the stray areas the packer puts behind it, its row tiles -- the figures the loader hands the launchers.
+HISPMV_API int hispmv_prep_vector_widths(const hispmv_prep* p, int n_cus, int64_t num_vecs, int64_t out[2]) {
+    if (!p || !out || n_cus <= 0 || num_vecs < 1) return HISPMV_EINVAL;
+    SliceStream copy = p->st;
+    const LaunchPlan g = make_plan(copy, n_cus);
+    const DeviceStream ds = pack_device_stream(copy, g, false, p->half_values);
+    SpmvDeviceMatrix d;
+    d.block_threads = g.block_threads; d.group_slices = g.group_slices;
+    d.lds_floats = g.lds_floats + ds.stray_floats; d.ytile_floats = g.ytile_floats;
+    d.rows = p->st.rows; d.cols = p->st.cols;
+    out[0] = spmv_batch_width(d, num_vecs);
+    out[1] = spmv_t_width(d, num_vecs);
+    return HISPMV_OK;
+}
+
 HISPMV_API int hispmv_prep_apply_plan(hispmv_prep* p, int n_cus, int64_t counts[2]) {
     if (!p || !counts || n_cus <= 0) return HISPMV_EINVAL;
     p->plan = make_plan(p->st, n_cus);

@@ -108,15 +108,17 @@ __device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, u
 }
 
 // y = beta * bias, 4 consecutive floats per thread.  Each thread reads what it writes: bias may be y.
-__global__ __launch_bounds__(256) void transpose_prologue_kernel(const float* bias, float* y, int n, float beta, int vec) {
+// Several vectors are ONE array of n floats to this kernel (y of vector v begins at v * cols); `period` > 0: they share one bias of
+// `period` floats (y[i] = beta * bias[i % period]; `vec` then requires period % 4 == 0), 0: bias is as long as y.
+__global__ __launch_bounds__(256) void transpose_prologue_kernel(const float* bias, float* y, int n, float beta, int vec, int period) {
     const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 >= n) return;
     if (vec && i0 + 3 < n) {
         float4 b = float4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (beta != 0.0f) { b = *(const float4*)(bias + i0); b.x *= beta; b.y *= beta; b.z *= beta; b.w *= beta; }
+        if (beta != 0.0f) { b = *(const float4*)(bias + (period ? i0 % period : i0)); b.x *= beta; b.y *= beta; b.z *= beta; b.w *= beta; }
         *(float4*)(y + i0) = b;
     } else {
-        for (long long i = i0; i < i0 + 4 && i < n; ++i) y[i] = beta != 0.0f ? beta * bias[i] : 0.0f;
+        for (long long i = i0; i < i0 + 4 && i < n; ++i) y[i] = beta != 0.0f ? beta * bias[period ? i % period : i] : 0.0f;
     }
 }
 
@@ -271,6 +273,167 @@ __global__ __launch_bounds__(1024) void spmv_slices_t_kernel(
     }
 }
 
+// NV vectors through one pass over the stream (hispmv_linear_device_t): slices_group_t with the roles batched_group has against
+// slices_group in the forward file.  Vector v reads x + v * rows and adds into y + v * cols.  A slice's words are decoded ONCE -- metas
+// c, values v, local rows lr stay in registers -- and the NV vectors then go through the body one after the other.
+// LDS: [NV accumulator windows of lds_floats each, stray areas included: window v at xs + v * lds_floats][ONE x tile per wavefront],
+// slice_lds_bytes(m, NV) in all.  Every vector has its own buffer descriptor over its `rows` floats of x, so the open row behind the
+// last slice reads 0 and not the next vector's x[0].  The first 64 floats of the next vector's tile and its open row are requested
+// before the current vector's elements are multiplied.
+template <int NV, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
+__device__ __forceinline__ void slices_group_t_nv(
+    const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const float* __restrict__ x, float* y,
+    float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows, long long group, int4 g) {
+    extern __shared__ float xs[];
+    constexpr unsigned kNoAccess = 0xffffffffu;
+    constexpr int kE = kSliceSteps * kLaneElems;
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
+    float* const xtile = xs + (USE_LDS ? lds_floats * NV : 0) + wave * ytile_floats;
+    const long long first = group * group_slices;
+    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
+    const int n_here = (int)(last > first ? last - first : 0);
+    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
+    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
+    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;
+    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
+    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
+    const int stray_at = win_floats + wave * kStraySlots;          // this wavefront's stray area inside every vector's window
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
+
+    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
+    int k_slice = wave;
+    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
+    SliceRaw<COMPACT, HALF> w;
+    int4 h = int4{0, 0, 0, 0};
+    if (local < n_here) {
+        h = load_int4(hdr + first + local);
+        request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    }
+    if (USE_LDS) {
+        for (int i = (int)threadIdx.x; i < lds_floats * NV; i += (int)blockDim.x) xs[i] = 0.0f;
+        __syncthreads();
+    }
+
+    while (local < n_here) {
+        const int row_first = __builtin_amdgcn_readfirstlane(h.x);
+        const int n_rows = __builtin_amdgcn_readfirstlane(h.z);
+        const long long cur = first + local;
+        unsigned c[kE];
+        float v[kE];
+        decode_metas<COMPACT, HALF>(w, c);
+        slice_values<COMPACT, HALF>(w, v);
+        unsigned sc = kNoAccess;
+        if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(cur * kStraySlots + lane) << 2, 0, 0);
+        int lr[kE];
+        int row = 0;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) {
+            int below = 0, total = 0;
+#pragma unroll
+            for (int k = 0; k < kLaneElems; ++k) {
+                const unsigned long long m = __builtin_amdgcn_ballot_w64((c[4 * j + k] & kRowEndBit) != 0);
+                below += lanes_below(m);
+                total += __builtin_popcountll(m);
+            }
+            int r = row + below;
+#pragma unroll
+            for (int k = 0; k < kLaneElems; ++k) {
+                lr[4 * j + k] = r;
+                r += (c[4 * j + k] & kRowEndBit) ? 1 : 0;
+            }
+            row += total;
+        }
+        k_slice += n_waves;
+        local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
+        if (local < n_here) {
+            h = load_int4(hdr + first + local);
+            request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+        }
+        // vector 0: the head of its tile (rows row_first + lane; past the end of x the descriptor gives 0) and its open row
+        __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
+        float t_head = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + lane) << 2, 0, 0));
+        float t_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+#pragma unroll 1
+        for (int vv = 0; vv < NV; ++vv) {
+            float* const win = xs + vv * lds_floats;
+            float* const yv = y + (size_t)vv * (size_t)cols;
+            if (lane <= n_rows && lane < ytile_floats) xtile[lane] = t_head;
+            for (int i = lane + 64; i <= n_rows && i < ytile_floats; i += 64)
+                xtile[i] = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + i) << 2, 0, 0));
+            const float x_open = t_open;
+            if (vv + 1 < NV) {
+                rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)(vv + 1) * (size_t)rows), 0, rows * 4, 0x00020000);
+                t_head = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + lane) << 2, 0, 0));
+                t_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+            }
+            __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order: the tile is complete for every lane)
+#pragma unroll
+            for (int i = 0; i < kE; ++i) {
+                const int li = lr[i] < ytile_floats ? lr[i] : ytile_floats - 1;
+                const float xt = xtile[li];
+                const float xr = lr[i] < ytile_floats ? xt : x_open;
+                if ((f2i(v[i]) & 0x7fffffff) == 0) continue;          // a +-0 slot adds nothing, whatever x holds
+                const float p = v[i] * xr;
+                if constexpr (COMPACT) {
+                    const int idx = (int)(c[i] & 0x7fffu);
+                    if (STRAYS && strays && idx >= win_floats) lds_add(win + stray_at + ((idx - win_floats) & (kStraySlots - 1)), p);
+                    else lds_add(win + idx, p);
+                } else {
+                    const unsigned ci = c[i] & ~kRowEndBit;
+                    if (USE_LDS && in_lds && !(ci & kGlobalColBit)) {
+                        if (ci < (unsigned)win_floats) lds_add(win + ci, p);
+                    } else {
+                        const unsigned col = ci & ~kGlobalColBit;
+                        if (col < (unsigned)cols) y_add(yv, col, alpha * p);
+                    }
+                }
+            }
+            if (STRAYS && strays) {       // this vector's strays of the slice leave for their columns; its area is zero again
+                __builtin_amdgcn_wave_barrier();
+                const float a = win[stray_at + lane];
+                win[stray_at + lane] = 0.0f;
+                if (sc != kNoAccess && sc < (unsigned)cols) y_add(yv, sc, alpha * a);
+            }
+            __builtin_amdgcn_wave_barrier();      // the tile is read: the next vector (or slice) may fill it
+        }
+    }
+    if (USE_LDS) {
+        __syncthreads();
+        const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
+        for (int f = wave; f < nf; f += n_waves) {
+            const int4 fr = load_int4(frags + f0 + f);
+            const int col0 = __builtin_amdgcn_readfirstlane(fr.x), len = __builtin_amdgcn_readfirstlane(fr.y), off = __builtin_amdgcn_readfirstlane(fr.z);
+#pragma unroll
+            for (int vv = 0; vv < NV; ++vv)
+                for (int i = lane; i < len; i += 64)
+                    if (col0 + i < cols && off + i < win_floats) y_add(y + (size_t)vv * (size_t)cols, (unsigned)(col0 + i), alpha * xs[vv * lds_floats + off + i]);
+        }
+    }
+}
+
+template <int NV, bool USE_LDS, bool STRAYS, bool HALF>
+__global__ __launch_bounds__(1024) void spmv_slices_t_nv_kernel(
+    const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
+    const float* __restrict__ x, float* y, float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows) {
+    const long long group = (long long)blockIdx.x;
+    if constexpr (USE_LDS) {
+        const int4 g = load_int4(groups + group);
+        const int gw = __builtin_amdgcn_readfirstlane(g.w);
+        if constexpr (HALF) {
+            if (gw & kGroupHalf) {
+                slices_group_t_nv<NV, true, true, STRAYS, true>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+                return;
+            }
+        }
+        if (gw & kGroupCompact)
+            slices_group_t_nv<NV, true, true, STRAYS, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+        else
+            slices_group_t_nv<NV, true, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+    } else {
+        slices_group_t_nv<NV, false, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, int4{0, 0, 0, 0});
+    }
+}
+
 // Dense: a workgroup of 256 threads takes rows [r0, r1) x kGemvTCols columns.  A thread owns 4 consecutive columns (one 16-byte load of
 // fp32 W per row, 8 bytes of bf16 W) and sums over the rows in registers, x[row] wave-uniform; the sums cross the LDS so that every
 // wave-instruction of the output covers 64 consecutive floats of y.  VEC: cols % 4 == 0 and W aligned; otherwise element loads (odd
@@ -329,6 +492,78 @@ __global__ __launch_bounds__(256) void gemv_t_kernel(const void* __restrict__ Wv
     }
 }
 
+// W[r][c0 .. c0 + 3] as fp32 (gemv_t_kernel's loads): zeros past `cols`
+template <bool BF16, bool VEC>
+__device__ __forceinline__ float4 gemv_t_load_w(const void* __restrict__ Wv, size_t at, int c0, int cols) {
+    float4 w = float4{0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (BF16) {
+        const uint16_t* W = (const uint16_t*)Wv;
+        if constexpr (VEC) {
+            const uint2 q = *(const uint2*)(W + at);
+            w.x = i2f((int)(q.x << 16)); w.y = i2f((int)(q.x & 0xffff0000u)); w.z = i2f((int)(q.y << 16)); w.w = i2f((int)(q.y & 0xffff0000u));
+        } else {
+            w.x = i2f((int)((unsigned)W[at] << 16));
+            if (c0 + 1 < cols) w.y = i2f((int)((unsigned)W[at + 1] << 16));
+            if (c0 + 2 < cols) w.z = i2f((int)((unsigned)W[at + 2] << 16));
+            if (c0 + 3 < cols) w.w = i2f((int)((unsigned)W[at + 3] << 16));
+        }
+    } else {
+        const float* W = (const float*)Wv;
+        if constexpr (VEC) {
+            w = *(const float4*)(W + at);
+        } else {
+            w.x = W[at];
+            if (c0 + 1 < cols) w.y = W[at + 1];
+            if (c0 + 2 < cols) w.z = W[at + 2];
+            if (c0 + 3 < cols) w.w = W[at + 3];
+        }
+    }
+    return w;
+}
+
+// gemv_t_kernel for NV vectors per pass over W (hispmv_linear_device_t): vector v reads x + v * rows and adds into y + v * cols.  A
+// thread owns 4 columns x NV sums, x[v * rows + r] is wave-uniform, W is read once; the LDS transposition holds NV x kGemvTCols floats.
+// Per vector the sum of a column is the one gemv_t_kernel forms (same row blocks, same order inside a block).
+template <bool BF16, bool VEC, int NV>
+__global__ __launch_bounds__(256) void gemv_t_nv_kernel(const void* __restrict__ Wv, int rows, int cols, const float* __restrict__ x, float* y,
+                                                       float alpha, int rows_per_block, int atomic) {
+    __shared__ float out[NV][kGemvTCols];
+    const int tid = (int)threadIdx.x;
+    const int cb = (int)blockIdx.x * kGemvTCols;
+    const int c0 = cb + tid * 4;
+    const int r0 = (int)blockIdx.y * rows_per_block;
+    const int r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    float4 a[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) a[v] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (c0 < cols) {
+#pragma unroll 4
+        for (int r = r0; r < r1; ++r) {
+            const float4 w = gemv_t_load_w<BF16, VEC>(Wv, (size_t)r * (size_t)cols + (size_t)c0, c0, cols);
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const float xr = x[(size_t)v * (size_t)rows + (size_t)r];
+                a[v].x += w.x * xr; a[v].y += w.y * xr; a[v].z += w.z * xr; a[v].w += w.w * xr;
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) { out[v][tid * 4 + 0] = a[v].x; out[v][tid * 4 + 1] = a[v].y; out[v][tid * 4 + 2] = a[v].z; out[v][tid * 4 + 3] = a[v].w; }
+    __syncthreads();
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        float* const yv = y + (size_t)v * (size_t)cols;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int col = cb + tid + 256 * k;
+            if (col >= cols) continue;
+            const float s = alpha * out[v][tid + 256 * k];
+            if (atomic) y_add(yv, (unsigned)col, s);
+            else yv[col] = yv[col] + s;            // one row block: this thread is the only writer of the column
+        }
+    }
+}
+
 template <auto Kernel>
 hipError_t raise_lds_limit() {
     static std::once_flag once;
@@ -349,11 +584,15 @@ hipError_t launch_slices_t(const SpmvDeviceMatrix& m, const float* x, float* y, 
 
 }  // namespace
 
-hipError_t launch_transpose_prologue(const float* bias, float* y, int32_t n, float beta, hipStream_t stream) {
+hipError_t launch_transpose_prologue(const float* bias, float* y, int32_t n, float beta, hipStream_t stream, int64_t vecs, int64_t bias_stride) {
     (void)hipGetLastError();
-    if (n <= 0) return hipSuccess;
-    const bool aligned = ((uintptr_t)y & 15) == 0 && (beta == 0.0f || ((uintptr_t)bias & 15) == 0);
-    hipLaunchKernelGGL(transpose_prologue_kernel, dim3((unsigned)(((int64_t)n + 1023) / 1024)), dim3(256), 0, stream, bias, y, (int)n, beta, aligned ? 1 : 0);
+    if (n <= 0 || vecs <= 0) return hipSuccess;
+    const int64_t total = (int64_t)n * vecs;
+    if (total >= (1LL << 30) || (bias_stride != 0 && bias_stride != n)) return hipErrorInvalidValue;
+    const bool shared = vecs > 1 && bias_stride == 0 && beta != 0.0f;        // one bias of n floats under every vector
+    const bool aligned = ((uintptr_t)y & 15) == 0 && (beta == 0.0f || ((uintptr_t)bias & 15) == 0) && (!shared || (n & 3) == 0);
+    hipLaunchKernelGGL(transpose_prologue_kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, stream, bias, y, (int)total, beta, aligned ? 1 : 0,
+                       shared ? (int)n : 0);
     return hipGetLastError();
 }
 
@@ -368,6 +607,43 @@ hipError_t launch_spmv_t(const SpmvDeviceMatrix& m, const float* x, float* y, fl
     if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
     if (m.has_strays) return m.has_half ? launch_slices_t<true, true, true>(m, x, y, alpha, stream) : launch_slices_t<true, true, false>(m, x, y, alpha, stream);
     return m.has_half ? launch_slices_t<true, false, true>(m, x, y, alpha, stream) : launch_slices_t<true, false, false>(m, x, y, alpha, stream);
+}
+
+// Plan classes of the multi-vector pass; spmv_t_width is where a class that a measurement shows no faster than single calls is narrowed.
+int spmv_t_width(const SpmvDeviceMatrix& m, int64_t vecs) {
+    for (int nv = kMaxBatch; nv >= 2; nv >>= 1) {
+        if (nv > vecs) continue;
+        if ((int64_t)m.cols * nv >= (1 << 30) || (int64_t)m.rows * nv >= (1 << 30)) continue;
+        if (slice_lds_bytes(m, nv) <= (size_t)kDynLdsMax) return nv;
+    }
+    return 1;
+}
+
+template <int NV>
+static hipError_t launch_spmv_t_width(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
+    const auto go = [&](auto kernel) {
+        const hipError_t e = raise_lds_limit<kernel()>();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel(), dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m, NV), stream, (const char*)m.words, m.hdr,
+                           m.groups, m.frags, x, y, alpha, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows);
+        return hipGetLastError();
+    };
+#define HISPMV_T_NV(L, S, H) go([] { return spmv_slices_t_nv_kernel<NV, L, S, H>; })
+    if (m.lds_floats <= 0) return HISPMV_T_NV(false, false, false);
+    if (m.has_strays) return m.has_half ? HISPMV_T_NV(true, true, true) : HISPMV_T_NV(true, true, false);
+    return m.has_half ? HISPMV_T_NV(true, false, true) : HISPMV_T_NV(true, false, false);
+#undef HISPMV_T_NV
+}
+
+hipError_t launch_spmv_t_nv(const SpmvDeviceMatrix& m, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (nv != 2 && nv != 4) return hipErrorInvalidValue;
+    if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
+    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || spmv_t_width(m, nv) != nv)
+        return hipErrorInvalidValue;
+    if (m.lds_floats <= 0 && (m.has_strays || m.has_half)) return hipErrorInvalidValue;
+    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
+    return nv == 4 ? launch_spmv_t_width<4>(m, x, y, alpha, stream) : launch_spmv_t_width<2>(m, x, y, alpha, stream);
 }
 
 // Row blocks per column block: enough workgroups to fill the chip twice over (1024 in all) while a block keeps at least 16 rows,
@@ -398,6 +674,37 @@ hipError_t launch_gemv_t(const void* W, int32_t rows, int32_t cols, bool bf16, c
         else hipLaunchKernelGGL((gemv_t_kernel<false, false>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
     }
     return hipGetLastError();
+}
+
+int gemv_t_width(int64_t vecs) { return vecs >= 8 ? 8 : vecs >= 4 ? 4 : vecs >= 2 ? 2 : 1; }
+
+template <int NV>
+static hipError_t launch_gemv_t_width(const void* W, int32_t rows, int32_t cols, bool bf16, const float* x, float* y, float alpha, hipStream_t stream) {
+    const int nb = gemv_t_row_blocks(rows, cols);
+    if (nb <= 0) return hipSuccess;
+    const int per = (rows + nb - 1) / nb;
+    const dim3 grid((unsigned)(((int64_t)cols + kGemvTCols - 1) / kGemvTCols), (unsigned)nb);
+    const bool vec = (cols & 3) == 0 && ((uintptr_t)W & (bf16 ? 7 : 15)) == 0;
+    const int atomic = nb > 1 ? 1 : 0;
+    if (bf16) {
+        if (vec) hipLaunchKernelGGL((gemv_t_nv_kernel<true, true, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+        else hipLaunchKernelGGL((gemv_t_nv_kernel<true, false, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+    } else {
+        if (vec) hipLaunchKernelGGL((gemv_t_nv_kernel<false, true, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+        else hipLaunchKernelGGL((gemv_t_nv_kernel<false, false, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_gemv_t_nv(const void* W, int32_t rows, int32_t cols, bool bf16, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
+    (void)hipGetLastError();
+    if ((int64_t)rows * nv >= (1 << 30) || (int64_t)cols * nv >= (1 << 30)) return hipErrorInvalidValue;
+    switch (nv) {
+        case 2: return launch_gemv_t_width<2>(W, rows, cols, bf16, x, y, alpha, stream);
+        case 4: return launch_gemv_t_width<4>(W, rows, cols, bf16, x, y, alpha, stream);
+        case 8: return launch_gemv_t_width<8>(W, rows, cols, bf16, x, y, alpha, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace hispmv

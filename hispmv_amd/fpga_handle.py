@@ -211,6 +211,31 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range")
         return {"transposable": bool(out[0]), "launches": int(out[1]), "atomic_bytes": int(out[2]), "direct_elems": int(out[3])}
 
+    def linear_device(self, matrix_idx: int, d_x: int, num_vecs: int, d_bias: int, d_y: int, alpha: float = 1.0, beta: float = 1.0,
+                      stream: int = 0) -> None:
+        """y[v] = alpha * A x[v] + beta * bias for num_vecs vectors on device pointers (ints): x is [num_vecs, cols], y [num_vecs, rows],
+        row-major and contiguous, one bias for all (hispmv_linear_device).  Asynchronous on `stream`.  With alpha = beta = 1 the bits of
+        `linear`.  One call per handle in flight: carries and partial vectors belong to the handle."""
+        self._check(lib.hispmv_linear_device(self._ctx, int(matrix_idx), C.c_void_p(d_x), int(num_vecs), C.c_void_p(d_bias), C.c_void_p(d_y),
+                                             float(alpha), float(beta), C.c_void_p(stream)))
+
+    def linear_device_t(self, matrix_idx: int, d_x: int, num_vecs: int, d_bias: int, d_y: int, alpha: float, beta: float,
+                        bias_stride: int = 0, stream: int = 0) -> None:
+        """y[v] = alpha * A^T x[v] + beta * bias[v * bias_stride] for num_vecs vectors on device pointers (ints): x is [num_vecs, rows],
+        y [num_vecs, cols] (hispmv_linear_device_t).  bias_stride 0 = one bias for all, cols = one per vector (then d_bias may be d_y:
+        in place).  The promises and preconditions of spmv_device_t; a tile-stream handle raises NotImplementedError."""
+        self._check(lib.hispmv_linear_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_x), int(num_vecs), C.c_void_p(d_bias), int(bias_stride),
+                                               C.c_void_p(d_y), float(alpha), float(beta), C.c_void_p(stream)))
+
+    def linear_info(self, matrix_idx: int, num_vecs: int) -> dict:
+        """{"width", "passes"} of linear_device (beta != 0) and {"width_t", "passes_t", "launches_t"} of linear_device_t for num_vecs
+        vectors on a handle (hispmv_linear_info): the vectors of the widest pass over the matrix, the passes, the launches."""
+        out = (C.c_int64 * 5)()
+        rc = lib.hispmv_linear_info(self._ctx, int(matrix_idx), int(num_vecs), out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range") if num_vecs >= 1 else ValueError("num_vecs must be at least 1")
+        return {"width": int(out[0]), "passes": int(out[1]), "width_t": int(out[2]), "passes_t": int(out[3]), "launches_t": int(out[4])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

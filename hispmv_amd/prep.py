@@ -168,6 +168,24 @@ def choose_format_from_csr(row_ptr, col_idx, values, rows: int, cols: int, n_cus
         lib.hispmv_prep_free(p)
 
 
+def vector_widths_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256, num_vecs: int = 4) -> dict:
+    """{"forward", "transposed"}: the widest pass (4, 2 or 1 vectors) linear_device and linear_device_t take for `num_vecs` vectors on
+    this matrix as a single-part slice stream planned for `n_cus` CUs (hispmv_prep_vector_widths): host-only."""
+    r = np.ascontiguousarray(coo_rows, dtype=np.int32)
+    c = np.ascontiguousarray(coo_cols, dtype=np.int32)
+    v = np.ascontiguousarray(coo_values, dtype=np.float32)
+    p = C.c_void_p()
+    if lib.hispmv_prep_from_coo(C.byref(p), C.c_void_p(r.ctypes.data), C.c_void_p(c.ctypes.data), C.c_void_p(v.ctypes.data), r.size, rows, cols) != HISPMV_OK:
+        raise ValueError(lib.hispmv_prep_last_error().decode())
+    try:
+        out = (C.c_int64 * 2)()
+        if lib.hispmv_prep_vector_widths(p, int(n_cus), int(num_vecs), out) != HISPMV_OK:
+            raise ValueError("bad vector_widths arguments")
+        return {"forward": int(out[0]), "transposed": int(out[1])}
+    finally:
+        lib.hispmv_prep_free(p)
+
+
 def window_membership(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256):
     """-> (inside, order): `inside[k]` for the matrix's CSR entries (1 = the entry's block of x lies in the LDS window of its
     workgroup, hispmv_prep_window_membership) and `order`, the permutation that brings the COO triplets into that CSR order."""

@@ -194,8 +194,8 @@ int hispmv_value_storage_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out
  *  - A sparse handle whose device format is the transposed tile stream (hispmv_matrix_info.format == 1) has no transposed kernel:
  *    HISPMV_ENOTSUP, and the message names the remedy, hispmv_set_transposable.  Every slice-stream handle (all its parts: column
  *    tiles, band tiles, stray split) and every dense handle is accepted.
- * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, several vectors per pass, host-pointer entries,
- * sharding over devices, a tile-stream kernel. */
+ * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, host-pointer entries, sharding over devices, a
+ * tile-stream kernel.  Several vectors per pass: hispmv_linear_device_t below. */
 int hispmv_spmv_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, const float* d_bias, float* d_y,
                          float alpha, float beta, void* stream);
 /* Context-wide switch, default off, may be flipped between creations (like hispmv_set_value_storage): a sparse handle created while
@@ -210,6 +210,56 @@ int hispmv_set_transposable(hispmv_ctx* ctx, int enable);
  * the direct adds scatter over up to 64 lines per wave-instruction, the expensive one.  Zeros for a handle that is not transposable
  * or not loaded. */
 int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
+
+/* ---- several vectors on device pointers (no reference counterpart: FpgaHandle::runLinear takes host vectors and relaunches per
+ * vector, fpga_handle.cpp:323-388) --------------------------------------------------------------------------------------------------
+ * The device-pointer forms of hispmv_linear and of hispmv_spmv_device_t for num_vecs vectors that lie one after the other, row-major
+ * and contiguous -- [num_vecs, cols] and [num_vecs, rows], the layout of a torch batch.  Asynchronous on `stream` (the stream rule
+ * above: NULL = the context's stream).  The argument checks come before any device call: NULL context, num_vecs < 1, NULL d_x or d_y,
+ * NULL d_bias with beta != 0, d_x == d_y -> HISPMV_EINVAL; rows * num_vecs or cols * num_vecs >= 2^30 -> HISPMV_EINVAL (the message
+ * says to split the batch); before hispmv_load_matrices -> HISPMV_ESTATE.
+ *
+ *   hispmv_linear_device:    y[v*rows + i] = alpha * (A x_v)[i] + beta * bias[i],   x_v = d_x + v*cols,   one bias for all vectors
+ *  - Every loaded handle is accepted, tile streams included.  It is the launch sequence of hispmv_linear on the caller's stream: up to
+ *    4 (slice stream) or 8 (dense, tile stream) vectors share a pass over the matrix, rows cut by slice boundaries always take the
+ *    fix-up variant.  With alpha = beta = 1 the result has the bits of hispmv_linear, and every vector the bits of a one-vector call
+ *    of this entry, whatever the batch around it.
+ *  - With beta == 0 a slice stream takes one vector per pass (the batched slice kernel reads a bias); hispmv_linear_info reports the
+ *    passes for beta != 0 only.
+ *  - ALIGNMENT OF d_x.  The window staging of the slice kernels and the dense and tile-stream passes read x with 16-byte loads at
+ *    x_v + a multiple of 16 floats -- the single-vector kernels as well as the multi-vector ones.  With several vectors the address of
+ *    vector v also depends on v * cols, which is why the batched slice pass asks for cols % 4 == 0 where the plan has a window.  A d_x
+ *    that is not 16-byte aligned is not refused: the call then takes one vector per pass, with the same bits.  That keeps such a call
+ *    on the launches hispmv_spmv_device makes for the same pointer; it does not make the 16-byte loads aligned.  They are global
+ *    loads, which gfx950 executes at any 4-byte address (tests pass a d_x shifted by one float through both routes); an aligned d_x
+ *    (hipMalloc, a torch tensor) is the layout the kernels were written and timed for.
+ *  - OWNERSHIP, as for hispmv_spmv_device_batch: the carries of cut rows and the partial vectors of column parts belong to the handle,
+ *    so one call per handle may be in flight; a second call on the same handle must be ordered behind the first (same stream, or an
+ *    event).
+ *
+ *   hispmv_linear_device_t:  y[v*cols + j] = alpha * (A^T x_v)[j] + beta * bias[v*bias_stride + j],   x_v = d_x + v*rows
+ *  - bias_stride is 0 (one bias of cols floats for all vectors) or cols (one per vector); anything else -> HISPMV_EINVAL.  With
+ *    bias_stride = cols, d_bias == d_y is allowed: y += alpha * A^T x per vector, in place.  (d_bias == d_y with bias_stride 0 and
+ *    several vectors -> HISPMV_EINVAL: vector 0 would overwrite the bias of the others.)
+ *  - The handles hispmv_spmv_device_t accepts, and its promises: a tile stream -> HISPMV_ENOTSUP with the same message; zero slots
+ *    add nothing; d_y must be coarse-grained device memory; the sums arrive through float atomics in no fixed order; alpha == 0 gives
+ *    exactly beta * bias per vector; beta == 0 does not read the bias; the handle's state is untouched, so calls may overlap each
+ *    other and forward calls.  No alignment condition on any pointer.
+ *  - One prologue launch covers all vectors.  The vectors then go in passes of the widest width that fits, 4, 2, 1 on a slice stream:
+ *    a pass of NV vectors keeps NV accumulator windows in the LDS, so NV is the largest of {4, 2} that is <= the vectors left and
+ *    whose windows fit the LDS of a CU for every part of the handle (a plan without a window always takes 4); dense handles go 8, 4,
+ *    2, 1.  A slice's words are read and decoded once per pass.  Width-1 passes are the launches of hispmv_spmv_device_t.
+ * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, a tile-stream transposed kernel, sharding over
+ * devices, host-pointer variants of these two entries, the gradient with respect to the matrix values (a sampled dense-dense product;
+ * hispmv_update_values_device is where its result would go), and any change to the widths of the forward path. */
+int hispmv_linear_device(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int64_t num_vecs, const float* d_bias, float* d_y,
+                         float alpha, float beta, void* stream);
+int hispmv_linear_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int64_t num_vecs, const float* d_bias, int64_t bias_stride,
+                           float* d_y, float alpha, float beta, void* stream);
+/* out = {forward (beta != 0, aligned d_x): vectors of the widest pass, passes over the matrix; transposed: vectors of the widest pass,
+ * passes, launches of the call (the prologue + one per part and pass)}.  Transposed figures are zeros for a tile stream, all five for
+ * a handle that is not loaded. */
+int hispmv_linear_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t out[5]);
 
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */
@@ -296,6 +346,10 @@ const int32_t* hispmv_prep_fix(const hispmv_prep* p);         /* n_split_rows x 
  * device needed): plan[0..5] = workgroup threads, slices per workgroup, x-window LDS floats, row-total LDS
  * floats per wavefront, workgroups, total dynamic LDS bytes per workgroup. */
 int hispmv_prep_plan(const hispmv_prep* p, int n_cus, int64_t plan[6]);
+
+/* The widest pass hispmv_linear_device (out[0]; beta != 0) and hispmv_linear_device_t (out[1]) take for num_vecs vectors on this
+ * stream as a single-part handle planned for n_cus compute units: 4, 2 or 1 (host-only, no device needed). */
+int hispmv_prep_vector_widths(const hispmv_prep* p, int n_cus, int64_t num_vecs, int64_t out[2]);
 
 /* The FORMAT AND TILING the loader would choose for this matrix on a device with n_cus compute units -- the MI355X analogue of
  * the reference's per-matrix configuration search (automation_tool/src/dse.py:23-95) -- computed by the same host-only function
