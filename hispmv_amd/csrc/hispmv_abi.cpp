@@ -185,6 +185,7 @@ int load_value_map(hispmv_ctx* c, Matrix& m, const std::vector<std::vector<Value
         Matrix::Part& p = m.parts[t];
         uint8_t* base0 = p.is_tts ? (uint8_t*)p.tdev.words : (uint8_t*)p.dev.words;
         uint8_t* base1 = (!p.is_tts && p.has_batch_dev) ? (uint8_t*)p.batch_dev.words : nullptr;
+        p.map_chunk_base = (int64_t)tab.size();           // (the value gradient reads the map by part and slice: hispmv_value_grad.h)
         for (const ValueChunk& q : chunks[t]) {
             if (q.off0 < 0 || q.off0 + kValueChunk * 4 > layout_bytes[t].first || (base1 && (q.off1 < 0 || q.off1 + kValueChunk * 4 > layout_bytes[t].second)))
                 return fail(c, HISPMV_EINVAL, "internal: value region outside its layout");
@@ -1162,6 +1163,83 @@ HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, 
                 e = nv == 1 ? launch_spmv_t(p.dev, xk, yk, alpha, s) : launch_spmv_t_nv(p.dev, nv, xk, yk, alpha, s);
                 if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_t");
             }
+        }
+        k += nv;
+    }
+    return HISPMV_OK;
+}
+
+// ---- value gradient (include/hispmv.h: hispmv_value_grad_device; kernels: hispmv_value_grad.hip) ---------------------------------
+namespace {
+
+// the entry accepts the handle: loaded, updatable (so it has a map, or is dense), and not a tile stream
+bool value_grad_accepts(const Matrix& m) {
+    if (!m.loaded || !m.updatable) return false;
+    if (m.dense) return true;
+    if (m.format != 0) return false;
+    for (auto& p : m.parts)
+        if (p.is_tts) return false;
+    return true;
+}
+
+}  // namespace
+
+HISPMV_API int hispmv_value_grad_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t out[4]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size() || num_vecs < 1) return HISPMV_EINVAL;
+    const Matrix& m = *c->mats[(size_t)idx];
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (!value_grad_accepts(m)) return HISPMV_OK;
+    out[0] = 1;
+    if (m.dense) { out[1] = num_vecs; out[2] = 1; out[3] = (m.rows > 0 && m.cols > 0) ? 1 : 0; return HISPMV_OK; }
+    for (int64_t k = 0; k < num_vecs;) {
+        const int nv = transposed_width(m, num_vecs - k);
+        out[1] = std::max<int64_t>(out[1], nv); out[2] += 1; k += nv;
+        for (auto& p : m.parts) out[3] += (p.dev.n_groups > 0 && m.upd_n > 0) ? 1 : 0;
+    }
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_value_grad_device(hispmv_ctx* c, int idx, const float* d_gy, const float* d_x, int64_t num_vecs, float* d_grad,
+                                        float alpha, float beta, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[idx];
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, "value_grad_device called before load_matrices");
+    if (!m.updatable) return fail(c, HISPMV_ESTATE, "value_grad_device: handle was not created with value updates on (hispmv_set_value_updates)");
+    if (!value_grad_accepts(m))
+        return fail(c, HISPMV_ENOTSUP, "value_grad_device: this handle is a transposed tile stream, which has no value-gradient kernel; create it after "
+                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    if (num_vecs < 1) return fail(c, HISPMV_EINVAL, "value_grad_device: num_vecs must be at least 1");
+    if (!d_gy || !d_x || (m.upd_n > 0 && !d_grad)) return fail(c, HISPMV_EINVAL, "NULL device vector");
+    if (d_grad && (d_grad == d_gy || d_grad == d_x)) return fail(c, HISPMV_EINVAL, "value_grad_device: grad must not be gy or x");
+    if ((int64_t)m.rows * num_vecs >= (1LL << 30) || (int64_t)m.cols * num_vecs >= (1LL << 30))
+        return fail(c, HISPMV_EINVAL, "value_grad_device: rows * num_vecs and cols * num_vecs must stay below 2^30 floats; split the batch");
+    if (m.upd_n == 0) return HISPMV_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (stream) c->user_stream = (hipStream_t)stream;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipError_t e;
+    if (alpha == 0.0f) {          // grad = beta * grad exactly, gy and x not read: the elementwise launch of the transposed prologue, in place
+        constexpr int64_t kPiece = 1LL << 29;
+        for (int64_t at = 0; at < m.upd_n; at += kPiece) {
+            e = launch_transpose_prologue(d_grad + at, d_grad + at, (int32_t)std::min(kPiece, m.upd_n - at), beta, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
+        }
+        return HISPMV_OK;
+    }
+    if (m.dense) {                // all vectors in one launch
+        e = launch_value_grad_dense(m.rows, m.cols, num_vecs, d_gy, d_x, d_grad, alpha, beta, s);
+        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_value_grad_dense");
+    }
+    // passes of the widest width that fits (4, 2, 1: the rule of hispmv_linear_device_t); the first stores alpha * s_0 + beta * grad,
+    // every later one grad + alpha * s_p
+    for (int64_t k = 0; k < num_vecs;) {
+        const int nv = transposed_width(m, num_vecs - k);
+        for (auto& p : m.parts) {
+            e = launch_value_grad(p.dev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
+                                  k == 0 ? beta : 1.0f, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_value_grad");
         }
         k += nv;
     }

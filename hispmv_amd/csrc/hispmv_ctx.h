@@ -28,6 +28,7 @@
 #include "hispmv_transpose.h"
 #include "hispmv_tts.h"
 #include "hispmv_update.h"
+#include "hispmv_value_grad.h"
 
 #define HISPMV_API extern "C" __attribute__((visibility("default")))
 
@@ -50,6 +51,7 @@ struct Matrix {
         hispmv::SpmvDeviceMatrix dev;                      //   of a slice stream
         hispmv::SpmvDeviceMatrix batch_dev;                //   ... in its batch layout (HostPart::has_batch_layout): same slices, headers' rows,
         bool has_batch_dev = false;                        //       carries and fix lists; its own groups, fragments, slice bytes and spill flags
+        int64_t map_chunk_base = 0;                        // updatable handles: the part's first chunk of the value map (chunk base + s = slice s; set at load)
     };
     std::vector<Part> parts;
     std::vector<float> dense_host;

@@ -236,6 +236,25 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range") if num_vecs >= 1 else ValueError("num_vecs must be at least 1")
         return {"width": int(out[0]), "passes": int(out[1]), "width_t": int(out[2]), "passes_t": int(out[3]), "launches_t": int(out[4])}
 
+    def value_grad_device(self, matrix_idx: int, d_gy: int, d_x: int, num_vecs: int, d_grad: int, alpha: float = 1.0, beta: float = 0.0,
+                          stream: int = 0) -> None:
+        """grad[k] = alpha * sum_v gy[v, row_k] * x[v, col_k] + beta * grad[k] for every entry k of the creation input of a loaded,
+        updatable handle, on device pointers (ints): gy is [num_vecs, rows], x [num_vecs, cols], grad holds value_update_info()["n"]
+        floats in the order update_values_device reads (hispmv_value_grad_device).  Asynchronous on `stream`.  Plain stores, one writer
+        per entry: the same bits run to run.  beta == 0 does not read grad.  A handle created with value updates off raises
+        AssertionError, a tile-stream handle NotImplementedError."""
+        self._check(lib.hispmv_value_grad_device(self._ctx, int(matrix_idx), C.c_void_p(d_gy), C.c_void_p(d_x), int(num_vecs), C.c_void_p(d_grad),
+                                                 float(alpha), float(beta), C.c_void_p(stream)))
+
+    def value_grad_info(self, matrix_idx: int, num_vecs: int) -> dict:
+        """{"accepted", "width", "passes", "launches"} of value_grad_device for num_vecs vectors on a handle (hispmv_value_grad_info):
+        the vectors of the widest pass, the passes, the launches of a call with alpha != 0; zeros for a handle it does not accept."""
+        out = (C.c_int64 * 4)()
+        rc = lib.hispmv_value_grad_info(self._ctx, int(matrix_idx), int(num_vecs), out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range") if num_vecs >= 1 else ValueError("num_vecs must be at least 1")
+        return {"accepted": bool(out[0]), "width": int(out[1]), "passes": int(out[2]), "launches": int(out[3])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

@@ -2,11 +2,26 @@
 FpgaHandle.linear_device and backward through FpgaHandle.linear_device_t, on torch's current stream, without the activations ever
 leaving the device (FpgaHandle.linear takes host vectors: two PCIe crossings per layer and batch).
 
-The matrix values are NOT differentiable here: no gradient flows to the handle.  The weight gradient is a sampled dense-dense product
-(grad_y^T x restricted to the sparsity pattern), which this library does not compute; FpgaHandle.update_values_device is where its
-result would go.  The backward pass is differentiable once (no double backward).  The autograd graph keeps a reference to the
-handle, which keeps the object alive but not open: the handle must not be closed between forward and backward (a closed handle makes
-backward raise, it does not launch).  torch is imported inside the functions, as in hispmv_amd/dist.py."""
+Without ``values`` the matrix values are NOT differentiable: no gradient flows to the handle.  With ``values=v`` -- a float32 CUDA
+tensor of the handle's n values in the order of its creation input, on an updatable handle (FpgaHandle.set_value_updates) -- the layer
+is trainable on the device: the forward pass first pushes v into the handle's layouts (FpgaHandle.update_values_device: one update
+pass per forward) and then multiplies; the backward pass returns grad_values[k] = sum_b grad_y[b, row_k] * x[b, col_k] through
+FpgaHandle.value_grad_device, a sampled dense-dense product restricted to the pattern, in the same order.  The handle holds ONE set of
+values: grad_x is computed with the values the handle holds at backward time, so nothing else may push values into the handle between
+a forward pass with ``values`` and its backward pass (another forward with other values, update_values).
+
+Streams: the launches go to torch's current stream by its handle.  torch's DEFAULT stream has the handle 0, which the library reads as
+"the context's own stream" (include/hispmv.h: the stream rule): the library's launches then run on a stream that is not ordered with
+torch's kernels on the default stream.  With ``values`` the layer orders the two itself when torch's current stream is the default
+stream: forward and backward each wait on the host for the default stream before their launches (``values`` was written there by the
+optimiser step) and for the context's stream after them (FpgaHandle.synchronize), so the natural loop ``v -= lr * v.grad`` is correct
+there, at the price of two host waits per pass.  Inside ``with torch.cuda.stream(torch.cuda.Stream()):`` everything is ordered on one
+real stream and nothing waits (examples/train_sparse_layer.py).  Without ``values`` the layer adds no wait, as before: on the default
+stream the caller synchronises between torch's operations and the layer.
+
+The backward pass is differentiable once (no double backward).  The autograd graph keeps a reference to the handle, which keeps the
+object alive but not open: the handle must not be closed between forward and backward (a closed handle makes backward raise, it does
+not launch).  torch is imported inside the functions, as in hispmv_amd/dist.py."""
 from __future__ import annotations
 
 
@@ -56,12 +71,83 @@ def _function(torch):
     return SparseLinear
 
 
-def sparse_linear(handle, idx: int, x, bias=None):
+def _function_values(torch):
+    fn = getattr(_function_values, "cached", None)
+    if fn is not None:
+        return fn
+
+    class SparseLinearValues(torch.autograd.Function):
+        """sparse_linear with ``values``: update, multiply; backward adds grad_values (value_grad_device, alpha = 1, beta = 0)."""
+
+        @staticmethod
+        def forward(ctx, x, bias, values, handle, idx, rows):
+            ctx.handle, ctx.idx, ctx.has_bias = handle, idx, bias is not None
+            current = torch.cuda.current_stream(x.device)
+            stream = current.cuda_stream
+            x = x.contiguous()
+            v = values.contiguous()
+            if stream == 0:                   # the default stream: the launches run on the context's own stream (module docstring)
+                current.synchronize()
+            handle.update_values_device(idx, v.data_ptr(), v.numel(), stream)
+            y = torch.empty((x.shape[0], rows), dtype=torch.float32, device=x.device)
+            b = bias.contiguous() if bias is not None else None
+            handle.linear_device(idx, x.data_ptr(), x.shape[0], b.data_ptr() if b is not None else 0, y.data_ptr(), 1.0,
+                                 1.0 if b is not None else 0.0, stream)
+            if stream == 0:
+                handle.synchronize()
+            ctx.cols, ctx.n = x.shape[1], v.numel()
+            if values.requires_grad:          # x is kept for the value gradient only
+                ctx.save_for_backward(x)
+            return y
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_y):
+            grad_x = grad_bias = grad_values = None
+            g = grad_y.contiguous()
+            current = torch.cuda.current_stream(g.device)
+            stream = current.cuda_stream
+            if ctx.has_bias and ctx.needs_input_grad[1]:
+                grad_bias = grad_y.sum(0)
+            if stream == 0 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):          # as in forward
+                current.synchronize()
+            if ctx.needs_input_grad[0]:
+                grad_x = torch.empty((g.shape[0], ctx.cols), dtype=torch.float32, device=g.device)
+                ctx.handle.linear_device_t(ctx.idx, g.data_ptr(), g.shape[0], 0, grad_x.data_ptr(), 1.0, 0.0, 0, stream)
+            if ctx.needs_input_grad[2]:
+                (x,) = ctx.saved_tensors
+                grad_values = torch.empty((ctx.n,), dtype=torch.float32, device=g.device)
+                ctx.handle.value_grad_device(ctx.idx, g.data_ptr(), x.data_ptr(), g.shape[0], grad_values.data_ptr(), 1.0, 0.0, stream)
+            if stream == 0 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
+                ctx.handle.synchronize()
+            return grad_x, grad_bias, grad_values, None, None, None
+
+    _function_values.cached = SparseLinearValues
+    return SparseLinearValues
+
+
+def sparse_linear(handle, idx: int, x, bias=None, values=None):
     """y = A x (+ bias) for the loaded matrix `idx` of `handle` (an FpgaHandle): x is a float32 CUDA tensor [B, cols] or [cols] (made
     contiguous), the result [B, rows] (or [rows]); bias, if given, a float32 CUDA tensor [rows].  Differentiable in x and bias (grad_x =
-    A^T grad_y through linear_device_t, grad_bias = grad_y.sum(0)); the matrix values are not differentiable.  Runs on torch's current
-    stream.  A wrong dtype raises TypeError, a wrong device or shape ValueError, before any launch.  The backward pass needs a handle
-    that linear_device_t accepts (a slice stream or a dense handle: FpgaHandle.set_transposable)."""
+    A^T grad_y through linear_device_t, grad_bias = grad_y.sum(0)).  Runs on torch's current stream.  A wrong dtype raises TypeError, a
+    wrong device or shape ValueError, before any launch.  The backward pass needs a handle that linear_device_t accepts (a slice stream
+    or a dense handle: FpgaHandle.set_transposable).
+
+    values=None: the matrix values are those the handle holds and are not differentiable; launches and autograd graph are those of a
+    call without the parameter.
+
+    values: a float32 CUDA tensor [n] on the device of x, n = handle.value_update_info(idx)["n"], in the order of the handle's creation
+    input (COO arrays, CSR values before the per-row sort, W row-major).  The handle must be updatable (created after
+    FpgaHandle.set_value_updates(True)); otherwise ValueError, before any launch; a wrong dtype TypeError, a wrong length or device
+    ValueError.  The forward pass pushes `values` into the handle (update_values_device on torch's current stream: one update pass per
+    forward) and multiplies.  If values.requires_grad, backward returns grad_values[k] = sum_b grad_y[b, row_k] * x[b, col_k] through
+    value_grad_device (alpha = 1, beta = 0: deterministic, no atomics), and x is saved for backward (only then).  grad_x uses the values
+    the handle holds at backward time: nothing else may push values into the handle between this forward and its backward.
+
+    Streams, with values: on torch's DEFAULT stream (handle 0, which the library reads as the context's own stream) forward and
+    backward each wait on the host for the default stream before their launches and for the context's stream after them, so
+    ``v -= lr * v.grad`` followed by the next forward is ordered; on any other current stream nothing waits.  A loop that should not
+    wait on the host runs inside ``with torch.cuda.stream(torch.cuda.Stream()):``."""
     import torch
     info = handle.matrix_info(idx)
     _check_tensor(torch, x, "x", info["cols"], (1, 2))
@@ -72,5 +158,14 @@ def sparse_linear(handle, idx: int, x, bias=None):
     if x.dim() == 2 and x.shape[0] == 0:
         raise ValueError("x holds no vector")
     one = x.dim() == 1
-    y = _function(torch).apply(x.unsqueeze(0) if one else x, bias, handle, int(idx), info["rows"])
+    if values is None:
+        y = _function(torch).apply(x.unsqueeze(0) if one else x, bias, handle, int(idx), info["rows"])
+        return y.squeeze(0) if one else y
+    upd = handle.value_update_info(idx)
+    if not upd["updatable"]:
+        raise ValueError("values needs an updatable handle: create it after FpgaHandle.set_value_updates(True)")
+    _check_tensor(torch, values, "values", upd["n"], (1,))
+    if values.device != x.device:
+        raise ValueError("values must be on the device of x")
+    y = _function_values(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])
     return y.squeeze(0) if one else y

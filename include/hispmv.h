@@ -30,7 +30,7 @@ extern "C" {
 #define HISPMV_ENOTDENSE  -5   /* dense handle requested on a context created without dense_overlay (spmv-helper.cpp:718) */
 #define HISPMV_EIO        -6   /* MatrixMarket file unreadable / malformed */
 #define HISPMV_ENOMEM     -7
-#define HISPMV_ENOTSUP    -8   /* the handle's device format has no kernel for the operation (hispmv_spmv_device_t on a tile stream) */
+#define HISPMV_ENOTSUP    -8   /* the handle's device format has no kernel for the operation (hispmv_spmv_device_t, hispmv_value_grad_device on a tile stream) */
 
 typedef struct hispmv_ctx hispmv_ctx;
 
@@ -250,8 +250,8 @@ int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4])
  *    whose windows fit the LDS of a CU for every part of the handle (a plan without a window always takes 4); dense handles go 8, 4,
  *    2, 1.  A slice's words are read and decoded once per pass.  Width-1 passes are the launches of hispmv_spmv_device_t.
  * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, a tile-stream transposed kernel, sharding over
- * devices, host-pointer variants of these two entries, the gradient with respect to the matrix values (a sampled dense-dense product;
- * hispmv_update_values_device is where its result would go), and any change to the widths of the forward path. */
+ * devices, host-pointer variants of these two entries, and any change to the widths of the forward path.  The gradient with respect to
+ * the matrix values is hispmv_value_grad_device below. */
 int hispmv_linear_device(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int64_t num_vecs, const float* d_bias, float* d_y,
                          float alpha, float beta, void* stream);
 int hispmv_linear_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int64_t num_vecs, const float* d_bias, int64_t bias_stride,
@@ -260,6 +260,45 @@ int hispmv_linear_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, in
  * passes, launches of the call (the prologue + one per part and pass)}.  Transposed figures are zeros for a tile stream, all five for
  * a handle that is not loaded. */
 int hispmv_linear_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t out[5]);
+
+/* ---- value gradient (no reference counterpart; a sampled dense-dense product: rocSPARSE / cuSPARSE SDDMM restricted to the pattern) ----
+ *   grad[k] = alpha * sum_v gy[v, row_k] * x[v, col_k] + beta * grad[k]        for every k in [0, n)
+ * on a loaded handle created with value updates on: the gradient of sum_v gy_v . (A x_v) with respect to the value of entry k of the
+ * creation input.  d_gy is [num_vecs, rows], d_x is [num_vecs, cols], row-major and contiguous (the layouts of hispmv_linear_device
+ * and hispmv_linear_device_t); d_grad holds n = hispmv_value_update_info(...)[1] floats in the ORDER OF THE CREATION INPUT, the order
+ * hispmv_update_values_device reads: the COO arrays (duplicates included, each with its own, equal gradient), col_idx / values of
+ * _from_csr before its per-row sort, W row-major for a dense handle.  Device pointers, asynchronous on `stream` (the stream rule
+ * above: NULL = the context's stream).  Nothing is stored for it: the row of a slice element is its slice's row base plus the row ends
+ * before it, its column is the meta, its input position is the value map of the handle.
+ *  - beta == 0: d_grad is not read; every one of its n positions is overwritten, whatever it held (NaN included).
+ *  - alpha == 0: the result is exactly beta * grad (zeros with beta == 0); gy and x are not read.  One elementwise launch.
+ *  - The gradient of an entry does not depend on its value: the kernels go by the map and do not read the values at all.  An explicit
+ *    zero of the input gets its gradient like every other entry (the zero-slot rule of the transposed product has no place here);
+ *    slots that hold no input entry (fillers of empty rows, row extensions, padding) write nothing.
+ *  - NO ATOMICS: every input entry lives in exactly one slot of the handle's first layouts, so each grad[k] has one writer per launch.
+ *    The result is deterministic: the same bits from run to run.
+ *  - ORDER OF THE SUMS.  On a slice stream the vectors go in passes of 4, 2, 1 by the rule of hispmv_linear_device_t (the largest of
+ *    {4, 2} that is <= the vectors left and whose x windows fit the LDS of a CU for every part; a plan without a window takes 4).
+ *    Inside a pass the sum s_p starts at +0 and takes the vectors ascending, every product and every add unfused.  The first pass
+ *    stores alpha * s_0 (+ beta * grad), every later pass grad + alpha * s_p.  A dense handle takes all vectors in one launch:
+ *    alpha * s (+ beta * grad), s summed ascending from +0.
+ *  - ACCEPTED: every loaded, updatable slice-stream handle (all its parts: column tiles, band tiles, stray split) and every loaded,
+ *    updatable dense handle.  Not loaded -> HISPMV_ESTATE; not created with value updates on -> HISPMV_ESTATE (the message names
+ *    hispmv_set_value_updates; a bf16 handle cannot be updatable and falls under this); the device format is the tile stream ->
+ *    HISPMV_ENOTSUP (the message names the remedy, hispmv_set_transposable, as for hispmv_spmv_device_t).
+ *  - The argument checks come before any device call: NULL context, num_vecs < 1, NULL d_gy or d_x, NULL d_grad with n > 0, d_grad
+ *    equal to d_gy or d_x, a bad index -> HISPMV_EINVAL; rows * num_vecs or cols * num_vecs >= 2^30 -> HISPMV_EINVAL (the message says
+ *    to split the batch).  No alignment condition on any pointer.
+ *  - HANDLE STATE: the entry reads metas, slice headers, fragment tables, stray columns and the value map.  It does not read the values
+ *    and does not touch carries, tickets or cached batch plans, so it may overlap forward, transposed and update calls on the same
+ *    handle (hispmv_update_values_device writes values only).
+ * Out of scope: a tile-stream kernel, bf16 handles (they have no map), gradients inside hispmv_spmv_device_batch or the step kernel,
+ * sharding over devices, host-pointer variants, passes wider than the 4-2-1 rule. */
+int hispmv_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gy, const float* d_x, int64_t num_vecs, float* d_grad,
+                             float alpha, float beta, void* stream);
+/* out = {1 if hispmv_value_grad_device accepts the (loaded) handle, vectors of the widest pass, passes, launches of a call with
+ * alpha != 0 (one per part and pass; dense: one)}.  Zeros for a handle that is not accepted or not loaded. */
+int hispmv_value_grad_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t out[4]);
 
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */
