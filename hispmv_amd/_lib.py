@@ -27,6 +27,10 @@ HISPMV_VALUES_FP32 = 0
 HISPMV_VALUES_BF16 = 1
 VALUE_STORAGES = {"fp32": HISPMV_VALUES_FP32, "bf16": HISPMV_VALUES_BF16}
 
+HISPMV_TRANSPOSABLE_OFF = 0
+HISPMV_TRANSPOSABLE_SLICES = 1
+HISPMV_TRANSPOSABLE_KEEP_FORMAT = 2
+
 
 class MatrixInfo(C.Structure):
     _fields_ = [

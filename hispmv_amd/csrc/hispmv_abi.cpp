@@ -120,7 +120,8 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
     m->rows = csr.rows; m->cols = csr.cols; m->nnz = csr.nnz();
     FormatOptions opts = c->format_opts;
     opts.half_values = c->value_storage == HISPMV_VALUES_BF16;      // (the values are rounded already: add_from_coo, _from_csr)
-    if (c->transposable) opts.format_mode = 0;                      // hispmv_set_transposable: keep the slice stream, as HISPMV_FORMAT=slices does
+    if (c->transposable == HISPMV_TRANSPOSABLE_SLICES) opts.format_mode = 0;      // hispmv_set_transposable: keep the slice stream, as HISPMV_FORMAT=slices does
+    m->keep_format = c->transposable == HISPMV_TRANSPOSABLE_KEEP_FORMAT;          // ... or the loader's own choice, a tile stream then marked as accepted
     m->value_storage = c->value_storage;
     FormatChoice ch = choose_format(std::move(csr), prebuilt, c->n_cus, opts, lap);
     m->format = ch.format; m->tile_kind = ch.tile_kind; m->col_tile_width = ch.col_tile_width; m->col_tile_base = ch.col_tile_base;
@@ -699,6 +700,9 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
             // of 8 K elements, not gather-bound)
             d.xlds_floats = (m.cols <= kTtsXldsMax && std::getenv("HISPMV_TTS_XLDS")) ? ((m.cols + 63) & ~63) : 0;
             if (tts_tile_lds_bytes(d) > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: tile stream exceeds the LDS of a CU");
+            // a transposed call (hispmv_tts_transpose.h): one launch, one float atomic per stored word that is neither filler nor padding
+            // (an upper bound: explicit zeros among them add nothing at run time)
+            m.t_launches += 1; m.t_direct += ts.nnz; m.t_atomic_bytes += 4 * ts.nnz;
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             p.tts = TtsStream{};
           }
@@ -891,7 +895,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
             m.t_launches = nb > 0 ? 1 : 0;
             m.t_atomic_bytes = nb > 1 ? (int64_t)nb * m.cols * 4 : 0;
         }
-        if (m.dense || m.format == 0) m.t_launches += 1;      // the prologue y = beta * bias
+        m.t_launches += 1;      // the prologue y = beta * bias (a tile stream reports its figures only when the entries accept it)
         m.loaded = true;
     }
     return HISPMV_OK;
@@ -995,14 +999,41 @@ HISPMV_API int hispmv_spmv_device(hispmv_ctx* c, int idx, const float* d_x, cons
 HISPMV_API int hispmv_set_transposable(hispmv_ctx* c, int enable) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    c->transposable = enable != 0;
+    if (enable != HISPMV_TRANSPOSABLE_OFF && enable != HISPMV_TRANSPOSABLE_SLICES && enable != HISPMV_TRANSPOSABLE_KEEP_FORMAT)
+        return fail(c, HISPMV_EINVAL, "set_transposable: unknown state (HISPMV_TRANSPOSABLE_OFF, _SLICES or _KEEP_FORMAT)");
+    c->transposable = enable;
     return HISPMV_OK;
 }
+
+namespace {
+
+// A tile-stream handle the transposed and gradient entries accept (hispmv_tts_transpose.h): created in state _KEEP_FORMAT, one part,
+// stream words for every row -- the standard and the small geometry.
+bool tts_transposable(const Matrix& m) {
+    return !m.dense && m.format == 1 && m.keep_format && m.parts.size() == 1 && m.parts[0].is_tts && tts_t_accepts(m.parts[0].tdev);
+}
+// the transposed and gradient entries accept the (loaded) handle: dense, a slice stream, or such a tile stream
+bool transposable_handle(const Matrix& m) { return m.dense || m.format == 0 || tts_transposable(m); }
+// HISPMV_ENOTSUP for a tile stream that is not accepted, with the remedies (or the geometry that has no kernel) in the message
+int refuse_tile_stream(hispmv_ctx* c, const Matrix& m, const char* who, const char* what) {
+    if (m.keep_format) {
+        const TtsDeviceMatrix& d = m.parts[0].tdev;
+        const char* geometry = d.zero_fill == 2 ? "tallgap" : d.threads == kTtsPairedThreads ? "paired" : "tall";
+        return fail(c, HISPMV_ENOTSUP, std::string(who) + ": this handle is a transposed tile stream in the " + geometry + " geometry (HISPMV_TTS_GEOMETRY), which has no " + what +
+                                           "; create it under the standard geometry, or after hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that "
+                                           "it keeps the slice stream");
+    }
+    return fail(c, HISPMV_ENOTSUP, std::string(who) + ": this handle is a transposed tile stream created with hispmv_set_transposable off, which has no " + what +
+                                       "; create it after hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream, or after "
+                                       "hispmv_set_transposable(ctx, 2) (FpgaHandle.set_transposable(\"keep_format\")) so that the tile stream itself is accepted");
+}
+
+}  // namespace
 
 HISPMV_API int hispmv_transpose_info(const hispmv_ctx* c, int idx, int64_t out[4]) {
     if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
     const Matrix& m = *c->mats[(size_t)idx];
-    const bool ok = m.loaded && (m.dense || m.format == 0);
+    const bool ok = m.loaded && transposable_handle(m);
     out[0] = ok ? 1 : 0; out[1] = ok ? m.t_launches : 0; out[2] = ok ? m.t_atomic_bytes : 0; out[3] = ok ? m.t_direct : 0;
     return HISPMV_OK;
 }
@@ -1016,9 +1047,7 @@ HISPMV_API int hispmv_spmv_device_t(hispmv_ctx* c, int idx, const float* d_x, co
     if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device_t called before load_matrices");
     if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
     if (d_x == d_y) return fail(c, HISPMV_EINVAL, "spmv_device_t: x and y must not be the same vector");
-    if (!m.dense && m.format != 0)
-        return fail(c, HISPMV_ENOTSUP, "spmv_device_t: this handle is a transposed tile stream, which has no transposed product; create it after "
-                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    if (!transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
     HIP_TRY(c, hipSetDevice(c->device));
     if (stream) c->user_stream = (hipStream_t)stream;
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -1029,6 +1058,11 @@ HISPMV_API int hispmv_spmv_device_t(hispmv_ctx* c, int idx, const float* d_x, co
     if (m.dense) {
         e = launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, d_x, d_y, alpha, s);
         if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_t");
+        return HISPMV_OK;
+    }
+    if (m.format == 1) {          // an accepted tile stream: one launch, no carries, no fix-up
+        e = launch_tts_t(m.parts[0].tdev, 1, d_x, d_y, alpha, s);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_tts_t");
         return HISPMV_OK;
     }
     for (auto& p : m.parts) {
@@ -1079,6 +1113,7 @@ void forward_passes(const Matrix& m, int64_t vecs, int64_t& widest, int64_t& pas
 }
 int transposed_width(const Matrix& m, int64_t left) {
     if (m.dense) return gemv_t_width(left);
+    if (m.format == 1) return tts_t_width(m.parts[0].tdev, left);      // (an accepted tile stream: one part)
     int nv = kMaxBatch;
     for (auto& p : m.parts) nv = std::min(nv, spmv_t_width(p.dev, left));
     return nv;
@@ -1092,12 +1127,13 @@ HISPMV_API int hispmv_linear_info(const hispmv_ctx* c, int idx, int64_t num_vecs
     for (int i = 0; i < 5; ++i) out[i] = 0;
     if (!m.loaded) return HISPMV_OK;
     forward_passes(m, num_vecs, out[0], out[1]);
-    if (!m.dense && m.format != 0) return HISPMV_OK;
+    if (!transposable_handle(m)) return HISPMV_OK;
     int64_t launches = 1;           // the prologue
     for (int64_t k = 0; k < num_vecs;) {
         const int nv = transposed_width(m, num_vecs - k);
         out[2] = std::max<int64_t>(out[2], nv); out[3] += 1; k += nv;
         if (m.dense) launches += 1;
+        else if (m.format == 1) launches += m.parts[0].tdev.n_tiles > 0 ? 1 : 0;
         else for (auto& p : m.parts) launches += p.dev.n_groups > 0 ? 1 : 0;
     }
     out[4] = launches;
@@ -1140,9 +1176,7 @@ HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, 
     if (bias_stride != 0 && bias_stride != m.cols) return fail(c, HISPMV_EINVAL, "linear_device_t: bias_stride must be 0 (one bias for all vectors) or cols");
     if (beta != 0.0f && d_bias == d_y && bias_stride == 0 && num_vecs > 1)
         return fail(c, HISPMV_EINVAL, "linear_device_t: d_bias == d_y needs bias_stride = cols (a shared bias would be overwritten by vector 0)");
-    if (!m.dense && m.format != 0)
-        return fail(c, HISPMV_ENOTSUP, "spmv_device_t: this handle is a transposed tile stream, which has no transposed product; create it after "
-                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    if (!transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
     HIP_TRY(c, hipSetDevice(c->device));
     if (stream) c->user_stream = (hipStream_t)stream;
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -1158,6 +1192,9 @@ HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, 
             e = nv == 1 ? launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, xk, yk, alpha, s)
                         : launch_gemv_t_nv(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, nv, xk, yk, alpha, s);
             if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_t");
+        } else if (m.format == 1) {
+            e = launch_tts_t(m.parts[0].tdev, nv, xk, yk, alpha, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_tts_t");
         } else {
             for (auto& p : m.parts) {
                 e = nv == 1 ? launch_spmv_t(p.dev, xk, yk, alpha, s) : launch_spmv_t_nv(p.dev, nv, xk, yk, alpha, s);
@@ -1172,11 +1209,11 @@ HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, 
 // ---- value gradient (include/hispmv.h: hispmv_value_grad_device; kernels: hispmv_value_grad.hip) ---------------------------------
 namespace {
 
-// the entry accepts the handle: loaded, updatable (so it has a map, or is dense), and not a tile stream
+// the entry accepts the handle: loaded, updatable (so it has a map, or is dense), and a slice stream or an accepted tile stream
 bool value_grad_accepts(const Matrix& m) {
     if (!m.loaded || !m.updatable) return false;
     if (m.dense) return true;
-    if (m.format != 0) return false;
+    if (m.format != 0) return tts_transposable(m);
     for (auto& p : m.parts)
         if (p.is_tts) return false;
     return true;
@@ -1194,7 +1231,8 @@ HISPMV_API int hispmv_value_grad_info(const hispmv_ctx* c, int idx, int64_t num_
     for (int64_t k = 0; k < num_vecs;) {
         const int nv = transposed_width(m, num_vecs - k);
         out[1] = std::max<int64_t>(out[1], nv); out[2] += 1; k += nv;
-        for (auto& p : m.parts) out[3] += (p.dev.n_groups > 0 && m.upd_n > 0) ? 1 : 0;
+        if (m.format == 1) out[3] += (m.parts[0].tdev.n_tiles > 0 && m.upd_n > 0) ? 1 : 0;
+        else for (auto& p : m.parts) out[3] += (p.dev.n_groups > 0 && m.upd_n > 0) ? 1 : 0;
     }
     return HISPMV_OK;
 }
@@ -1207,9 +1245,7 @@ HISPMV_API int hispmv_value_grad_device(hispmv_ctx* c, int idx, const float* d_g
     Matrix& m = *c->mats[idx];
     if (!m.loaded) return fail(c, HISPMV_ESTATE, "value_grad_device called before load_matrices");
     if (!m.updatable) return fail(c, HISPMV_ESTATE, "value_grad_device: handle was not created with value updates on (hispmv_set_value_updates)");
-    if (!value_grad_accepts(m))
-        return fail(c, HISPMV_ENOTSUP, "value_grad_device: this handle is a transposed tile stream, which has no value-gradient kernel; create it after "
-                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    if (!value_grad_accepts(m)) return refuse_tile_stream(c, m, "value_grad_device", "value-gradient kernel");
     if (num_vecs < 1) return fail(c, HISPMV_EINVAL, "value_grad_device: num_vecs must be at least 1");
     if (!d_gy || !d_x || (m.upd_n > 0 && !d_grad)) return fail(c, HISPMV_EINVAL, "NULL device vector");
     if (d_grad && (d_grad == d_gy || d_grad == d_x)) return fail(c, HISPMV_EINVAL, "value_grad_device: grad must not be gy or x");
@@ -1236,7 +1272,12 @@ HISPMV_API int hispmv_value_grad_device(hispmv_ctx* c, int idx, const float* d_g
     // every later one grad + alpha * s_p
     for (int64_t k = 0; k < num_vecs;) {
         const int nv = transposed_width(m, num_vecs - k);
-        for (auto& p : m.parts) {
+        if (m.format == 1) {
+            const Matrix::Part& p = m.parts[0];
+            e = launch_tts_value_grad(p.tdev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
+                                      k == 0 ? beta : 1.0f, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_tts_value_grad");
+        } else for (auto& p : m.parts) {
             e = launch_value_grad(p.dev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
                                   k == 0 ? beta : 1.0f, s);
             if (e != hipSuccess) return hip_fail(c, e, "launch_value_grad");

@@ -27,6 +27,7 @@
 #include "hispmv_prep_device.h"
 #include "hispmv_transpose.h"
 #include "hispmv_tts.h"
+#include "hispmv_tts_transpose.h"
 #include "hispmv_update.h"
 #include "hispmv_value_grad.h"
 
@@ -87,6 +88,9 @@ struct Matrix {
     // transposed product (hispmv_spmv_device_t; hispmv_transpose.h): what one call of it costs on this handle, counted at load from
     // the plan tables before they are released -- {launches, bytes of float atomic adds to y, stream elements that add to y directly}
     int64_t t_launches = 0, t_atomic_bytes = 0, t_direct = 0;
+    // created under hispmv_set_transposable(ctx, HISPMV_TRANSPOSABLE_KEEP_FORMAT): the loader's own format choice was kept, and if
+    // that is a tile stream the transposed and gradient entries accept it (hispmv_tts_transpose.h).  Taken at creation, like value storage.
+    bool keep_format = false;
     std::vector<void*> allocs;
 };
 
@@ -137,7 +141,8 @@ struct hispmv_ctx {
     // buffer of hispmv_update_values (host values) and of the load's first update
     bool value_updates = false;
     int value_storage = HISPMV_VALUES_FP32;     // hispmv_set_value_storage: what handles created from now on store their values as
-    bool transposable = false;                  // hispmv_set_transposable: sparse handles created from now on keep the slice stream (format_mode 0)
+    int transposable = HISPMV_TRANSPOSABLE_OFF; // hispmv_set_transposable: sparse handles created from now on keep the slice stream (_SLICES: format_mode 0),
+                                                //   or their own format with a tile stream among them marked for the transposed entries (_KEEP_FORMAT)
     float* h_upd = nullptr;
     int64_t cap_h_upd = 0;
     float* d_upd = nullptr;

@@ -190,16 +190,24 @@ class FpgaHandle:
         return {"storage": "bf16" if out[0] == _lib.HISPMV_VALUES_BF16 else "fp32", "slots_2byte": int(out[1]), "slots_4byte": int(out[2]),
                 "saved_bytes": int(out[3])}
 
-    def set_transposable(self, enable: bool) -> None:
-        """Sparse handles created from now on (until switched off) keep the slice stream, so that spmv_device_t accepts them
-        (hispmv_set_transposable)."""
-        self._check(lib.hispmv_set_transposable(self._ctx, int(bool(enable))))
+    def set_transposable(self, enable) -> None:
+        """The state sparse handles are created under from now on (hispmv_set_transposable): False / 0 = off; True / 1 = they keep the
+        slice stream, so that spmv_device_t, linear_device_t and value_grad_device accept them; "keep_format" / 2 = they keep the
+        format the loader picks, and a tile stream among them (one part, the standard or the small geometry) is accepted by the same
+        three entries through the tile-stream kernels.  Anything else raises ValueError."""
+        if isinstance(enable, str):
+            if enable != "keep_format":
+                raise ValueError('set_transposable takes False, True, "keep_format" or 0, 1, 2')
+            state = _lib.HISPMV_TRANSPOSABLE_KEEP_FORMAT
+        else:
+            state = int(enable)
+        self._check(lib.hispmv_set_transposable(self._ctx, state))
 
     def spmv_device_t(self, matrix_idx: int, d_x: int, d_bias: int, d_y: int, alpha: float, beta: float,
                       stream: int = 0) -> None:
         """y[cols] = alpha * A^T x[rows] + beta * bias[cols] on device pointers (ints), asynchronous on `stream` (hispmv_spmv_device_t).
         Sums arrive through float atomics: the last bits may differ from run to run.  d_y must be ordinary device memory (not fine-grained
-        or host-pinned).  A tile-stream handle raises NotImplementedError."""
+        or host-pinned).  A tile-stream handle raises NotImplementedError unless it was created under set_transposable("keep_format")."""
         self._check(lib.hispmv_spmv_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_x), C.c_void_p(d_bias),
                                              C.c_void_p(d_y), float(alpha), float(beta), C.c_void_p(stream)))
 
@@ -223,7 +231,7 @@ class FpgaHandle:
                         bias_stride: int = 0, stream: int = 0) -> None:
         """y[v] = alpha * A^T x[v] + beta * bias[v * bias_stride] for num_vecs vectors on device pointers (ints): x is [num_vecs, rows],
         y [num_vecs, cols] (hispmv_linear_device_t).  bias_stride 0 = one bias for all, cols = one per vector (then d_bias may be d_y:
-        in place).  The promises and preconditions of spmv_device_t; a tile-stream handle raises NotImplementedError."""
+        in place).  The promises and preconditions of spmv_device_t, the handles it accepts."""
         self._check(lib.hispmv_linear_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_x), int(num_vecs), C.c_void_p(d_bias), int(bias_stride),
                                                C.c_void_p(d_y), float(alpha), float(beta), C.c_void_p(stream)))
 
@@ -242,7 +250,7 @@ class FpgaHandle:
         updatable handle, on device pointers (ints): gy is [num_vecs, rows], x [num_vecs, cols], grad holds value_update_info()["n"]
         floats in the order update_values_device reads (hispmv_value_grad_device).  Asynchronous on `stream`.  Plain stores, one writer
         per entry: the same bits run to run.  beta == 0 does not read grad.  A handle created with value updates off raises
-        AssertionError, a tile-stream handle NotImplementedError."""
+        AssertionError, a tile-stream handle that was not created under set_transposable("keep_format") NotImplementedError."""
         self._check(lib.hispmv_value_grad_device(self._ctx, int(matrix_idx), C.c_void_p(d_gy), C.c_void_p(d_x), int(num_vecs), C.c_void_p(d_grad),
                                                  float(alpha), float(beta), C.c_void_p(stream)))
 

@@ -130,8 +130,9 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None):
     """y = A x (+ bias) for the loaded matrix `idx` of `handle` (an FpgaHandle): x is a float32 CUDA tensor [B, cols] or [cols] (made
     contiguous), the result [B, rows] (or [rows]); bias, if given, a float32 CUDA tensor [rows].  Differentiable in x and bias (grad_x =
     A^T grad_y through linear_device_t, grad_bias = grad_y.sum(0)).  Runs on torch's current stream.  A wrong dtype raises TypeError, a
-    wrong device or shape ValueError, before any launch.  The backward pass needs a handle that linear_device_t accepts (a slice stream
-    or a dense handle: FpgaHandle.set_transposable).
+    wrong device or shape ValueError, before any launch.  The backward pass needs a handle that linear_device_t accepts: a dense handle, a slice
+    stream (FpgaHandle.set_transposable(True) keeps it one) or a tile stream created under FpgaHandle.set_transposable("keep_format");
+    the same holds for grad_values.
 
     values=None: the matrix values are those the handle holds and are not differentiable; launches and autograd graph are those of a
     call without the parameter.

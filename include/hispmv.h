@@ -191,24 +191,40 @@ int hispmv_value_storage_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out
  *  - ORDER: the sums into one y[col] arrive through float atomic adds, in no fixed order.  The result may differ in the last bits
  *    from run to run and from the forward product of a handle created from the swapped COO; this entry does not keep the bit-for-bit
  *    promises of the forward entries.  The handle's own state (carries, tickets, cached batch plans) is not touched.
- *  - A sparse handle whose device format is the transposed tile stream (hispmv_matrix_info.format == 1) has no transposed kernel:
- *    HISPMV_ENOTSUP, and the message names the remedy, hispmv_set_transposable.  Every slice-stream handle (all its parts: column
- *    tiles, band tiles, stray split) and every dense handle is accepted.
- * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, host-pointer entries, sharding over devices, a
- * tile-stream kernel.  Several vectors per pass: hispmv_linear_device_t below. */
+ *  - ACCEPTED: every slice-stream handle (all its parts: column tiles, band tiles, stray split), every dense handle, and a sparse
+ *    handle whose device format is the transposed tile stream (hispmv_matrix_info.format == 1) when it was created under
+ *    hispmv_set_transposable(ctx, HISPMV_TRANSPOSABLE_KEEP_FORMAT) and is one part with stream words for every row (the standard
+ *    geometry and HISPMV_TTS_SMALL).  Such a handle runs the forward tile kernel backwards: x of a tile's rows in the LDS, expanded to
+ *    the block's row-major slots, scattered in column order -- the 64 atomics of a wave-instruction go to 64 consecutive columns of
+ *    the block's sort (hispmv_matrix_info.tts_lines_per_gather lines of y).  The carries of its cut rows are neither read nor written.
+ *    A tile stream created in state OFF -> HISPMV_ENOTSUP, and the message names both remedies (states SLICES and KEEP_FORMAT of
+ *    hispmv_set_transposable); the tall, tallgap and paired geometries (HISPMV_TTS_GEOMETRY) -> HISPMV_ENOTSUP in every state, and
+ *    the message names the geometry.
+ * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, host-pointer entries, sharding over devices,
+ * the tall, tallgap and paired tile-stream geometries.  Several vectors per pass: hispmv_linear_device_t below. */
 int hispmv_spmv_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, const float* d_bias, float* d_y,
                          float alpha, float beta, void* stream);
-/* Context-wide switch, default off, may be flipped between creations (like hispmv_set_value_storage): a sparse handle created while
- * it is on keeps the slice stream -- the format choice of that creation is the one HISPMV_FORMAT=slices makes for a whole process --
- * and is therefore accepted by hispmv_spmv_device_t.  Nothing else about the handle changes.  A handle created while the switch is
- * off that happens to be a slice stream is transposable all the same, and so is every dense handle. */
+/* Context-wide switch of three states, default OFF, may be flipped between creations (like hispmv_set_value_storage); the state is
+ * taken per handle at its creation.
+ *   HISPMV_TRANSPOSABLE_SLICES (1): a sparse handle created in this state keeps the slice stream -- the format choice of that
+ *     creation is the one HISPMV_FORMAT=slices makes for a whole process -- and is therefore accepted by hispmv_spmv_device_t.
+ *   HISPMV_TRANSPOSABLE_KEEP_FORMAT (2): a sparse handle created in this state keeps the loader's own format choice, and if that is a
+ *     tile stream the transposed and gradient entries accept it (see ACCEPTED above).  Nothing is stored for it: device_bytes of the
+ *     handle is what it is in state OFF.
+ * Nothing else about the handle changes.  A handle created in state OFF that happens to be a slice stream is transposable all the
+ * same, and so is every dense handle.  Any other value of `enable` -> HISPMV_EINVAL. */
+#define HISPMV_TRANSPOSABLE_OFF 0
+#define HISPMV_TRANSPOSABLE_SLICES 1
+#define HISPMV_TRANSPOSABLE_KEEP_FORMAT 2
 int hispmv_set_transposable(hispmv_ctx* ctx, int enable);
 /* out = {1 if hispmv_spmv_device_t accepts the (loaded) handle; launches of one call with alpha != 0 (the prologue y = beta * bias +
  * one per part); bytes of float atomic adds to y per call (window flushes + stray flushes + direct adds); stream elements that add
  * to y directly, one atomic each (elements outside their group's window, every stored slot -- fillers included, which add nothing
  * at run time -- of a group or plan without a window)}.  The flushes are 256 contiguous bytes per wave-instruction, the cheap shape;
- * the direct adds scatter over up to 64 lines per wave-instruction, the expensive one.  Zeros for a handle that is not transposable
- * or not loaded. */
+ * the direct adds scatter over up to 64 lines per wave-instruction, the expensive one.  An accepted tile stream reports {1, 1 + 1,
+ * 4 * nnz, nnz}, nnz the stored words that are neither filler nor padding: upper bounds, since a word whose value is +-0 (an explicit
+ * zero) issues no atomic; its adds touch tts_lines_per_gather lines per wave-instruction.  Zeros for a handle that is not
+ * transposable or not loaded. */
 int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
 
 /* ---- several vectors on device pointers (no reference counterpart: FpgaHandle::runLinear takes host vectors and relaunches per
@@ -241,7 +257,8 @@ int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4])
  *  - bias_stride is 0 (one bias of cols floats for all vectors) or cols (one per vector); anything else -> HISPMV_EINVAL.  With
  *    bias_stride = cols, d_bias == d_y is allowed: y += alpha * A^T x per vector, in place.  (d_bias == d_y with bias_stride 0 and
  *    several vectors -> HISPMV_EINVAL: vector 0 would overwrite the bias of the others.)
- *  - The handles hispmv_spmv_device_t accepts, and its promises: a tile stream -> HISPMV_ENOTSUP with the same message; zero slots
+ *  - The handles hispmv_spmv_device_t accepts, and its promises: a tile stream that is not accepted -> HISPMV_ENOTSUP with the same
+ *    messages; zero slots
  *    add nothing; d_y must be coarse-grained device memory; the sums arrive through float atomics in no fixed order; alpha == 0 gives
  *    exactly beta * bias per vector; beta == 0 does not read the bias; the handle's state is untouched, so calls may overlap each
  *    other and forward calls.  No alignment condition on any pointer.
@@ -249,7 +266,10 @@ int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4])
  *    a pass of NV vectors keeps NV accumulator windows in the LDS, so NV is the largest of {4, 2} that is <= the vectors left and
  *    whose windows fit the LDS of a CU for every part of the handle (a plan without a window always takes 4); dense handles go 8, 4,
  *    2, 1.  A slice's words are read and decoded once per pass.  Width-1 passes are the launches of hispmv_spmv_device_t.
- * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, a tile-stream transposed kernel, sharding over
+ *    An accepted tile stream keeps NV copies of a tile's x rows and of the staging in the LDS: NV is the largest of {4, 2} that is <=
+ *    the vectors left and for which NV * (accumulators + largest block in whole chunks + 64 + 64 floats) fits the LDS of a CU -- the
+ *    rule of the forward tile kernel without its x-in-LDS branch; otherwise 1.
+ * Out of scope: transposed calls inside hispmv_spmv_device_batch or the step kernel, sharding over
  * devices, host-pointer variants of these two entries, and any change to the widths of the forward path.  The gradient with respect to
  * the matrix values is hispmv_value_grad_device below. */
 int hispmv_linear_device(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int64_t num_vecs, const float* d_bias, float* d_y,
@@ -257,8 +277,8 @@ int hispmv_linear_device(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int6
 int hispmv_linear_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, int64_t num_vecs, const float* d_bias, int64_t bias_stride,
                            float* d_y, float alpha, float beta, void* stream);
 /* out = {forward (beta != 0, aligned d_x): vectors of the widest pass, passes over the matrix; transposed: vectors of the widest pass,
- * passes, launches of the call (the prologue + one per part and pass)}.  Transposed figures are zeros for a tile stream, all five for
- * a handle that is not loaded. */
+ * passes, launches of the call (the prologue + one per part and pass)}.  Transposed figures are zeros for a tile stream that
+ * hispmv_linear_device_t does not accept, all five for a handle that is not loaded. */
 int hispmv_linear_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t out[5]);
 
 /* ---- value gradient (no reference counterpart; a sampled dense-dense product: rocSPARSE / cuSPARSE SDDMM restricted to the pattern) ----
@@ -281,18 +301,21 @@ int hispmv_linear_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, 
  *    {4, 2} that is <= the vectors left and whose x windows fit the LDS of a CU for every part; a plan without a window takes 4).
  *    Inside a pass the sum s_p starts at +0 and takes the vectors ascending, every product and every add unfused.  The first pass
  *    stores alpha * s_0 (+ beta * grad), every later pass grad + alpha * s_p.  A dense handle takes all vectors in one launch:
- *    alpha * s (+ beta * grad), s summed ascending from +0.
- *  - ACCEPTED: every loaded, updatable slice-stream handle (all its parts: column tiles, band tiles, stray split) and every loaded,
- *    updatable dense handle.  Not loaded -> HISPMV_ESTATE; not created with value updates on -> HISPMV_ESTATE (the message names
- *    hispmv_set_value_updates; a bf16 handle cannot be updatable and falls under this); the device format is the tile stream ->
- *    HISPMV_ENOTSUP (the message names the remedy, hispmv_set_transposable, as for hispmv_spmv_device_t).
+ *    alpha * s (+ beta * grad), s summed ascending from +0.  An accepted tile stream follows the same contract with the widths
+ *    hispmv_linear_device_t takes on it.
+ *  - ACCEPTED: every loaded, updatable slice-stream handle (all its parts: column tiles, band tiles, stray split), every loaded,
+ *    updatable dense handle, and every loaded, updatable tile stream that hispmv_spmv_device_t accepts (created in state
+ *    HISPMV_TRANSPOSABLE_KEEP_FORMAT; hispmv_set_value_updates already refuses the other geometries and HISPMV_TTS_SMALL).  Not loaded
+ *    -> HISPMV_ESTATE; not created with value updates on -> HISPMV_ESTATE (the message names hispmv_set_value_updates; a bf16 handle
+ *    cannot be updatable and falls under this); a tile stream that is not accepted -> HISPMV_ENOTSUP (the messages of
+ *    hispmv_spmv_device_t), in this order.
  *  - The argument checks come before any device call: NULL context, num_vecs < 1, NULL d_gy or d_x, NULL d_grad with n > 0, d_grad
  *    equal to d_gy or d_x, a bad index -> HISPMV_EINVAL; rows * num_vecs or cols * num_vecs >= 2^30 -> HISPMV_EINVAL (the message says
  *    to split the batch).  No alignment condition on any pointer.
  *  - HANDLE STATE: the entry reads metas, slice headers, fragment tables, stray columns and the value map.  It does not read the values
  *    and does not touch carries, tickets or cached batch plans, so it may overlap forward, transposed and update calls on the same
  *    handle (hispmv_update_values_device writes values only).
- * Out of scope: a tile-stream kernel, bf16 handles (they have no map), gradients inside hispmv_spmv_device_batch or the step kernel,
+ * Out of scope: bf16 handles (they have no map), gradients inside hispmv_spmv_device_batch or the step kernel,
  * sharding over devices, host-pointer variants, passes wider than the 4-2-1 rule. */
 int hispmv_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gy, const float* d_x, int64_t num_vecs, float* d_grad,
                              float alpha, float beta, void* stream);
