@@ -4,7 +4,11 @@ product), a mean-squared loss against the outputs of a teacher layer with the sa
 product, grad_v through the value gradient: a sampled dense-dense product restricted to the pattern, no rows x cols matrix anywhere)
 and the SGD update  v -= lr * v.grad.  Prints the loss per step; it must fall.
 
-    python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1]
+--bf16 trains the same layer a second time on a handle that stores its values as bfloat16 (set_value_updates("any_storage")): v stays
+the fp32 master copy, every forward pass pushes it and the handle keeps R(v), the gradient is taken at the stored values
+(straight-through).  The final losses of the two runs are printed side by side; no threshold is applied to their difference.
+
+    python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1] [--bf16]
 """
 from __future__ import annotations
 
@@ -18,30 +22,17 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
-def main() -> None:
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--rows", type=int, default=2048)
-    ap.add_argument("--cols", type=int, default=1024)
-    ap.add_argument("--density", type=float, default=0.05)
-    ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--lr", type=float, default=0.1)
-    a = ap.parse_args()
+def train(a, r, c, start, teacher, storage: str) -> list:
+    """-> the loss of every step, on a handle with the given value storage"""
     import torch
     import pyhispmv
     from hispmv_amd.torch_ops import sparse_linear
 
-    rng = np.random.default_rng(0)
-    r, c = np.nonzero(rng.random((a.rows, a.cols)) < a.density)
-    r, c = r.astype(np.int32), c.astype(np.int32)
-    scale = np.float32(1.0 / np.sqrt(a.density * a.cols))
-    teacher = (rng.standard_normal(r.size).astype(np.float32)) * scale
-    start = (rng.standard_normal(r.size).astype(np.float32)) * scale
-
     h = pyhispmv.FpgaHandle("train.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
     try:
         h.set_transposable(True)          # the backward pass needs the slice stream
-        h.set_value_updates(True)         # ... and the value map
+        h.set_value_storage(storage)
+        h.set_value_updates("any_storage" if storage == "bf16" else True)         # ... and the value map
         i = h.create_sparse_handle(r, c, start, a.rows, a.cols)
         assert i >= 0
         h.load_matrices()
@@ -66,12 +57,37 @@ def main() -> None:
                     v -= a.lr * v.grad
                     v.grad = None
                 losses.append(float(loss.detach()))
-                print(f"step {step:2d}  loss {losses[-1]:.6f}")
+                print(f"[{storage}] step {step:2d}  loss {losses[-1]:.6f}")
         torch.cuda.synchronize()
         assert losses[-1] < losses[0], "the loss did not fall"
-        print(f"{r.size} values trained on a {a.rows} x {a.cols} pattern: loss {losses[0]:.4f} -> {losses[-1]:.4f}")
+        print(f"[{storage}] {r.size} values trained on a {a.rows} x {a.cols} pattern: loss {losses[0]:.4f} -> {losses[-1]:.4f}")
+        return losses
     finally:
         h.close()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--rows", type=int, default=2048)
+    ap.add_argument("--cols", type=int, default=1024)
+    ap.add_argument("--density", type=float, default=0.05)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--bf16", action="store_true", help="train a second time on a bf16 handle and print both final losses")
+    a = ap.parse_args()
+
+    rng = np.random.default_rng(0)
+    r, c = np.nonzero(rng.random((a.rows, a.cols)) < a.density)
+    r, c = r.astype(np.int32), c.astype(np.int32)
+    scale = np.float32(1.0 / np.sqrt(a.density * a.cols))
+    teacher = (rng.standard_normal(r.size).astype(np.float32)) * scale
+    start = (rng.standard_normal(r.size).astype(np.float32)) * scale
+
+    fp32 = train(a, r, c, start, teacher, "fp32")
+    if a.bf16:
+        bf16 = train(a, r, c, start, teacher, "bf16")
+        print(f"final loss after {a.steps} steps: fp32 handle {fp32[-1]:.6f}, bf16 handle {bf16[-1]:.6f}")
 
 
 if __name__ == "__main__":

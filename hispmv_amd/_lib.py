@@ -26,6 +26,9 @@ HISPMV_ENOTSUP = -8
 HISPMV_VALUES_FP32 = 0
 HISPMV_VALUES_BF16 = 1
 VALUE_STORAGES = {"fp32": HISPMV_VALUES_FP32, "bf16": HISPMV_VALUES_BF16}
+HISPMV_VALUE_UPDATES_OFF = 0
+HISPMV_VALUE_UPDATES_ON = 1
+HISPMV_VALUE_UPDATES_ANY_STORAGE = 2
 
 HISPMV_TRANSPOSABLE_OFF = 0
 HISPMV_TRANSPOSABLE_SLICES = 1
@@ -117,6 +120,7 @@ SIGNATURES = {
     "hispmv_prep_device_stream_on_device": (C.c_int, [_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hispmv_prep_frags": (_i32p, [_p]),
     "hispmv_prep_value_layouts": (C.c_int, [C.POINTER(_p), _p, _p, _p, C.c_int64, C.c_int32, C.c_int32, C.c_int, _i64p]),
+    "hispmv_prep_value_layouts_storage": (C.c_int, [C.POINTER(_p), _p, _p, _p, C.c_int64, C.c_int32, C.c_int32, C.c_int, C.c_int, _i64p]),
     "hispmv_prep_value_array": (C.c_void_p, [_p, C.c_int]),
     "hispmv_prep_csr_row_ptr": (_i64p, [_p]),
     "hispmv_prep_csr_col": (_i32p, [_p]),

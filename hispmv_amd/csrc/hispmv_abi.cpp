@@ -93,8 +93,9 @@ void round_values_to_bf16(const float* in, float* out, int64_t n) {
         std::memcpy(out + k, &u, 4);
     }
 }
+// (HISPMV_VALUE_UPDATES_ANY_STORAGE lifts this: the map of a bf16 handle is read on the host, add_sparse)
 int check_storage_and_updates(hispmv_ctx* c) {
-    if (c->value_storage == HISPMV_VALUES_BF16 && c->value_updates)
+    if (c->value_storage == HISPMV_VALUES_BF16 && c->value_updates && !c->updates_any_storage)
         return fail(c, HISPMV_EINVAL, "bf16 value storage and value updates are both on: the value map lives in 32-bit value slots (create the handle with one of the two switched off)");
     return HISPMV_OK;
 }
@@ -120,6 +121,7 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
     m->rows = csr.rows; m->cols = csr.cols; m->nnz = csr.nnz();
     FormatOptions opts = c->format_opts;
     opts.half_values = c->value_storage == HISPMV_VALUES_BF16;      // (the values are rounded already: add_from_coo, _from_csr)
+    opts.index_payloads = opts.half_values && real_values;          // ... or are index payloads: every part keeps its chunks of the map on the host
     if (c->transposable == HISPMV_TRANSPOSABLE_SLICES) opts.format_mode = 0;      // hispmv_set_transposable: keep the slice stream, as HISPMV_FORMAT=slices does
     m->keep_format = c->transposable == HISPMV_TRANSPOSABLE_KEEP_FORMAT;          // ... or the loader's own choice, a tile stream then marked as accepted
     m->value_storage = c->value_storage;
@@ -131,6 +133,7 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
         static_cast<HostPart&>(m->parts.back()) = std::move(hp);
     }
     for (auto& p : m->parts) {
+        if (p.is_tts && opts.index_payloads) p.value_map = host_value_map(p);       // (slice parts: pack_part, before their words went)
         if (p.is_tts) {
             m->n_slices += (int64_t)p.tts.col_base.size(); m->n_elems += p.tts.nnz + p.tts.n_fillers; m->n_split += (int64_t)p.tts.fix.size() / 4;
             m->device_bytes += p.tts.bytes();
@@ -182,6 +185,7 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
 int load_value_map(hispmv_ctx* c, Matrix& m, const std::vector<std::vector<ValueChunk>>& chunks, const std::vector<std::pair<int64_t, int64_t>>& layout_bytes) {
     std::vector<ValueChunkDev> tab;
     int64_t written = 0;
+    const bool bf16 = m.value_storage == HISPMV_VALUES_BF16;
     for (size_t t = 0; t < m.parts.size(); ++t) {
         Matrix::Part& p = m.parts[t];
         uint8_t* base0 = p.is_tts ? (uint8_t*)p.tdev.words : (uint8_t*)p.dev.words;
@@ -191,7 +195,7 @@ int load_value_map(hispmv_ctx* c, Matrix& m, const std::vector<std::vector<Value
             if (q.off0 < 0 || q.off0 + kValueChunk * 4 > layout_bytes[t].first || (base1 && (q.off1 < 0 || q.off1 + kValueChunk * 4 > layout_bytes[t].second)))
                 return fail(c, HISPMV_EINVAL, "internal: value region outside its layout");
             ValueChunkDev e;
-            e.map_off = (int64_t)tab.size() * kValueChunk;
+            e.map_off = (int64_t)tab.size() * kValueChunk | (q.kind0 == kChunkHalfSlice ? kChunkHalf0 : 0) | (base1 && q.kind1 == kChunkHalfSlice ? kChunkHalf1 : 0);
             e.dst0 = (float*)(base0 + q.off0);
             e.dst1 = base1 ? (float*)(base1 + q.off1) : nullptr;
             written += kValueChunk * (e.dst1 ? 2 : 1);
@@ -208,15 +212,25 @@ int load_value_map(hispmv_ctx* c, Matrix& m, const std::vector<std::vector<Value
         m.allocs.push_back(dt);
         m.d_map = (int32_t*)dm; m.d_upd_table = (ValueChunkDev*)dt;
         HIP_TRY(c, hipMemcpyAsync(dt, tab.data(), tab.size() * sizeof(ValueChunkDev), hipMemcpyHostToDevice, c->stream));
-        hipError_t e = launch_build_value_map(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->stream);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_build_value_map");
+        hipError_t e = hipSuccess;
+        if (bf16) {               // the map was read on the host (HostPart::value_map): a half slice holds no payloads
+            for (const Matrix::Part& p : m.parts) {
+                if (p.value_map.size() != chunks[(size_t)(&p - m.parts.data())].size() * (size_t)kValueChunk) return fail(c, HISPMV_EINVAL, "internal: a part's host value map does not match its chunks");
+                if (!p.value_map.empty()) HIP_TRY(c, hipMemcpyAsync(m.d_map + p.map_chunk_base * kValueChunk, p.value_map.data(), p.value_map.size() * 4, hipMemcpyHostToDevice, c->stream));
+            }
+        } else {
+            e = launch_build_value_map(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->stream);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_build_value_map");
+        }
         int rc;
         if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, m.upd_n)) != HISPMV_OK) return rc;
         if (m.upd_n > 0) HIP_TRY(c, hipMemcpyAsync(c->d_upd, m.upd_values.data(), (size_t)m.upd_n * 4, hipMemcpyHostToDevice, c->stream));
-        e = launch_update_values(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream);
+        e = bf16 ? launch_update_values_bf16(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream)
+                 : launch_update_values(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "launch_update_values");
         HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`tab` and the values are host locals / released next)
     }
+    for (Matrix::Part& p : m.parts) p.value_map = std::vector<int32_t>();
     m.upd_values = std::vector<float>();
     return HISPMV_OK;
 }
@@ -578,7 +592,7 @@ HISPMV_API int hispmv_create_sparse_handle_from_csr(hispmv_ctx* c, const int32_t
         csr.col.assign(ci, ci + nnz);
         if (c->value_updates) { real.assign(va, va + nnz); const std::vector<float> pl = index_payloads(nnz); csr.val.assign(pl.begin(), pl.end()); }   // input order: before the per-row sort
         else csr.val.assign(va, va + nnz);
-        if (c->value_storage == HISPMV_VALUES_BF16) round_values_to_bf16(csr.val.data(), csr.val.data(), nnz);
+        if (c->value_storage == HISPMV_VALUES_BF16 && !c->value_updates) round_values_to_bf16(csr.val.data(), csr.val.data(), nnz);      // (payloads stay whole; the load's update rounds the real values)
         for (int64_t k = 0; k < nnz; ++k) if (ci[k] < 0 || ci[k] >= cols) return fail(c, HISPMV_EINVAL, "CSR column outside matrix");
         sort_rows_by_column(csr);     // rows with unsorted columns (scipy: has_sorted_indices == False) are sorted, stably
         double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -607,7 +621,8 @@ HISPMV_API int hispmv_create_dense_handle(hispmv_ctx* c, const float* vals, int3
         (bf16 ? m->slots_2byte : m->slots_4byte) = m->nnz;
         m->saved_bytes = bf16 ? m->nnz * 2 : 0;
         if (c->arena_used + m->device_bytes > c->arena_budget) return HISPMV_FULL;
-        if (bf16) {           // W row-major as bf16: the upper halves of R(w)
+        if (bf16 && c->value_updates) m->dense_host.assign(vals, vals + m->nnz);      // rounded by the load's update (hispmv_update.h), as every later update is
+        else if (bf16) {      // W row-major as bf16: the upper halves of R(w)
             m->dense_host16.resize((size_t)m->nnz);
 #pragma omp parallel for num_threads(host_threads()) schedule(static)
             for (int64_t k = 0; k < m->nnz; ++k) {
@@ -645,7 +660,18 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
                 value_regions.push_back(value_chunks(p));
                 layout_bytes.emplace_back(p.is_tts ? (int64_t)p.tts.words.size() : p.dstream.n_bytes, p.has_batch_layout ? p.batch_dstream.n_bytes : 0);
             }
-        if (m.dense && m.value_storage == HISPMV_VALUES_BF16) {
+        if (m.dense && m.value_storage == HISPMV_VALUES_BF16 && m.updatable) {
+            // W is written by the update kernel from the fp32 creation values, staged in the context's update buffer
+            void* d = nullptr;
+            HIP_TRY(c, hipMalloc(&d, (size_t)m.nnz * 2));
+            m.allocs.push_back(d);
+            m.d_dense = (float*)d;
+            if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, m.nnz)) != HISPMV_OK) return rc;
+            HIP_TRY(c, hipMemcpyAsync(c->d_upd, m.dense_host.data(), (size_t)m.nnz * 4, hipMemcpyHostToDevice, c->stream));
+            const hipError_t e = launch_update_dense_bf16((uint16_t*)d, c->d_upd, m.nnz, c->stream);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_update_dense_bf16");
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        } else if (m.dense && m.value_storage == HISPMV_VALUES_BF16) {
             const uint16_t* d = nullptr;
             if ((rc = upload(c, m, m.dense_host16.data(), m.dense_host16.size(), &d)) != HISPMV_OK) return rc;
             m.d_dense = (float*)const_cast<uint16_t*>(d);      // (rows x cols bf16: every launch of this handle passes its storage along)
@@ -1358,7 +1384,8 @@ HISPMV_API int hispmv_value_storage_info(const hispmv_ctx* c, int idx, int64_t o
 HISPMV_API int hispmv_set_value_updates(hispmv_ctx* c, int enable) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    c->value_updates = enable != 0;
+    c->value_updates = enable != 0;          // (any value but 0 and _ANY_STORAGE is _ON, as before the third state existed)
+    c->updates_any_storage = enable == HISPMV_VALUE_UPDATES_ANY_STORAGE;
     return HISPMV_OK;
 }
 
@@ -1386,11 +1413,17 @@ int update_target(hispmv_ctx* c, int idx, const float* values, int64_t n, Matrix
 // d_values (device) into the layouts of m, asynchronous on s
 int issue_update(hispmv_ctx* c, Matrix& m, const float* d_values, hipStream_t s) {
     if (m.upd_n == 0) return HISPMV_OK;
+    const bool bf16 = m.value_storage == HISPMV_VALUES_BF16;
+    if (m.dense && bf16) {
+        const hipError_t e = launch_update_dense_bf16((uint16_t*)m.d_dense, d_values, m.upd_n, s);
+        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_update_dense_bf16");
+    }
     if (m.dense) {
         HIP_TRY(c, hipMemcpyAsync(m.d_dense, d_values, (size_t)m.upd_n * 4, hipMemcpyDeviceToDevice, s));
         return HISPMV_OK;
     }
-    const hipError_t e = launch_update_values(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s);
+    const hipError_t e = bf16 ? launch_update_values_bf16(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s)
+                              : launch_update_values(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s);
     return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_update_values");
 }
 

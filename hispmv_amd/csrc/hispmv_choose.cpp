@@ -113,6 +113,7 @@ void plan_part(HostPart& p, int n_cus) {
 }
 void pack_part(HostPart& p, const FormatOptions& opt) {
     if (opt.decide_only) return;
+    if (opt.half_values && opt.index_payloads) p.value_map = host_value_map(p);      // (before the words go; the half slices below then hold the upper halves of payloads until the load's update)
     p.dstream = pack_device_stream(p.st, p.plan, !opt.device_layout, opt.half_values);
     if (!opt.device_layout || opt.half_values) p.st.words = WordVec();   // the device layout replaces the host words (else the loader uploads them and lays them out there)
 }
@@ -549,27 +550,48 @@ std::vector<ValueChunk> value_chunks(const HostPart& p) {
     if (p.is_tts) {
         const int64_t n = (int64_t)p.tts.col_base.size();        // slices of 1024 words
         out.reserve((size_t)n);
-        for (int64_t s = 0; s < n; ++s) out.push_back({s * (int64_t)kTtsChunk * 8, -1});   // values at words + slice*8192, metas behind
+        for (int64_t s = 0; s < n; ++s) out.push_back({s * (int64_t)kTtsChunk * 8, -1, kChunkSlots32, kChunkSlots32});   // values at words + slice*8192, metas behind
         return out;
     }
     const int64_t n = p.st.n_slices;
-    // the byte offset of every slice in a device layout: groups of plan.group_slices slices, compact (6 KiB) or wide (8 KiB)
-    auto offsets = [n](const DeviceStream& d, const LaunchPlan& plan, std::vector<int64_t>& off) {
+    // the byte offset of every slice in a device layout: groups of plan.group_slices slices, half (4 KiB), compact (6 KiB) or wide (8 KiB)
+    auto offsets = [n](const DeviceStream& d, const LaunchPlan& plan, std::vector<int64_t>& off, std::vector<int32_t>& kind) {
         const int64_t G = plan.group_slices;
         off.assign((size_t)n, -1);
+        kind.assign((size_t)n, kChunkSlots32);
         for (int64_t s = 0; s < n; ++s) {
             const int64_t g = s / G;
             if ((size_t)g * 4 + 3 >= d.groups.size()) throw std::logic_error("value_chunks: group table shorter than the stream");
             const int32_t* e = d.groups.data() + g * 4;
-            off[(size_t)s] = (int64_t)e[2] * kSliceUnit + (s - g * G) * (e[3] ? kCompactSliceBytes : kWideSliceBytes);
+            const bool half = (e[3] & kGroupHalf) != 0;
+            off[(size_t)s] = (int64_t)e[2] * kSliceUnit + (s - g * G) * (half ? kHalfSliceBytes : e[3] ? kCompactSliceBytes : kWideSliceBytes);
+            kind[(size_t)s] = half ? kChunkHalfSlice : kChunkSlots32;
         }
     };
     std::vector<int64_t> a, b;
-    offsets(p.dstream, p.plan, a);
-    if (p.has_batch_layout) offsets(p.batch_dstream, p.batch_plan, b);
+    std::vector<int32_t> ka, kb;
+    offsets(p.dstream, p.plan, a, ka);
+    if (p.has_batch_layout) offsets(p.batch_dstream, p.batch_plan, b, kb);
     out.reserve((size_t)n);
-    for (int64_t s = 0; s < n; ++s) out.push_back({a[(size_t)s], p.has_batch_layout ? b[(size_t)s] : -1});
+    for (int64_t s = 0; s < n; ++s) out.push_back({a[(size_t)s], p.has_batch_layout ? b[(size_t)s] : -1, ka[(size_t)s], p.has_batch_layout ? kb[(size_t)s] : kChunkSlots32});
     return out;
+}
+
+std::vector<int32_t> host_value_map(const HostPart& p) {
+    std::vector<int32_t> map;
+    if (p.is_tts) {
+        const int64_t n = (int64_t)p.tts.col_base.size();
+        if ((int64_t)p.tts.words.size() < n * (int64_t)kTtsChunk * 8) throw std::logic_error("host_value_map: tile stream shorter than its slices");
+        map.resize((size_t)n * kSliceElems);
+        for (int64_t s = 0; s < n; ++s) std::memcpy(map.data() + s * kSliceElems, p.tts.words.data() + s * (int64_t)kTtsChunk * 8, (size_t)kSliceElems * 4);
+        return map;
+    }
+    const int64_t n = p.st.n_slices * kSliceElems;
+    if ((int64_t)p.st.words.size() < n) throw std::logic_error("host_value_map: the words of the stream were released");
+    map.resize((size_t)n);
+#pragma omp parallel for num_threads(host_threads()) schedule(static)
+    for (int64_t i = 0; i < n; ++i) map[(size_t)i] = (int32_t)(uint32_t)p.st.words[(size_t)i];
+    return map;
 }
 
 }  // namespace hispmv

@@ -37,6 +37,9 @@ struct HostPart {
     LaunchPlan batch_plan;
     DeviceStream batch_dstream;
     WordVec batch_words;                         // (device_layout only: the planned host words of the batch layout)
+    // updatable bf16 handles (FormatOptions::index_payloads): the part's chunks of the value map, read on the host -- a half slice
+    // has no room for a payload.  Slice s of the part is words [s * kSliceElems, (s + 1) * kSliceElems); released after the upload
+    std::vector<int32_t> value_map;
 };
 constexpr int kBatchGroupBelow = 80;
 
@@ -63,6 +66,8 @@ struct FormatOptions {
     int batch_group_below = kBatchGroupBelow;     // HISPMV_BATCH_GROUP_BELOW (experiments): resident groups shorter than this get the batch layout
     bool half_values = false;     // bf16 value storage (hispmv_set_value_storage; not an environment switch): the compact groups of every slice layout are packed
                                   //   as half slices, on the host whatever device_layout says.  The values are already rounded; plans and choices do not look at it
+    bool index_payloads = false;  // with half_values (updatable bf16 handles): the values are the index payloads bits(k + 1), NOT rounded; every part
+                                  //   keeps the payloads of its slices in element order (HostPart::value_map) before its half layouts are packed
     bool decide_only = false;     // skip the device layouts the decision does not need (tests: the choice, not the bytes)
     static FormatOptions from_env();
 };
@@ -102,9 +107,18 @@ FormatChoice choose_format(Csr&& csr, SliceStream* prebuilt, int n_cus, const Fo
 // slice of a slice stream (the batch layout has the same slices: its region of a slice is the same chunk's second destination), the
 // first 4096 B of every 8192-byte slice of a tile stream's words.  One chunk per region, in map order: {byte offset in the part's
 // layout (dstream / tts.words), byte offset in its batch layout or -1}.  Needs the host group tables (before the loader frees them).
+// bf16 value storage: the region of a slice of a HALF group is the whole 4096-byte half slice, the values being the first 8 bytes of
+// each 16-byte piece (hispmv_format.h) -- kind 1; every other region is kSliceElems fp32 slots as above -- kind 0.  A slice may be
+// half in one layout and wide in the other: one kind per destination.
+constexpr int kChunkSlots32 = 0, kChunkHalfSlice = 1;
 struct ValueChunk {
     int64_t off0, off1;
+    int32_t kind0 = kChunkSlots32, kind1 = kChunkSlots32;
 };
+// The part's chunks of the value map from its host tables when they hold index payloads: the value halves of a slice stream's words
+// (call before pack_part releases them) or the value regions of a tile stream's words.  Element order inside a slice is the same in
+// every layout, so this is word for word what the loader reads back from the fp32 layouts on the device.
+std::vector<int32_t> host_value_map(const HostPart& p);
 std::vector<ValueChunk> value_chunks(const HostPart& p);
 
 }  // namespace hispmv

@@ -71,7 +71,8 @@ struct Matrix {
     // vectors can apply the fix-ups of its rows itself (spmv_tail_multi_kernel); nullptr when a part has a long chain
     int32_t* d_fix_of_row = nullptr;
     // In-place value updates (hispmv_set_value_updates on at creation): the layouts were packed with the payloads bits(k + 1) of the
-    // input positions k; at load the map is read out of them and the real values (kept until then) are gathered in (hispmv_update.h)
+    // input positions k; at load the map is read out of them and the real values (kept until then) are gathered in (hispmv_update.h).
+    // A bf16 handle (HISPMV_VALUE_UPDATES_ANY_STORAGE) brings its map from the host (HostPart::value_map) and rounds in the update.
     bool updatable = false;
     int64_t upd_n = 0;                      // values an update takes (nnz of the input, rows * cols for a dense handle)
     int64_t map_slots = 0;                  // kValueChunk per chunk
@@ -140,6 +141,7 @@ struct hispmv_ctx {
     // value updates: the switch handles are created under (hispmv_set_value_updates), the pinned staging block and the device
     // buffer of hispmv_update_values (host values) and of the load's first update
     bool value_updates = false;
+    bool updates_any_storage = false;           // HISPMV_VALUE_UPDATES_ANY_STORAGE: bf16 handles are created updatable too instead of refused
     int value_storage = HISPMV_VALUES_FP32;     // hispmv_set_value_storage: what handles created from now on store their values as
     int transposable = HISPMV_TRANSPOSABLE_OFF; // hispmv_set_transposable: sparse handles created from now on keep the slice stream (_SLICES: format_mode 0),
                                                 //   or their own format with a tile stream among them marked for the transposed entries (_KEEP_FORMAT)
@@ -226,6 +228,7 @@ struct hispmv_prep {
     std::vector<uint8_t> vl_real, vl_index;
     std::vector<int32_t> vl_map;
     std::vector<int64_t> vl_chunks;
+    std::vector<int32_t> vl_kinds;      // per chunk destination: kChunkSlots32 / kChunkHalfSlice (hispmv_choose.h)
 };
 
 

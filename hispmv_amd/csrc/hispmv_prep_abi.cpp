@@ -267,9 +267,15 @@ HISPMV_API const int32_t* hispmv_prep_fix(const hispmv_prep* p) { return (const 
 // twice by the same host path: with the real values, and -- as for a handle created with value updates on -- with the index
 // payloads bits(k + 1).  The map is read out of the payload layouts' value regions (value_chunks) exactly as the loader reads it on
 // the device.  For tests: gathering the values through the map must give the real layouts byte for byte.
-HISPMV_API int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* r, const int32_t* cl, const float* v, int64_t nnz, int32_t rows,
-                                         int32_t cols, int n_cus, int64_t counts[8]) {
+// `storage` = HISPMV_VALUES_BF16: what a handle created under HISPMV_VALUE_UPDATES_ANY_STORAGE with bf16 storage gets.  The real
+// layouts are packed from R(values), half groups included; the payload layouts have the same group tables and metas, their half
+// slices hold no payloads (a 16-bit slot cannot), and the map is the one the loader uploads: the parts' HostPart::value_map, read
+// from the host words (host_value_map).  Array 4 names the kind of every chunk destination.
+HISPMV_API int hispmv_prep_value_layouts_storage(hispmv_prep** out, const int32_t* r, const int32_t* cl, const float* v, int64_t nnz, int32_t rows,
+                                                 int32_t cols, int n_cus, int storage, int64_t counts[8]) {
     if (!out) return HISPMV_EINVAL;
+    if (storage != HISPMV_VALUES_FP32 && storage != HISPMV_VALUES_BF16) { g_prep_err = "unknown value storage"; return HISPMV_EINVAL; }
+    const bool bf16 = storage == HISPMV_VALUES_BF16;
     host_threads();
     *out = nullptr;
     if (rows <= 0 || cols <= 0 || nnz < 0 || n_cus <= 0 || !counts || (nnz > 0 && (!r || !cl || !v))) { g_prep_err = "bad sparse matrix arguments"; return HISPMV_EINVAL; }
@@ -282,7 +288,15 @@ HISPMV_API int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* r, co
         std::vector<float> payloads((size_t)nnz);
         for (int64_t k = 0; k < nnz; ++k) { const uint32_t b = (uint32_t)(k + 1); std::memcpy(&payloads[(size_t)k], &b, 4); }
         int64_t info[4] = {0, 0, 0, 0};
+        opt.half_values = bf16;
+        std::vector<float> rounded;
+        if (bf16) {
+            rounded.resize((size_t)nnz);
+            for (int64_t k = 0; k < nnz; ++k) { uint32_t u; std::memcpy(&u, v + k, 4); u = round_bits_to_bf16(u); std::memcpy(&rounded[(size_t)k], &u, 4); }
+            v = rounded.data();
+        }
         auto pack = [&](const float* vals, std::vector<uint8_t>& bytes, bool record) {
+            opt.index_payloads = bf16 && record;
             FormatChoice ch = choose_format(coo_to_csr(rows, cols, nnz, r, cl, vals), nullptr, n_cus, opt);
             if (record) { info[0] = ch.format; info[1] = ch.parts.size() > 1 ? (ch.tile_kind ? ch.tile_kind : 1) : 0; info[2] = (int64_t)ch.parts.size(); }
             for (const HostPart& q : ch.parts) {
@@ -296,18 +310,26 @@ HISPMV_API int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* r, co
                 for (const ValueChunk& c : chunks) {
                     p->vl_chunks.push_back(base0 + c.off0);
                     p->vl_chunks.push_back(c.off1 >= 0 ? base1 + c.off1 : -1);
+                    p->vl_kinds.push_back(c.kind0);
+                    p->vl_kinds.push_back(c.off1 >= 0 ? c.kind1 : kChunkSlots32);
+                }
+                if (bf16) {           // the map as the loader gets it (slice parts: kept by pack_part; tile streams: read from their words)
+                    const std::vector<int32_t> part_map = q.is_tts ? host_value_map(q) : q.value_map;
+                    if (part_map.size() != chunks.size() * (size_t)kValueChunk) throw std::logic_error("internal: a part's host value map does not match its chunks");
+                    p->vl_map.insert(p->vl_map.end(), part_map.begin(), part_map.end());
                 }
             }
         };
         pack(v, p->vl_real, false);
         pack(payloads.data(), p->vl_index, true);
         const int64_t n_chunks = (int64_t)p->vl_chunks.size() / 2;
+        if (bf16 && (int64_t)p->vl_map.size() != n_chunks * kValueChunk) { g_prep_err = "internal: host value map size"; return HISPMV_EINVAL; }
         p->vl_map.resize((size_t)n_chunks * kValueChunk);
         int64_t written = 0;
         for (int64_t k = 0; k < n_chunks; ++k) {
             const int64_t off = p->vl_chunks[(size_t)k * 2];
             if (off < 0 || off + kValueChunk * 4 > (int64_t)p->vl_index.size()) { g_prep_err = "internal: value region outside its layout"; return HISPMV_EINVAL; }
-            std::memcpy(p->vl_map.data() + k * kValueChunk, p->vl_index.data() + off, kValueChunk * 4);
+            if (!bf16) std::memcpy(p->vl_map.data() + k * kValueChunk, p->vl_index.data() + off, kValueChunk * 4);
             written += kValueChunk * (p->vl_chunks[(size_t)k * 2 + 1] >= 0 ? 2 : 1);
         }
         counts[0] = (int64_t)p->vl_index.size(); counts[1] = (int64_t)p->vl_map.size(); counts[2] = n_chunks; counts[3] = written;
@@ -318,8 +340,14 @@ HISPMV_API int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* r, co
     } catch (const std::exception& ex) { g_prep_err = ex.what(); return HISPMV_EINVAL; }
 }
 
-// 0 = the layouts with the real values (counts[0] bytes), 1 = the same with the index payloads, 2 = the map (int32, counts[1]),
-// 3 = the chunks (counts[2] x int64 {byte offset of the first destination, of the second or -1}).
+HISPMV_API int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* r, const int32_t* cl, const float* v, int64_t nnz, int32_t rows,
+                                         int32_t cols, int n_cus, int64_t counts[8]) {
+    return hispmv_prep_value_layouts_storage(out, r, cl, v, nnz, rows, cols, n_cus, HISPMV_VALUES_FP32, counts);
+}
+
+// 0 = the layouts with the real values (counts[0] bytes; bf16 storage: packed from R(values), half groups included), 1 = the same
+// with the index payloads, 2 = the map (int32, counts[1]), 3 = the chunks (counts[2] x int64 {byte offset of the first destination,
+// of the second or -1}), 4 = the kinds (counts[2] x 2 int32, the shape of 3: 0 = 1024 fp32 slots, 1 = a half slice).
 HISPMV_API const void* hispmv_prep_value_array(const hispmv_prep* p, int which) {
     if (!p) return nullptr;
     switch (which) {
@@ -327,6 +355,7 @@ HISPMV_API const void* hispmv_prep_value_array(const hispmv_prep* p, int which) 
         case 1: return p->vl_index.data();
         case 2: return p->vl_map.data();
         case 3: return p->vl_chunks.data();
+        case 4: return p->vl_kinds.data();
         default: return nullptr;
     }
 }

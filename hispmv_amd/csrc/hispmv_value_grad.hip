@@ -55,13 +55,19 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t float_buffer(const float* p, i
 }
 
 // The metas of a slice as they arrive (hispmv_format.h): they begin at byte 4096 of a compact (2 KiB) and of a wide (4 KiB) slice; the
-// 4 KiB of values before them are not requested.
+// 4 KiB of values before them are not requested.  HALF (bf16 storage): the compact metas of step j, lane l are dwords 2 and 3 of the
+// 16-byte piece at (j * 64 + l) * 16; only those 8 bytes are requested, the bf16 values in dwords 0 and 1 are not.
 template <bool COMPACT> struct SliceMetas;
 template <> struct SliceMetas<true>  { uint2 m[kSliceSteps]; };
 template <> struct SliceMetas<false> { uint4 m[kSliceSteps]; };
-template <bool COMPACT>
+template <bool COMPACT, bool HALF = false>
 __device__ __forceinline__ void request_metas(SliceMetas<COMPACT>& s, const char* base, int lane) {
-    if constexpr (COMPACT) {
+    static_assert(COMPACT || !HALF, "only a compact group has a half form");
+    if constexpr (HALF) {
+        const uint2* pm = (const uint2*)(base + 8) + 2 * lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 128);
+    } else if constexpr (COMPACT) {
         const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
 #pragma unroll
         for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
@@ -98,12 +104,12 @@ __device__ __forceinline__ void store_grad(float* grad, long long n, int q, floa
     *p = r;
 }
 
-// The work of one workgroup on group `group` of a slice stream for a pass of NV vectors, for a group stored COMPACT (6 B per element)
-// or wide (8 B).  STRAYS: the plan has stray areas behind the window; whether THIS group uses them is bit 2 of its group word.
+// The work of one workgroup on group `group` of a slice stream for a pass of NV vectors, for a group stored COMPACT (6 B per element),
+// HALF (a compact group of a bf16 handle, 4 B) or wide (8 B).  STRAYS: the plan has stray areas behind the window; whether THIS group uses them is bit 2 of its group word.
 // LDS: [NV x windows of lds_floats each (the wavefronts' stray areas are a window's last floats): window v at xs + v * lds_floats]
 // [ONE gy tile of ytile_floats per wavefront], slice_lds_bytes(m, NV) in all.  Vector v reads gy + v * rows and x + v * cols, each
 // through its own buffer descriptor, so a row or column past the end reads 0 and not the next vector's first float.
-template <int NV, bool USE_LDS, bool COMPACT, bool STRAYS>
+template <int NV, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF = false>
 __device__ __forceinline__ void value_grad_group(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const int32_t* __restrict__ map,
     const float* __restrict__ gy, const float* __restrict__ x, float* grad, long long n, float alpha, float beta, long long n_slices,
@@ -115,7 +121,7 @@ __device__ __forceinline__ void value_grad_group(
     const long long first = group * group_slices;
     const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
     const int n_here = (int)(last > first ? last - first : 0);
-    constexpr int slice_bytes = COMPACT ? kCompactSliceBytes : kWideSliceBytes;
+    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
     const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
     const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;      // 0 fragments: the metas of this group are plain columns
     const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
@@ -132,7 +138,7 @@ __device__ __forceinline__ void value_grad_group(
     int4 h = int4{0, 0, 0, 0};
     if (local < n_here) {
         h = load_int4(hdr + first + local);
-        request_metas<COMPACT>(w, gbase + (size_t)local * slice_bytes, lane);
+        request_metas<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
     }
     if (USE_LDS) {
         if (in_lds) {
@@ -197,7 +203,7 @@ __device__ __forceinline__ void value_grad_group(
         local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
         if (local < n_here) {
             h = load_int4(hdr + first + local);
-            request_metas<COMPACT>(w, gbase + (size_t)local * slice_bytes, lane);
+            request_metas<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
         }
         float acc[kE];
 #pragma unroll
@@ -264,7 +270,8 @@ __device__ __forceinline__ void value_grad_group(
     }
 }
 
-template <int NV, bool USE_LDS, bool STRAYS>
+// HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
+template <int NV, bool USE_LDS, bool STRAYS, bool HALF>
 __global__ __launch_bounds__(1024) void value_grad_slices_kernel(
     const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
     const int32_t* __restrict__ map, const float* __restrict__ gy, const float* __restrict__ x, float* grad, long long n, float alpha, float beta,
@@ -272,7 +279,14 @@ __global__ __launch_bounds__(1024) void value_grad_slices_kernel(
     const long long group = (long long)blockIdx.x;
     if constexpr (USE_LDS) {
         const int4 g = load_int4(groups + group);
-        if (__builtin_amdgcn_readfirstlane(g.w) & kGroupCompact)
+        const int gw = __builtin_amdgcn_readfirstlane(g.w);
+        if constexpr (HALF) {
+            if (gw & kGroupHalf) {
+                value_grad_group<NV, true, true, STRAYS, true>(words, hdr, frags, map, gy, x, grad, n, alpha, beta, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+                return;
+            }
+        }
+        if (gw & kGroupCompact)
             value_grad_group<NV, true, true, STRAYS>(words, hdr, frags, map, gy, x, grad, n, alpha, beta, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
         else
             // (STRAYS goes to the wide body too: it uses no stray area, but its window ends where the wavefronts' stray areas begin)
@@ -351,9 +365,9 @@ hipError_t launch_value_grad_width(const SpmvDeviceMatrix& m, const int32_t* map
                            m.cols, m.rows);
         return hipGetLastError();
     };
-    if (m.lds_floats <= 0) return go([] { return value_grad_slices_kernel<NV, false, false>; });
-    if (m.has_strays) return go([] { return value_grad_slices_kernel<NV, true, true>; });
-    return go([] { return value_grad_slices_kernel<NV, true, false>; });
+    if (m.lds_floats <= 0) return go([] { return value_grad_slices_kernel<NV, false, false, false>; });
+    if (m.has_strays) return m.has_half ? go([] { return value_grad_slices_kernel<NV, true, true, true>; }) : go([] { return value_grad_slices_kernel<NV, true, true, false>; });
+    return m.has_half ? go([] { return value_grad_slices_kernel<NV, true, false, true>; }) : go([] { return value_grad_slices_kernel<NV, true, false, false>; });
 }
 
 }  // namespace
@@ -363,7 +377,8 @@ hipError_t launch_value_grad(const SpmvDeviceMatrix& m, int nv, const int32_t* m
     (void)hipGetLastError();
     if (nv != 1 && nv != 2 && nv != 4) return hipErrorInvalidValue;
     if (m.n_slices <= 0 || m.n_groups <= 0 || n <= 0) return hipSuccess;
-    if (!map || m.has_half) return hipErrorInvalidValue;           // (a bf16 handle has no map)
+    if (!map) return hipErrorInvalidValue;
+    if (m.lds_floats <= 0 && m.has_half) return hipErrorInvalidValue;          // half groups exist only in plans with a window
     if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || slice_lds_bytes(m, nv) > (size_t)kDynLdsMax)
         return hipErrorInvalidValue;
     if ((int64_t)m.cols * nv >= (1 << 30) || (int64_t)m.rows * nv >= (1 << 30)) return hipErrorInvalidValue;

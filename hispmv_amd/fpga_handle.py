@@ -151,9 +151,18 @@ class FpgaHandle:
         rc = lib.hispmv_create_sparse_handle_from_csr(self._ctx, _ptr(rp), _ptr(ci), _ptr(va), int(rows), int(cols))
         return rc if rc == _lib.HISPMV_FULL else self._check(rc)
 
-    def set_value_updates(self, enable: bool) -> None:
-        """Handles created from now on (until switched off) can have their values updated in place (hispmv_set_value_updates)."""
-        self._check(lib.hispmv_set_value_updates(self._ctx, int(bool(enable))))
+    def set_value_updates(self, enable) -> None:
+        """Handles created from now on (until switched off) can have their values updated in place (hispmv_set_value_updates).
+        True / False as ever: under True, creating a handle while the value storage is "bf16" raises ValueError.  "any_storage": fp32
+        handles exactly as under True, and bf16 handles are created updatable too -- their updates take fp32 values and round them on
+        the device to the nearest bfloat16 (ties to even).  Any other string raises ValueError."""
+        if isinstance(enable, str):
+            if enable != "any_storage":
+                raise ValueError('set_value_updates takes False, True or "any_storage"')
+            state = _lib.HISPMV_VALUE_UPDATES_ANY_STORAGE
+        else:
+            state = int(bool(enable))
+        self._check(lib.hispmv_set_value_updates(self._ctx, state))
 
     def update_values(self, matrix_idx: int, values) -> None:
         """New values for a loaded updatable handle, in the order of its creation input (COO arrays, CSR values before the per-row

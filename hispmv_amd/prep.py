@@ -269,17 +269,21 @@ def step_queue(slice_costs, tile_costs, n_wg: int = 256, mode: int = 0):
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 
-def value_layouts_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256) -> dict:
+def value_layouts_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int, n_cus: int = 256, value_storage: str = "fp32") -> dict:
     """Every device layout of the handle a COO input makes, packed twice on the host (hispmv_prep_value_layouts): `real` with the
     values, `index` with the index payloads of a handle created with value updates on; `map` (int32, read out of `index`) and
-    `chunks` ([n, 2] byte offsets of each chunk's first and second destination, -1 = none), plus the VALUE_LAYOUT_FIELDS counts."""
+    `chunks` ([n, 2] byte offsets of each chunk's first and second destination, -1 = none), plus the VALUE_LAYOUT_FIELDS counts.
+    value_storage="bf16": the layouts of an updatable bf16 handle -- `real` packed from the rounded values with its half groups, `map`
+    as the loader uploads it -- and `kinds` ([n, 2] int32 beside `chunks`: 0 = 1024 fp32 slots, 1 = a half slice)."""
+    if value_storage not in VALUE_STORAGES:
+        raise ValueError('value storage must be "fp32" or "bf16"')
     r = np.ascontiguousarray(coo_rows, dtype=np.int32)
     c = np.ascontiguousarray(coo_cols, dtype=np.int32)
     v = np.ascontiguousarray(coo_values, dtype=np.float32)
     p = C.c_void_p()
     cnt = (C.c_int64 * 8)()
-    rc = lib.hispmv_prep_value_layouts(C.byref(p), C.c_void_p(r.ctypes.data), C.c_void_p(c.ctypes.data), C.c_void_p(v.ctypes.data), r.size,
-                                       int(rows), int(cols), int(n_cus), cnt)
+    rc = lib.hispmv_prep_value_layouts_storage(C.byref(p), C.c_void_p(r.ctypes.data), C.c_void_p(c.ctypes.data), C.c_void_p(v.ctypes.data), r.size,
+                                               int(rows), int(cols), int(n_cus), VALUE_STORAGES[value_storage], cnt)
     if rc != HISPMV_OK:
         raise ValueError(lib.hispmv_prep_last_error().decode())
     try:
@@ -289,7 +293,7 @@ def value_layouts_from_coo(coo_rows, coo_cols, coo_values, rows: int, cols: int,
             ptr = lib.hispmv_prep_value_array(p, which)
             return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy() if (n and ptr) else np.zeros(0, dt)
         d.update(real=arr(0, d["bytes"], np.uint8), index=arr(1, d["bytes"], np.uint8), map=arr(2, d["map_slots"], np.int32),
-                 chunks=arr(3, 2 * d["chunks"], np.int64).reshape(-1, 2))
+                 chunks=arr(3, 2 * d["chunks"], np.int64).reshape(-1, 2), kinds=arr(4, 2 * d["chunks"], np.int32).reshape(-1, 2))
         return d
     finally:
         lib.hispmv_prep_free(p)

@@ -145,6 +145,12 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None):
     value_grad_device (alpha = 1, beta = 0: deterministic, no atomics), and x is saved for backward (only then).  grad_x uses the values
     the handle holds at backward time: nothing else may push values into the handle between this forward and its backward.
 
+    bf16 handles (value storage "bf16", created under FpgaHandle.set_value_updates("any_storage")): `values` is the fp32 MASTER COPY.
+    The forward pass pushes it and the update rounds on the device, so the handle stores R(values) (nearest bfloat16, ties to even)
+    and y, grad_x are computed with R(values).  grad_values is the gradient AT THE STORED VALUES, handed to the master copy as if
+    the rounding were the identity (straight-through): it does not depend on the values at all, and equals bit for bit what the
+    fp32 handle of the same input returns.  The optimiser steps the fp32 copy; steps smaller than half a bf16 ulp accumulate there.
+
     Streams, with values: on torch's DEFAULT stream (handle 0, which the library reads as the context's own stream) forward and
     backward each wait on the host for the default stream before their launches and for the context's stream after them, so
     ``v -= lr * v.grad`` followed by the next forward is ordered; on any other current stream nothing waits.  A loop that should not

@@ -142,7 +142,18 @@ int hispmv_spmv_device_batch(hispmv_ctx* ctx, int32_t n, const int32_t* idx, con
  * while it is off are exactly as before.  Values come in the order of the creation input: the COO arrays of
  * hispmv_create_sparse_handle (duplicates included), col_idx / values of _from_csr BEFORE its per-row sort, W row-major for a
  * dense handle.  hispmv_create_sparse_handle_from_mtx refuses (HISPMV_EINVAL) while the switch is on: its reader drops zeros and
- * mirrors symmetric entries.  So do the tile-stream experiments HISPMV_TTS_GEOMETRY (other than standard) and HISPMV_TTS_SMALL. */
+ * mirrors symmetric entries.  So do the tile-stream experiments HISPMV_TTS_GEOMETRY (other than standard) and HISPMV_TTS_SMALL.
+ * `enable` has three states.  HISPMV_VALUE_UPDATES_OFF; HISPMV_VALUE_UPDATES_ON: as above, and creating a handle while bf16 value
+ * storage is on as well is refused (HISPMV_EINVAL, see hispmv_set_value_storage); HISPMV_VALUE_UPDATES_ANY_STORAGE: fp32 handles
+ * exactly as under _ON (same layouts, map, device bytes), and a bf16 handle, sparse or dense, is accepted and becomes updatable.  Any
+ * other non-zero value means _ON.  An update of a bf16 handle takes fp32 values and ROUNDS THEM ON THE DEVICE with the R of
+ * hispmv_set_value_storage (nearest bfloat16, ties to even; +-Inf stay, a finite value above the largest bf16 becomes Inf, a NaN a
+ * quiet NaN with its sign, subnormals as bf16 has them): afterwards every entry returns the bits of a fresh bf16 handle created from
+ * those values.  Its map has the words of the fp32 handle of the same input; its device bytes are those of the plain bf16 handle
+ * plus the map and its chunk table. */
+#define HISPMV_VALUE_UPDATES_OFF 0
+#define HISPMV_VALUE_UPDATES_ON 1
+#define HISPMV_VALUE_UPDATES_ANY_STORAGE 2
 int hispmv_set_value_updates(hispmv_ctx* ctx, int enable);
 /* n = the number of values of the creation input.  HISPMV_ESTATE: the handle is not updatable or not loaded; HISPMV_EINVAL: wrong
  * n, NULL values, bad index.  Host values: returns when the device layout holds them (pinned staging, one copy, one launch). */
@@ -164,7 +175,8 @@ int hispmv_value_update_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[
  * and launch plan do not depend on the storage.  Where a layout has a kernel that reads 16-bit values its bytes shrink -- compact
  * slice groups (6 -> 4 bytes per element, stray-slot groups included), dense W (4 -> 2) --; wide groups, plans without a window and
  * the tile stream keep 32-bit slots that hold R(v).  Unknown storage or NULL context -> HISPMV_EINVAL.  Creating a handle while
- * value updates AND bf16 storage are both on -> HISPMV_EINVAL (the value map lives in 32-bit slots). */
+ * value updates (HISPMV_VALUE_UPDATES_ON) AND bf16 storage are both on -> HISPMV_EINVAL (the value map lives in 32-bit slots);
+ * HISPMV_VALUE_UPDATES_ANY_STORAGE is the opt-in under which such a handle is created, with its map read on the host. */
 #define HISPMV_VALUES_FP32 0
 #define HISPMV_VALUES_BF16 1
 int hispmv_set_value_storage(hispmv_ctx* ctx, int storage);
@@ -307,7 +319,7 @@ int hispmv_linear_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, 
  *    updatable dense handle, and every loaded, updatable tile stream that hispmv_spmv_device_t accepts (created in state
  *    HISPMV_TRANSPOSABLE_KEEP_FORMAT; hispmv_set_value_updates already refuses the other geometries and HISPMV_TTS_SMALL).  Not loaded
  *    -> HISPMV_ESTATE; not created with value updates on -> HISPMV_ESTATE (the message names hispmv_set_value_updates; a bf16 handle
- *    cannot be updatable and falls under this); a tile stream that is not accepted -> HISPMV_ENOTSUP (the messages of
+ *    created outside HISPMV_VALUE_UPDATES_ANY_STORAGE falls under this); a tile stream that is not accepted -> HISPMV_ENOTSUP (the messages of
  *    hispmv_spmv_device_t), in this order.
  *  - The argument checks come before any device call: NULL context, num_vecs < 1, NULL d_gy or d_x, NULL d_grad with n > 0, d_grad
  *    equal to d_gy or d_x, a bad index -> HISPMV_EINVAL; rows * num_vecs or cols * num_vecs >= 2^30 -> HISPMV_EINVAL (the message says
@@ -315,7 +327,9 @@ int hispmv_linear_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, 
  *  - HANDLE STATE: the entry reads metas, slice headers, fragment tables, stray columns and the value map.  It does not read the values
  *    and does not touch carries, tickets or cached batch plans, so it may overlap forward, transposed and update calls on the same
  *    handle (hispmv_update_values_device writes values only).
- * Out of scope: bf16 handles (they have no map), gradients inside hispmv_spmv_device_batch or the step kernel,
+ *  - A bf16 handle made updatable under HISPMV_VALUE_UPDATES_ANY_STORAGE is accepted like an fp32 one: its half groups are decoded for
+ *    their metas only, plan, pass widths and map are those of the fp32 handle of the same input, and so is every bit of grad.
+ * Out of scope: gradients inside hispmv_spmv_device_batch or the step kernel,
  * sharding over devices, host-pointer variants, passes wider than the 4-2-1 rule. */
 int hispmv_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gy, const float* d_x, int64_t num_vecs, float* d_grad,
                              float alpha, float beta, void* stream);
@@ -470,6 +484,13 @@ const int32_t* hispmv_prep_frags(const hispmv_prep* p);
  * 1024 map slots the byte offsets {first destination, second destination or -1} (int64 x 2).  For tests, no device needed. */
 int hispmv_prep_value_layouts(hispmv_prep** out, const int32_t* coo_rows, const int32_t* coo_cols, const float* coo_values, int64_t nnz,
                               int32_t rows, int32_t cols, int n_cus, int64_t counts[8]);
+/* The same with a value storage (HISPMV_VALUES_FP32: exactly the call above).  HISPMV_VALUES_BF16: the layouts of an updatable bf16
+ * handle (HISPMV_VALUE_UPDATES_ANY_STORAGE) -- array 0 packed from R(values), half groups included; array 1 the same layouts packed
+ * with the payloads (its half slices hold no usable values: an update overwrites them); array 2 the map as the loader uploads it,
+ * word for word that of the fp32 call; array 4 one int32 kind per chunk destination, in the shape of array 3: 0 = 1024 fp32 slots,
+ * 1 = a half slice, whose values are the first 8 bytes of each 16-byte piece (0 where array 3 holds -1). */
+int hispmv_prep_value_layouts_storage(hispmv_prep** out, const int32_t* coo_rows, const int32_t* coo_cols, const float* coo_values, int64_t nnz,
+                                      int32_t rows, int32_t cols, int n_cus, int storage, int64_t counts[8]);
 const void* hispmv_prep_value_array(const hispmv_prep* p, int which);
 
 /* Number of device / pinned-memory frees the runtime rejected since the library was loaded (a pointer released twice

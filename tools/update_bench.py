@@ -6,10 +6,13 @@ On the 20-matrix benchmark set and on the model_test layers (apps/model_test.py)
   * host update time (hispmv_update_values: pinned staging, one copy, the kernel, a synchronise), warmed, per round of all handles;
   * device update time (hispmv_update_values_device of every handle back to back on one stream), HIP events over warmed repeats;
   * bytes per round: 4 * map slots + 4 * slots written + 4 * values gathered, GB/s and the fraction of 8 TB/s.
+--bf16: the same handles a second time in the same context with bf16 value storage (set_value_updates("any_storage")), timed beside
+the fp32 ones in the same run (groups `*_bf16`; an update then reads 4-byte values and map words and writes 2 bytes per slot of a
+half slice or a dense W, 4 bytes per 32-bit slot).
 Prints one JSON line (and writes it to --out).  Kernel-only times: run it under `rocprofv3 --kernel-trace --stats -- python
 tools/update_bench.py` and read the update_values_kernel dispatches from the trace (the `kernels` view of its database).
 
-    python tools/update_bench.py [--reps 50] [--warmup 5] [--out FILE]
+    python tools/update_bench.py [--reps 50] [--warmup 5] [--bf16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -57,7 +60,9 @@ def group(torch, h, handles, reps, warmup):
     s.synchronize()
     h.synchronize()
     dev_ms = e0.elapsed_time(e1) / reps
-    byts = sum(4 * u["map_slots"] + 4 * u["written"] + 4 * u["n"] for u in infos)
+    # bytes written: by slot size (a dense handle has no map: its `written` values are the slots of W, 2 or 4 bytes each)
+    stores = [h.value_storage_info(i) for i, _ in handles]
+    byts = sum(4 * u["map_slots"] + 4 * u["n"] + (2 * s["slots_2byte"] + 4 * s["slots_4byte"]) for u, s in zip(infos, stores))
     return dict(handles=len(handles), values=sum(u["n"] for u in infos), map_slots=sum(u["map_slots"] for u in infos),
                 written=sum(u["written"] for u in infos), bytes=byts, device_ms=dev_ms, host_ms=host_ms,
                 gbps=byts / (dev_ms * 1e-3) / 1e9, frac_8tbs=byts / (dev_ms * 1e-3) / HBM_PEAK)
@@ -87,6 +92,7 @@ def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--bf16", action="store_true", help="also time the same handles with bf16 value storage, in the same run")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -105,9 +111,15 @@ def main() -> None:
         h.close()
     h = pyhispmv.FpgaHandle("bench.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
     h.set_arena_bytes(64 << 30)
-    h.set_value_updates(True)
+    h.set_value_updates("any_storage" if a.bf16 else True)          # (fp32 handles are the same in both states)
     try:
         set_h, lay_h, t_set, t_lay = create_all(h, set_mats, layers)
+        if a.bf16:
+            h.set_value_storage("bf16")
+            set_b, lay_b, b_set, b_lay = create_all(h, set_mats, layers)
+            h.set_value_storage("fp32")
+            out["set20_bf16"] = dict(group(torch, h, set_b, a.reps, a.warmup), create_load_updatable_s=b_set)
+            out["model_test_layers_bf16"] = dict(group(torch, h, lay_b, a.reps, a.warmup), create_load_updatable_s=b_lay)
         out["set20"] = dict(group(torch, h, set_h, a.reps, a.warmup), create_load_plain_s=p_set, create_load_updatable_s=t_set)
         out["model_test_layers"] = dict(group(torch, h, lay_h, a.reps, a.warmup), create_load_plain_s=p_lay, create_load_updatable_s=t_lay)
     finally:

@@ -9,10 +9,12 @@ alternately (medians and spread):
   (t)  torch              (gy.T @ x)[r, c]                       the dense rows x cols product and a gather, the only route without (g)
 Matrices: the two seeded sparse layers of examples/model_check.py (hispmv_amd.matrices.model_test_layers; created with
 set_transposable and set_value_updates on) and one dense shape, 1024 x 4096.
+--bf16: every matrix a second time with bf16 value storage (set_value_updates("any_storage")), measured in the same run beside its
+fp32 twin (rows named `... bf16`); the gradient reads no values, so what differs is the slice stride and the 8-of-16-byte meta pieces.
 `spread` is the largest (max - min) / median over the rounds of (g): a ratio closer to 1 than that is not a difference.  Prints a
 table and one JSON line, and writes the line to --out.
 
-    python tools/value_grad_bench.py [--rounds 5] [--reps 10] [--vecs 1,4,16,64] [--out profiles/value_grad_bench.json]
+    python tools/value_grad_bench.py [--rounds 5] [--reps 10] [--vecs 1,4,16,64] [--bf16] [--out profiles/value_grad_bench.json]
 """
 from __future__ import annotations
 
@@ -91,6 +93,7 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--vecs", default="1,4,16,64")
+    ap.add_argument("--bf16", action="store_true", help="also measure every matrix with bf16 value storage, in the same run")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     vecs = [int(v) for v in a.vecs.split(",")]
@@ -103,13 +106,16 @@ def main() -> None:
     todo = []
     try:
         h.set_transposable(True)
-        h.set_value_updates(True)
-        for kind, w, rows, cols, _b in M.model_test_layers()[1:]:
-            todo.append((f"sparse layer {rows} x {cols}", h.create_sparse_handle(*w, rows, cols), w[0], w[1]))
-        rows, cols = 1024, 4096
-        W = (np.random.default_rng(3).random((rows, cols), dtype=np.float32) - np.float32(0.5)) * np.float32(0.05)
-        k = np.arange(rows * cols, dtype=np.int64)
-        todo.append((f"dense {rows} x {cols}", h.create_dense_handle(W.reshape(-1), rows, cols), k // cols, k % cols))
+        h.set_value_updates("any_storage" if a.bf16 else True)
+        rows_d, cols_d = 1024, 4096
+        W = (np.random.default_rng(3).random((rows_d, cols_d), dtype=np.float32) - np.float32(0.5)) * np.float32(0.05)
+        k = np.arange(rows_d * cols_d, dtype=np.int64)
+        for storage in ("fp32", "bf16") if a.bf16 else ("fp32",):
+            h.set_value_storage(storage)
+            tag = " bf16" if storage == "bf16" else ""
+            for kind, w, rows, cols, _b in M.model_test_layers()[1:]:
+                todo.append((f"sparse layer {rows} x {cols}{tag}", h.create_sparse_handle(*w, rows, cols), w[0], w[1]))
+            todo.append((f"dense {rows_d} x {cols_d}{tag}", h.create_dense_handle(W.reshape(-1), rows_d, cols_d), k // cols_d, k % cols_d))
         assert all(q[1] >= 0 for q in todo), todo
         h.load_matrices()
         out = [measure(torch, h, name, i, r, c, B, a.rounds, a.reps) for name, i, r, c in todo for B in vecs]
