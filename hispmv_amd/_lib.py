@@ -83,6 +83,7 @@ SIGNATURES = {
     "hispmv_last_kernel_ms": (C.c_float, [_p]),
     "hispmv_batch_graph_stats": (C.c_int, [_p, C.POINTER(C.c_int64)]),
     "hispmv_batch_call_info": (C.c_int, [_p, C.POINTER(C.c_int64)]),
+    "hispmv_set_step_half": (C.c_int, [_p, C.c_int]),
     "hispmv_spmv_device_batch": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p, C.c_float, C.c_float, _p]),
     "hispmv_set_value_updates": (C.c_int, [_p, C.c_int]),
     "hispmv_update_values": (C.c_int, [_p, C.c_int, _p, C.c_int64]),

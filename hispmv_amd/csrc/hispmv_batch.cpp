@@ -214,7 +214,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
     if (c->step_kernel && shared_chip && !c->cu_split && !c->batch_graphs) {
         bool ok = true;
         size_t lds = 0;
-        bool strays = false;
+        bool strays = false, half = false;
         for (const auto& l : plan.launches) {
             if (l.kind == 4) ok = false;
             if (l.kind == 0) {
@@ -224,10 +224,11 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                     const size_t one = slice_lds_bytes(*d);
                     lds = std::max(lds, d->block_threads == 256 ? 4 * one : one);
                     strays = strays || d->has_strays;
-                    // a handle with half groups (bf16 value storage): the step kernel has no instantiation that reads them -- the call
-                    // runs as separate grids (what HISPMV_STEP_KERNEL=0 does; DESIGN.md 2.6: the candidate instantiation compiles to 128 VGPRs without
-                    // scratch, but was not measured)
-                    ok = ok && !d->has_half;
+                    // a handle with half groups (bf16 value storage): spmv_step_kernel has no body that reads them.  By default the call
+                    // runs as separate grids (what HISPMV_STEP_KERNEL=0 does); under hispmv_set_step_half / HISPMV_STEP_HALF=1 it
+                    // qualifies and the launch takes spmv_step_half_kernel (opt-in, with the measurements)
+                    ok = ok && (c->step_half || !d->has_half);
+                    half = half || d->has_half;
                 }
             }
             if (l.kind == 3) {
@@ -255,10 +256,21 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                         // CU time for the 1024-thread groups of the set), 2.5-fold for groups that gather through L2; + the window staging
                         const bool window = d.lds_floats > 0;
                         const double per_slice = window ? 0.27 : 0.68;
+                        // a HALF group (4 KiB slices): the compact figure scaled by its bytes, 4096 / 6144 = 0.18 us per slice -- a starting value,
+                        // HISPMV_STEP_COST_HALF overrides it (what was measured).  Which groups of a bf16 part are half says its
+                        // device group table (the host copy is gone after the upload); its wide groups cost what they cost in an fp32 part.
+                        static const double per_half_slice = std::getenv("HISPMV_STEP_COST_HALF") ? std::atof(std::getenv("HISPMV_STEP_COST_HALF"))
+                                                                                                  : 0.27 * (double)kHalfSliceBytes / (double)kCompactSliceBytes;
+                        std::vector<int4> gtab;
+                        if (d.has_half && d.block_threads == 1024 && ng > 0) {      // (the four-group items of a 256-thread plan are not priced by bytes)
+                            gtab.resize((size_t)ng);
+                            HIP_TRY(c, hipMemcpy(gtab.data(), d.groups, gtab.size() * sizeof(int4), hipMemcpyDeviceToHost));
+                        }
                         if (d.block_threads == 1024) {
                             for (int64_t g = 0; g < ng; ++g) {
                                 const int64_t n_here = std::min<int64_t>(d.group_slices, d.n_slices - g * d.group_slices);
-                                q[0].push_back(QItem{0u | (entry << 8), (uint32_t)g, 1.0 + per_slice * (double)n_here + (double)d.lds_floats * 4.0 / 40000.0, 0});
+                                const double ps = !gtab.empty() && (gtab[(size_t)g].w & kGroupHalf) ? per_half_slice : per_slice;
+                                q[0].push_back(QItem{0u | (entry << 8), (uint32_t)g, 1.0 + ps * (double)n_here + (double)d.lds_floats * 4.0 / 40000.0, 0});
                             }
                         } else {
                             for (int64_t g = 0; g < ng; g += 4) {
@@ -314,6 +326,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                 L.step_workgroups = (int)std::min<size_t>((size_t)W, order.size());
                 L.step_lds = lds;
                 L.step_strays = strays;
+                L.step_half = half;
                 for (const auto& l : plan.launches) L.weight += l.weight;
                 // the launches it replaces go; their device tables with them
                 std::vector<hispmv_ctx::BatchLaunch> keep;
@@ -549,7 +562,8 @@ int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float*
     std::vector<const float*> no_bias;
     if (!bias) { no_bias.assign((size_t)n, nullptr); bias = no_bias.data(); }
     // the launches of this call signature: built once, replayed afterwards (beta enters the tables; alpha is a kernel argument)
-    std::vector<uint64_t> key{(uint64_t)n, (uint64_t)__builtin_bit_cast(uint32_t, beta)};
+    // (+ the state of hispmv_set_step_half: a plan built under the other state is another plan)
+    std::vector<uint64_t> key{(uint64_t)n, (uint64_t)__builtin_bit_cast(uint32_t, beta) | (c->step_half ? 1ull << 32 : 0ull)};
     for (int i = 0; i < n; ++i) {
         key.push_back((uint64_t)idx[i]); key.push_back((uint64_t)(uintptr_t)d_x[i]);
         key.push_back((uint64_t)(uintptr_t)(beta != 0.0f ? bias[i] : nullptr)); key.push_back((uint64_t)(uintptr_t)d_y[i]);
@@ -601,7 +615,7 @@ int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float*
             }
             if (l.kind == 0) e = launch_spmv_multi(l.parts.data(), (int)l.parts.size(), l.item_tiles.data(), (int)l.item_tiles.size(), (const MultiEntry*)l.d_table, alpha, ls);
             else if (l.kind == 3) e = launch_tts_multi(l.tts.data(), (int)l.tts.size(), l.item_tiles.data(), (int)l.item_tiles.size(), (const TtsEntry*)l.d_table, alpha, ls);
-            else if (l.kind == 6) e = launch_spmv_step((const MultiEntry*)l.d_table, (const TtsEntry*)l.d_table2, l.d_items, l.n_items, l.d_sync, l.step_workgroups, l.step_lds, l.step_strays, alpha, ls);
+            else if (l.kind == 6) e = launch_spmv_step((const MultiEntry*)l.d_table, (const TtsEntry*)l.d_table2, l.d_items, l.n_items, l.d_sync, l.step_workgroups, l.step_lds, l.step_strays, l.step_half, alpha, ls);
             else if (l.kind == 4) e = launch_gemv_multi(l.gemv.data(), (int)l.gemv.size(), (const GemvEntry*)l.d_table, alpha, ls);
             else if (l.kind == 1) e = launch_fixup_multi(l.parts.data(), l.ys.data(), (int)l.parts.size(), (const MultiFixEntry*)l.d_table, alpha, ls);
             else if (l.kind == 5) {
@@ -699,6 +713,16 @@ HISPMV_API int hispmv_batch_call_info(hispmv_ctx* c, int64_t out[4]) {
     std::lock_guard<std::mutex> g(c->mu);
     if (c->last_batch[0] < 0) return fail(c, HISPMV_ESTATE, "no batch call yet");
     for (int i = 0; i < 4; ++i) out[i] = c->last_batch[i];
+    return HISPMV_OK;
+}
+
+// The switch of spmv_step_half_kernel (include/hispmv.h).  No device call: the state is part of a cached batch plan's key, so a call issued
+// after the setter finds (or builds) the plan of the new state, and the plans of the other state stay valid for the work that is in flight.
+HISPMV_API int hispmv_set_step_half(hispmv_ctx* c, int enable) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (enable != 0 && enable != 1) return fail(c, HISPMV_EINVAL, "hispmv_set_step_half: enable must be 0 or 1");
+    c->step_half = enable == 1;
     return HISPMV_OK;
 }
 

@@ -180,10 +180,11 @@ hipError_t launch_tts_multi(const TtsEntry* entries, int n, const uint8_t* item_
 // drawn by `workgroups` persistent 1024-thread workgroups.  d_items: n_items x {kind | table entry << 8, index}:
 // kind 0 = group `index` of slice_table[entry] (a 1024-thread plan), 1 = groups index .. index + 3 of a 256-thread plan, 2 = tile
 // `index` of tts_table[entry] (standard geometry, x gathered through the cache).  d_sync: two zeroed words the kernel rearms itself.
-// `strays`: some slice part has stray slots.
+// `strays`: some slice part has stray slots.  `half`: some slice part has half groups (bf16 value storage) -- the launch takes
+// spmv_step_half_kernel, whose slice items know the half, compact and wide bodies; without it, spmv_step_kernel as ever.
 struct StepArgs { const MultiEntry* slice_table; const TtsEntry* tts_table; const int2* items; unsigned* sync; unsigned n_items; float alpha; int pad, ticket_word; };
 hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_tts_table, const void* d_items, unsigned n_items,
-                            unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, float alpha, hipStream_t stream);
+                            unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, bool half, float alpha, hipStream_t stream);
 
 // Dense overlay: y = alpha*W*x + beta*bias, W row-major rows x cols.
 // bf16: W is rows x cols bfloat16 (bf16 value storage): fp32 x, products and sums; 16-byte loads of W when cols % 8 == 0.

@@ -1915,6 +1915,76 @@ __global__ __launch_bounds__(1024) void spmv_step_kernel(StepArgs args) {
         }
     }
 }
+// ... when a slice part of the call has half groups (bf16 value storage; opt-in: hispmv_set_step_half).  The same text with the HALF = 1
+// bodies in its slice items (half, compact and wide: fp32 handles share the queue with bf16 ones); tiles run the same body -- a bf16
+// tile stream keeps 32-bit slots.  A kernel of its own, neither a template parameter of spmv_step_kernel nor a shared body function:
+// calls without half groups run exactly the instantiations above (profiles/step_half_kernel_identity.txt).
+template <bool STRAYS>
+__global__ __launch_bounds__(1024) void spmv_step_half_kernel(StepArgs args) {
+    extern __shared__ float step_lds[];      // the ticket's LDS word: the last four bytes of the dynamic LDS (see spmv_step_kernel)
+    unsigned& s_next = *(unsigned*)(step_lds + args.ticket_word);
+    if (threadIdx.x == 0) s_next = __hip_atomic_fetch_add(args.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+#pragma unroll 1
+    for (;;) {
+        // nothing of the queue lives in registers across an item: the arguments are read again from the kernel-argument segment
+        typedef const __attribute__((address_space(4))) StepArgs* KernArgs;
+        KernArgs ap = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ap));
+        const StepArgs a{ap->slice_table, ap->tts_table, ap->items, ap->sync, ap->n_items, ap->alpha, 0, ap->ticket_word};
+        unsigned& s_next = *(unsigned*)(step_lds + a.ticket_word);
+        const unsigned it = s_next;
+        if (it >= a.n_items) break;
+        __syncthreads();                    // every thread has read the ticket: its slot may take the next one
+        unsigned next = 0;                  // the NEXT item's ticket is drawn first thing
+        if (threadIdx.x == 0) next = __hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int2 item = load_const(a.items + __builtin_amdgcn_readfirstlane((int)it));
+        const unsigned kind = (unsigned)__builtin_amdgcn_readfirstlane(item.x) & 3u;
+        const int entry = (int)((unsigned)__builtin_amdgcn_readfirstlane(item.x) >> 8);
+        const long long index = (long long)(unsigned)__builtin_amdgcn_readfirstlane(item.y);
+        unsigned tid = threadIdx.x;         // the thread index, opaque per item
+        asm volatile("" : "+v"(tid));
+        const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
+        WGT_BEGIN();
+        if (kind == 2) {
+            // a tile: the next ticket is parked in the LDS BEFORE the tile starts (no register to hold it across the body)
+            if (tid == 0) s_next = next;
+            const TtsEntry e = load_const(a.tts_table + entry);
+            if (e.beta != 0.0f) tts_tile_body<true>(e.m, e.x, e.bias, e.y, a.alpha, e.beta, (int)index, tid);
+            else tts_tile_body<false>(e.m, e.x, e.y, e.y, a.alpha, 0.0f, (int)index, tid);
+        } else {
+            // slice groups: the next ticket stays in flight while the item runs and is consumed behind it
+            const MultiEntry t = load_const(a.slice_table + entry);
+            const LookbackArgs lb{};
+            // kind 0: the workgroup is the group's; kind 1: four groups of a 256-thread plan, wavefronts 4q .. 4q+3 take group index + q
+            // (a sub-block past the part's last group: the empty group of slices_body -- the wide body, one barrier like the others)
+            const SubBlock sb = kind == 0 ? SubBlock{wave, 16, 0, (int)(tid & 63)} : SubBlock{wave & 3, 4, (wave >> 2) * (t.lds_floats + 4 * t.ytile_floats), (int)(tid & 63)};
+            const long long group = kind == 0 ? index : index + (wave >> 2);
+            if (t.beta != 0.0f)
+                slices_body<true, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, a.alpha, t.beta,
+                                                          t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
+            else
+                slices_body<false, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, a.alpha, 0.0f,
+                                                           t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
+            if (tid == 0) s_next = next;
+        }
+        // the item's LDS is free and the next ticket visible behind this barrier
+#ifdef HISPMV_WG_TRACE
+        WGT_END(kind == 2 ? 3 : kind == 0 ? 1 : 2, entry, index);        // (contains the barrier)
+#else
+        __syncthreads();
+#endif
+    }
+    // every workgroup draws exactly one ticket past the end; the last one out rearms the queue for the next launch
+    if (threadIdx.x == 0) {
+        unsigned* const sync = ((const __attribute__((address_space(4))) StepArgs*)__builtin_amdgcn_kernarg_segment_ptr())->sync;
+        const unsigned done = __hip_atomic_fetch_add(sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (done == gridDim.x - 1) {
+            __hip_atomic_store(sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
 
 // LDS of the NV-vector / x-in-LDS kernels: per vector the accumulators, one staging area (largest block of the matrix), 64
 // tails and -- xlds -- a copy of x
@@ -2006,7 +2076,7 @@ hipError_t launch_tts_multi(const TtsEntry* entries, int n, const uint8_t* item_
 }
 
 hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_tts_table, const void* d_items, unsigned n_items,
-                            unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, float alpha, hipStream_t stream) {
+                            unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, bool half, float alpha, hipStream_t stream) {
     clear_stale_error();
     if (n_items == 0) return hipSuccess;
     if (workgroups <= 0 || lds_bytes > kDynLdsMax) return hipErrorInvalidValue;
@@ -2015,8 +2085,9 @@ hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_t
     lds_bytes = ticket_byte + 16;
     if (lds_bytes > kLdsPerCu) return hipErrorInvalidValue;
     const StepArgs a{d_slice_table, d_tts_table, (const int2*)d_items, d_sync, n_items, alpha, 0, (int)(ticket_byte / 4)};
-    return with_bools({strays}, [&](auto STRAYS) {
-        return launch<spmv_step_kernel<STRAYS()>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
+    return with_bools({strays, half}, [&](auto STRAYS, auto HALF) {
+        if constexpr (HALF()) return launch<spmv_step_half_kernel<STRAYS()>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
+        else return launch<spmv_step_kernel<STRAYS()>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
     });
 }
 

@@ -348,3 +348,8 @@ class FpgaHandle:
         out = (C.c_int64 * 4)()
         self._check(lib.hispmv_batch_call_info(self._ctx, out))
         return {"launches": int(out[0]), "step_kernel": bool(out[1]), "items": int(out[2]), "streams": int(out[3])}
+
+    def set_step_half(self, enable: bool) -> None:
+        """Batch calls that hold a bf16 handle with half groups run through the step kernel too (hispmv_set_step_half; default off:
+        such calls run as grids).  Calls issued from now on run under the new state; the result bits are those of the grids."""
+        self._check(lib.hispmv_set_step_half(self._ctx, int(bool(enable))))

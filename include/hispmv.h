@@ -118,9 +118,22 @@ float hispmv_last_kernel_ms(hispmv_ctx* ctx);
 int hispmv_batch_graph_stats(hispmv_ctx* ctx, int64_t out[2]);
 /* How the LAST hispmv_spmv_device_batch call of this context was issued (diagnostics; bench.py names the kernels of its step from
  * it): out = {launches of the call, 1 if its slice groups and tiles ran as items of the step kernel's queue (one persistent
- * workgroup per CU, hispmv_kernels.hip: spmv_step_kernel), items of that queue, HIP streams the main launches were spread over}.
+ * workgroup per CU, hispmv_kernels.hip: spmv_step_kernel, or spmv_step_half_kernel for a call with half groups under
+ * hispmv_set_step_half), items of that queue, HIP streams the main launches were spread over}.
  * HISPMV_ESTATE before the first batch call. */
 int hispmv_batch_call_info(hispmv_ctx* ctx, int64_t out[4]);
+/* Batch calls with bf16 handles through the step kernel (opt-in, default OFF; HISPMV_STEP_HALF=1 sets the same flag when the context is
+ * created).  enable: 0 or 1; anything else, or a NULL context, is HISPMV_EINVAL (checked before any device call).
+ * OFF: a batch call that holds a part with half groups (a bf16 handle whose slice layout has compact groups, hispmv_set_value_storage)
+ * runs as separate grids on two lanes, whatever else it holds.  ON: such a call qualifies for the step kernel under the same
+ * conditions as a call of fp32 handles (HISPMV_STEP_KERNEL not 0, the call shares the chip, 1024- or 256-thread slice plans and
+ * standard tile streams, no dense handle); it is planned from the parts' batch layouts and runs hispmv_kernels.hip:
+ * spmv_step_half_kernel, whose slice items read half, compact and wide groups -- hispmv_batch_call_info then reports it like any step
+ * call.  A call WITHOUT half groups takes spmv_step_kernel in either state.  HISPMV_STEP_KERNEL=0 still wins.
+ * A batch call issued after the setter runs under the new state: the state is part of the key of the cached batch plans, so a
+ * plan built under the other state is not reused (and stays valid for work still in flight).
+ * The result bits are those of the grids: every item runs the body the grids run, on the same slices in the same order. */
+int hispmv_set_step_half(hispmv_ctx* ctx, int enable);
 
 /* n independent SpMVs y_i = alpha*A_i*x_i + beta*bias_i on loaded handles idx[i] in as few launches as possible: the
  * workgroups of all matrices with the same workgroup size share ONE grid (plus one fix-up launch), so small matrices no
