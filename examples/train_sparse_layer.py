@@ -8,7 +8,11 @@ and the SGD update  v -= lr * v.grad.  Prints the loss per step; it must fall.
 the fp32 master copy, every forward pass pushes it and the handle keeps R(v), the gradient is taken at the stored values
 (straight-through).  The final losses of the two runs are printed side by side; no threshold is applied to their difference.
 
+--companion creates the layer under set_transposable("companion"): the handle stores its transpose as well, grad_x runs the forward
+kernels over it (no atomics), and two runs print the same losses bit for bit.  companion_info says what the second copy costs.
+
     python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1] [--bf16]
+                                          [--companion]
 """
 from __future__ import annotations
 
@@ -30,12 +34,15 @@ def train(a, r, c, start, teacher, storage: str) -> list:
 
     h = pyhispmv.FpgaHandle("train.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
     try:
-        h.set_transposable(True)          # the backward pass needs the slice stream
+        # the backward pass needs the slice stream -- or, --companion, runs over a stored transpose and keeps the loader's own format
+        h.set_transposable("companion" if a.companion else True)
         h.set_value_storage(storage)
         h.set_value_updates("any_storage" if storage == "bf16" else True)         # ... and the value map
         i = h.create_sparse_handle(r, c, start, a.rows, a.cols)
         assert i >= 0
         h.load_matrices()
+        if a.companion:
+            print(f"[{storage}] companion_info: {h.companion_info(i)} (the handle: {h.matrix_info(i)['device_bytes']} device bytes in all)")
         dev = torch.device("cuda", 0)
         gen = torch.Generator(device=dev).manual_seed(0)
         x = torch.randn((a.batch, a.cols), dtype=torch.float32, device=dev, generator=gen)
@@ -75,6 +82,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--bf16", action="store_true", help="train a second time on a bf16 handle and print both final losses")
+    ap.add_argument("--companion", action="store_true", help="store the transpose with the handle: a deterministic backward pass, for its bytes")
     a = ap.parse_args()
 
     rng = np.random.default_rng(0)

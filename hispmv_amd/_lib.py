@@ -33,6 +33,7 @@ HISPMV_VALUE_UPDATES_ANY_STORAGE = 2
 HISPMV_TRANSPOSABLE_OFF = 0
 HISPMV_TRANSPOSABLE_SLICES = 1
 HISPMV_TRANSPOSABLE_KEEP_FORMAT = 2
+HISPMV_TRANSPOSABLE_COMPANION = 3
 
 
 class MatrixInfo(C.Structure):
@@ -95,6 +96,7 @@ SIGNATURES = {
     "hispmv_spmv_device_t": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, _p]),
     "hispmv_set_transposable": (C.c_int, [_p, C.c_int]),
     "hispmv_transpose_info": (C.c_int, [_p, C.c_int, _i64p]),
+    "hispmv_companion_info": (C.c_int, [_p, C.c_int, _i64p]),
     "hispmv_linear_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, _p, C.c_float, C.c_float, _p]),
     "hispmv_linear_device_t": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, _p, C.c_float, C.c_float, _p]),
     "hispmv_linear_info": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
@@ -114,6 +116,7 @@ SIGNATURES = {
     "hispmv_prep_choose_format": (C.c_int, [_p, C.c_int, _i64p]),
     "hispmv_prep_step_queue": (C.c_int, [_p, C.c_int32, _p, C.c_int32, C.c_int32, C.c_int32, _p, _p]),
     "hispmv_prep_window_membership": (C.c_int, [_p, C.c_int, C.c_void_p]),
+    "hispmv_prep_swapped_coo_from_csr": (C.c_int, [_p, _p, C.c_int32, _p, _p]),
     "hispmv_prep_apply_plan": (C.c_int, [_p, C.c_int, _i64p]),
     "hispmv_prep_groups": (_i32p, [_p]),
     "hispmv_prep_device_stream": (C.c_int, [_p, _i64p]),

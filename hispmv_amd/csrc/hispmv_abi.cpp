@@ -49,6 +49,7 @@ void free_matrix_device(Matrix& m) {
     for (auto& p : m.parts) p.dev = SpmvDeviceMatrix{};
     m.d_dense = nullptr; m.d_ypart = nullptr; m.d_fix_of_row = nullptr; m.d_map = nullptr; m.d_upd_table = nullptr;
     m.loaded = false;
+    if (m.companion) free_matrix_device(*m.companion);
 }
 
 int ensure_vec(hispmv_ctx* c, float** p, int64_t* cap, int64_t n) {
@@ -104,7 +105,9 @@ int check_storage_and_updates(hispmv_ctx* c) {
 // "offset + size > MAX_BUFFER_SIZE_BYTES -> return -1", fpga_handle.cpp:192-195).  The format and tiling decision itself is
 // host-only code: choose_format (hispmv_choose.cpp).
 // real_values (updatable handles): the creation input's values in input order; csr then holds their index payloads.
-int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = nullptr, std::vector<float>* real_values = nullptr) {
+// make_sparse prepares the matrix and counts its bytes, register_sparse charges the arena and lists it -- with its stored transpose
+// (`companion`: made from the swapped input, Matrix::companion), when there is one, as ONE capacity check on the sum.
+std::unique_ptr<Matrix> make_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt, const std::vector<float>* real_values, bool companion) {
     auto t0 = std::chrono::steady_clock::now();
     // HISPMV_PREP_TRACE=1: the phases of the host side of preprocessing on stderr (diagnostics)
     static const bool trace = std::getenv("HISPMV_PREP_TRACE") != nullptr;
@@ -123,7 +126,9 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
     opts.half_values = c->value_storage == HISPMV_VALUES_BF16;      // (the values are rounded already: add_from_coo, _from_csr)
     opts.index_payloads = opts.half_values && real_values;          // ... or are index payloads: every part keeps its chunks of the map on the host
     if (c->transposable == HISPMV_TRANSPOSABLE_SLICES) opts.format_mode = 0;      // hispmv_set_transposable: keep the slice stream, as HISPMV_FORMAT=slices does
-    m->keep_format = c->transposable == HISPMV_TRANSPOSABLE_KEEP_FORMAT;          // ... or the loader's own choice, a tile stream then marked as accepted
+    // ... or the loader's own choice, a tile stream then marked as accepted (_COMPANION: the same, the stored transpose besides)
+    m->keep_format = !companion && (c->transposable == HISPMV_TRANSPOSABLE_KEEP_FORMAT || c->transposable == HISPMV_TRANSPOSABLE_COMPANION);
+    if (companion) opts.batch_layout = false;      // only step-kernel calls read a batch layout, and a companion is never part of one
     m->value_storage = c->value_storage;
     FormatChoice ch = choose_format(std::move(csr), prebuilt, c->n_cus, opts, lap);
     m->format = ch.format; m->tile_kind = ch.tile_kind; m->col_tile_width = ch.col_tile_width; m->col_tile_base = ch.col_tile_base;
@@ -170,12 +175,25 @@ int add_sparse(hispmv_ctx* c, Csr&& csr, double t_csr, SliceStream* prebuilt = n
         m->plan_threads = m->parts[0].plan.block_threads; m->plan_group = m->parts[0].plan.group_slices; m->plan_lds = m->parts[0].plan.lds_floats;
     }
     m->prep_seconds = t_csr + std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return m;
+}
+int register_sparse(hispmv_ctx* c, std::unique_ptr<Matrix> m, std::unique_ptr<Matrix> companion, std::vector<float>* real_values) {
+    if (companion) { m->device_bytes += companion->device_bytes; m->prep_seconds += companion->prep_seconds; }
     if (c->arena_used + m->device_bytes > c->arena_budget) return HISPMV_FULL;
+    if (real_values && companion) companion->upd_values = *real_values;      // (each load gathers the creation values into its own layouts)
     if (real_values) m->upd_values = std::move(*real_values);
     c->arena_used += m->device_bytes;
     m->index = (int)c->mats.size();
+    if (companion) { companion->index = kCompanionId + m->index; m->companion = std::move(companion); }
     c->mats.push_back(std::move(m));
     return (int)c->mats.size() - 1;
+}
+// Creation in state HISPMV_TRANSPOSABLE_COMPANION: the rule of check_updatable -- the forward launches of a stored transpose are those of
+// the standard tile geometry.
+int check_companion(hispmv_ctx* c) {
+    if (c->transposable == HISPMV_TRANSPOSABLE_COMPANION && (c->format_opts.tts_geometry != 0 || c->format_opts.tts_small))
+        return fail(c, HISPMV_EINVAL, "set_transposable(companion): not supported with HISPMV_TTS_GEOMETRY other than standard or HISPMV_TTS_SMALL (experiments)");
+    return HISPMV_OK;
 }
 
 // The load's part of value updates, once the layouts of `m` are on the device (packed with index payloads): the chunk table, the
@@ -280,10 +298,11 @@ void transpose_costs(Matrix& m, const HostPart& p, const SpmvDeviceMatrix& d) {
 int launch_matrix(hispmv_ctx* c, Matrix& m, const float* d_x, const float* d_bias, float* d_y,
                   float alpha, float beta, hipStream_t s, bool fixup_only = false) {
     if (!m.dense && (m.parts.size() > 1 || (m.format == 1 && m.parts[0].tdev.zero_fill)) && m.index >= 0) {
+        // (a stored transpose goes the same way under its internal id, hispmv_ctx::matrix: the bits of a handle made from the swapped input)
         // column tiles: all of them in ONE grid (+ one fix-up, one merge launch) through the batch machinery -- launched
         // one after the other each tile had the chip to itself for half the work (mouse_gene 48 -> 40 us)
         const int32_t idx = m.index;
-        return spmv_batch_locked(c, 1, &idx, &d_x, &d_bias, &d_y, alpha, beta, s);
+        return spmv_batch_locked(c, 1, &idx, &d_x, &d_bias, &d_y, alpha, beta, s, idx >= kCompanionId);
     }
     if (m.dense) {
         hipError_t e = launch_gemv(m.d_dense, m.rows, m.cols, d_x, d_bias, d_y, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
@@ -502,13 +521,32 @@ HISPMV_API int hispmv_set_arena_bytes(hispmv_ctx* c, int64_t bytes) {
 }
 HISPMV_API int64_t hispmv_arena_bytes_used(const hispmv_ctx* c) { return c ? c->arena_used : 0; }
 
-// COO -> handle, on the device or on the host (hispmv_ctx::prep_mode)
+// COO -> prepared matrix, on the device or on the host (hispmv_ctx::prep_mode); `v` as the packers take it (rounded, or index payloads)
+static int make_from_coo(hispmv_ctx* c, int32_t rows, int32_t cols, int64_t nnz, const int32_t* r, const int32_t* cl, const float* v,
+                         std::chrono::steady_clock::time_point t0, const std::vector<float>* real_values, bool companion, std::unique_ptr<Matrix>& out) {
+    const bool on_device = c->prep_mode == 1 || (c->prep_mode == 2 && nnz >= (2 << 20));
+    if (on_device) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        Csr csr; SliceStream st; std::string err;
+        if (!prep_on_device(rows, cols, nnz, r, cl, v, csr, st, c->last_prep_times, err))
+            return fail(c, err.find("outside") != std::string::npos || err.find("dimension") != std::string::npos ? HISPMV_EINVAL : HISPMV_EDEVICE, err);
+        double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        out = make_sparse(c, std::move(csr), t, &st, real_values, companion);
+        return HISPMV_OK;
+    }
+    Csr csr = coo_to_csr(rows, cols, nnz, r, cl, v);
+    double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    out = make_sparse(c, std::move(csr), t, nullptr, real_values, companion);
+    return HISPMV_OK;
+}
+
+// COO -> handle (and, in state HISPMV_TRANSPOSABLE_COMPANION, its stored transpose)
 static int add_from_coo(hispmv_ctx* c, int32_t rows, int32_t cols, int64_t nnz, const int32_t* r, const int32_t* cl, const float* v) {
     auto t0 = std::chrono::steady_clock::now();
-    const bool on_device = c->prep_mode == 1 || (c->prep_mode == 2 && nnz >= (2 << 20));
     std::vector<float> real, payloads, rounded;
     {
-        const int rc = check_storage_and_updates(c);
+        int rc = check_storage_and_updates(c);
+        if (rc == HISPMV_OK) rc = check_companion(c);
         if (rc != HISPMV_OK) return rc;
     }
     if (c->value_storage == HISPMV_VALUES_BF16) {      // rounded once, here: the host and the device preprocessor see R(v)
@@ -524,17 +562,13 @@ static int add_from_coo(hispmv_ctx* c, int32_t rows, int32_t cols, int64_t nnz, 
         v = payloads.data();
     }
     std::vector<float>* const real_values = c->value_updates ? &real : nullptr;
-    if (on_device) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        Csr csr; SliceStream st; std::string err;
-        if (!prep_on_device(rows, cols, nnz, r, cl, v, csr, st, c->last_prep_times, err))
-            return fail(c, err.find("outside") != std::string::npos || err.find("dimension") != std::string::npos ? HISPMV_EINVAL : HISPMV_EDEVICE, err);
-        double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return add_sparse(c, std::move(csr), t, &st, real_values);
-    }
-    Csr csr = coo_to_csr(rows, cols, nnz, r, cl, v);
-    double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return add_sparse(c, std::move(csr), t, nullptr, real_values);
+    std::unique_ptr<Matrix> m, companion;
+    int rc = make_from_coo(c, rows, cols, nnz, r, cl, v, t0, real_values, false, m);
+    // the stored transpose: the swapped input, the same values (rounded, or index payloads) in the same order
+    if (rc == HISPMV_OK && c->transposable == HISPMV_TRANSPOSABLE_COMPANION)
+        rc = make_from_coo(c, cols, rows, nnz, cl, r, v, std::chrono::steady_clock::now(), real_values, true, companion);
+    if (rc != HISPMV_OK) return rc;
+    return register_sparse(c, std::move(m), std::move(companion), real_values);
 }
 
 HISPMV_API int hispmv_create_sparse_handle(hispmv_ctx* c, const int32_t* r, const int32_t* cl, const float* v,
@@ -583,7 +617,8 @@ HISPMV_API int hispmv_create_sparse_handle_from_csr(hispmv_ctx* c, const int32_t
         if (nnz > 0 && (!ci || !va)) return fail(c, HISPMV_EINVAL, "col_idx / values are NULL");
         std::vector<float> real;
         {
-            const int rc = check_storage_and_updates(c);
+            int rc = check_storage_and_updates(c);
+            if (rc == HISPMV_OK) rc = check_companion(c);
             if (rc != HISPMV_OK) return rc;
         }
         if (c->value_updates) {
@@ -595,9 +630,23 @@ HISPMV_API int hispmv_create_sparse_handle_from_csr(hispmv_ctx* c, const int32_t
         else csr.val.assign(va, va + nnz);
         if (c->value_storage == HISPMV_VALUES_BF16 && !c->value_updates) round_values_to_bf16(csr.val.data(), csr.val.data(), nnz);      // (payloads stay whole; the load's update rounds the real values)
         for (int64_t k = 0; k < nnz; ++k) if (ci[k] < 0 || ci[k] >= cols) return fail(c, HISPMV_EINVAL, "CSR column outside matrix");
+        std::vector<float>* const real_values = c->value_updates ? &real : nullptr;
+        // the stored transpose: the swapped COO in input order -- row_ptr expanded BEFORE the per-row sort, so that entry k is entry k
+        // of the value order -- with the values as the packers take them (rounded, or index payloads)
+        std::unique_ptr<Matrix> companion;
+        const double t_own = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (c->transposable == HISPMV_TRANSPOSABLE_COMPANION) {
+            const auto tc = std::chrono::steady_clock::now();
+            std::vector<int32_t> entry_rows((size_t)nnz);
+            csr_entry_rows(rows, rp, entry_rows.data());
+            const std::vector<float> vals(csr.val.begin(), csr.val.end());
+            const int rc = make_from_coo(c, cols, rows, nnz, ci, entry_rows.data(), vals.data(), tc, real_values, true, companion);
+            if (rc != HISPMV_OK) return rc;
+        }
+        const auto t1 = std::chrono::steady_clock::now();      // (the companion's time is in its own prep_seconds)
         sort_rows_by_column(csr);     // rows with unsorted columns (scipy: has_sorted_indices == False) are sorted, stably
-        double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return add_sparse(c, std::move(csr), t, nullptr, c->value_updates ? &real : nullptr);
+        double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() + t_own;
+        return register_sparse(c, make_sparse(c, std::move(csr), t, nullptr, real_values, false), std::move(companion), real_values);
     } catch (const std::bad_alloc&) { return fail(c, HISPMV_ENOMEM, "host out of memory");
     } catch (const std::exception& ex) { return fail(c, HISPMV_EINVAL, ex.what()); }
 }
@@ -642,288 +691,296 @@ HISPMV_API int hispmv_create_dense_handle(hispmv_ctx* c, const float* vals, int3
     } catch (const std::bad_alloc&) { return fail(c, HISPMV_ENOMEM, "host out of memory"); }
 }
 
+// Uploads one prepared matrix (a handle, or the stored transpose of one) and releases its host tables.
+static int load_matrix(hispmv_ctx* c, Matrix& m) {
+    if (m.loaded) return HISPMV_OK;
+    int rc;
+    // (scratch of the device layout -- the uploaded host words of the parts --, freed once the stream has drained, also on an error return)
+    struct Scratch { std::vector<void*> v; void push_back(void* p) { v.push_back(p); } ~Scratch() { for (void* p : v) (void)hipFree(p); } } layout_scratch;
+    std::vector<std::vector<int32_t>> tts_fix_rows;       // tile streams: the rows cut into pieces, per part (fix list order)
+    // value updates: the value regions of every part and the sizes of its layouts, while the host tables exist
+    std::vector<std::vector<ValueChunk>> value_regions;
+    std::vector<std::pair<int64_t, int64_t>> layout_bytes;
+    if (m.updatable && !m.dense)
+        for (const Matrix::Part& p : m.parts) {
+            value_regions.push_back(value_chunks(p));
+            layout_bytes.emplace_back(p.is_tts ? (int64_t)p.tts.words.size() : p.dstream.n_bytes, p.has_batch_layout ? p.batch_dstream.n_bytes : 0);
+        }
+    if (m.dense && m.value_storage == HISPMV_VALUES_BF16 && m.updatable) {
+        // W is written by the update kernel from the fp32 creation values, staged in the context's update buffer
+        void* d = nullptr;
+        HIP_TRY(c, hipMalloc(&d, (size_t)m.nnz * 2));
+        m.allocs.push_back(d);
+        m.d_dense = (float*)d;
+        if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, m.nnz)) != HISPMV_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_upd, m.dense_host.data(), (size_t)m.nnz * 4, hipMemcpyHostToDevice, c->stream));
+        const hipError_t e = launch_update_dense_bf16((uint16_t*)d, c->d_upd, m.nnz, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "launch_update_dense_bf16");
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (m.dense && m.value_storage == HISPMV_VALUES_BF16) {
+        const uint16_t* d = nullptr;
+        if ((rc = upload(c, m, m.dense_host16.data(), m.dense_host16.size(), &d)) != HISPMV_OK) return rc;
+        m.d_dense = (float*)const_cast<uint16_t*>(d);      // (rows x cols bf16: every launch of this handle passes its storage along)
+    } else if (m.dense) {
+        const float* d = nullptr;
+        if ((rc = upload(c, m, m.dense_host.data(), m.dense_host.size(), &d)) != HISPMV_OK) return rc;
+        m.d_dense = const_cast<float*>(d);
+    } else if (m.format == 1) {
+      for (Matrix::Part& p : m.parts) {
+        TtsStream& ts = p.tts;
+        tts_fix_rows.emplace_back();
+        for (size_t k = 0; k + 3 < ts.fix.size(); k += 4) tts_fix_rows.back().push_back(ts.fix[k]);
+        const uint8_t* dw = nullptr; const int32_t* dcb = nullptr; const uint16_t* dfl = nullptr; const int32_t* dci = nullptr;
+        const TtsTile* dt = nullptr; const TtsBlock* db = nullptr;
+        if ((rc = upload(c, m, ts.words.data(), ts.words.size(), &dw)) != HISPMV_OK) return rc;
+        if ((rc = upload(c, m, ts.col_base.data(), ts.col_base.size(), &dcb)) != HISPMV_OK) return rc;
+        if ((rc = upload(c, m, ts.flags.data(), ts.flags.size(), &dfl)) != HISPMV_OK) return rc;
+        const uint16_t* dfh = nullptr;
+        std::vector<uint32_t> planes;          // gap-coded row ends: both planes of the codes in one word per lane and chunk
+        if (!ts.flags_hi.empty()) {
+            planes.resize(ts.flags.size());
+            for (size_t q = 0; q < planes.size(); ++q) planes[q] = (uint32_t)ts.flags[q] | ((uint32_t)ts.flags_hi[q] << 16);
+            const uint32_t* dp = nullptr;
+            if ((rc = upload(c, m, planes.data(), planes.size(), &dp)) != HISPMV_OK) return rc;
+            HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`planes` is a local)
+            dfh = (const uint16_t*)dp;
+        }
+        if ((rc = upload(c, m, ts.chunk_info.data(), ts.chunk_info.size(), &dci)) != HISPMV_OK) return rc;
+        if ((rc = upload(c, m, ts.tiles.data(), ts.tiles.size(), &dt)) != HISPMV_OK) return rc;
+        if ((rc = upload(c, m, ts.blocks.data(), ts.blocks.size(), &db)) != HISPMV_OK) return rc;
+        TtsDeviceMatrix& d = p.tdev;
+        d.words = dw; d.col_base = dcb; d.flags = dfl; d.flags_hi = dfh; d.chunk_info = (const int2*)dci; d.tiles = (const int4*)dt; d.blocks = (const int4*)db;
+        d.n_tiles = (int32_t)ts.tiles.size(); d.rows = m.rows; d.cols = m.cols;
+        if (!ts.fix.empty()) {       // rows cut into pieces: carry slots + the slice stream's fix-up entries
+            const int32_t* dfix = nullptr;
+            if ((rc = upload(c, m, ts.fix.data(), ts.fix.size(), &dfix)) != HISPMV_OK) return rc;
+            void* carry = nullptr;
+            HIP_TRY(c, hipMalloc(&carry, (size_t)std::max(ts.n_carry, 1) * kTtsMaxVectors * sizeof(float)));      // one set per vector of a batched launch
+            m.allocs.push_back(carry);
+            HIP_TRY(c, hipMemsetAsync(carry, 0, (size_t)std::max(ts.n_carry, 1) * kTtsMaxVectors * sizeof(float), c->stream));
+            d.n_carry = ts.n_carry;
+            d.fix = (const int4*)dfix; d.n_fix = (int32_t)(ts.fix.size() / 4); d.carry = (float*)carry;
+            // (the same three fields where the multi-matrix fix-up launch looks for them)
+            p.dev.fix_short = d.fix; p.dev.n_fix_short = d.n_fix; p.dev.carry = d.carry; p.dev.n_fix_long = 0;
+        }
+        d.acc_floats = (ts.max_rows + 63) & ~63; d.threads = ts.geometry.threads;
+        d.zero_fill = ts.geometry.zero_fill ? 1 : ts.geometry.gap_rows ? 2 : 0;
+        d.staging_floats = ts.geometry.max_slots + 64;        // (the dummy slot of padding words sits behind the last real one)
+        d.batch_stage_floats = ((ts.max_slots + kTtsChunk - 1) / kTtsChunk) * kTtsChunk + 64;
+        // x in the LDS for short x (HISPMV_TTS_XLDS=1; off by default -- measured slower on the 1024 x 8192 layer of
+        // apps/model_test.py: 16.7 against 15.1 us alone, 8 vectors 74 against 58 us: that layer's tiles are latency chains
+        // of 8 K elements, not gather-bound)
+        d.xlds_floats = (m.cols <= kTtsXldsMax && std::getenv("HISPMV_TTS_XLDS")) ? ((m.cols + 63) & ~63) : 0;
+        if (tts_tile_lds_bytes(d) > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: tile stream exceeds the LDS of a CU");
+        // a transposed call (hispmv_tts_transpose.h): one launch, one float atomic per stored word that is neither filler nor padding
+        // (an upper bound: explicit zeros among them add nothing at run time)
+        m.t_launches += 1; m.t_direct += ts.nnz; m.t_atomic_bytes += 4 * ts.nnz;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        p.tts = TtsStream{};
+      }
+    } else {
+        for (auto& p : m.parts) {
+            const uint8_t* dw = nullptr; const SliceHdr* dh = nullptr; const FixEntry *fs = nullptr, *fl = nullptr;
+            const int32_t* dg = nullptr; const Frag* dfr = nullptr;
+            const int64_t ns = p.st.n_slices;
+            if ((rc = upload(c, m, p.dstream.groups.data(), p.dstream.groups.size(), &dg)) != HISPMV_OK) return rc;
+            if ((rc = upload(c, m, p.plan.frags.data(), p.plan.frags.size(), &dfr)) != HISPMV_OK) return rc;
+            // the slices in their device layout: packed on the host (HISPMV_LAYOUT=host) or laid out HERE from the uploaded host words
+            const bool lay_out = p.dstream.bytes.empty() && p.dstream.n_bytes > 0;
+            uint64_t* d_host_words = nullptr;
+            if (!lay_out) {
+                if ((rc = upload(c, m, p.dstream.bytes.data(), p.dstream.bytes.size(), &dw)) != HISPMV_OK) return rc;
+            } else {
+                if ((int64_t)p.st.words.size() != ns * kSliceElems) return fail(c, HISPMV_EINVAL, "internal: host words missing for the device layout");
+                void* blk = nullptr;
+                HIP_TRY(c, hipMalloc(&blk, (size_t)p.dstream.n_bytes));
+                m.allocs.push_back(blk);
+                dw = (const uint8_t*)blk;
+                HIP_TRY(c, hipMalloc((void**)&d_host_words, p.st.words.size() * sizeof(uint64_t)));
+                layout_scratch.push_back(d_host_words);
+                HIP_TRY(c, hipMemcpyAsync(d_host_words, p.st.words.data(), p.st.words.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+            }
+            // device header: {row_base, chain_len, rows ending in the slice, 1 if some of its elements lie outside
+            // the group's x window} (the column window of a slice is only needed by the planner)
+            std::vector<SliceHdr>& hh = p.st.hdr;
+            int max_rows = 1;
+            for (int64_t sl = 0; sl < ns; ++sl) {
+                const int nr = (sl + 1 < ns ? hh[sl + 1].row_base : m.rows) - hh[sl].row_base;
+                hh[sl].x_base = nr;
+                hh[sl].x_span = (!p.plan.slice_spills.empty() && p.plan.slice_spills[(size_t)sl]) ? 1 : 0;
+                max_rows = std::max(max_rows, nr);
+            }
+            uint32_t* d_stray_cols = nullptr;
+            if (!p.dstream.any_stray) {
+                if ((rc = upload(c, m, hh.data(), hh.size(), &dh)) != HISPMV_OK) return rc;
+            } else if (lay_out) {
+                void* blk = nullptr;
+                const size_t hb = hh.size() * sizeof(SliceHdr), sb = (size_t)ns * kStraySlots * sizeof(uint32_t);
+                HIP_TRY(c, hipMalloc(&blk, hb + sb));
+                m.allocs.push_back(blk);
+                HIP_TRY(c, hipMemcpyAsync(blk, hh.data(), hb, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(c, hipMemsetAsync((char*)blk + hb, 0xff, sb, c->stream));        // 0xffffffff = no stray
+                dh = (const SliceHdr*)blk;
+                d_stray_cols = (uint32_t*)((char*)blk + hb);
+            } else {
+                // stray slots: the columns of every slice's strays (64 x u32 per slice) live BEHIND the headers in one
+                // allocation -- the kernels reach them as hdr + n_slices, no further pointer to carry around
+                void* blk = nullptr;
+                const size_t hb = hh.size() * sizeof(SliceHdr), sb = p.dstream.stray_cols.size() * sizeof(uint32_t);
+                HIP_TRY(c, hipMalloc(&blk, hb + sb));
+                m.allocs.push_back(blk);
+                HIP_TRY(c, hipMemcpyAsync(blk, hh.data(), hb, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync((char*)blk + hb, p.dstream.stray_cols.data(), sb, hipMemcpyHostToDevice, c->stream));
+                dh = (const SliceHdr*)blk;
+            }
+            if (lay_out) {
+                const int e = layout_on_device(d_host_words, ns, p.plan.group_slices, dg, p.plan.lds_floats, p.plan.block_threads / 64,
+                                               (uint8_t*)dw, d_stray_cols, c->stream);
+                if (e != 0) return hip_fail(c, (hipError_t)e, "layout_on_device");
+            }
+            if ((rc = upload(c, m, p.fix_short.data(), p.fix_short.size(), &fs)) != HISPMV_OK) return rc;
+            if ((rc = upload(c, m, p.fix_long.data(), p.fix_long.size(), &fl)) != HISPMV_OK) return rc;
+            // carry per slice; {carry, launch tag} granules and the group ticket of the look-back variant
+            void *carry = nullptr, *gran = nullptr, *ticket = nullptr;
+            const size_t n1 = (size_t)std::max<int64_t>(ns, 1);
+            HIP_TRY(c, hipMalloc(&carry, n1 * kMaxBatch * sizeof(float)));      // one set per vector of a batched pass
+            m.allocs.push_back(carry);
+            HIP_TRY(c, hipMemsetAsync(carry, 0, n1 * kMaxBatch * sizeof(float), c->stream));
+            HIP_TRY(c, hipMalloc(&gran, n1 * sizeof(unsigned long long)));
+            m.allocs.push_back(gran);
+            HIP_TRY(c, hipMemsetAsync(gran, 0, n1 * sizeof(unsigned long long), c->stream));
+            HIP_TRY(c, hipMalloc(&ticket, sizeof(unsigned long long)));
+            m.allocs.push_back(ticket);
+            HIP_TRY(c, hipMemsetAsync(ticket, 0, sizeof(unsigned long long), c->stream));
+            SpmvDeviceMatrix& d = p.dev;
+            d.words = dw; d.hdr = (const int4*)dh; d.groups = (const int4*)dg; d.frags = (const int4*)dfr;
+            d.fix_short = (const int4*)fs; d.fix_long = (const int4*)fl;
+            d.carry = (float*)carry; d.gran = (unsigned long long*)gran; d.ticket = (unsigned long long*)ticket;
+            d.err = c->d_err; d.launches = 0; d.ticket_launches = 0;
+            d.n_slices = ns; d.n_groups = (ns + p.plan.group_slices - 1) / p.plan.group_slices;
+            d.group_slices = p.plan.group_slices; d.block_threads = p.plan.block_threads;
+            d.lds_floats = p.plan.lds_floats + p.dstream.stray_floats;        // the x window + the wavefronts' stray areas behind it
+            d.ytile_floats = std::min(kSliceElems, (max_rows + 63) & ~63);
+            const size_t lds_plain = slice_lds_bytes(d);
+            if (lds_plain > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: launch plan exceeds the LDS of a CU");
+            const bool mailbox_fits = slice_lds_bytes(d, 1, true) <= kDynLdsMax;
+            d.n_fix_short = (int32_t)p.fix_short.size(); d.n_fix_long = (int32_t)p.fix_long.size();
+            d.rows = m.rows; d.cols = m.cols;
+            // co-residency of the whole grid: workgroups per CU by LDS and waves (conservative: <= 4 blocks,
+            // <= 16 waves per CU; MI355X_MICROARCH.md "Residency")
+            const int lds_b = std::max(1, (int)lds_plain + 64);
+            const int per_cu = std::max(1, std::min({4, kLdsPerCu / lds_b, 16 / (d.block_threads / 64)}));
+            const bool resident = d.n_groups <= (int64_t)c->n_cus * per_cu;
+            const bool one_round = d.group_slices <= d.block_threads / 64;
+            // carry_mode: 0 fix-up launch; 1 look-back for every plan, workgroups in blockIdx order (relies on the
+            // dispatcher starting workgroups in increasing id order -- observed, not contractual; the wait is
+            // bounded and reports instead of hanging); 3 the same with start-order tickets (contract-safe);
+            // 2 (auto) look-back when the whole grid is co-resident (every workgroup is running, so waiting for an
+            // earlier slice cannot deadlock) AND every wavefront has one slice (small matrices, where the second
+            // launch costs as much as the kernel), fix-up otherwise; 5 ("resident") look-back for every co-resident
+            // grid: correct, but measured slower than main kernel + fix-up launch on the large matrices
+            // (PFlow_742 71.6 vs 65.2 us, TSOPF 35.5 vs 33.6: wavefronts that run ahead wait for slower neighbours)
+            d.lookback = (c->carry_mode == 1 || c->carry_mode == 3 || (c->carry_mode == 2 && resident && one_round) ||
+                          (c->carry_mode == 5 && resident)) && mailbox_fits;
+            d.use_ticket = c->carry_mode == 3;
+            if (m.parts.size() > 1) { d.lookback = false; d.use_ticket = false; }      // column tiles share one grid: fix-up launch
+            // stray slots: the packer placed every slice's strays by the slice's position in the ROTATED walk of the fix-up
+            // variant; the look-back variant walks its groups in slice order
+            d.has_strays = p.dstream.stray_floats > 0;
+            d.has_half = p.dstream.half_values && p.dstream.compact_slices > 0;
+            if (d.has_strays) { d.lookback = false; d.use_ticket = false; }
+            transpose_costs(m, p, d);
+            // the batch layout (hispmv_choose.h): its own group table, fragments, slice bytes and headers (the spill flags differ);
+            // rows, carries, fix lists and the error word are the part's
+            if (p.has_batch_layout) {
+                SpmvDeviceMatrix b = d;
+                const int32_t* bg = nullptr; const Frag* bf = nullptr; const uint8_t* bw = nullptr; const SliceHdr* bh = nullptr;
+                if ((rc = upload(c, m, p.batch_dstream.groups.data(), p.batch_dstream.groups.size(), &bg)) != HISPMV_OK) return rc;
+                if ((rc = upload(c, m, p.batch_plan.frags.data(), p.batch_plan.frags.size(), &bf)) != HISPMV_OK) return rc;
+                std::vector<SliceHdr> bhh = hh;
+                for (int64_t sl = 0; sl < ns; ++sl) bhh[(size_t)sl].x_span = (!p.batch_plan.slice_spills.empty() && p.batch_plan.slice_spills[(size_t)sl]) ? 1 : 0;
+                uint32_t* b_stray = nullptr;
+                {
+                    void* blk = nullptr;
+                    const size_t hb = bhh.size() * sizeof(SliceHdr), sb = p.batch_dstream.any_stray ? (size_t)ns * kStraySlots * sizeof(uint32_t) : 0;
+                    HIP_TRY(c, hipMalloc(&blk, hb + sb));
+                    m.allocs.push_back(blk);
+                    HIP_TRY(c, hipMemcpy(blk, bhh.data(), hb, hipMemcpyHostToDevice));            // (`bhh` is a local: synchronous)
+                    if (sb && !p.batch_dstream.stray_cols.empty()) HIP_TRY(c, hipMemcpy((char*)blk + hb, p.batch_dstream.stray_cols.data(), sb, hipMemcpyHostToDevice));
+                    else if (sb) HIP_TRY(c, hipMemsetAsync((char*)blk + hb, 0xff, sb, c->stream));
+                    bh = (const SliceHdr*)blk;
+                    b_stray = sb ? (uint32_t*)((char*)blk + hb) : nullptr;
+                }
+                if (!p.batch_dstream.bytes.empty()) {
+                    if ((rc = upload(c, m, p.batch_dstream.bytes.data(), p.batch_dstream.bytes.size(), &bw)) != HISPMV_OK) return rc;
+                } else {
+                    void* blk = nullptr; uint64_t* tmp = nullptr;
+                    HIP_TRY(c, hipMalloc(&blk, (size_t)p.batch_dstream.n_bytes));
+                    m.allocs.push_back(blk);
+                    bw = (const uint8_t*)blk;
+                    HIP_TRY(c, hipMalloc((void**)&tmp, p.batch_words.size() * sizeof(uint64_t)));
+                    layout_scratch.push_back(tmp);
+                    HIP_TRY(c, hipMemcpyAsync(tmp, p.batch_words.data(), p.batch_words.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+                    const int e = layout_on_device(tmp, ns, p.batch_plan.group_slices, bg, p.batch_plan.lds_floats, p.batch_plan.block_threads / 64, (uint8_t*)blk, b_stray, c->stream);
+                    if (e != 0) return hip_fail(c, (hipError_t)e, "layout_on_device");
+                }
+                b.words = bw; b.hdr = (const int4*)bh; b.groups = (const int4*)bg; b.frags = (const int4*)bf;
+                b.group_slices = p.batch_plan.group_slices; b.n_groups = (ns + p.batch_plan.group_slices - 1) / p.batch_plan.group_slices;
+                b.lds_floats = p.batch_plan.lds_floats + p.batch_dstream.stray_floats;
+                b.has_strays = p.batch_dstream.stray_floats > 0;
+                b.has_half = p.batch_dstream.half_values && p.batch_dstream.compact_slices > 0;
+                b.lookback = false; b.use_ticket = false;
+                if (slice_lds_bytes(b) <= kDynLdsMax) { p.batch_dev = b; p.has_batch_dev = true; }
+            }
+        }
+    }
+    if (!m.dense && m.parts.size() > 1) {
+        void* yp = nullptr;
+        HIP_TRY(c, hipMalloc(&yp, (m.parts.size() - 1) * (size_t)kMaxBatch * m.rows * sizeof(float)));
+        m.allocs.push_back(yp);
+        m.d_ypart = (float*)yp;
+        // row -> fix entry of every part (short chains only: a part with a long chain keeps the two-launch tail)
+        bool fusable = m.parts.size() <= (size_t)kTailMaxParts;
+        for (auto& p : m.parts) fusable = fusable && (p.is_tts || p.fix_long.empty());
+        if (fusable) {
+            std::vector<int32_t> of((size_t)m.parts.size() * m.rows, -1);
+            for (size_t t = 0; t < m.parts.size(); ++t) {
+                int32_t* o = of.data() + t * (size_t)m.rows;
+                if (m.parts[t].is_tts) { const std::vector<int32_t>& f = tts_fix_rows[t]; for (size_t k = 0; k < f.size(); ++k) o[f[k]] = (int32_t)k; }
+                else for (size_t k = 0; k < m.parts[t].fix_short.size(); ++k) o[m.parts[t].fix_short[k].row] = (int32_t)k;
+            }
+            const int32_t* d_of = nullptr;
+            if ((rc = upload(c, m, of.data(), of.size(), &d_of)) != HISPMV_OK) return rc;
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            m.d_fix_of_row = const_cast<int32_t*>(d_of);
+        }
+    }
+    if (m.updatable && !m.dense && (rc = load_value_map(c, m, value_regions, layout_bytes)) != HISPMV_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // host copies are no longer needed
+    for (auto& p : m.parts) { p.st = SliceStream{}; p.fix_short = {}; p.fix_long = {}; p.plan.groups = {}; p.plan.frags = {}; p.dstream = DeviceStream{};
+                              p.batch_plan.groups = {}; p.batch_plan.frags = {}; p.batch_plan.slice_spills = {}; p.batch_dstream = DeviceStream{}; p.batch_words = WordVec(); }
+    m.dense_host = {};
+    m.dense_host16 = {};
+    if (m.dense) {          // transposed product of a dense handle: the row blocks add their column sums to y (plain stores when there is one)
+        const int nb = gemv_t_row_blocks(m.rows, m.cols);
+        m.t_launches = nb > 0 ? 1 : 0;
+        m.t_atomic_bytes = nb > 1 ? (int64_t)nb * m.cols * 4 : 0;
+    }
+    m.t_launches += 1;      // the prologue y = beta * bias (a tile stream reports its figures only when the entries accept it)
+    m.loaded = true;
+    return HISPMV_OK;
+}
+
 HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     HIP_TRY(c, hipSetDevice(c->device));
     for (auto& mp : c->mats) {
-        Matrix& m = *mp;
-        if (m.loaded) continue;
         int rc;
-        // (scratch of the device layout -- the uploaded host words of the parts --, freed once the stream has drained, also on an error return)
-        struct Scratch { std::vector<void*> v; void push_back(void* p) { v.push_back(p); } ~Scratch() { for (void* p : v) (void)hipFree(p); } } layout_scratch;
-        std::vector<std::vector<int32_t>> tts_fix_rows;       // tile streams: the rows cut into pieces, per part (fix list order)
-        // value updates: the value regions of every part and the sizes of its layouts, while the host tables exist
-        std::vector<std::vector<ValueChunk>> value_regions;
-        std::vector<std::pair<int64_t, int64_t>> layout_bytes;
-        if (m.updatable && !m.dense)
-            for (const Matrix::Part& p : m.parts) {
-                value_regions.push_back(value_chunks(p));
-                layout_bytes.emplace_back(p.is_tts ? (int64_t)p.tts.words.size() : p.dstream.n_bytes, p.has_batch_layout ? p.batch_dstream.n_bytes : 0);
-            }
-        if (m.dense && m.value_storage == HISPMV_VALUES_BF16 && m.updatable) {
-            // W is written by the update kernel from the fp32 creation values, staged in the context's update buffer
-            void* d = nullptr;
-            HIP_TRY(c, hipMalloc(&d, (size_t)m.nnz * 2));
-            m.allocs.push_back(d);
-            m.d_dense = (float*)d;
-            if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, m.nnz)) != HISPMV_OK) return rc;
-            HIP_TRY(c, hipMemcpyAsync(c->d_upd, m.dense_host.data(), (size_t)m.nnz * 4, hipMemcpyHostToDevice, c->stream));
-            const hipError_t e = launch_update_dense_bf16((uint16_t*)d, c->d_upd, m.nnz, c->stream);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_update_dense_bf16");
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        } else if (m.dense && m.value_storage == HISPMV_VALUES_BF16) {
-            const uint16_t* d = nullptr;
-            if ((rc = upload(c, m, m.dense_host16.data(), m.dense_host16.size(), &d)) != HISPMV_OK) return rc;
-            m.d_dense = (float*)const_cast<uint16_t*>(d);      // (rows x cols bf16: every launch of this handle passes its storage along)
-        } else if (m.dense) {
-            const float* d = nullptr;
-            if ((rc = upload(c, m, m.dense_host.data(), m.dense_host.size(), &d)) != HISPMV_OK) return rc;
-            m.d_dense = const_cast<float*>(d);
-        } else if (m.format == 1) {
-          for (Matrix::Part& p : m.parts) {
-            TtsStream& ts = p.tts;
-            tts_fix_rows.emplace_back();
-            for (size_t k = 0; k + 3 < ts.fix.size(); k += 4) tts_fix_rows.back().push_back(ts.fix[k]);
-            const uint8_t* dw = nullptr; const int32_t* dcb = nullptr; const uint16_t* dfl = nullptr; const int32_t* dci = nullptr;
-            const TtsTile* dt = nullptr; const TtsBlock* db = nullptr;
-            if ((rc = upload(c, m, ts.words.data(), ts.words.size(), &dw)) != HISPMV_OK) return rc;
-            if ((rc = upload(c, m, ts.col_base.data(), ts.col_base.size(), &dcb)) != HISPMV_OK) return rc;
-            if ((rc = upload(c, m, ts.flags.data(), ts.flags.size(), &dfl)) != HISPMV_OK) return rc;
-            const uint16_t* dfh = nullptr;
-            std::vector<uint32_t> planes;          // gap-coded row ends: both planes of the codes in one word per lane and chunk
-            if (!ts.flags_hi.empty()) {
-                planes.resize(ts.flags.size());
-                for (size_t q = 0; q < planes.size(); ++q) planes[q] = (uint32_t)ts.flags[q] | ((uint32_t)ts.flags_hi[q] << 16);
-                const uint32_t* dp = nullptr;
-                if ((rc = upload(c, m, planes.data(), planes.size(), &dp)) != HISPMV_OK) return rc;
-                HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`planes` is a local)
-                dfh = (const uint16_t*)dp;
-            }
-            if ((rc = upload(c, m, ts.chunk_info.data(), ts.chunk_info.size(), &dci)) != HISPMV_OK) return rc;
-            if ((rc = upload(c, m, ts.tiles.data(), ts.tiles.size(), &dt)) != HISPMV_OK) return rc;
-            if ((rc = upload(c, m, ts.blocks.data(), ts.blocks.size(), &db)) != HISPMV_OK) return rc;
-            TtsDeviceMatrix& d = p.tdev;
-            d.words = dw; d.col_base = dcb; d.flags = dfl; d.flags_hi = dfh; d.chunk_info = (const int2*)dci; d.tiles = (const int4*)dt; d.blocks = (const int4*)db;
-            d.n_tiles = (int32_t)ts.tiles.size(); d.rows = m.rows; d.cols = m.cols;
-            if (!ts.fix.empty()) {       // rows cut into pieces: carry slots + the slice stream's fix-up entries
-                const int32_t* dfix = nullptr;
-                if ((rc = upload(c, m, ts.fix.data(), ts.fix.size(), &dfix)) != HISPMV_OK) return rc;
-                void* carry = nullptr;
-                HIP_TRY(c, hipMalloc(&carry, (size_t)std::max(ts.n_carry, 1) * kTtsMaxVectors * sizeof(float)));      // one set per vector of a batched launch
-                m.allocs.push_back(carry);
-                HIP_TRY(c, hipMemsetAsync(carry, 0, (size_t)std::max(ts.n_carry, 1) * kTtsMaxVectors * sizeof(float), c->stream));
-                d.n_carry = ts.n_carry;
-                d.fix = (const int4*)dfix; d.n_fix = (int32_t)(ts.fix.size() / 4); d.carry = (float*)carry;
-                // (the same three fields where the multi-matrix fix-up launch looks for them)
-                p.dev.fix_short = d.fix; p.dev.n_fix_short = d.n_fix; p.dev.carry = d.carry; p.dev.n_fix_long = 0;
-            }
-            d.acc_floats = (ts.max_rows + 63) & ~63; d.threads = ts.geometry.threads;
-            d.zero_fill = ts.geometry.zero_fill ? 1 : ts.geometry.gap_rows ? 2 : 0;
-            d.staging_floats = ts.geometry.max_slots + 64;        // (the dummy slot of padding words sits behind the last real one)
-            d.batch_stage_floats = ((ts.max_slots + kTtsChunk - 1) / kTtsChunk) * kTtsChunk + 64;
-            // x in the LDS for short x (HISPMV_TTS_XLDS=1; off by default -- measured slower on the 1024 x 8192 layer of
-            // apps/model_test.py: 16.7 against 15.1 us alone, 8 vectors 74 against 58 us: that layer's tiles are latency chains
-            // of 8 K elements, not gather-bound)
-            d.xlds_floats = (m.cols <= kTtsXldsMax && std::getenv("HISPMV_TTS_XLDS")) ? ((m.cols + 63) & ~63) : 0;
-            if (tts_tile_lds_bytes(d) > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: tile stream exceeds the LDS of a CU");
-            // a transposed call (hispmv_tts_transpose.h): one launch, one float atomic per stored word that is neither filler nor padding
-            // (an upper bound: explicit zeros among them add nothing at run time)
-            m.t_launches += 1; m.t_direct += ts.nnz; m.t_atomic_bytes += 4 * ts.nnz;
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            p.tts = TtsStream{};
-          }
-        } else {
-            for (auto& p : m.parts) {
-                const uint8_t* dw = nullptr; const SliceHdr* dh = nullptr; const FixEntry *fs = nullptr, *fl = nullptr;
-                const int32_t* dg = nullptr; const Frag* dfr = nullptr;
-                const int64_t ns = p.st.n_slices;
-                if ((rc = upload(c, m, p.dstream.groups.data(), p.dstream.groups.size(), &dg)) != HISPMV_OK) return rc;
-                if ((rc = upload(c, m, p.plan.frags.data(), p.plan.frags.size(), &dfr)) != HISPMV_OK) return rc;
-                // the slices in their device layout: packed on the host (HISPMV_LAYOUT=host) or laid out HERE from the uploaded host words
-                const bool lay_out = p.dstream.bytes.empty() && p.dstream.n_bytes > 0;
-                uint64_t* d_host_words = nullptr;
-                if (!lay_out) {
-                    if ((rc = upload(c, m, p.dstream.bytes.data(), p.dstream.bytes.size(), &dw)) != HISPMV_OK) return rc;
-                } else {
-                    if ((int64_t)p.st.words.size() != ns * kSliceElems) return fail(c, HISPMV_EINVAL, "internal: host words missing for the device layout");
-                    void* blk = nullptr;
-                    HIP_TRY(c, hipMalloc(&blk, (size_t)p.dstream.n_bytes));
-                    m.allocs.push_back(blk);
-                    dw = (const uint8_t*)blk;
-                    HIP_TRY(c, hipMalloc((void**)&d_host_words, p.st.words.size() * sizeof(uint64_t)));
-                    layout_scratch.push_back(d_host_words);
-                    HIP_TRY(c, hipMemcpyAsync(d_host_words, p.st.words.data(), p.st.words.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-                }
-                // device header: {row_base, chain_len, rows ending in the slice, 1 if some of its elements lie outside
-                // the group's x window} (the column window of a slice is only needed by the planner)
-                std::vector<SliceHdr>& hh = p.st.hdr;
-                int max_rows = 1;
-                for (int64_t sl = 0; sl < ns; ++sl) {
-                    const int nr = (sl + 1 < ns ? hh[sl + 1].row_base : m.rows) - hh[sl].row_base;
-                    hh[sl].x_base = nr;
-                    hh[sl].x_span = (!p.plan.slice_spills.empty() && p.plan.slice_spills[(size_t)sl]) ? 1 : 0;
-                    max_rows = std::max(max_rows, nr);
-                }
-                uint32_t* d_stray_cols = nullptr;
-                if (!p.dstream.any_stray) {
-                    if ((rc = upload(c, m, hh.data(), hh.size(), &dh)) != HISPMV_OK) return rc;
-                } else if (lay_out) {
-                    void* blk = nullptr;
-                    const size_t hb = hh.size() * sizeof(SliceHdr), sb = (size_t)ns * kStraySlots * sizeof(uint32_t);
-                    HIP_TRY(c, hipMalloc(&blk, hb + sb));
-                    m.allocs.push_back(blk);
-                    HIP_TRY(c, hipMemcpyAsync(blk, hh.data(), hb, hipMemcpyHostToDevice, c->stream));
-                    HIP_TRY(c, hipMemsetAsync((char*)blk + hb, 0xff, sb, c->stream));        // 0xffffffff = no stray
-                    dh = (const SliceHdr*)blk;
-                    d_stray_cols = (uint32_t*)((char*)blk + hb);
-                } else {
-                    // stray slots: the columns of every slice's strays (64 x u32 per slice) live BEHIND the headers in one
-                    // allocation -- the kernels reach them as hdr + n_slices, no further pointer to carry around
-                    void* blk = nullptr;
-                    const size_t hb = hh.size() * sizeof(SliceHdr), sb = p.dstream.stray_cols.size() * sizeof(uint32_t);
-                    HIP_TRY(c, hipMalloc(&blk, hb + sb));
-                    m.allocs.push_back(blk);
-                    HIP_TRY(c, hipMemcpyAsync(blk, hh.data(), hb, hipMemcpyHostToDevice, c->stream));
-                    HIP_TRY(c, hipMemcpyAsync((char*)blk + hb, p.dstream.stray_cols.data(), sb, hipMemcpyHostToDevice, c->stream));
-                    dh = (const SliceHdr*)blk;
-                }
-                if (lay_out) {
-                    const int e = layout_on_device(d_host_words, ns, p.plan.group_slices, dg, p.plan.lds_floats, p.plan.block_threads / 64,
-                                                   (uint8_t*)dw, d_stray_cols, c->stream);
-                    if (e != 0) return hip_fail(c, (hipError_t)e, "layout_on_device");
-                }
-                if ((rc = upload(c, m, p.fix_short.data(), p.fix_short.size(), &fs)) != HISPMV_OK) return rc;
-                if ((rc = upload(c, m, p.fix_long.data(), p.fix_long.size(), &fl)) != HISPMV_OK) return rc;
-                // carry per slice; {carry, launch tag} granules and the group ticket of the look-back variant
-                void *carry = nullptr, *gran = nullptr, *ticket = nullptr;
-                const size_t n1 = (size_t)std::max<int64_t>(ns, 1);
-                HIP_TRY(c, hipMalloc(&carry, n1 * kMaxBatch * sizeof(float)));      // one set per vector of a batched pass
-                m.allocs.push_back(carry);
-                HIP_TRY(c, hipMemsetAsync(carry, 0, n1 * kMaxBatch * sizeof(float), c->stream));
-                HIP_TRY(c, hipMalloc(&gran, n1 * sizeof(unsigned long long)));
-                m.allocs.push_back(gran);
-                HIP_TRY(c, hipMemsetAsync(gran, 0, n1 * sizeof(unsigned long long), c->stream));
-                HIP_TRY(c, hipMalloc(&ticket, sizeof(unsigned long long)));
-                m.allocs.push_back(ticket);
-                HIP_TRY(c, hipMemsetAsync(ticket, 0, sizeof(unsigned long long), c->stream));
-                SpmvDeviceMatrix& d = p.dev;
-                d.words = dw; d.hdr = (const int4*)dh; d.groups = (const int4*)dg; d.frags = (const int4*)dfr;
-                d.fix_short = (const int4*)fs; d.fix_long = (const int4*)fl;
-                d.carry = (float*)carry; d.gran = (unsigned long long*)gran; d.ticket = (unsigned long long*)ticket;
-                d.err = c->d_err; d.launches = 0; d.ticket_launches = 0;
-                d.n_slices = ns; d.n_groups = (ns + p.plan.group_slices - 1) / p.plan.group_slices;
-                d.group_slices = p.plan.group_slices; d.block_threads = p.plan.block_threads;
-                d.lds_floats = p.plan.lds_floats + p.dstream.stray_floats;        // the x window + the wavefronts' stray areas behind it
-                d.ytile_floats = std::min(kSliceElems, (max_rows + 63) & ~63);
-                const size_t lds_plain = slice_lds_bytes(d);
-                if (lds_plain > kDynLdsMax) return fail(c, HISPMV_EINVAL, "internal: launch plan exceeds the LDS of a CU");
-                const bool mailbox_fits = slice_lds_bytes(d, 1, true) <= kDynLdsMax;
-                d.n_fix_short = (int32_t)p.fix_short.size(); d.n_fix_long = (int32_t)p.fix_long.size();
-                d.rows = m.rows; d.cols = m.cols;
-                // co-residency of the whole grid: workgroups per CU by LDS and waves (conservative: <= 4 blocks,
-                // <= 16 waves per CU; MI355X_MICROARCH.md "Residency")
-                const int lds_b = std::max(1, (int)lds_plain + 64);
-                const int per_cu = std::max(1, std::min({4, kLdsPerCu / lds_b, 16 / (d.block_threads / 64)}));
-                const bool resident = d.n_groups <= (int64_t)c->n_cus * per_cu;
-                const bool one_round = d.group_slices <= d.block_threads / 64;
-                // carry_mode: 0 fix-up launch; 1 look-back for every plan, workgroups in blockIdx order (relies on the
-                // dispatcher starting workgroups in increasing id order -- observed, not contractual; the wait is
-                // bounded and reports instead of hanging); 3 the same with start-order tickets (contract-safe);
-                // 2 (auto) look-back when the whole grid is co-resident (every workgroup is running, so waiting for an
-                // earlier slice cannot deadlock) AND every wavefront has one slice (small matrices, where the second
-                // launch costs as much as the kernel), fix-up otherwise; 5 ("resident") look-back for every co-resident
-                // grid: correct, but measured slower than main kernel + fix-up launch on the large matrices
-                // (PFlow_742 71.6 vs 65.2 us, TSOPF 35.5 vs 33.6: wavefronts that run ahead wait for slower neighbours)
-                d.lookback = (c->carry_mode == 1 || c->carry_mode == 3 || (c->carry_mode == 2 && resident && one_round) ||
-                              (c->carry_mode == 5 && resident)) && mailbox_fits;
-                d.use_ticket = c->carry_mode == 3;
-                if (m.parts.size() > 1) { d.lookback = false; d.use_ticket = false; }      // column tiles share one grid: fix-up launch
-                // stray slots: the packer placed every slice's strays by the slice's position in the ROTATED walk of the fix-up
-                // variant; the look-back variant walks its groups in slice order
-                d.has_strays = p.dstream.stray_floats > 0;
-                d.has_half = p.dstream.half_values && p.dstream.compact_slices > 0;
-                if (d.has_strays) { d.lookback = false; d.use_ticket = false; }
-                transpose_costs(m, p, d);
-                // the batch layout (hispmv_choose.h): its own group table, fragments, slice bytes and headers (the spill flags differ);
-                // rows, carries, fix lists and the error word are the part's
-                if (p.has_batch_layout) {
-                    SpmvDeviceMatrix b = d;
-                    const int32_t* bg = nullptr; const Frag* bf = nullptr; const uint8_t* bw = nullptr; const SliceHdr* bh = nullptr;
-                    if ((rc = upload(c, m, p.batch_dstream.groups.data(), p.batch_dstream.groups.size(), &bg)) != HISPMV_OK) return rc;
-                    if ((rc = upload(c, m, p.batch_plan.frags.data(), p.batch_plan.frags.size(), &bf)) != HISPMV_OK) return rc;
-                    std::vector<SliceHdr> bhh = hh;
-                    for (int64_t sl = 0; sl < ns; ++sl) bhh[(size_t)sl].x_span = (!p.batch_plan.slice_spills.empty() && p.batch_plan.slice_spills[(size_t)sl]) ? 1 : 0;
-                    uint32_t* b_stray = nullptr;
-                    {
-                        void* blk = nullptr;
-                        const size_t hb = bhh.size() * sizeof(SliceHdr), sb = p.batch_dstream.any_stray ? (size_t)ns * kStraySlots * sizeof(uint32_t) : 0;
-                        HIP_TRY(c, hipMalloc(&blk, hb + sb));
-                        m.allocs.push_back(blk);
-                        HIP_TRY(c, hipMemcpy(blk, bhh.data(), hb, hipMemcpyHostToDevice));            // (`bhh` is a local: synchronous)
-                        if (sb && !p.batch_dstream.stray_cols.empty()) HIP_TRY(c, hipMemcpy((char*)blk + hb, p.batch_dstream.stray_cols.data(), sb, hipMemcpyHostToDevice));
-                        else if (sb) HIP_TRY(c, hipMemsetAsync((char*)blk + hb, 0xff, sb, c->stream));
-                        bh = (const SliceHdr*)blk;
-                        b_stray = sb ? (uint32_t*)((char*)blk + hb) : nullptr;
-                    }
-                    if (!p.batch_dstream.bytes.empty()) {
-                        if ((rc = upload(c, m, p.batch_dstream.bytes.data(), p.batch_dstream.bytes.size(), &bw)) != HISPMV_OK) return rc;
-                    } else {
-                        void* blk = nullptr; uint64_t* tmp = nullptr;
-                        HIP_TRY(c, hipMalloc(&blk, (size_t)p.batch_dstream.n_bytes));
-                        m.allocs.push_back(blk);
-                        bw = (const uint8_t*)blk;
-                        HIP_TRY(c, hipMalloc((void**)&tmp, p.batch_words.size() * sizeof(uint64_t)));
-                        layout_scratch.push_back(tmp);
-                        HIP_TRY(c, hipMemcpyAsync(tmp, p.batch_words.data(), p.batch_words.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-                        const int e = layout_on_device(tmp, ns, p.batch_plan.group_slices, bg, p.batch_plan.lds_floats, p.batch_plan.block_threads / 64, (uint8_t*)blk, b_stray, c->stream);
-                        if (e != 0) return hip_fail(c, (hipError_t)e, "layout_on_device");
-                    }
-                    b.words = bw; b.hdr = (const int4*)bh; b.groups = (const int4*)bg; b.frags = (const int4*)bf;
-                    b.group_slices = p.batch_plan.group_slices; b.n_groups = (ns + p.batch_plan.group_slices - 1) / p.batch_plan.group_slices;
-                    b.lds_floats = p.batch_plan.lds_floats + p.batch_dstream.stray_floats;
-                    b.has_strays = p.batch_dstream.stray_floats > 0;
-                    b.has_half = p.batch_dstream.half_values && p.batch_dstream.compact_slices > 0;
-                    b.lookback = false; b.use_ticket = false;
-                    if (slice_lds_bytes(b) <= kDynLdsMax) { p.batch_dev = b; p.has_batch_dev = true; }
-                }
-            }
-        }
-        if (!m.dense && m.parts.size() > 1) {
-            void* yp = nullptr;
-            HIP_TRY(c, hipMalloc(&yp, (m.parts.size() - 1) * (size_t)kMaxBatch * m.rows * sizeof(float)));
-            m.allocs.push_back(yp);
-            m.d_ypart = (float*)yp;
-            // row -> fix entry of every part (short chains only: a part with a long chain keeps the two-launch tail)
-            bool fusable = m.parts.size() <= (size_t)kTailMaxParts;
-            for (auto& p : m.parts) fusable = fusable && (p.is_tts || p.fix_long.empty());
-            if (fusable) {
-                std::vector<int32_t> of((size_t)m.parts.size() * m.rows, -1);
-                for (size_t t = 0; t < m.parts.size(); ++t) {
-                    int32_t* o = of.data() + t * (size_t)m.rows;
-                    if (m.parts[t].is_tts) { const std::vector<int32_t>& f = tts_fix_rows[t]; for (size_t k = 0; k < f.size(); ++k) o[f[k]] = (int32_t)k; }
-                    else for (size_t k = 0; k < m.parts[t].fix_short.size(); ++k) o[m.parts[t].fix_short[k].row] = (int32_t)k;
-                }
-                const int32_t* d_of = nullptr;
-                if ((rc = upload(c, m, of.data(), of.size(), &d_of)) != HISPMV_OK) return rc;
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                m.d_fix_of_row = const_cast<int32_t*>(d_of);
-            }
-        }
-        if (m.updatable && !m.dense && (rc = load_value_map(c, m, value_regions, layout_bytes)) != HISPMV_OK) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        // host copies are no longer needed
-        for (auto& p : m.parts) { p.st = SliceStream{}; p.fix_short = {}; p.fix_long = {}; p.plan.groups = {}; p.plan.frags = {}; p.dstream = DeviceStream{};
-                                  p.batch_plan.groups = {}; p.batch_plan.frags = {}; p.batch_plan.slice_spills = {}; p.batch_dstream = DeviceStream{}; p.batch_words = WordVec(); }
-        m.dense_host = {};
-        m.dense_host16 = {};
-        if (m.dense) {          // transposed product of a dense handle: the row blocks add their column sums to y (plain stores when there is one)
-            const int nb = gemv_t_row_blocks(m.rows, m.cols);
-            m.t_launches = nb > 0 ? 1 : 0;
-            m.t_atomic_bytes = nb > 1 ? (int64_t)nb * m.cols * 4 : 0;
-        }
-        m.t_launches += 1;      // the prologue y = beta * bias (a tile stream reports its figures only when the entries accept it)
-        m.loaded = true;
+        // the stored transpose first: its owner counts as loaded only with it
+        if (mp->companion && (rc = load_matrix(c, *mp->companion)) != HISPMV_OK) return rc;
+        if ((rc = load_matrix(c, *mp)) != HISPMV_OK) return rc;
     }
     return HISPMV_OK;
 }
@@ -1026,8 +1083,8 @@ HISPMV_API int hispmv_spmv_device(hispmv_ctx* c, int idx, const float* d_x, cons
 HISPMV_API int hispmv_set_transposable(hispmv_ctx* c, int enable) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    if (enable != HISPMV_TRANSPOSABLE_OFF && enable != HISPMV_TRANSPOSABLE_SLICES && enable != HISPMV_TRANSPOSABLE_KEEP_FORMAT)
-        return fail(c, HISPMV_EINVAL, "set_transposable: unknown state (HISPMV_TRANSPOSABLE_OFF, _SLICES or _KEEP_FORMAT)");
+    if (enable != HISPMV_TRANSPOSABLE_OFF && enable != HISPMV_TRANSPOSABLE_SLICES && enable != HISPMV_TRANSPOSABLE_KEEP_FORMAT && enable != HISPMV_TRANSPOSABLE_COMPANION)
+        return fail(c, HISPMV_EINVAL, "set_transposable: unknown state (HISPMV_TRANSPOSABLE_OFF, _SLICES, _KEEP_FORMAT or _COMPANION)");
     c->transposable = enable;
     return HISPMV_OK;
 }
@@ -1055,11 +1112,104 @@ int refuse_tile_stream(hispmv_ctx* c, const Matrix& m, const char* who, const ch
                                        "hispmv_set_transposable(ctx, 2) (FpgaHandle.set_transposable(\"keep_format\")) so that the tile stream itself is accepted");
 }
 
+// ---- the stored transpose (include/hispmv.h: HISPMV_TRANSPOSABLE_COMPANION) ------------------------------------------------------------
+// The transposed entries of a handle that owns one run the FORWARD launches of `t` = *owner.companion (t.rows = owner.cols): no atomic,
+// per vector the bits of a one-vector hispmv_linear_device call on a handle made from the swapped input.  Its own launch routine:
+// launch_matrix_vectors and the behaviour of hispmv_linear_device are not touched.
+
+// Vectors of the next pass: the widths launch_matrix_vectors takes for beta != 0, for every beta.  per_vector_bias: the batched tile
+// kernel takes one shared bias, so such a call goes one vector per launch on a tile stream.
+int companion_width(const Matrix& t, int64_t left, bool per_vector_bias) {
+    if (left < 2) return 1;
+    if (t.format == 1) {
+        if (t.parts.size() != 1 || t.parts[0].tdev.zero_fill || per_vector_bias) return 1;
+        const int nv = tts_batch_width(t.parts[0].tdev, left);
+        return nv >= 2 ? nv : (int)std::min<int64_t>(left, kTtsMaxVectors);
+    }
+    int nv = kMaxBatch;
+    for (auto& p : t.parts) nv = std::min(nv, spmv_batch_width(p.dev, left));
+    return nv;
+}
+// Launches of one pass of nv vectors (alpha != 0).  A one-vector pass over a cut matrix is a batch call of one matrix (launch_matrix):
+// one grid per workgroup size (and stray class) among its parts, then its tail -- one launch where the merge applies the fix-ups itself.
+int64_t companion_pass_launches(const Matrix& t, int nv) {
+    auto chains = [](const SpmvDeviceMatrix& d) { return (d.n_fix_short > 0 ? 1 : 0) + (d.n_fix_long > 0 ? 1 : 0); };
+    if (t.format == 1 && t.parts.size() == 1 && !t.parts[0].tdev.zero_fill) {
+        const TtsDeviceMatrix& d = t.parts[0].tdev;
+        return d.n_tiles > 0 ? 1 + (d.n_fix > 0 ? 1 : 0) : 0;
+    }
+    if (t.parts.size() == 1) return (t.parts[0].dev.n_slices > 0 ? 1 : 0) + chains(t.parts[0].dev);
+    int64_t n = 0;
+    if (nv > 1) {
+        for (auto& p : t.parts) n += (p.dev.n_slices > 0 ? 1 : 0) + chains(p.dev);
+        return n + 1;       // + the merge
+    }
+    std::vector<int> classes;
+    for (auto& p : t.parts) {
+        const int cls = p.is_tts ? -1 : p.dev.block_threads * 2 + (p.dev.has_strays ? 1 : 0);
+        if (std::find(classes.begin(), classes.end(), cls) == classes.end()) classes.push_back(cls);
+        if (!p.is_tts && p.dev.n_fix_long > 0) n += 1;
+    }
+    return n + (int64_t)classes.size() + (t.d_fix_of_row ? 1 : 2);
+}
+
+int launch_companion(hispmv_ctx* c, Matrix& owner, int64_t vecs, const float* d_x, const float* d_bias, int64_t bias_stride, float* d_y,
+                     float alpha, float beta, hipStream_t s) {
+    Matrix& t = *owner.companion;
+    if (!t.loaded) return fail(c, HISPMV_ESTATE, "internal: the stored transpose is not loaded");
+    if (alpha == 0.0f) {          // y is exactly beta * bias, per vector; neither x nor the matrix is read
+        const hipError_t e = launch_transpose_prologue(d_bias, d_y, t.rows, beta, s, vecs, bias_stride);
+        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_transpose_prologue");
+    }
+    const bool has_bias = beta != 0.0f;
+    const bool one_by_one = ((uintptr_t)d_x & 15) != 0;       // (the rule of hispmv_linear_device: an unusual pointer stays off the batched passes)
+    for (int64_t k = 0; k < vecs;) {
+        const int nv = one_by_one ? 1 : companion_width(t, vecs - k, has_bias && bias_stride != 0);
+        const float* xk = d_x + k * t.cols;
+        const float* bk = has_bias ? d_bias + k * bias_stride : nullptr;
+        float* yk = d_y + k * t.rows;
+        if (nv < 2) {
+            const int rc = launch_matrix(c, t, xk, bk, yk, alpha, beta, s, true);
+            if (rc != HISPMV_OK) return rc;
+        } else if (t.format == 1) {
+            const hipError_t e = launch_tts_batched(t.parts[0].tdev, nv, xk, bk, yk, alpha, beta, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_tts_batched");
+        } else {
+            for (size_t q = 0; q < t.parts.size(); ++q) {
+                // part 0: the bias (shared, or one per vector); part q > 0: the nv partial vectors of that part, no bias
+                const hipError_t e = (q == 0) ? launch_spmv_batched(t.parts[q].dev, nv, xk, bk, (int)bias_stride, yk, alpha, beta, s)
+                                              : launch_spmv_batched(t.parts[q].dev, nv, xk, nullptr, 0, t.d_ypart + (q - 1) * (size_t)kMaxBatch * t.rows, alpha, 0.0f, s);
+                if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_batched");
+            }
+            if (t.parts.size() > 1) {
+                const hipError_t e = launch_merge_parts(yk, t.d_ypart, (int)t.parts.size() - 1, (int64_t)kMaxBatch * t.rows, t.rows, nv, t.rows, t.rows, s);
+                if (e != hipSuccess) return hip_fail(c, e, "launch_merge_parts");
+            }
+        }
+        k += nv;
+    }
+    return HISPMV_OK;
+}
+
 }  // namespace
+
+HISPMV_API int hispmv_companion_info(const hispmv_ctx* c, int idx, int64_t out[6]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    const Matrix* t = c->mats[(size_t)idx]->companion.get();
+    if (!t) return HISPMV_OK;
+    out[0] = 1; out[1] = t->format; out[2] = (int64_t)t->parts.size(); out[3] = t->device_bytes; out[4] = t->map_slots;
+    out[5] = t->parts.size() > 1 ? (t->tile_kind ? t->tile_kind : 1) : 0;
+    return HISPMV_OK;
+}
 
 HISPMV_API int hispmv_transpose_info(const hispmv_ctx* c, int idx, int64_t out[4]) {
     if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
     const Matrix& m = *c->mats[(size_t)idx];
+    if (m.companion) {          // forward launches over the stored transpose: no atomic
+        out[0] = m.loaded ? 1 : 0; out[1] = m.loaded ? companion_pass_launches(*m.companion, 1) : 0; out[2] = 0; out[3] = 0;
+        return HISPMV_OK;
+    }
     const bool ok = m.loaded && transposable_handle(m);
     out[0] = ok ? 1 : 0; out[1] = ok ? m.t_launches : 0; out[2] = ok ? m.t_atomic_bytes : 0; out[3] = ok ? m.t_direct : 0;
     return HISPMV_OK;
@@ -1074,6 +1224,11 @@ HISPMV_API int hispmv_spmv_device_t(hispmv_ctx* c, int idx, const float* d_x, co
     if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device_t called before load_matrices");
     if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
     if (d_x == d_y) return fail(c, HISPMV_EINVAL, "spmv_device_t: x and y must not be the same vector");
+    if (m.companion) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (stream) c->user_stream = (hipStream_t)stream;
+        return launch_companion(c, m, 1, d_x, d_bias, 0, d_y, alpha, beta, stream ? (hipStream_t)stream : c->stream);
+    }
     if (!transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
     HIP_TRY(c, hipSetDevice(c->device));
     if (stream) c->user_stream = (hipStream_t)stream;
@@ -1154,6 +1309,13 @@ HISPMV_API int hispmv_linear_info(const hispmv_ctx* c, int idx, int64_t num_vecs
     for (int i = 0; i < 5; ++i) out[i] = 0;
     if (!m.loaded) return HISPMV_OK;
     forward_passes(m, num_vecs, out[0], out[1]);
+    if (m.companion) {          // the passes of launch_companion with a shared bias and an aligned d_x
+        for (int64_t k = 0; k < num_vecs;) {
+            const int nv = companion_width(*m.companion, num_vecs - k, false);
+            out[2] = std::max<int64_t>(out[2], nv); out[3] += 1; out[4] += companion_pass_launches(*m.companion, nv); k += nv;
+        }
+        return HISPMV_OK;
+    }
     if (!transposable_handle(m)) return HISPMV_OK;
     int64_t launches = 1;           // the prologue
     for (int64_t k = 0; k < num_vecs;) {
@@ -1203,6 +1365,11 @@ HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, 
     if (bias_stride != 0 && bias_stride != m.cols) return fail(c, HISPMV_EINVAL, "linear_device_t: bias_stride must be 0 (one bias for all vectors) or cols");
     if (beta != 0.0f && d_bias == d_y && bias_stride == 0 && num_vecs > 1)
         return fail(c, HISPMV_EINVAL, "linear_device_t: d_bias == d_y needs bias_stride = cols (a shared bias would be overwritten by vector 0)");
+    if (m.companion) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (stream) c->user_stream = (hipStream_t)stream;
+        return launch_companion(c, m, num_vecs, d_x, d_bias, bias_stride, d_y, alpha, beta, stream ? (hipStream_t)stream : c->stream);
+    }
     if (!transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
     HIP_TRY(c, hipSetDevice(c->device));
     if (stream) c->user_stream = (hipStream_t)stream;
@@ -1393,7 +1560,7 @@ HISPMV_API int hispmv_set_value_updates(hispmv_ctx* c, int enable) {
 HISPMV_API int hispmv_value_update_info(const hispmv_ctx* c, int idx, int64_t out[4]) {
     if (!c || !out || idx < 0 || idx >= (int)c->mats.size()) return HISPMV_EINVAL;
     const Matrix& m = *c->mats[idx];
-    out[0] = m.updatable ? 1 : 0; out[1] = m.upd_n; out[2] = m.map_slots; out[3] = m.upd_written;
+    out[0] = m.updatable ? 1 : 0; out[1] = m.upd_n; out[2] = m.map_slots; out[3] = m.upd_written + (m.companion ? m.companion->upd_written : 0);
     return HISPMV_OK;
 }
 
@@ -1425,7 +1592,8 @@ int issue_update(hispmv_ctx* c, Matrix& m, const float* d_values, hipStream_t s)
     }
     const hipError_t e = bf16 ? launch_update_values_bf16(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s)
                               : launch_update_values(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s);
-    return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_update_values");
+    if (e != hipSuccess) return hip_fail(c, e, "launch_update_values");
+    return m.companion ? issue_update(c, *m.companion, d_values, s) : HISPMV_OK;      // the stored transpose: the same values through its own map
 }
 
 }  // namespace

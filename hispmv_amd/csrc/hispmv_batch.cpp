@@ -55,12 +55,12 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
     // BATCH layout where it has one: groups twice as long, hispmv_choose.h)
     const bool shared_chip = c->batch_streams > 1 && plan.stream_bytes >= c->batch_streams_min_bytes && !std::getenv("HISPMV_NO_BATCH_LAYOUT");
     auto dev_of = [&](const Ref& r) -> SpmvDeviceMatrix& {
-        Matrix::Part& p = c->mats[idx[r.i]]->parts[r.t];
+        Matrix::Part& p = c->matrix(idx[r.i]).parts[r.t];
         if (shared_chip && long_groups && p.has_batch_dev) { used_long_groups = true; return p.batch_dev; }
         return p.dev;
     };
     auto out_of = [&](const Ref& r) -> float* {
-        Matrix& m = *c->mats[idx[r.i]];
+        Matrix& m = c->matrix(idx[r.i]);
         return r.t == 0 ? d_y[r.i] : m.d_ypart + (r.t - 1) * (size_t)kMaxBatch * m.rows;
     };
     const bool pin = !std::getenv("HISPMV_NO_XCD_PIN");
@@ -73,9 +73,9 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
         // after the other, the 512..2048-wide GeMVs of cpu/run_gemv.sh cost a launch latency each: 77 us for the five
         // sizes against 56 us of streaming)
         std::vector<int> dense;
-        for (int i = 0; i < n; ++i) if (c->mats[idx[i]]->dense) dense.push_back(i);
+        for (int i = 0; i < n; ++i) if (c->matrix(idx[i]).dense) dense.push_back(i);
         std::stable_sort(dense.begin(), dense.end(), [&](int a, int b) {
-            const Matrix& ma = *c->mats[idx[a]]; const Matrix& mb = *c->mats[idx[b]];
+            const Matrix& ma = c->matrix(idx[a]); const Matrix& mb = c->matrix(idx[b]);
             return (int64_t)ma.rows * ma.cols > (int64_t)mb.rows * mb.cols;
         });
         for (size_t k0 = 0; k0 < dense.size(); k0 += kMultiMax) {
@@ -83,7 +83,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
             l.kind = 4;
             for (size_t k = k0; k < std::min(dense.size(), k0 + (size_t)kMultiMax); ++k) {
                 const int i = dense[k];
-                const Matrix& m = *c->mats[idx[i]];
+                const Matrix& m = c->matrix(idx[i]);
                 l.gemv.push_back(GemvEntry{m.d_dense, d_x[i], bias[i], d_y[i], m.rows, m.cols, beta, m.value_storage == HISPMV_VALUES_BF16 ? 1 : 0});
             }
             plan.launches.push_back(std::move(l));
@@ -97,7 +97,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
     };
     std::vector<int> tts_classes;                // staging size = the geometry (hispmv_tts.h): small 13 K, standard 28 K, tall 23 K, paired 11 K
     for (int i = 0; i < n; ++i) {
-        const Matrix& m = *c->mats[idx[i]];
+        const Matrix& m = c->matrix(idx[i]);
         if (m.dense || m.format != 1) continue;
         const int cls = tts_class(m);
         if (std::find(tts_classes.begin(), tts_classes.end(), cls) == tts_classes.end()) tts_classes.push_back(cls);
@@ -118,16 +118,16 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
         };
         std::vector<int> order;                  // matrices with the longest tiles first (a CU holds one tile at a time)
         for (int i = 0; i < n; ++i) {
-            const Matrix& m = *c->mats[idx[i]];
+            const Matrix& m = c->matrix(idx[i]);
             if (m.dense || m.format != 1) continue;
             if (tts_class(m) == geometry) order.push_back(i);
         }
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            const Matrix& ma = *c->mats[idx[a]]; const Matrix& mb = *c->mats[idx[b]];
+            const Matrix& ma = c->matrix(idx[a]); const Matrix& mb = c->matrix(idx[b]);
             return ma.n_elems / std::max(1, ma.parts[0].tdev.n_tiles) > mb.n_elems / std::max(1, mb.parts[0].tdev.n_tiles);
         });
         for (int i : order) {
-            Matrix& m = *c->mats[idx[i]];
+            Matrix& m = c->matrix(idx[i]);
             if (l.tts.size() + m.parts.size() > (size_t)kMultiMax) { const int rc0 = flush(); if (rc0 != HISPMV_OK) return rc0; }
             // the column parts of a tall-geometry matrix: one item, pinned to XCD subsets (part 0 writes y with the bias,
             // part t > 0 alpha*A_t*x into the handle's partial vector: the merge launch adds it)
@@ -143,7 +143,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
         if (rc0 != HISPMV_OK) return rc0;
     }
     for (int i = 0; i < n; ++i) {
-        const Matrix& m = *c->mats[idx[i]];
+        const Matrix& m = c->matrix(idx[i]);
         if (m.dense || m.format == 1) continue;
         if (m.l2_tiles && pin) {                 // the L2-sized column tiles of a matrix: one item, pinned to XCD subsets
             Item it{{}, m.parts[0].dev.block_threads, 0};
@@ -297,7 +297,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                         if (n_blocks > 0) HIP_TRY(c, hipMemcpy(blocks.data(), te.m.blocks, blocks.size() * sizeof(int4), hipMemcpyDeviceToHost));
                         // 0.85 us per 1024-element slice with 23 lines of x per gather (soc-Pokec), scaled by the line model of DESIGN.md 2.2
                         double lines = 23.0;
-                        for (int i = 0; i < n; ++i) { const Matrix& m = *c->mats[idx[i]]; if (!m.dense && m.format == 1 && m.parts[0].tdev.words == te.m.words && m.tts_lines_per_gather > 0) lines = m.tts_lines_per_gather; }
+                        for (int i = 0; i < n; ++i) { const Matrix& m = c->matrix(idx[i]); if (!m.dense && m.format == 1 && m.parts[0].tdev.words == te.m.words && m.tts_lines_per_gather > 0) lines = m.tts_lines_per_gather; }
                         static const double tile_scale = std::getenv("HISPMV_STEP_TILE_SCALE") ? std::atof(std::getenv("HISPMV_STEP_TILE_SCALE")) : 1.0;
                         const double per_slice = tile_scale * 0.85 * (50.0 + 2.8 * lines) / (50.0 + 2.8 * 23.0);
                         for (int t = 0; t < te.m.n_tiles; ++t) {
@@ -357,7 +357,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
     if (long_groups && used_long_groups && !step_taken) return HISPMV_OK;        // (planned again from the first layouts: build_batch_plan)
     std::vector<Ref> fixrefs = refs;                            // + tile streams that cut long rows into pieces
     for (int i = 0; i < n; ++i) {
-        const Matrix& m = *c->mats[idx[i]];
+        const Matrix& m = c->matrix(idx[i]);
         if (!m.dense && m.format == 1)
             for (size_t t = 0; t < m.parts.size(); ++t) if (m.parts[t].tdev.n_fix > 0) fixrefs.push_back(Ref{i, t});
     }
@@ -398,14 +398,14 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
     std::vector<int> tiled;
     bool fused = !std::getenv("HISPMV_NO_FUSED_TAIL");
     for (int i = 0; i < n; ++i) {
-        const Matrix& m = *c->mats[idx[i]];
+        const Matrix& m = c->matrix(idx[i]);
         if (m.dense || m.parts.size() < 2) continue;
         tiled.push_back(i);
         fused = fused && m.d_fix_of_row != nullptr;
     }
     if (fused) {
         std::vector<Ref> plain;                                 // parts whose cut rows the fix-up blocks finish
-        for (const Ref& r : fixrefs) if (c->mats[idx[r.i]]->parts.size() < 2) plain.push_back(r);
+        for (const Ref& r : fixrefs) if (c->matrix(idx[r.i]).parts.size() < 2) plain.push_back(r);
         fused = plain.size() <= (size_t)kMultiMax && tiled.size() <= (size_t)kMultiMax;
         // HISPMV_LANE_TAILS=1 (experiment, r4_lane_tails.sh): one tail per LANE, enqueued on the lane's own stream right behind its main
         // launches -- no cross-stream join in front of it -- with the cut rows and merges of the matrices whose parts all ran in that
@@ -424,7 +424,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
             std::vector<Ref> rest_plain; std::vector<int> rest_tiled;
             for (const Ref& r : plain) { const int ln = lane_of_out(out_of(r), &dev_of(r)); if (ln >= 0) lane_plain[(size_t)ln].push_back(r); else rest_plain.push_back(r); }
             for (int i : tiled) {
-                Matrix& m = *c->mats[idx[i]];
+                Matrix& m = c->matrix(idx[i]);
                 int ln = -2;
                 for (size_t t = 0; t < m.parts.size(); ++t) { const int q = lane_of_out(out_of(Ref{i, t}), &m.parts[t].dev); ln = ln == -2 ? q : (ln == q ? ln : -1); }
                 if (ln >= 0) lane_tiled[(size_t)ln].push_back(i); else rest_tiled.push_back(i);
@@ -442,7 +442,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                     any = any || d.n_fix_short > 0 || d.n_fix_long > 0;
                 }
                 for (int i : ti) {
-                    Matrix& m = *c->mats[idx[i]];
+                    Matrix& m = c->matrix(idx[i]);
                     TailMergeEntry e{};
                     e.y = d_y[i]; e.parts = m.d_ypart; e.part_stride = (long long)kMaxBatch * m.rows; e.n_parts = (int32_t)m.parts.size() - 1; e.rows = m.rows;
                     e.fix_of_row = m.d_fix_of_row;
@@ -479,7 +479,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                 any = any || d.n_fix_short > 0 || d.n_fix_long > 0;
             }
             for (int i : tiled) {
-                Matrix& m = *c->mats[idx[i]];
+                Matrix& m = c->matrix(idx[i]);
                 TailMergeEntry e{};
                 e.y = d_y[i]; e.parts = m.d_ypart; e.part_stride = (long long)kMaxBatch * m.rows; e.n_parts = (int32_t)m.parts.size() - 1; e.rows = m.rows;
                 e.fix_of_row = m.d_fix_of_row;
@@ -526,7 +526,7 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
         return r2;
     };
     for (int i : tiled) {                                       // merge of the column-tile partial vectors
-        Matrix& m = *c->mats[idx[i]];
+        Matrix& m = c->matrix(idx[i]);
         merges.push_back(MultiMergeEntry{d_y[i], m.d_ypart, (long long)kMaxBatch * m.rows, (int32_t)m.parts.size() - 1, m.rows});
         merge_rows.push_back(m.rows);
         if ((int)merges.size() == kMultiMax && (rc = flush_merges()) != HISPMV_OK) return rc;
@@ -544,11 +544,11 @@ HISPMV_API int hispmv_spmv_device_batch(hispmv_ctx* c, int32_t n, const int32_t*
 
 namespace hispmv {
 int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float* const* d_x, const float* const* d_bias,
-                      float* const* d_y, float alpha, float beta, hipStream_t s) {
+                      float* const* d_y, float alpha, float beta, hipStream_t s, bool companions) {
     if (n < 0 || (n > 0 && (!idx || !d_x || !d_y || (beta != 0.0f && !d_bias)))) return fail(c, HISPMV_EINVAL, "NULL argument");
     for (int i = 0; i < n; ++i) {
-        if (idx[i] < 0 || idx[i] >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-        const Matrix& m = *c->mats[idx[i]];
+        if (!c->has_matrix(idx[i], companions)) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");      // (companions: the stored transpose of a handle, hispmv_abi.cpp)
+        const Matrix& m = c->matrix(idx[i]);
         if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device_batch called before load_matrices");
         if (!d_x[i] || !d_y[i] || (beta != 0.0f && !d_bias[i])) return fail(c, HISPMV_EINVAL, "NULL device vector");
         for (int k = 0; k < i; ++k) {
@@ -575,7 +575,7 @@ int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float*
         c->batch_plans.emplace_back();
         c->batch_plans.back().key = key;
         for (int i = 0; i < n; ++i) {
-            const Matrix& mi = *c->mats[idx[i]];
+            const Matrix& mi = c->matrix(idx[i]);
             c->batch_plans.back().stream_bytes += mi.dense ? 4 * (int64_t)mi.rows * mi.cols : 8 * mi.nnz;
         }
         const int rc = build_batch_plan(c, c->batch_plans.back(), n, idx, d_x, bias, d_y, beta);

@@ -92,8 +92,15 @@ struct Matrix {
     // created under hispmv_set_transposable(ctx, HISPMV_TRANSPOSABLE_KEEP_FORMAT): the loader's own format choice was kept, and if
     // that is a tile stream the transposed and gradient entries accept it (hispmv_tts_transpose.h).  Taken at creation, like value storage.
     bool keep_format = false;
+    // created under HISPMV_TRANSPOSABLE_COMPANION: the stored transpose, a second matrix for A^T made from the swapped creation input
+    // (rows and cols exchanged, same entry order) under the same switches, without a batch layout.  Not in the context's handle list:
+    // `index` of a companion is kCompanionId + its owner's index, the id a cached batch plan keys on (hispmv_ctx::matrix).  The
+    // owner's device_bytes and prep_seconds include the companion's; every value update writes both; the transposed entries run the
+    // companion's forward launches (hispmv_abi.cpp: launch_companion).
+    std::unique_ptr<Matrix> companion;
     std::vector<void*> allocs;
 };
+constexpr int kCompanionId = 1 << 30;       // (handle indices stay far below: every handle costs arena bytes)
 
 }  // namespace hispmv
 
@@ -129,6 +136,12 @@ struct hispmv_ctx {
     std::mutex mu;
     std::string err;
     std::vector<std::unique_ptr<hispmv::Matrix>> mats;
+    // a handle by index, or -- id >= kCompanionId, internal callers only -- the companion of handle id - kCompanionId
+    bool has_matrix(int id, bool companions) const {
+        if (id >= 0 && id < (int)mats.size()) return true;
+        return companions && id >= hispmv::kCompanionId && id - hispmv::kCompanionId < (int)mats.size() && mats[(size_t)(id - hispmv::kCompanionId)]->companion;
+    }
+    hispmv::Matrix& matrix(int id) const { return id >= hispmv::kCompanionId ? *mats[(size_t)(id - hispmv::kCompanionId)]->companion : *mats[(size_t)id]; }
     int selected = -1;
     int64_t arena_budget = 0, arena_used = 0;
     float *d_x = nullptr, *d_y = nullptr;     // device vectors of run_kernel / linear: [x | bias] and y
@@ -147,7 +160,8 @@ struct hispmv_ctx {
     bool updates_any_storage = false;           // HISPMV_VALUE_UPDATES_ANY_STORAGE: bf16 handles are created updatable too instead of refused
     int value_storage = HISPMV_VALUES_FP32;     // hispmv_set_value_storage: what handles created from now on store their values as
     int transposable = HISPMV_TRANSPOSABLE_OFF; // hispmv_set_transposable: sparse handles created from now on keep the slice stream (_SLICES: format_mode 0),
-                                                //   or their own format with a tile stream among them marked for the transposed entries (_KEEP_FORMAT)
+                                                //   or their own format with a tile stream among them marked for the transposed entries (_KEEP_FORMAT),
+                                                //   or that and a stored transpose besides (_COMPANION: Matrix::companion)
     float* h_upd = nullptr;
     int64_t cap_h_upd = 0;
     float* d_upd = nullptr;
@@ -264,6 +278,6 @@ template <class T> void host_free(T*& p) {
 int check_device_error(hispmv_ctx* c);      // hispmv_abi.cpp
 void free_batch_plans(hispmv_ctx* c);       // hispmv_batch.cpp
 int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float* const* d_x, const float* const* d_bias,
-                      float* const* d_y, float alpha, float beta, hipStream_t s);
+                      float* const* d_y, float alpha, float beta, hipStream_t s, bool companions = false);
 
 }  // namespace hispmv

@@ -161,6 +161,12 @@ void sort_rows_by_column(Csr& m) {
     }
 }
 
+void csr_entry_rows(int32_t rows, const int32_t* row_ptr, int32_t* out) {
+#pragma omp parallel for num_threads(host_threads()) schedule(static, 1024)
+    for (int32_t i = 0; i < rows; ++i)
+        for (int64_t k = row_ptr[i]; k < row_ptr[(size_t)i + 1]; ++k) out[k] = i;
+}
+
 // First touch of a freshly allocated buffer by all threads (one write per page): a copy into it -- a device-to-host download,
 // done by one runtime thread -- then finds the pages mapped instead of faulting them in one by one.
 void prefault_parallel(void* p, size_t bytes) {

@@ -93,6 +93,10 @@ Csr coo_to_csr(int32_t rows, int32_t cols, int64_t nnz, const int32_t* r, const 
 // Stable per-row sort by column of a CSR whose rows may be unsorted (rows already ascending are left alone).
 void sort_rows_by_column(Csr& m);
 
+// The row of every CSR entry in input order: out[k] = i for row_ptr[i] <= k < row_ptr[i + 1] (row_ptr starts at 0, non-decreasing).
+// With col_idx as the rows this is the swapped COO a stored transpose is made from (hispmv_ctx.h: Matrix::companion).
+void csr_entry_rows(int32_t rows, const int32_t* row_ptr, int32_t* out);
+
 // Element offset of every row in the slice stream (fillers for empty rows, row-aligned slices): rows + 1 entries.
 std::vector<int64_t> stream_row_offsets(int32_t rows, const int64_t* row_ptr);
 

@@ -94,6 +94,17 @@ HISPMV_API int hispmv_prep_choose_format(const hispmv_prep* p, int n_cus, int64_
     } catch (const std::exception& ex) { g_prep_err = ex.what(); return HISPMV_EINVAL; }
 }
 
+HISPMV_API int hispmv_prep_swapped_coo_from_csr(const int32_t* row_ptr, const int32_t* col_idx, int32_t rows, int32_t* out_rows, int32_t* out_cols) {
+    if (!row_ptr || rows <= 0 || row_ptr[0] != 0) { g_prep_err = "bad CSR arguments"; return HISPMV_EINVAL; }
+    for (int32_t i = 0; i < rows; ++i) if (row_ptr[i + 1] < row_ptr[i]) { g_prep_err = "row_ptr must be non-decreasing"; return HISPMV_EINVAL; }
+    const int64_t nnz = row_ptr[rows];
+    if (nnz > 0 && (!col_idx || !out_rows || !out_cols)) { g_prep_err = "bad CSR arguments"; return HISPMV_EINVAL; }
+    host_threads();
+    if (nnz > 0) std::memcpy(out_rows, col_idx, (size_t)nnz * sizeof(int32_t));
+    csr_entry_rows(rows, row_ptr, out_cols);
+    return HISPMV_OK;
+}
+
 HISPMV_API int hispmv_prep_step_queue(const double* slice_costs, int32_t n_slice, const double* tile_costs, int32_t n_tile, int32_t n_wg, int32_t mode,
                                       int32_t* out_class, int32_t* out_index) {
     if (n_slice < 0 || n_tile < 0 || n_wg <= 0 || mode < 0 || (mode > 4 && mode < 16) || mode > 255 || (n_slice > 0 && !slice_costs) || (n_tile > 0 && !tile_costs) ||

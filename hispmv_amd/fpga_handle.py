@@ -199,24 +199,48 @@ class FpgaHandle:
         return {"storage": "bf16" if out[0] == _lib.HISPMV_VALUES_BF16 else "fp32", "slots_2byte": int(out[1]), "slots_4byte": int(out[2]),
                 "saved_bytes": int(out[3])}
 
+    @staticmethod
+    def transposable_state(enable) -> int:
+        """The integer state of hispmv_set_transposable that `enable` spells: False / True / 0, 1, 2 as they are, "keep_format" = 2,
+        "companion" = 3.  The stored transpose costs arena bytes, so it is asked for by name only: the bare integer 3 raises
+        ValueError, as it did before the state existed, and so does any other string.  (Other integers are the library's to judge.)"""
+        if isinstance(enable, str):
+            states = {"keep_format": _lib.HISPMV_TRANSPOSABLE_KEEP_FORMAT, "companion": _lib.HISPMV_TRANSPOSABLE_COMPANION}
+            if enable not in states:
+                raise ValueError('set_transposable takes False, True, "keep_format", "companion" or 0, 1, 2')
+            return states[enable]
+        if int(enable) == _lib.HISPMV_TRANSPOSABLE_COMPANION:
+            raise ValueError('set_transposable: the stored transpose is asked for by name, set_transposable("companion"), not by the integer 3')
+        return int(enable)
+
     def set_transposable(self, enable) -> None:
         """The state sparse handles are created under from now on (hispmv_set_transposable): False / 0 = off; True / 1 = they keep the
         slice stream, so that spmv_device_t, linear_device_t and value_grad_device accept them; "keep_format" / 2 = they keep the
         format the loader picks, and a tile stream among them (one part, the standard or the small geometry) is accepted by the same
-        three entries through the tile-stream kernels.  Anything else raises ValueError."""
-        if isinstance(enable, str):
-            if enable != "keep_format":
-                raise ValueError('set_transposable takes False, True, "keep_format" or 0, 1, 2')
-            state = _lib.HISPMV_TRANSPOSABLE_KEEP_FORMAT
-        else:
-            state = int(enable)
-        self._check(lib.hispmv_set_transposable(self._ctx, state))
+        three entries through the tile-stream kernels; "companion" (by name only) = as "keep_format", and the handle also owns a stored transpose
+        (companion_info): spmv_device_t and linear_device_t then run the forward kernels over it, without atomics, for the price of
+        its device bytes and creation time.  Anything else raises ValueError."""
+        self._check(lib.hispmv_set_transposable(self._ctx, self.transposable_state(enable)))
+
+    def companion_info(self, matrix_idx: int) -> dict:
+        """{"has", "format", "parts", "device_bytes", "map_slots", "tile_kind"} of the stored transpose of a handle
+        (hispmv_companion_info); has is False and the rest zero for a handle without one."""
+        out = (C.c_int64 * 6)()
+        rc = lib.hispmv_companion_info(self._ctx, int(matrix_idx), out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range")
+        return {"has": bool(out[0]), "format": int(out[1]), "parts": int(out[2]), "device_bytes": int(out[3]), "map_slots": int(out[4]),
+                "tile_kind": int(out[5])}
 
     def spmv_device_t(self, matrix_idx: int, d_x: int, d_bias: int, d_y: int, alpha: float, beta: float,
                       stream: int = 0) -> None:
         """y[cols] = alpha * A^T x[rows] + beta * bias[cols] on device pointers (ints), asynchronous on `stream` (hispmv_spmv_device_t).
-        Sums arrive through float atomics: the last bits may differ from run to run.  d_y must be ordinary device memory (not fine-grained
-        or host-pinned).  A tile-stream handle raises NotImplementedError unless it was created under set_transposable("keep_format")."""
+        Two contracts.  Without a stored transpose the sums arrive through float atomics: the last bits may differ from run to run, a
+        +-0 slot adds nothing, and d_y must be ordinary device memory (not fine-grained or host-pinned); a tile-stream handle raises
+        NotImplementedError unless it was created under set_transposable("keep_format").  A handle created under
+        set_transposable("companion") runs the forward kernels over its stored transpose: plain stores into any device-writable d_y,
+        and the bits of a one-vector linear_device call on a handle made from the swapped COO -- the same from run to run, zero slots
+        and non-finite inputs as in that forward product; one transposed call per handle in flight."""
         self._check(lib.hispmv_spmv_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_x), C.c_void_p(d_bias),
                                              C.c_void_p(d_y), float(alpha), float(beta), C.c_void_p(stream)))
 
@@ -240,7 +264,10 @@ class FpgaHandle:
                         bias_stride: int = 0, stream: int = 0) -> None:
         """y[v] = alpha * A^T x[v] + beta * bias[v * bias_stride] for num_vecs vectors on device pointers (ints): x is [num_vecs, rows],
         y [num_vecs, cols] (hispmv_linear_device_t).  bias_stride 0 = one bias for all, cols = one per vector (then d_bias may be d_y:
-        in place).  The promises and preconditions of spmv_device_t, the handles it accepts."""
+        in place).  The promises and preconditions of spmv_device_t and the handles it accepts, under both of its contracts: atomics in
+        no fixed order without a stored transpose; with one (set_transposable("companion")) every vector has the bits of a one-vector
+        linear_device call on a handle made from the swapped COO, whatever num_vecs, and the vectors go in the passes linear_device
+        takes there (a per-vector bias on a tile-stream companion: one vector per launch)."""
         self._check(lib.hispmv_linear_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_x), int(num_vecs), C.c_void_p(d_bias), int(bias_stride),
                                                C.c_void_p(d_y), float(alpha), float(beta), C.c_void_p(stream)))
 

@@ -132,7 +132,10 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None):
     A^T grad_y through linear_device_t, grad_bias = grad_y.sum(0)).  Runs on torch's current stream.  A wrong dtype raises TypeError, a
     wrong device or shape ValueError, before any launch.  The backward pass needs a handle that linear_device_t accepts: a dense handle, a slice
     stream (FpgaHandle.set_transposable(True) keeps it one) or a tile stream created under FpgaHandle.set_transposable("keep_format");
-    the same holds for grad_values.
+    the same holds for grad_values.  For a deterministic backward create the handle under FpgaHandle.set_transposable("companion"):
+    grad_x then runs the forward kernels over the handle's stored transpose and has the same bits from run to run, like y and
+    grad_values.  That costs the device bytes and creation time of a second copy of the matrix (FpgaHandle.companion_info), and every
+    value update writes both.
 
     values=None: the matrix values are those the handle holds and are not differentiable; launches and autograd graph are those of a
     call without the parameter.

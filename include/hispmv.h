@@ -229,19 +229,64 @@ int hispmv_value_storage_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out
  * the tall, tallgap and paired tile-stream geometries.  Several vectors per pass: hispmv_linear_device_t below. */
 int hispmv_spmv_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_x, const float* d_bias, float* d_y,
                          float alpha, float beta, void* stream);
-/* Context-wide switch of three states, default OFF, may be flipped between creations (like hispmv_set_value_storage); the state is
+/* Context-wide switch of four states, default OFF, may be flipped between creations (like hispmv_set_value_storage); the state is
  * taken per handle at its creation.
  *   HISPMV_TRANSPOSABLE_SLICES (1): a sparse handle created in this state keeps the slice stream -- the format choice of that
  *     creation is the one HISPMV_FORMAT=slices makes for a whole process -- and is therefore accepted by hispmv_spmv_device_t.
  *   HISPMV_TRANSPOSABLE_KEEP_FORMAT (2): a sparse handle created in this state keeps the loader's own format choice, and if that is a
  *     tile stream the transposed and gradient entries accept it (see ACCEPTED above).  Nothing is stored for it: device_bytes of the
  *     handle is what it is in state OFF.
+ *   HISPMV_TRANSPOSABLE_COMPANION (3): a sparse handle created in this state is what state KEEP_FORMAT makes it, and owns a STORED
+ *     TRANSPOSE besides (the "companion", below): the transposed entries then issue no atomic.
  * Nothing else about the handle changes.  A handle created in state OFF that happens to be a slice stream is transposable all the
  * same, and so is every dense handle.  Any other value of `enable` -> HISPMV_EINVAL. */
 #define HISPMV_TRANSPOSABLE_OFF 0
 #define HISPMV_TRANSPOSABLE_SLICES 1
 #define HISPMV_TRANSPOSABLE_KEEP_FORMAT 2
+#define HISPMV_TRANSPOSABLE_COMPANION 3
 int hispmv_set_transposable(hispmv_ctx* ctx, int enable);
+/* ---- the stored transpose (HISPMV_TRANSPOSABLE_COMPANION) ---------------------------------------------------------------------------
+ * The companion of a sparse handle is a second, hidden matrix for A^T, made by the ordinary creation path from the SWAPPED INPUT: for
+ * the entries (rows[k], cols[k], values[k]) of a rows x cols input it is (cols[k], rows[k], values[k]) with dimensions cols x rows --
+ * the same entry order k, duplicates and explicit zeros kept.  hispmv_create_sparse_handle_from_csr expands row_ptr to the row of
+ * every entry in input order (before its per-row sort), so entry k is entry k of the documented value order; _from_mtx swaps the
+ * entries its reader produced (and stays refused together with value updates).  The companion is created under the context's format
+ * options, value storage and value-updates switch as they stand at that creation, and may come out as a slice stream, a cut matrix
+ * (column tiles, band tiles, stray split) or a standard-geometry tile stream; it builds no batch layout, since it is never part of a
+ * batch call.  It is not a handle: indices, hispmv_num_matrices and creation order are what they are without it.  Dense handles
+ * ignore the state.  Creation in this state under HISPMV_TTS_GEOMETRY other than standard or under HISPMV_TTS_SMALL -> HISPMV_EINVAL.
+ *  - ARENA: device_bytes (and prep_seconds) of the handle is the sum of both, the companion's value map and chunk table included on an
+ *    updatable handle.  The capacity check runs once, on the sum: when it does not fit, creation returns HISPMV_FULL, nothing is
+ *    registered or charged and the context is as before the call.  hispmv_value_storage_info and the plan fields of
+ *    hispmv_get_matrix_info describe the handle's own layouts, as without a companion.
+ *  - LOAD: hispmv_load_matrices uploads the companion with its owner and, on an updatable handle, builds its value map the same way.
+ *  - UPDATES: hispmv_update_values(_device) takes the same n values in the same order and writes the handle's layouts, its batch layout
+ *    and the companion's layouts on the call's stream.  hispmv_value_update_info out[3] includes the companion's slots, out[1] is n.
+ *  - TRANSPOSED ENTRIES: hispmv_spmv_device_t and hispmv_linear_device_t on such a handle run the forward launches over the companion.
+ *    Their argument checks are unchanged.  In place of the ORDER, ZERO SLOTS and "ordinary device memory" clauses above:
+ *      BITS: for every vector v, y_v has the bits of a one-vector hispmv_linear_device call (the fix-up carry variant) on a handle
+ *        created from the swapped input under the same switches, with bias_v, alpha and beta -- whatever the batch around the vector,
+ *        and from run to run.
+ *      ZERO SLOTS and non-finite inputs behave as in that forward product: the rule "a +-0 slot adds nothing" of the atomics route
+ *        does NOT apply (0 * Inf is NaN here, as in every forward call).
+ *      alpha == 0 still gives exactly beta * bias per vector through the prologue launch and reads neither x nor the matrix;
+ *        beta == 0 does not read the bias.  bias_stride = cols and d_bias == d_y keep working: every y element's bias is read by the
+ *        thread that stores it.
+ *      WIDTHS: the vectors go in passes of the widths hispmv_linear_device takes on the companion for beta != 0 -- 4, 2, 1 on a slice
+ *        stream or cut matrix, the tile-stream rules on a tile stream -- for beta == 0 too.  A per-vector bias on a tile-stream
+ *        companion takes one vector per launch (the batched tile kernel takes one shared bias).  A d_x that is not 16-byte aligned,
+ *        or rows % 4 != 0 where the companion's plan has a window, falls to width 1, with the same bits.
+ *      d_y may be any memory the device can write: the stores are plain.
+ *      OWNERSHIP: the companion's carries and partial vectors belong to the handle, so ONE transposed call per handle may be in
+ *        flight.  A forward and a transposed call on the same handle may overlap: they use separate matrices, carries and partial
+ *        vectors.  hispmv_value_grad_device reads only the handle's own layouts and is unchanged.
+ *  - hispmv_transpose_info reports {1, launches of a one-vector call, 0, 0}; hispmv_linear_info reports the companion route's widest
+ *    pass, passes and launches (shared bias, aligned d_x) in its three transposed fields.  For a cut companion's one-vector passes the
+ *    launch figure is that of a batch call of one matrix: one grid per workgroup size among its parts, plus its tail.
+ * There is no per-call choice between the two routes, and no companion inside hispmv_spmv_device_batch.
+ * hispmv_companion_info: out = {1 if the handle owns a companion, its format (hispmv_matrix_info.format), its parts, its device bytes,
+ * its value map slots, its tile kind (hispmv_matrix_info.tile_kind)}; zeros for a handle without one. */
+int hispmv_companion_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[6]);
 /* out = {1 if hispmv_spmv_device_t accepts the (loaded) handle; launches of one call with alpha != 0 (the prologue y = beta * bias +
  * one per part); bytes of float atomic adds to y per call (window flushes + stray flushes + direct adds); stream elements that add
  * to y directly, one atomic each (elements outside their group's window, every stored slot -- fillers included, which add nothing
@@ -249,7 +294,7 @@ int hispmv_set_transposable(hispmv_ctx* ctx, int enable);
  * the direct adds scatter over up to 64 lines per wave-instruction, the expensive one.  An accepted tile stream reports {1, 1 + 1,
  * 4 * nnz, nnz}, nnz the stored words that are neither filler nor padding: upper bounds, since a word whose value is +-0 (an explicit
  * zero) issues no atomic; its adds touch tts_lines_per_gather lines per wave-instruction.  Zeros for a handle that is not
- * transposable or not loaded. */
+ * transposable or not loaded.  A handle with a stored transpose: {1, launches of a one-vector call over it, 0, 0} (see above). */
 int hispmv_transpose_info(const hispmv_ctx* ctx, int matrix_idx, int64_t out[4]);
 
 /* ---- several vectors on device pointers (no reference counterpart: FpgaHandle::runLinear takes host vectors and relaunches per
@@ -463,6 +508,12 @@ int hispmv_prep_step_queue(const double* slice_costs, int32_t n_slice, const dou
  * plan for n_cus compute units, 0 for the entries that gather through L2 -- the criterion by which the loader splits a matrix with a
  * few per cent of stray couplings into a windowed part and a stray part (hispmv_matrix_info.tile_kind 3). */
 int hispmv_prep_window_membership(const hispmv_prep* p, int n_cus, uint8_t* inside);
+
+/* The swapped COO of a CSR input in INPUT ORDER -- what hispmv_create_sparse_handle_from_csr makes a stored transpose from
+ * (HISPMV_TRANSPOSABLE_COMPANION): for entry k of col_idx, in ascending k and before any per-row sort, out_rows[k] = col_idx[k] and
+ * out_cols[k] = the row whose row_ptr range holds k.  Both outputs hold row_ptr[rows] entries.  row_ptr must start at 0 and be
+ * non-decreasing -> HISPMV_EINVAL otherwise. */
+int hispmv_prep_swapped_coo_from_csr(const int32_t* row_ptr, const int32_t* col_idx, int32_t rows, int32_t* out_rows, int32_t* out_cols);
 
 /* Applies that plan to the prepared stream IN PLACE (the words of LDS-staged groups then carry window
  * indices instead of columns -- or 0x40000000 | column for the elements of the group whose 64-byte block of x
