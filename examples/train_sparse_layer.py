@@ -11,8 +11,13 @@ the fp32 master copy, every forward pass pushes it and the handle keeps R(v), th
 --companion creates the layer under set_transposable("companion"): the handle stores its transpose as well, grad_x runs the forward
 kernels over it (no atomics), and two runs print the same losses bit for bit.  companion_info says what the second copy costs.
 
+--spmm routes the forward product and grad_x through the wide-batch entries (sparse_linear(..., spmm=True)): the activations are
+transposed to feature-major, the lanes of a wavefront are the vectors of the batch and the matrix is read once per tile of up to 256
+vectors.  It needs a slice-stream handle (without --companion the handle always is one; with it, grad_x runs over the stored
+transpose when that is a slice stream and through the atomics otherwise).  The update pass and the value gradient are unchanged.
+
     python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1] [--bf16]
-                                          [--companion]
+                                          [--companion] [--spmm]
 """
 from __future__ import annotations
 
@@ -55,9 +60,9 @@ def train(a, r, c, start, teacher, storage: str) -> list:
         # sparse_linear(values=...) orders with two host waits per pass.  On one real stream nothing waits.
         with torch.cuda.stream(torch.cuda.Stream(device=dev)):
             with torch.no_grad():
-                target = sparse_linear(h, i, x, bias, values=teacher_d)
+                target = sparse_linear(h, i, x, bias, values=teacher_d, spmm=a.spmm)
             for step in range(a.steps):
-                y = sparse_linear(h, i, x, bias, values=v)
+                y = sparse_linear(h, i, x, bias, values=v, spmm=a.spmm)
                 loss = ((y - target) ** 2).mean() * a.rows
                 loss.backward()
                 with torch.no_grad():
@@ -83,6 +88,7 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--bf16", action="store_true", help="train a second time on a bf16 handle and print both final losses")
     ap.add_argument("--companion", action="store_true", help="store the transpose with the handle: a deterministic backward pass, for its bytes")
+    ap.add_argument("--spmm", action="store_true", help="forward and grad_x through the wide-batch entries (feature-major operands, lanes across vectors)")
     a = ap.parse_args()
 
     rng = np.random.default_rng(0)

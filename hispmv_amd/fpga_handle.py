@@ -299,6 +299,42 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range") if num_vecs >= 1 else ValueError("num_vecs must be at least 1")
         return {"accepted": bool(out[0]), "width": int(out[1]), "passes": int(out[2]), "launches": int(out[3])}
 
+    def spmm_device(self, matrix_idx: int, d_xt: int, num_vecs: int, d_bias: int, d_yt: int, alpha: float = 1.0, beta: float = 0.0,
+                    ld_x=None, ld_y=None, bias_stride: int = 0, work: int = 0, work_bytes: int = 0, stream: int = 0) -> None:
+        """yt[r, v] = alpha * sum_k a_rk * xt[k, v] + beta * bias for num_vecs vectors on device pointers (ints), operands FEATURE-MAJOR:
+        xt is [cols, ld_x], yt [rows, ld_y], row-major, ld (default num_vecs) >= num_vecs (hispmv_spmm_device).  The lanes of a wavefront
+        are vectors and the matrix is read once per tile of up to 256 vectors, not once per 4 as in linear_device.  bias_stride 0: d_bias
+        is bias[rows]; ld_y: a matrix laid out like yt, which may be yt (in place).  `work` points at work_bytes >=
+        spmm_info(...)["work_bytes"] bytes of the caller's; nothing is kept in the handle, so calls with different workspaces may overlap.
+        No atomics: the bits of a vector depend neither on the batch nor on the run (they are not linear_device's bits).  Asynchronous on
+        `stream`.  Slice-stream handles only: a tile-stream or dense handle raises NotImplementedError."""
+        self._check(lib.hispmv_spmm_device(self._ctx, int(matrix_idx), C.c_void_p(d_xt), int(num_vecs), int(num_vecs if ld_x is None else ld_x),
+                                           C.c_void_p(d_bias), int(bias_stride), C.c_void_p(d_yt), int(num_vecs if ld_y is None else ld_y),
+                                           float(alpha), float(beta), C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def spmm_device_t(self, matrix_idx: int, d_xt: int, num_vecs: int, d_bias: int, d_yt: int, alpha: float = 1.0, beta: float = 0.0,
+                      ld_x=None, ld_y=None, bias_stride: int = 0, work: int = 0, work_bytes: int = 0, stream: int = 0) -> None:
+        """spmm_device with A^T: xt is [rows, ld_x], yt [cols, ld_y] (hispmv_spmm_device_t); work_bytes >= spmm_info(...)["work_bytes_t"].
+        Runs the same launches over the handle's stored transpose: only a handle created under set_transposable("companion") whose
+        companion is a slice stream is accepted, any other raises NotImplementedError.  Per vector the bits of spmm_device on a handle
+        made from the swapped COO."""
+        self._check(lib.hispmv_spmm_device_t(self._ctx, int(matrix_idx), C.c_void_p(d_xt), int(num_vecs), int(num_vecs if ld_x is None else ld_x),
+                                             C.c_void_p(d_bias), int(bias_stride), C.c_void_p(d_yt), int(num_vecs if ld_y is None else ld_y),
+                                             float(alpha), float(beta), C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def spmm_info(self, matrix_idx: int, num_vecs: int, ld=None) -> dict:
+        """{"accepted", "accepted_t", "vl", "tiles", "launches", "work_bytes", "work_bytes_t"} of spmm_device / spmm_device_t for num_vecs
+        vectors with ld_x = ld_y = ld (default num_vecs) and 16-byte aligned pointers (hispmv_spmm_info): the vectors per lane of the
+        first tile, the vector tiles, the launches of a call with alpha != 0, the workspace bytes (valid for every alignment)."""
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_spmm_info(self._ctx, int(matrix_idx), int(num_vecs), int(num_vecs if ld is None else ld), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError("num_vecs must be at least 1 and ld at least num_vecs")
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "accepted_t": bool(out[1]), "vl": int(out[2]), "tiles": int(out[3]), "launches": int(out[4]),
+                "work_bytes": int(out[5]), "work_bytes_t": int(out[6])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

@@ -266,6 +266,16 @@ def step_queue(slice_costs, tile_costs, n_wg: int = 256, mode: int = 0):
     return cls, idx
 
 
+def spmm_tiles(cols: int, num_vecs: int, ld=None, align_bytes: int = 16) -> dict:
+    """The vector tiles of a wide call (hispmv_prep_spmm_tiles), host-only: {"vl", "tiles", "last_vecs", "vl_last"} for num_vecs
+    vectors against a matrix of `cols` columns, leading dimension ld (default num_vecs), pointers aligned to align_bytes."""
+    out = (C.c_int64 * 4)()
+    rc = lib.hispmv_prep_spmm_tiles(int(cols), int(num_vecs), int(num_vecs if ld is None else ld), int(align_bytes), out)
+    if rc != HISPMV_OK:
+        raise ValueError("hispmv_prep_spmm_tiles: cols, num_vecs, ld and align_bytes must be at least 1, ld at least num_vecs")
+    return {"vl": int(out[0]), "tiles": int(out[1]), "last_vecs": int(out[2]), "vl_last": int(out[3])}
+
+
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 

@@ -19,6 +19,9 @@ there, at the price of two host waits per pass.  Inside ``with torch.cuda.stream
 real stream and nothing waits (examples/train_sparse_layer.py).  Without ``values`` the layer adds no wait, as before: on the default
 stream the caller synchronises between torch's operations and the layer.
 
+``spmm=True`` routes the forward product and grad_x through the wide-batch entries (FpgaHandle.spmm_device / spmm_device_t) on
+feature-major copies of the activations; the default route is unchanged (see sparse_linear).
+
 The backward pass is differentiable once (no double backward).  The autograd graph keeps a reference to the handle, which keeps the
 object alive but not open: the handle must not be closed between forward and backward (a closed handle makes backward raise, it does
 not launch).  torch is imported inside the functions, as in hispmv_amd/dist.py."""
@@ -126,7 +129,104 @@ def _function_values(torch):
     return SparseLinearValues
 
 
-def sparse_linear(handle, idx: int, x, bias=None, values=None):
+def _function_spmm(torch):
+    fn = getattr(_function_spmm, "cached", None)
+    if fn is not None:
+        return fn
+
+    def operands(a, n_out, work_bytes, ld):
+        """torch's side of a wide call on a [B, n_in] tensor: -> (at [n_in, ld] with the batch in its first B columns, out [n_out, ld],
+        the workspace).  ld is B rounded up to 4, so that every batch takes the lane widths its size allows; the pad columns of
+        `at` are zeros and those of `out` are not written."""
+        B = a.shape[0]
+        if ld == B:
+            at = a.t().contiguous()
+        else:
+            at = torch.zeros((a.shape[1], ld), dtype=torch.float32, device=a.device)
+            at[:, :B] = a.t()
+        out = torch.empty((n_out, ld), dtype=torch.float32, device=a.device)
+        work = torch.empty((max(work_bytes, 4) + 3) // 4, dtype=torch.float32, device=a.device)
+        return at, out, work
+
+    class SparseLinearSpmm(torch.autograd.Function):
+        """sparse_linear with spmm=True: forward through spmm_device, grad_x through spmm_device_t where the handle has a slice-stream
+        companion (linear_device_t otherwise); `values` (or None), the update pass and the value gradient as in the other two functions.
+        Every pass first lets torch build what the library reads (the transposed activations, contiguous bias and values, the result
+        and the workspace) and only then launches.  On torch's default stream (handle 0 = the context's own stream, which is not
+        ordered with torch's kernels) it waits on the host between the two, and again for the context's stream behind the launches;
+        torch's temporaries stay referenced until that second wait is over."""
+
+        @staticmethod
+        def forward(ctx, x, bias, values, handle, idx, rows):
+            ctx.handle, ctx.idx, ctx.has_bias, ctx.has_values = handle, idx, bias is not None, values is not None
+            current = torch.cuda.current_stream(x.device)
+            stream = current.cuda_stream
+            B = x.shape[0]
+            ld = (B + 3) & ~3
+            info = handle.spmm_info(idx, B, ld)
+            v = values.contiguous() if values is not None else None
+            b = bias.contiguous() if bias is not None else None
+            xt, yt, work = operands(x, rows, info["work_bytes"], ld)
+            if stream == 0:
+                current.synchronize()          # torch's kernels above are done before the context's stream reads their results
+            if v is not None:
+                handle.update_values_device(idx, v.data_ptr(), v.numel(), stream)
+                ctx.n = v.numel()
+            handle.spmm_device(idx, xt.data_ptr(), B, b.data_ptr() if b is not None else 0, yt.data_ptr(), 1.0, 1.0 if b is not None else 0.0,
+                               ld_x=ld, ld_y=ld, work=work.data_ptr(), work_bytes=info["work_bytes"], stream=stream)
+            if stream == 0:
+                handle.synchronize()           # ... and xt, work, b, v are released only behind the launches that read them
+            del xt, work, b, v
+            ctx.cols = x.shape[1]
+            if values is not None and values.requires_grad:          # x is kept for the value gradient only
+                ctx.save_for_backward(x.contiguous())
+            return yt[:, :B].t()
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_y):
+            grad_x = grad_bias = grad_values = None
+            handle, idx = ctx.handle, ctx.idx
+            current = torch.cuda.current_stream(grad_y.device)
+            stream = current.cuda_stream
+            B = grad_y.shape[0]
+            ld = (B + 3) & ~3
+            if ctx.has_bias and ctx.needs_input_grad[1]:
+                grad_bias = grad_y.sum(0)
+            want_x, want_v = ctx.needs_input_grad[0], ctx.has_values and ctx.needs_input_grad[2]
+            # torch's side first: everything the launches below read or write
+            info = handle.spmm_info(idx, B, ld) if want_x else None
+            wide_t = want_x and info["accepted_t"]
+            g = gt = gxt = work = x = None
+            if wide_t:
+                gt, gxt, work = operands(grad_y, ctx.cols, info["work_bytes_t"], ld)
+            if want_v or (want_x and not wide_t):
+                g = grad_y.contiguous()
+            if want_x and not wide_t:
+                grad_x = torch.empty((B, ctx.cols), dtype=torch.float32, device=grad_y.device)
+            if want_v:
+                (x,) = ctx.saved_tensors
+                grad_values = torch.empty((ctx.n,), dtype=torch.float32, device=grad_y.device)
+            if stream == 0 and (want_x or want_v):
+                current.synchronize()
+            if wide_t:
+                handle.spmm_device_t(idx, gt.data_ptr(), B, 0, gxt.data_ptr(), 1.0, 0.0, ld_x=ld, ld_y=ld, work=work.data_ptr(),
+                                     work_bytes=info["work_bytes_t"], stream=stream)
+                grad_x = gxt[:, :B].t()
+            elif want_x:
+                handle.linear_device_t(idx, g.data_ptr(), B, 0, grad_x.data_ptr(), 1.0, 0.0, 0, stream)
+            if want_v:
+                handle.value_grad_device(idx, g.data_ptr(), x.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, stream)
+            if stream == 0 and (want_x or want_v):
+                handle.synchronize()
+            del g, gt, work
+            return grad_x, grad_bias, grad_values, None, None, None
+
+    _function_spmm.cached = SparseLinearSpmm
+    return SparseLinearSpmm
+
+
+def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = False):
     """y = A x (+ bias) for the loaded matrix `idx` of `handle` (an FpgaHandle): x is a float32 CUDA tensor [B, cols] or [cols] (made
     contiguous), the result [B, rows] (or [rows]); bias, if given, a float32 CUDA tensor [rows].  Differentiable in x and bias (grad_x =
     A^T grad_y through linear_device_t, grad_bias = grad_y.sum(0)).  Runs on torch's current stream.  A wrong dtype raises TypeError, a
@@ -157,7 +257,19 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None):
     Streams, with values: on torch's DEFAULT stream (handle 0, which the library reads as the context's own stream) forward and
     backward each wait on the host for the default stream before their launches and for the context's stream after them, so
     ``v -= lr * v.grad`` followed by the next forward is ordered; on any other current stream nothing waits.  A loop that should not
-    wait on the host runs inside ``with torch.cuda.stream(torch.cuda.Stream()):``."""
+    wait on the host runs inside ``with torch.cuda.stream(torch.cuda.Stream()):``.
+
+    spmm=False (default): nothing changes -- the launches and the autograd graph of a call without the parameter.  spmm=True routes the
+    products through the wide-batch entries (FpgaHandle.spmm_device): forward transposes x to feature-major ([cols, B], contiguous),
+    allocates the result and the workspace with torch.empty on the current stream, multiplies with the shared bias and returns the
+    transposed view [B, rows] of the result; grad_x does the same through spmm_device_t when the handle owns a slice-stream companion
+    (FpgaHandle.set_transposable("companion"): deterministic), and falls back to linear_device_t otherwise.  The matrix is then read
+    once per tile of up to 256 vectors instead of once per 4.  y and grad_x are deterministic but are not the bits of spmm=False (the
+    row sums are sequential, not a segmented scan).  A handle spmm_device does not accept (a tile stream, a dense handle) raises
+    NotImplementedError before any launch.  With `values`, the update pass and value_grad_device stay as they are.  The feature-major
+    copies have a leading dimension of B rounded up to 4 (pad columns zero), so that an odd batch still takes the lane widths its size
+    allows.  On torch's default stream every pass waits on the host after torch has built those copies and again behind the library's
+    launches (the context's stream is not ordered with torch's kernels)."""
     import torch
     info = handle.matrix_info(idx)
     _check_tensor(torch, x, "x", info["cols"], (1, 2))
@@ -168,6 +280,12 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None):
     if x.dim() == 2 and x.shape[0] == 0:
         raise ValueError("x holds no vector")
     one = x.dim() == 1
+    if spmm and not handle.spmm_info(idx, 1)["accepted"]:
+        raise NotImplementedError("sparse_linear(spmm=True) needs a loaded slice-stream handle (FpgaHandle.set_transposable(True) keeps a sparse "
+                                  "handle one); tile-stream and dense handles have no wide-batch kernel")
+    if values is None and spmm:
+        y = _function_spmm(torch).apply(x.unsqueeze(0) if one else x, bias, None, handle, int(idx), info["rows"])
+        return y.squeeze(0) if one else y
     if values is None:
         y = _function(torch).apply(x.unsqueeze(0) if one else x, bias, handle, int(idx), info["rows"])
         return y.squeeze(0) if one else y
@@ -177,5 +295,8 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None):
     _check_tensor(torch, values, "values", upd["n"], (1,))
     if values.device != x.device:
         raise ValueError("values must be on the device of x")
+    if spmm:
+        y = _function_spmm(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])
+        return y.squeeze(0) if one else y
     y = _function_values(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])
     return y.squeeze(0) if one else y

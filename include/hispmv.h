@@ -395,6 +395,58 @@ int hispmv_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gy,
  * alpha != 0 (one per part and pass; dense: one)}.  Zeros for a handle that is not accepted or not loaded. */
 int hispmv_value_grad_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t out[4]);
 
+/* ---- wide batch on feature-major operands (no reference counterpart: the reference relaunches per vector) --------------------------
+ *   hispmv_spmm_device:    yt[r, v] = alpha * sum_k a_rk * xt[k, v] + beta * bias,      r < rows, v < num_vecs
+ *   hispmv_spmm_device_t:  the same with A^T: xt is [rows, ld_x], yt is [cols, ld_y]
+ * d_xt is [cols, ld_x], d_yt is [rows, ld_y], row-major, ld_x, ld_y >= num_vecs >= 1: one stored element of A needs one contiguous run
+ * of num_vecs floats of xt.  The 64 lanes of a wavefront are 64 * VL vectors (VL = 4, 2 or 1 consecutive vectors per lane), the stored
+ * elements are walked in stream order, and the matrix stream is read once per tile of 64 * VL vectors -- hispmv_linear_device reads it
+ * once per 4 vectors.  Device pointers, 4-byte aligned, asynchronous on `stream` (the stream rule above: NULL = the context's stream).
+ *  - BIAS: bias_stride == 0: d_bias is one vector of rows floats, bias[r] under every vector; bias_stride == ld_y: d_bias is a matrix
+ *    laid out like d_yt and may BE d_yt (yt = alpha * A xt + beta * yt in place); anything else -> HISPMV_EINVAL.  beta == 0 never reads
+ *    d_bias (it may be NULL or hold NaN).  alpha == 0 gives exactly beta * bias; neither xt nor the matrix is read.
+ *  - The floats num_vecs .. ld_y - 1 of a row of d_yt are not written.
+ *  - ZERO SLOTS: a stored slot whose value is +-0 contributes nothing, whatever xt holds (fillers of empty rows, row extensions,
+ *    padding, explicit zeros): the rule of hispmv_spmv_device_t.
+ *  - BITS: no float atomics, no look-back, no waiting between workgroups.  Every yt[r, v] has exactly one writer per launch, and its
+ *    sum has a fixed order: inside a slice the elements in stream order from +0; a row cut by slice boundaries is the partial sums of
+ *    its slices in ascending order from +0; then alpha * sum + beta * bias, every product and add unfused.  The bits of vector v
+ *    therefore depend neither on num_vecs, nor on the tile or VL that carried it, nor on the run.  They are NOT the bits of
+ *    hispmv_linear_device, whose row sums come out of a segmented scan.
+ *  - ACCEPTED: every loaded sparse handle whose device format is the slice stream, whatever its groups (no window, compact, wide, stray
+ *    slots, half) and parts (column tiles, band tiles, the two parts of a stray split).  The parts run one after the other on the
+ *    stream inside every vector tile: part 0 with the caller's beta * bias, each later part adding into d_yt in place.  A tile-stream
+ *    handle -> HISPMV_ENOTSUP (the message names hispmv_set_transposable(ctx, 1), which keeps the slice stream); a dense handle ->
+ *    HISPMV_ENOTSUP (a wide batch against a dense W is a GEMM).  hispmv_spmm_device_t is accepted only on a handle created in state
+ *    HISPMV_TRANSPOSABLE_COMPANION whose stored transpose is a slice stream, and runs the same launches over it: per vector the bits of
+ *    hispmv_spmm_device on a handle made from the swapped input; any other handle -> HISPMV_ENOTSUP (the message names the state).
+ *  - WORKSPACE: d_work holds at least the bytes hispmv_spmm_info reports for (num_vecs, ld) -- per slice of the largest part, two
+ *    partial sums of 64 * VL floats for the rows cut by slice boundaries -- and is the caller's: the library allocates nothing for these
+ *    entries and keeps no per-handle state for them.  Two calls on one handle with two workspaces may therefore be in flight at once
+ *    (unlike hispmv_linear_device); two calls that share a workspace must be ordered.  Its contents mean nothing between calls.
+ *  - Errors, all before any launch: not loaded -> HISPMV_ESTATE; HISPMV_ENOTSUP as above; num_vecs < 1, ld_x or ld_y < num_vecs,
+ *    work_bytes smaller than hispmv_spmm_info reports for (num_vecs, ld_x, ld_y), NULL d_xt or d_yt, NULL d_bias with beta != 0,
+ *    d_xt == d_yt, d_bias == d_yt with bias_stride 0, a bad index -> HISPMV_EINVAL.
+ * Out of scope: tile-stream and dense handles, a transposed wide product without a stored transpose, a wide value gradient, wide calls
+ * inside hispmv_spmv_device_batch or the step kernel, sharding over devices, host-pointer variants, bf16 activations. */
+int hispmv_spmm_device(hispmv_ctx* ctx, int matrix_idx, const float* d_xt, int64_t num_vecs, int64_t ld_x, const float* d_bias,
+                       int64_t bias_stride, float* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
+int hispmv_spmm_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_xt, int64_t num_vecs, int64_t ld_x, const float* d_bias,
+                         int64_t bias_stride, float* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
+/* For num_vecs vectors with ld_x = ld_y = ld and 16-byte aligned pointers, out = {1 if hispmv_spmm_device accepts the (loaded) handle,
+ * 1 if hispmv_spmm_device_t does, VL of the first vector tile, vector tiles, launches of a call with alpha != 0 (per tile and part the
+ * slice grid, and the cut rows where the part has any), work_bytes of hispmv_spmm_device, work_bytes of hispmv_spmm_device_t, 0}.
+ * out[2..5] describe the forward entry and are zeros where it is not accepted.  Pointers aligned to less than 16 bytes may take a
+ * smaller VL (hispmv_prep_spmm_tiles) and more tiles; the workspace figures hold for every alignment.  Zeros for a handle that is not loaded. */
+int hispmv_spmm_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t ld, int64_t out[8]);
+/* The vector tiles of a wide call (host-only, no device needed).  A lane owns VL in {4, 2, 1} consecutive vectors and reads them with
+ * one dwordx4, dwordx2 or dword load per stored element; a tile is 64 * VL vectors.  Every tile takes the largest VL such that
+ *   (a) 64 * (VL / 2) < vectors left;   (b) cols * 64 * VL * 4 <= 8 MiB: VL 4 up to 8192 columns, VL 2 up to 16384 (a cap
+ *   on the columns taken from a measurement at 8192, not a cache bound: DESIGN.md 2.12);   (c) ld % VL == 0 and align_bytes % (4 * VL) == 0.
+ * The last tile is masked per lane.  out = {VL of the first tile, tiles, vectors in the last tile, VL of the last tile}.  cols,
+ * num_vecs, ld or align_bytes < 1, or ld < num_vecs -> HISPMV_EINVAL. */
+int hispmv_prep_spmm_tiles(int64_t cols, int64_t num_vecs, int64_t ld, int64_t align_bytes, int64_t out[4]);
+
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */
 float hispmv_time_device(hispmv_ctx* ctx, int matrix_idx, const float* d_x, const float* d_bias, float* d_y,
