@@ -16,8 +16,11 @@ transposed to feature-major, the lanes of a wavefront are the vectors of the bat
 vectors.  It needs a slice-stream handle (without --companion the handle always is one; with it, grad_x runs over the stored
 transpose when that is a slice stream and through the atomics otherwise).  The update pass and the value gradient are unchanged.
 
+--wide-grad (implies --spmm) takes the value gradient through the wide-batch entry as well (sparse_linear(..., wide_grad=True)): the
+feature-major copies of x and grad_y serve all three products of a step.
+
     python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1] [--bf16]
-                                          [--companion] [--spmm]
+                                          [--companion] [--spmm] [--wide-grad]
 """
 from __future__ import annotations
 
@@ -60,9 +63,9 @@ def train(a, r, c, start, teacher, storage: str) -> list:
         # sparse_linear(values=...) orders with two host waits per pass.  On one real stream nothing waits.
         with torch.cuda.stream(torch.cuda.Stream(device=dev)):
             with torch.no_grad():
-                target = sparse_linear(h, i, x, bias, values=teacher_d, spmm=a.spmm)
+                target = sparse_linear(h, i, x, bias, values=teacher_d, spmm=a.spmm, wide_grad=a.wide_grad)
             for step in range(a.steps):
-                y = sparse_linear(h, i, x, bias, values=v, spmm=a.spmm)
+                y = sparse_linear(h, i, x, bias, values=v, spmm=a.spmm, wide_grad=a.wide_grad)
                 loss = ((y - target) ** 2).mean() * a.rows
                 loss.backward()
                 with torch.no_grad():
@@ -89,7 +92,9 @@ def main() -> None:
     ap.add_argument("--bf16", action="store_true", help="train a second time on a bf16 handle and print both final losses")
     ap.add_argument("--companion", action="store_true", help="store the transpose with the handle: a deterministic backward pass, for its bytes")
     ap.add_argument("--spmm", action="store_true", help="forward and grad_x through the wide-batch entries (feature-major operands, lanes across vectors)")
+    ap.add_argument("--wide-grad", action="store_true", help="the value gradient through the wide-batch entry as well (implies --spmm)")
     a = ap.parse_args()
+    a.spmm = a.spmm or a.wide_grad
 
     rng = np.random.default_rng(0)
     r, c = np.nonzero(rng.random((a.rows, a.cols)) < a.density)

@@ -1,8 +1,10 @@
 // hispmv_spmm_abi.cpp -- the wide-batch entries of the C ABI (include/hispmv.h: hispmv_spmm_device, hispmv_spmm_device_t,
-// hispmv_spmm_info, hispmv_prep_spmm_tiles) over the launchers of hispmv_spmm.h.  A translation unit of its own: the entries read a
-// loaded handle's device tables and keep nothing in it, so the other entry points are not touched.
+// hispmv_spmm_info, hispmv_prep_spmm_tiles, hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_info) over the launchers of
+// hispmv_spmm.h and hispmv_spmm_grad.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
+// nothing in it, so the other entry points are not touched.
 #include "hispmv_ctx.h"
 #include "hispmv_spmm.h"
+#include "hispmv_spmm_grad.h"
 
 using namespace hispmv;
 
@@ -135,4 +137,80 @@ HISPMV_API int hispmv_spmm_device_t(hispmv_ctx* c, int idx, const float* d_xt, i
                                            "; create it after hispmv_set_transposable(ctx, 3) (FpgaHandle.set_transposable(\"companion\"))");
     if (!t->loaded) return fail(c, HISPMV_ESTATE, "internal: the stored transpose is not loaded");
     return run_spmm(c, *t, "spmm_device_t", d_xt, num_vecs, ld_x, d_bias, bias_stride, d_yt, ld_y, alpha, beta, d_work, work_bytes, stream);
+}
+
+// ---- wide-batch value gradient (include/hispmv.h: hispmv_spmm_value_grad_device; kernels: hispmv_spmm_grad.hip) ---------------------
+namespace {
+
+// launches of one vector tile: one per part that holds slices (none for a handle without entries)
+int64_t grad_launches_of(const Matrix& m) {
+    if (m.upd_n <= 0) return 0;
+    int64_t n = 0;
+    for (auto& p : m.parts) n += (p.dev.n_slices > 0 && p.dev.n_groups > 0) ? 1 : 0;
+    return n;
+}
+
+}  // namespace
+
+HISPMV_API int hispmv_spmm_value_grad_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t ld, int64_t out[4]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size() || num_vecs < 1 || ld < num_vecs) return HISPMV_EINVAL;
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    const Matrix& m = *c->mats[(size_t)idx];
+    if (!m.loaded || !m.updatable || !spmm_accepts(m)) return HISPMV_OK;
+    const SpmmTiles tl = spmm_tiles(m.cols, num_vecs, ld, ld, 16);
+    out[0] = 1; out[1] = tl.vl_first; out[2] = tl.tiles; out[3] = grad_launches_of(m) * tl.tiles;
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_spmm_value_grad_device(hispmv_ctx* c, int idx, const float* d_gyt, int64_t ld_gy, const float* d_xt, int64_t ld_x, int64_t num_vecs,
+                                             float* d_grad, float alpha, float beta, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[(size_t)idx];
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmm_value_grad_device called before load_matrices");
+    if (m.dense)
+        return fail(c, HISPMV_ENOTSUP, "spmm_value_grad_device: this is a dense handle; the value gradient of a dense W over a wide batch is a GEMM (gyt * xt^T), "
+                                       "which this library leaves to a GEMM library");
+    if (!spmm_accepts(m))
+        return fail(c, HISPMV_ENOTSUP, "spmm_value_grad_device: this handle is a transposed tile stream, which has no wide-batch kernel; create it after "
+                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    if (!m.updatable) return fail(c, HISPMV_ESTATE, "spmm_value_grad_device: handle was not created with value updates on (hispmv_set_value_updates)");
+    const std::string w("spmm_value_grad_device");
+    if (num_vecs < 1) return fail(c, HISPMV_EINVAL, w + ": num_vecs must be at least 1");
+    if (num_vecs > 0x7fffffffLL) return fail(c, HISPMV_EINVAL, w + ": num_vecs must stay below 2^31");
+    if (ld_gy < num_vecs || ld_x < num_vecs) return fail(c, HISPMV_EINVAL, w + ": ld_gy and ld_x must be at least num_vecs");
+    if (!d_gyt || !d_xt || (m.upd_n > 0 && !d_grad)) return fail(c, HISPMV_EINVAL, "NULL device vector");
+    if (d_grad && ((const float*)d_grad == d_gyt || (const float*)d_grad == d_xt)) return fail(c, HISPMV_EINVAL, w + ": grad must not be gyt or xt");
+    if (((uintptr_t)d_gyt | (uintptr_t)d_xt | (uintptr_t)d_grad) & 3) return fail(c, HISPMV_EINVAL, w + ": device pointers must be 4-byte aligned");
+    if (m.upd_n == 0) return HISPMV_OK;
+    // every argument is accepted: from here on the call is one hispmv_synchronize waits for
+    if (stream) c->user_stream = (hipStream_t)stream;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (alpha == 0.0f) {          // grad = beta * grad exactly, gyt and xt not read: the elementwise launch of the transposed prologue, in place
+        constexpr int64_t kPiece = 1LL << 29;
+        for (int64_t at = 0; at < m.upd_n; at += kPiece) {
+            const hipError_t e = launch_transpose_prologue(d_grad + at, d_grad + at, (int32_t)std::min(kPiece, m.upd_n - at), beta, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
+        }
+        return HISPMV_OK;
+    }
+    // Vector tiles one after the other -- the first with the caller's beta, every later one adding in place -- and inside a tile the
+    // parts one after the other, each with its own chunks of the value map: every input entry lives in exactly one slot over all
+    // parts, so a part writes only its own entries.  A lane's VL floats must be one aligned load in every row of gyt and xt.
+    const int64_t align = std::min(pointer_align(d_gyt), pointer_align(d_xt));
+    SpmmGradOperands a{};
+    a.gyt = d_gyt; a.xt = d_xt; a.grad = d_grad; a.ld_gy = ld_gy; a.ld_x = ld_x; a.n = m.upd_n; a.n_vecs = (int)num_vecs; a.alpha = alpha;
+    for (int64_t k = 0; k < num_vecs;) {
+        const int vl = spmm_vl(m.cols, num_vecs - k, ld_x, ld_gy, align);
+        a.tile0 = (int)k; a.beta = k == 0 ? beta : 1.0f;
+        for (auto& p : m.parts) {
+            if (p.dev.n_slices <= 0) continue;
+            const hipError_t e = launch_spmm_grad_part(p.dev, vl, m.d_map + p.map_chunk_base * kValueChunk, a, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_spmm_grad_part");
+        }
+        k += std::min<int64_t>(num_vecs - k, 64 * vl);
+    }
+    return HISPMV_OK;
 }

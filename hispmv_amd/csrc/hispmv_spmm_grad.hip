@@ -1,0 +1,413 @@
+// hispmv_spmm_grad.hip -- the kernels of the wide-batch value gradient (hispmv_spmm_grad.h): grad[k] = alpha * sum_v gyt[row_k, v] *
+// xt[col_k, v] + beta * grad[k] on the slice stream of a loaded, updatable handle, operands feature-major.  Stands on its own like
+// hispmv_spmm.hip: the few decode helpers of the slice format it needs are its own copies, so that hispmv_kernels.hip, hispmv_spmm.hip
+// and hispmv_value_grad.hip are untouched by this file.
+//
+// Roles, against the wide-batch product (hispmv_spmm.hip: spmm_group) and the value gradient of 4 vectors (hispmv_value_grad.hip):
+//   wide-batch product                          value gradient (4-2-1)                     wide-batch value gradient
+//   a lane owns VL vectors                      a lane owns 16 elements of the slice       a lane owns VL vectors
+//   values and metas of a slice                 the metas only                             the metas only
+//   window words hold COLUMN NUMBERS            x window staged per vector                 window words hold column numbers
+//   a lane sums a row sequentially              16 products per lane, summed over vectors  VL products per lane and element, then the sum
+//                                                                                          over the 64 lanes: a butterfly over 64 elements
+//   carry + fix-up launch for cut rows          none                                       none: every element is independent
+// An explicit zero of the input has a map word like every other entry and gets its gradient; a slot whose map word is 0 (fillers,
+// row extensions, padding) writes nothing.
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+
+#include "hispmv_format.h"
+#include "hispmv_spmm_grad.h"
+#include "hispmv_update.h"
+
+namespace hispmv {
+
+namespace {
+
+#define HISPMV_W_GLOBAL __attribute__((address_space(1)))
+__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
+__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
+__device__ __forceinline__ uint4 load_words(const uint4* p) {
+    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+    const u4v v = __builtin_nontemporal_load((const HISPMV_W_GLOBAL u4v*)p);
+    return uint4{v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ uint2 load_words2(const uint2* p) {
+    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+    const u2v v = __builtin_nontemporal_load((const HISPMV_W_GLOBAL u2v*)p);
+    return uint2{v.x, v.y};
+}
+__device__ __forceinline__ int4 load_int4(const int4* p) {
+    typedef int i4v __attribute__((ext_vector_type(4)));
+    const i4v v = *(const HISPMV_W_GLOBAL i4v*)p;
+    return int4{v.x, v.y, v.z, v.w};
+}
+
+// The metas of a slice as they arrive (hispmv_format.h): they begin at byte 4096 of a compact and of a wide slice; the 4 KiB of values
+// before them are not requested.  HALF (bf16 storage): the compact metas of step j, lane l are dwords 2 and 3 of the 16-byte piece at
+// (j * 64 + l) * 16; only those 8 bytes are requested.
+template <bool COMPACT> struct SliceMetas;
+template <> struct SliceMetas<true>  { uint2 m[kSliceSteps]; };
+template <> struct SliceMetas<false> { uint4 m[kSliceSteps]; };
+template <bool COMPACT, bool HALF>
+__device__ __forceinline__ void request_metas(SliceMetas<COMPACT>& s, const char* base, int lane) {
+    static_assert(COMPACT || !HALF, "only a compact group has a half form");
+    if constexpr (HALF) {
+        const uint2* pm = (const uint2*)(base + 8) + 2 * lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 128);
+    } else if constexpr (COMPACT) {
+        const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
+    } else {
+        const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
+    }
+}
+// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j
+template <bool COMPACT>
+__device__ __forceinline__ void decode_metas(const SliceMetas<COMPACT>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
+    if constexpr (COMPACT) {
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) {
+            const unsigned a = s.m[j].x, b = s.m[j].y;
+            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
+            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
+            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
+            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
+    }
+}
+
+// VL consecutive floats of a lane: one dword, dwordx2 or dwordx4 load (the tile rule makes the address a multiple of 4 * VL)
+template <int VL> __device__ __forceinline__ void load_vl(const float* p, float (&x)[VL]) {
+    if constexpr (VL == 4) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v q = *(const HISPMV_W_GLOBAL f4v*)p;
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+    } else if constexpr (VL == 2) {
+        typedef float f2v __attribute__((ext_vector_type(2)));
+        const f2v q = *(const HISPMV_W_GLOBAL f2v*)p;
+        x[0] = q.x; x[1] = q.y;
+    } else {
+        x[0] = *(const HISPMV_W_GLOBAL float*)p;
+    }
+}
+
+// ---- the sum over the 64 lanes, 64 elements at a time -----------------------------------------------------------------------------
+// a, b: the per-lane partials of two elements (level 0), or two values that each hold, in every lane, the sum over the lane's block of
+// 2^LV lanes of one of 2^LV elements -- the element the lane's low LV bits name.  The merge keeps a in the lanes whose bit LV is 0 and b
+// in the others and adds the partner lane's (lane ^ 2^LV) copy of the same value: the result holds sums over blocks of 2^(LV + 1) lanes
+// of 2^(LV + 1) elements, a's where bit LV of the lane is 0.  Level 0 adds lanes (2i, 2i + 1), level 1 pairs of pairs, and so on: the
+// tree of every element is the same pairwise tree, whichever lanes it ends in (IEEE addition commutes).
+//   xor 1, 2: select, select, DPP quad_perm, add.     xor 8: the same with DPP row_ror:8.
+//   xor 4: no row operation swaps the banks of a row, so the partner's copy arrives by row_shl:4 for a (read in the lanes with bit 2
+//          clear) and by row_shr:4 for b (read in the others): add, add, select.
+//   xor 16, 32: v_permlane16_swap / v_permlane32_swap (gfx950) exchange the odd rows (upper half) of a with the even rows (lower half)
+//          of b; after it the two registers ARE kept and partner's copy, so the merge is swap, add -- no select.
+template <int CTRL> __device__ __forceinline__ float dpp_move(float v) {
+    return i2f(__builtin_amdgcn_update_dpp(0, f2i(v), CTRL, 0xf, 0xf, true));
+}
+template <int LV> __device__ __forceinline__ float merge(float a, float b, int lane) {
+    if constexpr (LV == 0 || LV == 1 || LV == 3) {
+        constexpr int ctrl = LV == 0 ? 0xB1 /* quad_perm:[1,0,3,2] */ : LV == 1 ? 0x4E /* quad_perm:[2,3,0,1] */ : 0x128 /* row_ror:8 */;
+        const bool hi = (lane >> LV) & 1;
+        const float keep = hi ? b : a, send = hi ? a : b;
+        return keep + dpp_move<ctrl>(send);
+    } else if constexpr (LV == 2) {
+        const float sa = a + dpp_move<0x104 /* row_shl:4: lane l reads lane l + 4 */>(a);
+        const float sb = b + dpp_move<0x114 /* row_shr:4: lane l reads lane l - 4 */>(b);
+        return (lane & 4) ? sb : sa;
+    } else if constexpr (LV == 4) {
+        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)f2i(a), (unsigned)f2i(b), false, false);
+        return i2f((int)r[0]) + i2f((int)r[1]);
+    } else {
+        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)f2i(a), (unsigned)f2i(b), false, false);
+        return i2f((int)r[0]) + i2f((int)r[1]);
+    }
+}
+// The "binary counter" of one element position k: slot[LV - 1] holds a value of level LV that waits for its partner.  Pair P (0 .. 31)
+// of a step brings the level-1 value of lanes 2P and 2P + 1's elements; it is merged upwards as far as the bits of P carry.  Behind pair
+// 31 the return value is the level-6 value: lane L holds the total of the element of lane L.  (P is wave-uniform: scalar branches.)
+struct Counter { float slot[5]; };
+__device__ __forceinline__ float counter_push(Counter& c, float t, int P, int lane) {
+    if (!(P & 1)) { c.slot[0] = t; return t; }
+    t = merge<1>(c.slot[0], t, lane);
+    if (!(P & 2)) { c.slot[1] = t; return t; }
+    t = merge<2>(c.slot[1], t, lane);
+    if (!(P & 4)) { c.slot[2] = t; return t; }
+    t = merge<3>(c.slot[2], t, lane);
+    if (!(P & 8)) { c.slot[3] = t; return t; }
+    t = merge<4>(c.slot[3], t, lane);
+    if (!(P & 16)) { c.slot[4] = t; return t; }
+    return merge<5>(c.slot[4], t, lane);
+}
+
+// grad[q - 1] = alpha * s + beta * grad[q - 1] for a map word q that names an input entry; this lane is its only writer
+__device__ __forceinline__ void store_grad(float* grad, long long n, int q, float s, float alpha, float beta) {
+    if (q < 1 || (long long)q > n) return;
+    float* const p = grad + (q - 1);
+    float r = alpha * s;
+    if (beta != 0.0f) r = r + beta * *p;
+    *p = r;
+}
+
+constexpr unsigned kNoCol = 0xffffffffu;           // a window slot, stray slot or meta that names no column of xt
+constexpr unsigned kSkipMeta = 0xfffffffeu;        // broadcast word of an element without a column of xt: column << 1 | row end otherwise
+
+// The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
+// LDS: the forward launch's window of lds_floats words (the wavefronts' stray areas are its last words), holding column numbers.
+template <int VL, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
+__device__ __forceinline__ void spmm_grad_group(
+    const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const int32_t* __restrict__ map,
+    const SpmmGradOperands& a, long long n_slices, int group_slices, int lds_floats, int cols, int rows, long long group, int4 g) {
+    extern __shared__ unsigned colwin[];
+    constexpr int kE = kSliceSteps * kLaneElems;
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
+    const long long first = group * group_slices;
+    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
+    const int n_here = (int)(last > first ? last - first : 0);
+    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
+    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
+    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;      // 0 fragments: the metas of this group are plain columns
+    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
+    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
+    unsigned* const stray_area = colwin + win_floats + wave * kStraySlots;
+    // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
+    const unsigned* const stray_cols = (const unsigned*)(hdr + n_slices);
+
+    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the window is filled
+    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
+    int k_slice = wave;
+    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
+    SliceMetas<COMPACT> w;
+    int4 h = int4{0, 0, 0, 0};
+    if (local < n_here) {
+        h = load_int4(hdr + first + local);
+        request_metas<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    }
+    if (USE_LDS) {
+        // the window in column numbers: for every fragment {col_start, len, lds_off}, col_start + i at lds_off + i; no column elsewhere
+        for (int i = (int)threadIdx.x; i < lds_floats; i += (int)blockDim.x) colwin[i] = kNoCol;
+        __syncthreads();
+        const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
+        for (int f = wave; f < nf; f += n_waves) {
+            const int4 fr = load_int4(frags + f0 + f);
+            const int col0 = __builtin_amdgcn_readfirstlane(fr.x), len = __builtin_amdgcn_readfirstlane(fr.y), off = __builtin_amdgcn_readfirstlane(fr.z);
+            for (int i = lane; i < len; i += 64)
+                if (off + i >= 0 && off + i < win_floats) colwin[off + i] = (unsigned)(col0 + i);
+        }
+        __syncthreads();
+    }
+
+    // A lane past the batch reads the floats of lane 0 (always inside the row).  keep[i]: the lane's vector i is below n_vecs; the
+    // PRODUCT of every other one is masked to +0, so that neither a pad float of gyt nor one of xt (NaN, say) gets into a sum.
+    const int lane_vec = a.tile0 + lane * VL;
+    const unsigned lane_bytes = lane_vec < a.n_vecs ? (unsigned)(lane * VL * 4) : 0u;      // (a uniform row address + these 32 bits: one scalar-base load)
+    const float* const xtile = a.xt + a.tile0;
+    const float* const gtile = a.gyt + a.tile0;
+    bool keep[VL];
+#pragma unroll
+    for (int i = 0; i < VL; ++i) keep[i] = lane_vec + i < a.n_vecs;
+    // gyt[row, the lane's vectors]; a row past the matrix (elements of padding behind the last row) reads row 0: its map word is 0
+    const auto load_gy = [&](float (&d)[VL], int row) {
+        const int rc = (row >= 0 && row < rows) ? row : 0;
+        load_vl<VL>((const float*)((const char*)(gtile + (size_t)rc * (size_t)a.ld_gy) + lane_bytes), d);
+    };
+
+    while (local < n_here) {
+        // the row of the slice's first element, even when that row began slices earlier; an element's row is this plus the row ends
+        // passed so far in the slice, in stream order (the decode of value_grad_group)
+        int row = __builtin_amdgcn_readfirstlane(h.x);
+        const long long cur = first + local;
+        float gy[VL], gy_next[VL];      // of `row` and of row + 1, requested one row end ahead
+        load_gy(gy, row);
+        load_gy(gy_next, row + 1);
+        unsigned c[kE];
+        decode_metas<COMPACT>(w, c);
+        if (STRAYS && strays) {
+            stray_area[lane] = ((const HISPMV_W_GLOBAL unsigned*)stray_cols)[cur * kStraySlots + lane];
+            __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order)
+        }
+        // every meta -> column << 1 | row end, or kSkipMeta | row end for a column outside xt (padding, fillers, kNoCol)
+        unsigned meta[kE];
+#pragma unroll
+        for (int i = 0; i < kE; ++i) {
+            const unsigned end = c[i] >> 31;
+            unsigned col;
+            if constexpr (COMPACT) {
+                const int idx = (int)(c[i] & 0x7fffu);
+                if (STRAYS && strays && idx >= win_floats) col = stray_area[(idx - win_floats) & (kStraySlots - 1)];
+                else col = idx < lds_floats ? colwin[idx] : kNoCol;
+            } else {
+                const unsigned ci = c[i] & ~kRowEndBit;
+                if (USE_LDS && in_lds && !(ci & kGlobalColBit)) col = ci < (unsigned)win_floats ? colwin[ci] : kNoCol;
+                else col = ci & ~kGlobalColBit;
+            }
+            meta[i] = (col < (unsigned)cols ? col << 1 : kSkipMeta) | end;
+        }
+
+        // the 1024 elements in stream order: step j, lane L, element k.  The meta of an element is wave-uniform (readlane); every lane
+        // gathers its VL floats of that column's row of xt.  The gathers carry no branch: an element without a column reads row 0 of
+        // xt (its sum is dropped at the store: its map word is 0).
+        // NK elements per gather: the four of a lane, or -- VL 4, 16 bytes per lane and element -- its two halves one after the other
+        constexpr int NK = VL == 4 ? kLaneElems / 2 : kLaneElems;
+        struct Gathered { unsigned m[NK]; float x[NK][VL]; };
+        const auto gather = [&](Gathered& q, int j, int L, int k0) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                q.m[k] = (unsigned)__builtin_amdgcn_readlane((int)meta[4 * j + k0 + k], L);
+                load_vl<VL>((const float*)((const char*)(xtile + (size_t)(q.m[k] < kSkipMeta ? q.m[k] >> 1 : 0u) * (size_t)a.ld_x) + lane_bytes), q.x[k]);
+            }
+        };
+        // -> the lane's partial of each of the four elements; behind a row end (wave-uniform) gyt of the next row
+        const auto consume = [&](const Gathered& q, float (&p)[kLaneElems], int k0) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                float s = 0.0f;
+#pragma unroll
+                for (int i = 0; i < VL; ++i) s = s + (keep[i] ? gy[i] * q.x[k][i] : 0.0f);
+                asm volatile("" : "+v"(s));      // the sum is formed HERE: left alone, hipcc sinks the products below the row-end branches and keeps every gathered float live
+                p[k0 + k] = s;
+                if (q.m[k] & 1u) {
+                    row += 1;
+#pragma unroll
+                    for (int i = 0; i < VL; ++i) gy[i] = gy_next[i];
+                    load_gy(gy_next, row + 1);
+                }
+            }
+        };
+        const int4* const mp = (const int4*)(map + (size_t)cur * kValueChunk) + lane;
+#pragma unroll
+        for (int j = 0; j < kSliceSteps; ++j) {
+            // (slots and totals begin defined: read-before-write cannot be ruled out at compile time, and an undefined slot would be
+            //  live around the whole slice loop -- 20 registers through the decode)
+            Counter cnt[kLaneElems] = {};
+            float total[kLaneElems] = {0.0f, 0.0f, 0.0f, 0.0f};
+            float pa[kLaneElems], pb[kLaneElems];
+            if (j == kSliceSteps - 1) {
+                // the next slice of this wavefront, requested a quarter of a slice ahead: by now the metas of the first three steps are
+                // dead, so the request costs no register at the peak (the 256 elements of this step hide it)
+                k_slice += n_waves;
+                local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
+                if (local < n_here) {
+                    h = load_int4(hdr + first + local);
+                    request_metas<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+                }
+            }
+            if constexpr (VL < 4) {
+                Gathered qa, qb;
+                gather(qa, j, 0, 0);
+#pragma unroll 1
+                for (int P = 0; P < 32; ++P) {
+                    gather(qb, j, 2 * P + 1, 0);
+                    consume(qa, pa, 0);
+                    gather(qa, j, P < 31 ? 2 * P + 2 : 63, 0);      // (behind lane 62 the elements of lane 63 once more: dropped)
+                    consume(qb, pb, 0);
+#pragma unroll
+                    for (int k = 0; k < kLaneElems; ++k) total[k] = counter_push(cnt[k], merge<0>(pa[k], pb[k], lane), P, lane);
+                }
+            } else {      // the same in halves of a lane's elements: two gathers of two 16-byte elements in flight
+                Gathered qa, qb;
+                gather(qa, j, 0, 0);
+#pragma unroll 1
+                for (int P = 0; P < 32; ++P) {
+                    gather(qb, j, 2 * P, 2);
+                    consume(qa, pa, 0);
+                    gather(qa, j, 2 * P + 1, 0);
+                    consume(qb, pa, 2);
+                    gather(qb, j, 2 * P + 1, 2);
+                    consume(qa, pb, 0);
+                    gather(qa, j, P < 31 ? 2 * P + 2 : 63, 0);      // (behind lane 63 its first two elements once more: dropped)
+                    consume(qb, pb, 2);
+#pragma unroll
+                    for (int k = 0; k < kLaneElems; ++k) total[k] = counter_push(cnt[k], merge<0>(pa[k], pb[k], lane), P, lane);
+                }
+            }
+            // lane L holds the totals of its own elements (j, L, 0 .. 3): the four map words of slot j * 64 + L, loaded only now
+            const int4 q = load_int4(mp + j * 64);
+            store_grad(a.grad, a.n, q.x, total[0], a.alpha, a.beta);
+            store_grad(a.grad, a.n, q.y, total[1], a.alpha, a.beta);
+            store_grad(a.grad, a.n, q.z, total[2], a.alpha, a.beta);
+            store_grad(a.grad, a.n, q.w, total[3], a.alpha, a.beta);
+        }
+        if (STRAYS && strays) __builtin_amdgcn_wave_barrier();           // the stray area is read: the next slice may fill it
+    }
+}
+
+// HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
+template <int VL, bool USE_LDS, bool STRAYS, bool HALF>
+__global__ __launch_bounds__(1024) void spmm_grad_slices_kernel(
+    const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
+    const int32_t* __restrict__ map, SpmmGradOperands a, long long n_slices, int group_slices, int lds_floats, int cols, int rows) {
+    const long long group = (long long)blockIdx.x;
+    if constexpr (USE_LDS) {
+        const int4 g = load_int4(groups + group);
+        const int gw = __builtin_amdgcn_readfirstlane(g.w);
+        if constexpr (HALF) {
+            if (gw & kGroupHalf) {
+                spmm_grad_group<VL, true, true, STRAYS, true>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+                return;
+            }
+        }
+        if (gw & kGroupCompact)
+            spmm_grad_group<VL, true, true, STRAYS, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+        else
+            spmm_grad_group<VL, true, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+    } else {
+        spmm_grad_group<VL, false, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, int4{0, 0, 0, 0});
+    }
+}
+
+template <auto Kernel>
+hipError_t raise_lds_limit() {
+    static std::once_flag once;
+    static hipError_t status = hipSuccess;
+    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
+    return status;
+}
+
+template <int VL>
+hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+    const auto go = [&](auto kernel) {
+        const hipError_t e = raise_lds_limit<kernel()>();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel(), dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
+                           m.groups, m.frags, map, a, (long long)m.n_slices, m.group_slices, m.lds_floats, m.cols, m.rows);
+        return hipGetLastError();
+    };
+#define HISPMV_W_KERNEL(L, S, H) go([] { return spmm_grad_slices_kernel<VL, L, S, H>; })
+    if (m.lds_floats <= 0) return HISPMV_W_KERNEL(false, false, false);
+    if (m.has_strays) return m.has_half ? HISPMV_W_KERNEL(true, true, true) : HISPMV_W_KERNEL(true, true, false);
+    return m.has_half ? HISPMV_W_KERNEL(true, false, true) : HISPMV_W_KERNEL(true, false, false);
+#undef HISPMV_W_KERNEL
+}
+
+}  // namespace
+
+hipError_t launch_spmm_grad_part(const SpmvDeviceMatrix& m, int vl, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (m.n_slices <= 0 || m.n_groups <= 0 || a.n <= 0) return hipSuccess;
+    if (!map) return hipErrorInvalidValue;
+    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || (size_t)m.lds_floats * 4 > (size_t)kDynLdsMax)
+        return hipErrorInvalidValue;
+    // stray slots and half groups exist only in plans with a window (hispmv_abi.cpp)
+    if (m.lds_floats <= 0 && (m.has_strays || m.has_half)) return hipErrorInvalidValue;
+    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
+    if (m.rows <= 0 || m.cols <= 0) return hipErrorInvalidValue;          // (rows 0 and columns 0 of gyt and xt are read for elements without a place)
+    if (!a.gyt || !a.xt || !a.grad || a.n_vecs < 1 || a.tile0 < 0 || a.tile0 >= a.n_vecs || a.ld_x < a.n_vecs || a.ld_gy < a.n_vecs) return hipErrorInvalidValue;
+    switch (vl) {
+        case 4: return launch_slices<4>(m, map, a, stream);
+        case 2: return launch_slices<2>(m, map, a, stream);
+        case 1: return launch_slices<1>(m, map, a, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace hispmv

@@ -335,6 +335,32 @@ class FpgaHandle:
         return {"accepted": bool(out[0]), "accepted_t": bool(out[1]), "vl": int(out[2]), "tiles": int(out[3]), "launches": int(out[4]),
                 "work_bytes": int(out[5]), "work_bytes_t": int(out[6])}
 
+    def spmm_value_grad_device(self, matrix_idx: int, d_gyt: int, d_xt: int, num_vecs: int, d_grad: int, alpha: float = 1.0, beta: float = 0.0,
+                               ld_gy=None, ld_x=None, stream: int = 0) -> None:
+        """grad[k] = alpha * sum_v gyt[row_k, v] * xt[col_k, v] + beta * grad[k] for every entry k of the creation input of a loaded,
+        updatable slice-stream handle, on device pointers (ints), operands FEATURE-MAJOR as in spmm_device: gyt is [rows, ld_gy], xt
+        [cols, ld_x], row-major, ld (default num_vecs) >= num_vecs; the pad floats of a row are never used (hispmv_spmm_value_grad_device).
+        The lanes of a wavefront are vectors and the slice stream (its metas only) is read once per tile of up to 256 vectors, not once
+        per 4 as in value_grad_device.  No workspace, no atomics, nothing kept in the handle; plain stores, one writer per entry: the
+        same bits run to run.  The bits depend on (num_vecs, ld, alignment) through the lane width and the tiles: they are not the bits
+        of value_grad_device and not independent of the batch.  beta == 0 does not read grad.  Asynchronous on `stream`.  A tile-stream
+        or dense handle raises NotImplementedError, a handle created with value updates off AssertionError, a bad argument ValueError."""
+        self._check(lib.hispmv_spmm_value_grad_device(self._ctx, int(matrix_idx), C.c_void_p(d_gyt), int(num_vecs if ld_gy is None else ld_gy),
+                                                      C.c_void_p(d_xt), int(num_vecs if ld_x is None else ld_x), int(num_vecs), C.c_void_p(d_grad),
+                                                      float(alpha), float(beta), C.c_void_p(stream)))
+
+    def spmm_value_grad_info(self, matrix_idx: int, num_vecs: int, ld=None) -> dict:
+        """{"accepted", "vl", "tiles", "launches"} of spmm_value_grad_device for num_vecs vectors with ld_gy = ld_x = ld (default num_vecs)
+        and 16-byte aligned pointers (hispmv_spmm_value_grad_info): the vectors per lane of the first tile, the vector tiles, the launches
+        of a call with alpha != 0 (one per tile and part that holds slices); zeros for a handle it does not accept."""
+        out = (C.c_int64 * 4)()
+        rc = lib.hispmv_spmm_value_grad_info(self._ctx, int(matrix_idx), int(num_vecs), int(num_vecs if ld is None else ld), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError("num_vecs must be at least 1 and ld at least num_vecs")
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "vl": int(out[1]), "tiles": int(out[2]), "launches": int(out[3])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

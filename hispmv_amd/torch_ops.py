@@ -20,7 +20,8 @@ real stream and nothing waits (examples/train_sparse_layer.py).  Without ``value
 stream the caller synchronises between torch's operations and the layer.
 
 ``spmm=True`` routes the forward product and grad_x through the wide-batch entries (FpgaHandle.spmm_device / spmm_device_t) on
-feature-major copies of the activations; the default route is unchanged (see sparse_linear).
+feature-major copies of the activations; ``wide_grad=True`` on top of it takes grad_values through the wide-batch value gradient
+(FpgaHandle.spmm_value_grad_device) on the same copies.  The default route is unchanged (see sparse_linear).
 
 The backward pass is differentiable once (no double backward).  The autograd graph keeps a reference to the handle, which keeps the
 object alive but not open: the handle must not be closed between forward and backward (a closed handle makes backward raise, it does
@@ -226,7 +227,103 @@ def _function_spmm(torch):
     return SparseLinearSpmm
 
 
-def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = False):
+def _function_spmm_wide(torch):
+    fn = getattr(_function_spmm_wide, "cached", None)
+    if fn is not None:
+        return fn
+
+    def feature_major(a, ld):
+        """[B, n] -> [n, ld] with the batch in the first B columns and zeros in the pad columns"""
+        B = a.shape[0]
+        if ld == B:
+            return a.t().contiguous()
+        at = torch.zeros((a.shape[1], ld), dtype=torch.float32, device=a.device)
+        at[:, :B] = a.t()
+        return at
+
+    def workspace(work_bytes, device):
+        return torch.empty((max(work_bytes, 4) + 3) // 4, dtype=torch.float32, device=device)
+
+    class SparseLinearSpmmWide(torch.autograd.Function):
+        """sparse_linear with spmm=True, wide_grad=True and values: SparseLinearSpmm with the value gradient through
+        spmm_value_grad_device.  The forward pass keeps the feature-major xt it built for spmm_device (not x); the backward pass builds
+        the feature-major grad_y once, for spmm_device_t and for the value gradient.  Stream ordering as in SparseLinearSpmm: on torch's
+        default stream a host wait between torch's side and the launches and another behind them, torch's temporaries referenced
+        until the second is over."""
+
+        @staticmethod
+        def forward(ctx, x, bias, values, handle, idx, rows):
+            ctx.handle, ctx.idx, ctx.has_bias = handle, idx, bias is not None
+            current = torch.cuda.current_stream(x.device)
+            stream = current.cuda_stream
+            B = x.shape[0]
+            ld = (B + 3) & ~3
+            info = handle.spmm_info(idx, B, ld)
+            v = values.contiguous()
+            b = bias.contiguous() if bias is not None else None
+            xt = feature_major(x, ld)
+            yt = torch.empty((rows, ld), dtype=torch.float32, device=x.device)
+            work = workspace(info["work_bytes"], x.device)
+            if stream == 0:
+                current.synchronize()
+            handle.update_values_device(idx, v.data_ptr(), v.numel(), stream)
+            handle.spmm_device(idx, xt.data_ptr(), B, b.data_ptr() if b is not None else 0, yt.data_ptr(), 1.0, 1.0 if b is not None else 0.0,
+                               ld_x=ld, ld_y=ld, work=work.data_ptr(), work_bytes=info["work_bytes"], stream=stream)
+            if stream == 0:
+                handle.synchronize()
+            ctx.cols, ctx.n = x.shape[1], v.numel()
+            if values.requires_grad:          # the feature-major copy is kept for the value gradient only
+                ctx.save_for_backward(xt)
+            del xt, work, b, v
+            return yt[:, :B].t()
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_y):
+            grad_x = grad_bias = grad_values = None
+            handle, idx = ctx.handle, ctx.idx
+            current = torch.cuda.current_stream(grad_y.device)
+            stream = current.cuda_stream
+            B = grad_y.shape[0]
+            ld = (B + 3) & ~3
+            if ctx.has_bias and ctx.needs_input_grad[1]:
+                grad_bias = grad_y.sum(0)
+            want_x, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+            # torch's side first: everything the launches below read or write
+            info = handle.spmm_info(idx, B, ld) if want_x else None
+            wide_t = want_x and info["accepted_t"]
+            g = gt = gxt = work = xt = None
+            if wide_t or want_v:
+                gt = feature_major(grad_y, ld)          # ONE copy, for both products
+            if wide_t:
+                gxt = torch.empty((ctx.cols, ld), dtype=torch.float32, device=grad_y.device)
+                work = workspace(info["work_bytes_t"], grad_y.device)
+            elif want_x:
+                g = grad_y.contiguous()
+                grad_x = torch.empty((B, ctx.cols), dtype=torch.float32, device=grad_y.device)
+            if want_v:
+                (xt,) = ctx.saved_tensors
+                grad_values = torch.empty((ctx.n,), dtype=torch.float32, device=grad_y.device)
+            if stream == 0 and (want_x or want_v):
+                current.synchronize()
+            if wide_t:
+                handle.spmm_device_t(idx, gt.data_ptr(), B, 0, gxt.data_ptr(), 1.0, 0.0, ld_x=ld, ld_y=ld, work=work.data_ptr(),
+                                     work_bytes=info["work_bytes_t"], stream=stream)
+                grad_x = gxt[:, :B].t()
+            elif want_x:
+                handle.linear_device_t(idx, g.data_ptr(), B, 0, grad_x.data_ptr(), 1.0, 0.0, 0, stream)
+            if want_v:
+                handle.spmm_value_grad_device(idx, gt.data_ptr(), xt.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, ld_gy=ld, ld_x=ld, stream=stream)
+            if stream == 0 and (want_x or want_v):
+                handle.synchronize()
+            del g, gt, work, xt
+            return grad_x, grad_bias, grad_values, None, None, None
+
+    _function_spmm_wide.cached = SparseLinearSpmmWide
+    return SparseLinearSpmmWide
+
+
+def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = False, wide_grad: bool = False):
     """y = A x (+ bias) for the loaded matrix `idx` of `handle` (an FpgaHandle): x is a float32 CUDA tensor [B, cols] or [cols] (made
     contiguous), the result [B, rows] (or [rows]); bias, if given, a float32 CUDA tensor [rows].  Differentiable in x and bias (grad_x =
     A^T grad_y through linear_device_t, grad_bias = grad_y.sum(0)).  Runs on torch's current stream.  A wrong dtype raises TypeError, a
@@ -269,8 +366,19 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     NotImplementedError before any launch.  With `values`, the update pass and value_grad_device stay as they are.  The feature-major
     copies have a leading dimension of B rounded up to 4 (pad columns zero), so that an odd batch still takes the lane widths its size
     allows.  On torch's default stream every pass waits on the host after torch has built those copies and again behind the library's
-    launches (the context's stream is not ordered with torch's kernels)."""
+    launches (the context's stream is not ordered with torch's kernels).
+
+    wide_grad=False (default): nothing changes.  wide_grad=True needs spmm=True and `values` (otherwise ValueError, before any launch)
+    and takes grad_values through FpgaHandle.spmm_value_grad_device: the forward pass saves the feature-major copy of x it built
+    anyway (instead of x), the backward pass builds the feature-major grad_y once and uses it for spmm_device_t (where the handle has
+    a slice-stream companion) and for the value gradient, which then reads the slice stream once per tile of up to 256 vectors
+    instead of once per 4.  y and grad_x keep the bits of spmm=True; grad_values is deterministic, but its bits are not those of
+    value_grad_device and depend on the batch size (the sums go lane by lane, then over the lanes as a pairwise tree)."""
     import torch
+    if wide_grad and not spmm:
+        raise ValueError("wide_grad=True needs spmm=True")
+    if wide_grad and values is None:
+        raise ValueError("wide_grad=True needs values")
     info = handle.matrix_info(idx)
     _check_tensor(torch, x, "x", info["cols"], (1, 2))
     if bias is not None:
@@ -296,7 +404,8 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     if values.device != x.device:
         raise ValueError("values must be on the device of x")
     if spmm:
-        y = _function_spmm(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])
+        fn = _function_spmm_wide(torch) if wide_grad else _function_spmm(torch)
+        y = fn.apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])
         return y.squeeze(0) if one else y
     y = _function_values(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])
     return y.squeeze(0) if one else y

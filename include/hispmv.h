@@ -427,7 +427,7 @@ int hispmv_value_grad_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_ve
  *  - Errors, all before any launch: not loaded -> HISPMV_ESTATE; HISPMV_ENOTSUP as above; num_vecs < 1, ld_x or ld_y < num_vecs,
  *    work_bytes smaller than hispmv_spmm_info reports for (num_vecs, ld_x, ld_y), NULL d_xt or d_yt, NULL d_bias with beta != 0,
  *    d_xt == d_yt, d_bias == d_yt with bias_stride 0, a bad index -> HISPMV_EINVAL.
- * Out of scope: tile-stream and dense handles, a transposed wide product without a stored transpose, a wide value gradient, wide calls
+ * Out of scope: tile-stream and dense handles, a transposed wide product without a stored transpose, wide calls
  * inside hispmv_spmv_device_batch or the step kernel, sharding over devices, host-pointer variants, bf16 activations. */
 int hispmv_spmm_device(hispmv_ctx* ctx, int matrix_idx, const float* d_xt, int64_t num_vecs, int64_t ld_x, const float* d_bias,
                        int64_t bias_stride, float* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
@@ -439,6 +439,42 @@ int hispmv_spmm_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_xt, int
  * out[2..5] describe the forward entry and are zeros where it is not accepted.  Pointers aligned to less than 16 bytes may take a
  * smaller VL (hispmv_prep_spmm_tiles) and more tiles; the workspace figures hold for every alignment.  Zeros for a handle that is not loaded. */
 int hispmv_spmm_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t ld, int64_t out[8]);
+/* ---- wide-batch value gradient on feature-major operands -------------------------------------------------------------------------
+ *   grad[k] = alpha * sum_{v < num_vecs} gyt[row_k, v] * xt[col_k, v] + beta * grad[k]
+ * for every entry k of the creation input of a loaded, updatable slice-stream handle: hispmv_value_grad_device on the operand layout of
+ * hispmv_spmm_device.  d_gyt is [rows, ld_gy], d_xt is [cols, ld_x], row-major, ld_gy, ld_x >= num_vecs >= 1; the pad floats num_vecs ..
+ * ld - 1 of a row are never used (they may hold NaN).  d_grad holds n floats in the order hispmv_update_values_device reads.  Grid, groups
+ * and walk are those of hispmv_spmm_device: the 64 lanes of a wavefront are 64 * VL vectors and the slice stream -- its metas only: the
+ * values are never touched -- is read once per tile of 64 * VL vectors, where hispmv_value_grad_device reads it once per 4 vectors.
+ * Device pointers, 4-byte aligned, asynchronous on `stream` (the stream rule above: NULL = the context's stream).
+ *  - beta == 0: d_grad is not read; every one of its n positions is overwritten, whatever it held.  alpha == 0: exactly beta * grad
+ *    (zeros with beta == 0); gyt and xt are not read.  One elementwise launch.
+ *  - An explicit zero of the input gets its gradient like every other entry (the +-0 rule of hispmv_spmm_device has no place here);
+ *    slots that hold no input entry write nothing.
+ *  - TILES: vector tiles go one after the other by the rule of hispmv_prep_spmm_tiles, with align_bytes the smaller alignment of d_gyt
+ *    and d_xt; the first tile stores alpha * s + beta * grad, every later one grad + alpha * s.  Inside a tile the parts of the handle
+ *    run one after the other, each on its own entries.  No workspace, no second launch, no atomics, nothing kept in the handle.
+ *  - BITS: every grad[k] has one writer per launch.  The sum s of an entry over one tile has a fixed order: the VL products of a lane
+ *    ascending from +0, every product and add unfused; then the pairwise tree over the 64 lanes (lanes 2i and 2i + 1, then pairs of
+ *    pairs, ...).  Two identical calls give identical bits.  The bits depend on (num_vecs, ld, alignment) through VL and the tiles:
+ *    they are NOT the bits of hispmv_value_grad_device and they are NOT independent of the batch.
+ *  - ACCEPTED: every loaded, updatable handle that hispmv_spmm_device accepts -- every slice-stream group kind, column tiles, band
+ *    tiles, both parts of a stray split; fp32, and bf16 created under HISPMV_VALUE_UPDATES_ANY_STORAGE (same plan, same map, same bits).
+ *    Not loaded -> HISPMV_ESTATE; a dense handle -> HISPMV_ENOTSUP (this is a GEMM); a tile stream -> HISPMV_ENOTSUP (the message names
+ *    hispmv_set_transposable(ctx, 1)); not created with value updates on -> HISPMV_ESTATE (the message names hispmv_set_value_updates),
+ *    in this order.
+ *  - Argument errors, all before any launch: num_vecs < 1, ld_gy or ld_x < num_vecs, NULL d_gyt or d_xt, NULL d_grad with n > 0, a
+ *    pointer that is not 4-byte aligned, d_grad equal to d_gyt or d_xt, a bad index -> HISPMV_EINVAL.
+ *  - HANDLE STATE: the entry reads metas, slice headers, fragment tables, stray columns and the value map, and writes nothing but
+ *    d_grad: it may overlap forward, transposed, wide and update calls on the same handle.
+ * Out of scope: tile-stream and dense handles, gradients inside hispmv_spmv_device_batch or the step kernel, sharding over devices,
+ * host-pointer variants, bf16 activations. */
+int hispmv_spmm_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gyt, int64_t ld_gy, const float* d_xt, int64_t ld_x,
+                                  int64_t num_vecs, float* d_grad, float alpha, float beta, void* stream);
+/* out = {1 if hispmv_spmm_value_grad_device accepts the (loaded) handle, VL of the first tile, vector tiles, launches of a call with
+ * alpha != 0 (one per tile and part that holds slices; 0 for a handle without entries)} for ld_gy = ld_x = ld and 16-byte aligned
+ * pointers.  Zeros for a handle that is not accepted or not loaded.  num_vecs < 1 or ld < num_vecs -> HISPMV_EINVAL. */
+int hispmv_spmm_value_grad_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t ld, int64_t out[4]);
 /* The vector tiles of a wide call (host-only, no device needed).  A lane owns VL in {4, 2, 1} consecutive vectors and reads them with
  * one dwordx4, dwordx2 or dword load per stored element; a tile is 64 * VL vectors.  Every tile takes the largest VL such that
  *   (a) 64 * (VL / 2) < vectors left;   (b) cols * 64 * VL * 4 <= 8 MiB: VL 4 up to 8192 columns, VL 2 up to 16384 (a cap
