@@ -1,7 +1,7 @@
 // hispmv_spmm.hip -- the kernels of the wide-batch product (hispmv_spmm.h): yt[rows, B] = alpha * A * xt[cols, B] + beta * bias on the
-// slice stream of a loaded handle, operands feature-major.  Stands on its own like hispmv_transpose.hip: the few decode helpers of
-// the slice format it needs (the slice request, decode_metas, the bf16 widening) are its own copies, so that hispmv_kernels.hip --
-// and with it every forward kernel -- is untouched by this file.
+// slice stream of a loaded handle, operands feature-major.  What it needs of the slice format (the slice request, decode_metas, the bf16
+// widening, the launch checks) it shares with the other four satellite files: hispmv_slice_walk.h.
+// hispmv_kernels.hip takes no part in that and keeps its own text, so that no forward kernel is touched from here.
 //
 // Roles, against the forward slice kernel (hispmv_kernels.hip: slices_group):
 //   forward                                           wide batch
@@ -14,118 +14,12 @@
 // VL that carried it, nor on the run.  A stored slot whose value is +-0 contributes nothing, whatever xt holds.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
-#include "hispmv_format.h"
+#include "hispmv_slice_walk.h"
 #include "hispmv_spmm.h"
 
 namespace hispmv {
 
 namespace {
-
-#define HISPMV_M_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_M_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ uint2 load_words2(const uint2* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    const u2v v = __builtin_nontemporal_load((const HISPMV_M_GLOBAL u2v*)p);
-    return uint2{v.x, v.y};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_M_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
-
-// A slice as it arrives (hispmv_format.h; the forward kernel's SliceRaw): per step 4 values and 4 metas per lane, or -- HALF -- one
-// 16-byte piece {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16}.
-template <bool COMPACT, bool HALF = false> struct SliceRaw;
-template <> struct SliceRaw<true>  { uint4 v[kSliceSteps]; uint2 m[kSliceSteps]; };
-template <> struct SliceRaw<false> { uint4 v[kSliceSteps]; uint4 m[kSliceSteps]; };
-template <> struct SliceRaw<true, true> { uint4 q[kSliceSteps]; };
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void request_slice(SliceRaw<COMPACT, HALF>& s, const char* base, int lane) {
-    if constexpr (HALF) {
-        const uint4* pq = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.q[j] = load_words(pq + j * 64);
-    } else {
-        const uint4* pv = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.v[j] = load_words(pv + j * 64);
-        if constexpr (COMPACT) {
-            const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
-        } else {
-            const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
-        }
-    }
-}
-// the fp32 bits of the lane's 16 values: as stored, or the bf16 halves of a dword widened
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, float (&v)[kSliceSteps * kLaneElems]) {
-#pragma unroll
-    for (int j = 0; j < kSliceSteps; ++j) {
-        if constexpr (HALF) {
-            v[4 * j + 0] = i2f((int)(s.q[j].x << 16)); v[4 * j + 1] = i2f((int)(s.q[j].x & 0xffff0000u));
-            v[4 * j + 2] = i2f((int)(s.q[j].y << 16)); v[4 * j + 3] = i2f((int)(s.q[j].y & 0xffff0000u));
-        } else {
-            v[4 * j + 0] = i2f((int)s.v[j].x); v[4 * j + 1] = i2f((int)s.v[j].y); v[4 * j + 2] = i2f((int)s.v[j].z); v[4 * j + 3] = i2f((int)s.v[j].w);
-        }
-    }
-}
-// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
-    if constexpr (COMPACT) {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            unsigned a, b;
-            if constexpr (HALF) { a = s.q[j].z; b = s.q[j].w; } else { a = s.m[j].x; b = s.m[j].y; }
-            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
-            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
-            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
-            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
-    }
-}
-
-// VL consecutive floats of a lane: one dword, dwordx2 or dwordx4 access (the tile rule makes the address a multiple of 4 * VL)
-template <int VL> __device__ __forceinline__ void load_vl(const float* p, float (&x)[VL]) {
-    if constexpr (VL == 4) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const f4v q = *(const HISPMV_M_GLOBAL f4v*)p;
-        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-    } else if constexpr (VL == 2) {
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        const f2v q = *(const HISPMV_M_GLOBAL f2v*)p;
-        x[0] = q.x; x[1] = q.y;
-    } else {
-        x[0] = *(const HISPMV_M_GLOBAL float*)p;
-    }
-}
-template <int VL> __device__ __forceinline__ void store_vl(float* p, const float (&x)[VL]) {
-    if constexpr (VL == 4) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        *(HISPMV_M_GLOBAL f4v*)p = f4v{x[0], x[1], x[2], x[3]};
-    } else if constexpr (VL == 2) {
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        *(HISPMV_M_GLOBAL f2v*)p = f2v{x[0], x[1]};
-    } else {
-        *(HISPMV_M_GLOBAL float*)p = x[0];
-    }
-}
 
 // yt[row, lane's vectors] = alpha * acc + beta * bias: the one expression every finished row goes through, in the slice kernel and in
 // the fix-up alike.  A lane stores only its vectors below n_vecs (the pad floats n_vecs .. ld_y - 1 of a row are never written); it
@@ -139,7 +33,7 @@ __device__ __forceinline__ void store_row(const SpmmOperands& a, int row, int la
     if (a.beta != 0.0f) {
         float b[VL];
         if (a.bias_stride == 0) {
-            const float s = ((const HISPMV_M_GLOBAL float*)a.bias)[row];
+            const float s = ((const HISPMV_GLOBAL float*)a.bias)[row];
 #pragma unroll
             for (int i = 0; i < VL; ++i) b[i] = s;
         } else {
@@ -148,7 +42,7 @@ __device__ __forceinline__ void store_row(const SpmmOperands& a, int row, int la
                 load_vl<VL>(bp, b);
             } else {
 #pragma unroll
-                for (int i = 0; i < VL; ++i) b[i] = i < live ? ((const HISPMV_M_GLOBAL float*)bp)[i] : 0.0f;
+                for (int i = 0; i < VL; ++i) b[i] = i < live ? ((const HISPMV_GLOBAL float*)bp)[i] : 0.0f;
             }
         }
 #pragma unroll
@@ -162,12 +56,9 @@ __device__ __forceinline__ void store_row(const SpmmOperands& a, int row, int la
     } else {
 #pragma unroll
         for (int i = 0; i < VL; ++i)
-            if (i < live) ((HISPMV_M_GLOBAL float*)yp)[i] = out[i];
+            if (i < live) ((HISPMV_GLOBAL float*)yp)[i] = out[i];
     }
 }
-
-constexpr unsigned kNoCol = 0xffffffffu;           // a window slot, stray slot or meta that names no column of xt
-constexpr unsigned kSkipMeta = 0xfffffffeu;        // broadcast word of an element that is not multiplied: column << 1 | row end otherwise
 
 // The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
 // LDS: the forward launch's window of lds_floats words (the wavefronts' stray areas are its last words), holding column numbers.
@@ -180,41 +71,20 @@ __device__ __forceinline__ void spmm_group(
     extern __shared__ unsigned colwin[];
     constexpr int kE = kSliceSteps * kLaneElems;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
-    const long long first = group * group_slices;
-    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
-    const int n_here = (int)(last > first ? last - first : 0);
-    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
-    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
-    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;      // 0 fragments: the metas of this group are plain columns
-    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
-    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
-    unsigned* const stray_area = colwin + win_floats + wave * kStraySlots;
+    // the forward kernel's walk; the first request leaves before the window is filled
+    auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
+    const bool strays = wk.strays;
+    unsigned* const stray_area = colwin + wk.win_floats + wave * kStraySlots;
     // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
     const unsigned* const stray_cols = (const unsigned*)(hdr + n_slices);
 
-    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the window is filled
-    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
-    int k_slice = wave;
-    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
     SliceRaw<COMPACT, HALF> w;
     int4 h = int4{0, 0, 0, 0};
-    if (local < n_here) {
-        h = load_int4(hdr + first + local);
-        request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    if (wk.live()) {
+        h = load_int4(hdr + wk.cur());
+        request_slice<COMPACT, HALF>(w, wk.slice(), lane);
     }
-    if (USE_LDS) {
-        // the window in column numbers: for every fragment {col_start, len, lds_off}, col_start + i at lds_off + i; no column elsewhere
-        for (int i = (int)threadIdx.x; i < lds_floats; i += (int)blockDim.x) colwin[i] = kNoCol;
-        __syncthreads();
-        const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
-        for (int f = wave; f < nf; f += n_waves) {
-            const int4 fr = load_int4(frags + f0 + f);
-            const int col0 = __builtin_amdgcn_readfirstlane(fr.x), len = __builtin_amdgcn_readfirstlane(fr.y), off = __builtin_amdgcn_readfirstlane(fr.z);
-            for (int i = lane; i < len; i += 64)
-                if (off + i >= 0 && off + i < win_floats) colwin[off + i] = (unsigned)(col0 + i);
-        }
-        __syncthreads();
-    }
+    if (USE_LDS) fill_column_window(colwin, frags, g, wk.in_lds, lds_floats, wk.win_floats, lane, wave, n_waves);
 
     // a lane past the batch gathers the floats of lane 0 (always inside the row) and stores nothing
     const int lane_vec = a.tile0 + lane * VL;
@@ -222,42 +92,27 @@ __device__ __forceinline__ void spmm_group(
     float* const open_w = a.work;
     float* const head_w = a.work + (size_t)n_slices * (64 * VL);
 
-    while (local < n_here) {
+    while (wk.live()) {
         const int row_first = __builtin_amdgcn_readfirstlane(h.x);      // first row that ends in this slice
         const int chain_len = __builtin_amdgcn_readfirstlane(h.y);      // > 0: that row began chain_len slices earlier (a row of the fix tables)
-        const long long cur = first + local;
+        const long long cur = wk.cur();
         unsigned c[kE];
         float v[kE];
         decode_metas<COMPACT, HALF>(w, c);
         slice_values<COMPACT, HALF>(w, v);
         if (STRAYS && strays) {
-            stray_area[lane] = ((const HISPMV_M_GLOBAL unsigned*)stray_cols)[cur * kStraySlots + lane];
+            stray_area[lane] = ((const HISPMV_GLOBAL unsigned*)stray_cols)[cur * kStraySlots + lane];
             __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order)
         }
         // every meta -> column << 1 | row end, or kSkipMeta | row end for a +-0 value or a column outside xt
         unsigned meta[kE];
-#pragma unroll
-        for (int i = 0; i < kE; ++i) {
-            const unsigned end = c[i] >> 31;
-            unsigned col;
-            if constexpr (COMPACT) {
-                const int idx = (int)(c[i] & 0x7fffu);
-                if (STRAYS && strays && idx >= win_floats) col = stray_area[(idx - win_floats) & (kStraySlots - 1)];
-                else col = idx < lds_floats ? colwin[idx] : kNoCol;
-            } else {
-                const unsigned ci = c[i] & ~kRowEndBit;
-                if (USE_LDS && in_lds && !(ci & kGlobalColBit)) col = ci < (unsigned)win_floats ? colwin[ci] : kNoCol;
-                else col = ci & ~kGlobalColBit;
-            }
-            const bool live = col < (unsigned)cols && (f2i(v[i]) & 0x7fffffff) != 0;
-            meta[i] = (live ? col << 1 : kSkipMeta) | end;
-        }
+        resolve_columns<USE_LDS, COMPACT, STRAYS>(c, meta, colwin, stray_area, wk.in_lds, strays, wk.win_floats, lds_floats,
+                                                  [&](unsigned col, int i) { return col < (unsigned)cols && (f2i(v[i]) & 0x7fffffff) != 0; });
         // the next slice of this wavefront, into the registers the copies above have left
-        k_slice += n_waves;
-        local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
-        if (local < n_here) {
-            h = load_int4(hdr + first + local);
-            request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+        wk.advance();
+        if (wk.live()) {
+            h = load_int4(hdr + wk.cur());
+            request_slice<COMPACT, HALF>(w, wk.slice(), lane);
         }
 
         // the 1024 elements in stream order: step j, lane L, element k.  Value and meta of an element are wave-uniform (readlane);
@@ -382,28 +237,16 @@ __global__ __launch_bounds__(256) void spmm_bias_kernel(SpmmOperands a, long lon
     *yp = a.beta != 0.0f ? a.beta * (a.bias_stride == 0 ? a.bias[row] : a.bias[row * a.bias_stride + v]) : 0.0f;
 }
 
-template <auto Kernel>
-hipError_t raise_lds_limit() {
-    static std::once_flag once;
-    static hipError_t status = hipSuccess;
-    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
-    return status;
-}
-
 template <int VL>
 hipError_t launch_slices(const SpmvDeviceMatrix& m, const SpmmOperands& a, hipStream_t stream) {
-    const auto go = [&](auto kernel) {
-        const hipError_t e = raise_lds_limit<kernel()>();
+    return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
+        constexpr auto kernel = spmm_slices_kernel<VL, USE_LDS(), STRAYS(), HALF()>;
+        const hipError_t e = raise_lds_limit<kernel>();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel(), dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
+        hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
                            m.groups, m.frags, a, (long long)m.n_slices, m.group_slices, m.lds_floats, m.cols, m.rows);
         return hipGetLastError();
-    };
-#define HISPMV_M_KERNEL(L, S, H) go([] { return spmm_slices_kernel<VL, L, S, H>; })
-    if (m.lds_floats <= 0) return HISPMV_M_KERNEL(false, false, false);
-    if (m.has_strays) return m.has_half ? HISPMV_M_KERNEL(true, true, true) : HISPMV_M_KERNEL(true, true, false);
-    return m.has_half ? HISPMV_M_KERNEL(true, false, true) : HISPMV_M_KERNEL(true, false, false);
-#undef HISPMV_M_KERNEL
+    });
 }
 
 template <int VL>
@@ -422,11 +265,7 @@ hipError_t launch_part(const SpmvDeviceMatrix& m, const SpmmOperands& a, hipStre
 hipError_t launch_spmm_part(const SpmvDeviceMatrix& m, int vl, const SpmmOperands& a, hipStream_t stream) {
     (void)hipGetLastError();
     if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
-    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || (size_t)m.lds_floats * 4 > (size_t)kDynLdsMax)
-        return hipErrorInvalidValue;
-    // stray slots and half groups exist only in plans with a window (hispmv_abi.cpp)
-    if (m.lds_floats <= 0 && (m.has_strays || m.has_half)) return hipErrorInvalidValue;
-    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
+    if (!slice_geometry_ok(m, (size_t)m.lds_floats * 4)) return hipErrorInvalidValue;
     if (!a.xt || !a.yt || !a.work || a.n_vecs < 1 || a.tile0 < 0 || a.tile0 >= a.n_vecs || a.ld_x < a.n_vecs || a.ld_y < a.n_vecs) return hipErrorInvalidValue;
     if (a.beta != 0.0f && (!a.bias || (a.bias_stride != 0 && a.bias_stride != a.ld_y))) return hipErrorInvalidValue;
     switch (vl) {

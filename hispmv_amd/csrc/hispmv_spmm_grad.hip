@@ -1,7 +1,7 @@
 // hispmv_spmm_grad.hip -- the kernels of the wide-batch value gradient (hispmv_spmm_grad.h): grad[k] = alpha * sum_v gyt[row_k, v] *
-// xt[col_k, v] + beta * grad[k] on the slice stream of a loaded, updatable handle, operands feature-major.  Stands on its own like
-// hispmv_spmm.hip: the few decode helpers of the slice format it needs are its own copies, so that hispmv_kernels.hip, hispmv_spmm.hip
-// and hispmv_value_grad.hip are untouched by this file.
+// xt[col_k, v] + beta * grad[k] on the slice stream of a loaded, updatable handle, operands feature-major.  What it needs of the slice
+// format (the meta request, decode_metas, store_grad, the launch checks) it shares with the other four satellite
+// files: hispmv_slice_walk.h.  hispmv_kernels.hip takes no part in that and keeps its own text, so that no forward kernel is touched from here.
 //
 // Roles, against the wide-batch product (hispmv_spmm.hip: spmm_group) and the value gradient of 4 vectors (hispmv_value_grad.hip):
 //   wide-batch product                          value gradient (4-2-1)                     wide-batch value gradient
@@ -15,90 +15,13 @@
 // row extensions, padding) writes nothing.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
-#include "hispmv_format.h"
+#include "hispmv_slice_walk.h"
 #include "hispmv_spmm_grad.h"
 #include "hispmv_update.h"
 
 namespace hispmv {
 
 namespace {
-
-#define HISPMV_W_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_W_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ uint2 load_words2(const uint2* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    const u2v v = __builtin_nontemporal_load((const HISPMV_W_GLOBAL u2v*)p);
-    return uint2{v.x, v.y};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_W_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
-
-// The metas of a slice as they arrive (hispmv_format.h): they begin at byte 4096 of a compact and of a wide slice; the 4 KiB of values
-// before them are not requested.  HALF (bf16 storage): the compact metas of step j, lane l are dwords 2 and 3 of the 16-byte piece at
-// (j * 64 + l) * 16; only those 8 bytes are requested.
-template <bool COMPACT> struct SliceMetas;
-template <> struct SliceMetas<true>  { uint2 m[kSliceSteps]; };
-template <> struct SliceMetas<false> { uint4 m[kSliceSteps]; };
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void request_metas(SliceMetas<COMPACT>& s, const char* base, int lane) {
-    static_assert(COMPACT || !HALF, "only a compact group has a half form");
-    if constexpr (HALF) {
-        const uint2* pm = (const uint2*)(base + 8) + 2 * lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 128);
-    } else if constexpr (COMPACT) {
-        const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
-    } else {
-        const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
-    }
-}
-// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j
-template <bool COMPACT>
-__device__ __forceinline__ void decode_metas(const SliceMetas<COMPACT>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
-    if constexpr (COMPACT) {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            const unsigned a = s.m[j].x, b = s.m[j].y;
-            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
-            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
-            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
-            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
-    }
-}
-
-// VL consecutive floats of a lane: one dword, dwordx2 or dwordx4 load (the tile rule makes the address a multiple of 4 * VL)
-template <int VL> __device__ __forceinline__ void load_vl(const float* p, float (&x)[VL]) {
-    if constexpr (VL == 4) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const f4v q = *(const HISPMV_W_GLOBAL f4v*)p;
-        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-    } else if constexpr (VL == 2) {
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        const f2v q = *(const HISPMV_W_GLOBAL f2v*)p;
-        x[0] = q.x; x[1] = q.y;
-    } else {
-        x[0] = *(const HISPMV_W_GLOBAL float*)p;
-    }
-}
 
 // ---- the sum over the 64 lanes, 64 elements at a time -----------------------------------------------------------------------------
 // a, b: the per-lane partials of two elements (level 0), or two values that each hold, in every lane, the sum over the lane's block of
@@ -149,18 +72,6 @@ __device__ __forceinline__ float counter_push(Counter& c, float t, int P, int la
     return merge<5>(c.slot[4], t, lane);
 }
 
-// grad[q - 1] = alpha * s + beta * grad[q - 1] for a map word q that names an input entry; this lane is its only writer
-__device__ __forceinline__ void store_grad(float* grad, long long n, int q, float s, float alpha, float beta) {
-    if (q < 1 || (long long)q > n) return;
-    float* const p = grad + (q - 1);
-    float r = alpha * s;
-    if (beta != 0.0f) r = r + beta * *p;
-    *p = r;
-}
-
-constexpr unsigned kNoCol = 0xffffffffu;           // a window slot, stray slot or meta that names no column of xt
-constexpr unsigned kSkipMeta = 0xfffffffeu;        // broadcast word of an element without a column of xt: column << 1 | row end otherwise
-
 // The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
 // LDS: the forward launch's window of lds_floats words (the wavefronts' stray areas are its last words), holding column numbers.
 template <int VL, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
@@ -170,41 +81,20 @@ __device__ __forceinline__ void spmm_grad_group(
     extern __shared__ unsigned colwin[];
     constexpr int kE = kSliceSteps * kLaneElems;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
-    const long long first = group * group_slices;
-    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
-    const int n_here = (int)(last > first ? last - first : 0);
-    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
-    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
-    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;      // 0 fragments: the metas of this group are plain columns
-    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
-    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
-    unsigned* const stray_area = colwin + win_floats + wave * kStraySlots;
+    // the forward kernel's walk; the first request leaves before the window is filled
+    auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
+    const bool strays = wk.strays;
+    unsigned* const stray_area = colwin + wk.win_floats + wave * kStraySlots;
     // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
     const unsigned* const stray_cols = (const unsigned*)(hdr + n_slices);
 
-    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the window is filled
-    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
-    int k_slice = wave;
-    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
     SliceMetas<COMPACT> w;
     int4 h = int4{0, 0, 0, 0};
-    if (local < n_here) {
-        h = load_int4(hdr + first + local);
-        request_metas<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    if (wk.live()) {
+        h = load_int4(hdr + wk.cur());
+        request_metas<COMPACT, HALF>(w, wk.slice(), lane);
     }
-    if (USE_LDS) {
-        // the window in column numbers: for every fragment {col_start, len, lds_off}, col_start + i at lds_off + i; no column elsewhere
-        for (int i = (int)threadIdx.x; i < lds_floats; i += (int)blockDim.x) colwin[i] = kNoCol;
-        __syncthreads();
-        const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
-        for (int f = wave; f < nf; f += n_waves) {
-            const int4 fr = load_int4(frags + f0 + f);
-            const int col0 = __builtin_amdgcn_readfirstlane(fr.x), len = __builtin_amdgcn_readfirstlane(fr.y), off = __builtin_amdgcn_readfirstlane(fr.z);
-            for (int i = lane; i < len; i += 64)
-                if (off + i >= 0 && off + i < win_floats) colwin[off + i] = (unsigned)(col0 + i);
-        }
-        __syncthreads();
-    }
+    if (USE_LDS) fill_column_window(colwin, frags, g, wk.in_lds, lds_floats, wk.win_floats, lane, wave, n_waves);
 
     // A lane past the batch reads the floats of lane 0 (always inside the row).  keep[i]: the lane's vector i is below n_vecs; the
     // PRODUCT of every other one is masked to +0, so that neither a pad float of gyt nor one of xt (NaN, say) gets into a sum.
@@ -221,37 +111,24 @@ __device__ __forceinline__ void spmm_grad_group(
         load_vl<VL>((const float*)((const char*)(gtile + (size_t)rc * (size_t)a.ld_gy) + lane_bytes), d);
     };
 
-    while (local < n_here) {
+    while (wk.live()) {
         // the row of the slice's first element, even when that row began slices earlier; an element's row is this plus the row ends
         // passed so far in the slice, in stream order (the decode of value_grad_group)
         int row = __builtin_amdgcn_readfirstlane(h.x);
-        const long long cur = first + local;
+        const long long cur = wk.cur();
         float gy[VL], gy_next[VL];      // of `row` and of row + 1, requested one row end ahead
         load_gy(gy, row);
         load_gy(gy_next, row + 1);
         unsigned c[kE];
         decode_metas<COMPACT>(w, c);
         if (STRAYS && strays) {
-            stray_area[lane] = ((const HISPMV_W_GLOBAL unsigned*)stray_cols)[cur * kStraySlots + lane];
+            stray_area[lane] = ((const HISPMV_GLOBAL unsigned*)stray_cols)[cur * kStraySlots + lane];
             __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order)
         }
         // every meta -> column << 1 | row end, or kSkipMeta | row end for a column outside xt (padding, fillers, kNoCol)
         unsigned meta[kE];
-#pragma unroll
-        for (int i = 0; i < kE; ++i) {
-            const unsigned end = c[i] >> 31;
-            unsigned col;
-            if constexpr (COMPACT) {
-                const int idx = (int)(c[i] & 0x7fffu);
-                if (STRAYS && strays && idx >= win_floats) col = stray_area[(idx - win_floats) & (kStraySlots - 1)];
-                else col = idx < lds_floats ? colwin[idx] : kNoCol;
-            } else {
-                const unsigned ci = c[i] & ~kRowEndBit;
-                if (USE_LDS && in_lds && !(ci & kGlobalColBit)) col = ci < (unsigned)win_floats ? colwin[ci] : kNoCol;
-                else col = ci & ~kGlobalColBit;
-            }
-            meta[i] = (col < (unsigned)cols ? col << 1 : kSkipMeta) | end;
-        }
+        resolve_columns<USE_LDS, COMPACT, STRAYS>(c, meta, colwin, stray_area, wk.in_lds, strays, wk.win_floats, lds_floats,
+                                                  [&](unsigned col, int) { return col < (unsigned)cols; });
 
         // the 1024 elements in stream order: step j, lane L, element k.  The meta of an element is wave-uniform (readlane); every lane
         // gathers its VL floats of that column's row of xt.  The gathers carry no branch: an element without a column reads row 0 of
@@ -294,11 +171,10 @@ __device__ __forceinline__ void spmm_grad_group(
             if (j == kSliceSteps - 1) {
                 // the next slice of this wavefront, requested a quarter of a slice ahead: by now the metas of the first three steps are
                 // dead, so the request costs no register at the peak (the 256 elements of this step hide it)
-                k_slice += n_waves;
-                local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
-                if (local < n_here) {
-                    h = load_int4(hdr + first + local);
-                    request_metas<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+                wk.advance();
+                if (wk.live()) {
+                    h = load_int4(hdr + wk.cur());
+                    request_metas<COMPACT, HALF>(w, wk.slice(), lane);
                 }
             }
             if constexpr (VL < 4) {
@@ -365,28 +241,16 @@ __global__ __launch_bounds__(1024) void spmm_grad_slices_kernel(
     }
 }
 
-template <auto Kernel>
-hipError_t raise_lds_limit() {
-    static std::once_flag once;
-    static hipError_t status = hipSuccess;
-    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
-    return status;
-}
-
 template <int VL>
 hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
-    const auto go = [&](auto kernel) {
-        const hipError_t e = raise_lds_limit<kernel()>();
+    return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
+        constexpr auto kernel = spmm_grad_slices_kernel<VL, USE_LDS(), STRAYS(), HALF()>;
+        const hipError_t e = raise_lds_limit<kernel>();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel(), dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
+        hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
                            m.groups, m.frags, map, a, (long long)m.n_slices, m.group_slices, m.lds_floats, m.cols, m.rows);
         return hipGetLastError();
-    };
-#define HISPMV_W_KERNEL(L, S, H) go([] { return spmm_grad_slices_kernel<VL, L, S, H>; })
-    if (m.lds_floats <= 0) return HISPMV_W_KERNEL(false, false, false);
-    if (m.has_strays) return m.has_half ? HISPMV_W_KERNEL(true, true, true) : HISPMV_W_KERNEL(true, true, false);
-    return m.has_half ? HISPMV_W_KERNEL(true, false, true) : HISPMV_W_KERNEL(true, false, false);
-#undef HISPMV_W_KERNEL
+    });
 }
 
 }  // namespace
@@ -395,11 +259,7 @@ hipError_t launch_spmm_grad_part(const SpmvDeviceMatrix& m, int vl, const int32_
     (void)hipGetLastError();
     if (m.n_slices <= 0 || m.n_groups <= 0 || a.n <= 0) return hipSuccess;
     if (!map) return hipErrorInvalidValue;
-    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || (size_t)m.lds_floats * 4 > (size_t)kDynLdsMax)
-        return hipErrorInvalidValue;
-    // stray slots and half groups exist only in plans with a window (hispmv_abi.cpp)
-    if (m.lds_floats <= 0 && (m.has_strays || m.has_half)) return hipErrorInvalidValue;
-    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
+    if (!slice_geometry_ok(m, (size_t)m.lds_floats * 4)) return hipErrorInvalidValue;
     if (m.rows <= 0 || m.cols <= 0) return hipErrorInvalidValue;          // (rows 0 and columns 0 of gyt and xt are read for elements without a place)
     if (!a.gyt || !a.xt || !a.grad || a.n_vecs < 1 || a.tile0 < 0 || a.tile0 >= a.n_vecs || a.ld_x < a.n_vecs || a.ld_gy < a.n_vecs) return hipErrorInvalidValue;
     switch (vl) {

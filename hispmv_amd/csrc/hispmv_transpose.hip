@@ -1,7 +1,7 @@
 // hispmv_transpose.hip -- the kernels of the transposed product (hispmv_transpose.h): y[cols] = alpha * A^T * x[rows] + beta * bias[cols]
-// on the slice streams and dense layouts of loaded handles.  Stands on its own like hispmv_update.hip: the few decode helpers of the
-// slice format it needs (the slice request, decode_metas, the bf16 widening) are its own copies, so that hispmv_kernels.hip -- and with
-// it every forward kernel -- is untouched by this file.
+// on the slice streams and dense layouts of loaded handles.  What it needs of the slice format (the slice request, decode_metas, the bf16
+// widening, the launch checks) it shares with the other four satellite files: hispmv_slice_walk.h.
+// hispmv_kernels.hip takes no part in that and keeps its own text, so that no forward kernel is touched from here.
 //
 // Roles, against the forward slice kernel (hispmv_kernels.hip: slices_group):
 //   forward                                           transposed
@@ -13,99 +13,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 
-#include "hispmv_format.h"
+#include "hispmv_slice_walk.h"
 #include "hispmv_transpose.h"
 
 namespace hispmv {
 
 namespace {
 
-#define HISPMV_T_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_T_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ uint2 load_words2(const uint2* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    const u2v v = __builtin_nontemporal_load((const HISPMV_T_GLOBAL u2v*)p);
-    return uint2{v.x, v.y};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_T_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-// The float adds: ds_add_f32 into the LDS, global_atomic_add_f32 (no return value) into y.
+// The float adds: ds_add_f32 into the LDS here, global_atomic_add_f32 (no return value) into y with y_add.
 __device__ __forceinline__ void lds_add(float* p, float v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void y_add(float* y, unsigned col, float v) { (void)atomicAdd(y + col, v); }
-
-// A slice as it arrives (hispmv_format.h; the forward kernel's SliceRaw): per step 4 values and 4 metas per lane, or -- HALF -- one
-// 16-byte piece {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16}.
-template <bool COMPACT, bool HALF = false> struct SliceRaw;
-template <> struct SliceRaw<true>  { uint4 v[kSliceSteps]; uint2 m[kSliceSteps]; };
-template <> struct SliceRaw<false> { uint4 v[kSliceSteps]; uint4 m[kSliceSteps]; };
-template <> struct SliceRaw<true, true> { uint4 q[kSliceSteps]; };
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void request_slice(SliceRaw<COMPACT, HALF>& s, const char* base, int lane) {
-    if constexpr (HALF) {
-        const uint4* pq = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.q[j] = load_words(pq + j * 64);
-    } else {
-        const uint4* pv = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.v[j] = load_words(pv + j * 64);
-        if constexpr (COMPACT) {
-            const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
-        } else {
-            const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
-        }
-    }
-}
-// the fp32 bits of the lane's 16 values: as stored, or the bf16 halves of a dword widened
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, float (&v)[kSliceSteps * kLaneElems]) {
-#pragma unroll
-    for (int j = 0; j < kSliceSteps; ++j) {
-        if constexpr (HALF) {
-            v[4 * j + 0] = i2f((int)(s.q[j].x << 16)); v[4 * j + 1] = i2f((int)(s.q[j].x & 0xffff0000u));
-            v[4 * j + 2] = i2f((int)(s.q[j].y << 16)); v[4 * j + 3] = i2f((int)(s.q[j].y & 0xffff0000u));
-        } else {
-            v[4 * j + 0] = i2f((int)s.v[j].x); v[4 * j + 1] = i2f((int)s.v[j].y); v[4 * j + 2] = i2f((int)s.v[j].z); v[4 * j + 3] = i2f((int)s.v[j].w);
-        }
-    }
-}
-// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
-    if constexpr (COMPACT) {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            unsigned a, b;
-            if constexpr (HALF) { a = s.q[j].z; b = s.q[j].w; } else { a = s.m[j].x; b = s.m[j].y; }
-            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
-            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
-            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
-            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
-    }
-}
 
 // y = beta * bias, 4 consecutive floats per thread.  Each thread reads what it writes: bias may be y.
 // Several vectors are ONE array of n floats to this kernel (y of vector v begins at v * cols); `period` > 0: they share one bias of
@@ -130,43 +47,34 @@ __device__ __forceinline__ void slices_group_t(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const float* __restrict__ x, float* y,
     float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows, long long group, int4 g) {
     extern __shared__ float xs[];
-    constexpr unsigned kNoAccess = 0xffffffffu;
     constexpr int kE = kSliceSteps * kLaneElems;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
     // x is reached through a buffer descriptor over `rows` floats: a row past the end (the open row behind the last slice) reads as 0
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
     float* const xtile = xs + (USE_LDS ? lds_floats : 0) + wave * ytile_floats;
-    const long long first = group * group_slices;
-    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
-    const int n_here = (int)(last > first ? last - first : 0);
-    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
-    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
-    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;      // 0 fragments: the metas of this group are plain columns
-    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
-    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
+    // the forward kernel's walk; the first request leaves before the window is zeroed
+    auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
+    const bool in_lds = wk.in_lds, strays = wk.strays;
+    const int win_floats = wk.win_floats;
     float* const stray_area = xs + win_floats + wave * kStraySlots;
     // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
 
-    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the window is zeroed
-    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
-    int k_slice = wave;
-    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
     SliceRaw<COMPACT, HALF> w;
     int4 h = int4{0, 0, 0, 0};
-    if (local < n_here) {
-        h = load_int4(hdr + first + local);
-        request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    if (wk.live()) {
+        h = load_int4(hdr + wk.cur());
+        request_slice<COMPACT, HALF>(w, wk.slice(), lane);
     }
     if (USE_LDS) {
         for (int i = (int)threadIdx.x; i < lds_floats; i += (int)blockDim.x) xs[i] = 0.0f;
         __syncthreads();
     }
 
-    while (local < n_here) {
+    while (wk.live()) {
         const int row_first = __builtin_amdgcn_readfirstlane(h.x);      // first row that ends in this slice
         const int n_rows = __builtin_amdgcn_readfirstlane(h.z);         // rows that end in it; its elements lie in rows row_first .. row_first + n_rows
-        const long long cur = first + local;
+        const long long cur = wk.cur();
         unsigned c[kE];
         float v[kE];
         decode_metas<COMPACT, HALF>(w, c);
@@ -177,32 +85,13 @@ __device__ __forceinline__ void slices_group_t(
         const float x_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
         unsigned sc = kNoAccess;
         if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(cur * kStraySlots + lane) << 2, 0, 0);
-        // local row of every element = row ends before it in the slice (the forward kernel's ballots, plus the lane's own ends)
         int lr[kE];
-        int row = 0;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            int below = 0, total = 0;
-#pragma unroll
-            for (int k = 0; k < kLaneElems; ++k) {
-                const unsigned long long m = __builtin_amdgcn_ballot_w64((c[4 * j + k] & kRowEndBit) != 0);
-                below += lanes_below(m);
-                total += __builtin_popcountll(m);
-            }
-            int r = row + below;
-#pragma unroll
-            for (int k = 0; k < kLaneElems; ++k) {
-                lr[4 * j + k] = r;
-                r += (c[4 * j + k] & kRowEndBit) ? 1 : 0;
-            }
-            row += total;
-        }
+        local_rows(c, lr);
         // the next slice of this wavefront, into the registers the copies above have left
-        k_slice += n_waves;
-        local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
-        if (local < n_here) {
-            h = load_int4(hdr + first + local);
-            request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+        wk.advance();
+        if (wk.live()) {
+            h = load_int4(hdr + wk.cur());
+            request_slice<COMPACT, HALF>(w, wk.slice(), lane);
         }
         __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order: the tile is complete for every lane)
 #pragma unroll
@@ -285,39 +174,30 @@ __device__ __forceinline__ void slices_group_t_nv(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const float* __restrict__ x, float* y,
     float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows, long long group, int4 g) {
     extern __shared__ float xs[];
-    constexpr unsigned kNoAccess = 0xffffffffu;
     constexpr int kE = kSliceSteps * kLaneElems;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
     float* const xtile = xs + (USE_LDS ? lds_floats * NV : 0) + wave * ytile_floats;
-    const long long first = group * group_slices;
-    const long long last = (first + group_slices < n_slices) ? first + group_slices : n_slices;
-    const int n_here = (int)(last > first ? last - first : 0);
-    constexpr int slice_bytes = HALF ? kHalfSliceBytes : COMPACT ? kCompactSliceBytes : kWideSliceBytes;
-    const char* const gbase = stream + (USE_LDS ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(g.z) * kSliceUnit : (size_t)first * kWideSliceBytes);
-    const bool in_lds = USE_LDS && __builtin_amdgcn_readfirstlane(g.y) > 0;
-    const bool strays = STRAYS && COMPACT && (__builtin_amdgcn_readfirstlane(g.w) & kGroupStrays) != 0;
-    const int win_floats = lds_floats - (STRAYS ? n_waves * kStraySlots : 0);
+    auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
+    const bool in_lds = wk.in_lds, strays = wk.strays;
+    const int win_floats = wk.win_floats;
     const int stray_at = win_floats + wave * kStraySlots;          // this wavefront's stray area inside every vector's window
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
 
-    const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
-    int k_slice = wave;
-    int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
     SliceRaw<COMPACT, HALF> w;
     int4 h = int4{0, 0, 0, 0};
-    if (local < n_here) {
-        h = load_int4(hdr + first + local);
-        request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+    if (wk.live()) {
+        h = load_int4(hdr + wk.cur());
+        request_slice<COMPACT, HALF>(w, wk.slice(), lane);
     }
     if (USE_LDS) {
         for (int i = (int)threadIdx.x; i < lds_floats * NV; i += (int)blockDim.x) xs[i] = 0.0f;
         __syncthreads();
     }
 
-    while (local < n_here) {
+    while (wk.live()) {
         const int row_first = __builtin_amdgcn_readfirstlane(h.x);
         const int n_rows = __builtin_amdgcn_readfirstlane(h.z);
-        const long long cur = first + local;
+        const long long cur = wk.cur();
         unsigned c[kE];
         float v[kE];
         decode_metas<COMPACT, HALF>(w, c);
@@ -325,29 +205,11 @@ __device__ __forceinline__ void slices_group_t_nv(
         unsigned sc = kNoAccess;
         if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(cur * kStraySlots + lane) << 2, 0, 0);
         int lr[kE];
-        int row = 0;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            int below = 0, total = 0;
-#pragma unroll
-            for (int k = 0; k < kLaneElems; ++k) {
-                const unsigned long long m = __builtin_amdgcn_ballot_w64((c[4 * j + k] & kRowEndBit) != 0);
-                below += lanes_below(m);
-                total += __builtin_popcountll(m);
-            }
-            int r = row + below;
-#pragma unroll
-            for (int k = 0; k < kLaneElems; ++k) {
-                lr[4 * j + k] = r;
-                r += (c[4 * j + k] & kRowEndBit) ? 1 : 0;
-            }
-            row += total;
-        }
-        k_slice += n_waves;
-        local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
-        if (local < n_here) {
-            h = load_int4(hdr + first + local);
-            request_slice<COMPACT, HALF>(w, gbase + (size_t)local * slice_bytes, lane);
+        local_rows(c, lr);
+        wk.advance();
+        if (wk.live()) {
+            h = load_int4(hdr + wk.cur());
+            request_slice<COMPACT, HALF>(w, wk.slice(), lane);
         }
         // vector 0: the head of its tile (rows row_first + lane; past the end of x the descriptor gives 0) and its open row
         __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
@@ -564,22 +426,23 @@ __global__ __launch_bounds__(256) void gemv_t_nv_kernel(const void* __restrict__
     }
 }
 
-template <auto Kernel>
-hipError_t raise_lds_limit() {
-    static std::once_flag once;
-    static hipError_t status = hipSuccess;
-    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
-    return status;
+// the kernel of a pass of NV vectors (1: the single-vector kernel)
+template <int NV, bool USE_LDS, bool STRAYS, bool HALF>
+constexpr auto slices_t_kernel() {
+    if constexpr (NV == 1) return spmv_slices_t_kernel<USE_LDS, STRAYS, HALF>;
+    else return spmv_slices_t_nv_kernel<NV, USE_LDS, STRAYS, HALF>;
 }
 
-template <bool USE_LDS, bool STRAYS, bool HALF>
+template <int NV>
 hipError_t launch_slices_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
-    constexpr auto kernel = spmv_slices_t_kernel<USE_LDS, STRAYS, HALF>;
-    const hipError_t e = raise_lds_limit<kernel>();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m), stream, (const char*)m.words, m.hdr,
-                       m.groups, m.frags, x, y, alpha, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows);
-    return hipGetLastError();
+    return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
+        constexpr auto kernel = slices_t_kernel<NV, USE_LDS(), STRAYS(), HALF()>();
+        const hipError_t e = raise_lds_limit<kernel>();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m, NV), stream, (const char*)m.words, m.hdr,
+                           m.groups, m.frags, x, y, alpha, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -599,14 +462,8 @@ hipError_t launch_transpose_prologue(const float* bias, float* y, int32_t n, flo
 hipError_t launch_spmv_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
     (void)hipGetLastError();
     if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
-    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || slice_lds_bytes(m) > (size_t)kDynLdsMax)
-        return hipErrorInvalidValue;
-    // stray slots and half groups exist only in plans with a window (hispmv_abi.cpp)
-    const bool window = m.lds_floats > 0;
-    if (!window) return (m.has_strays || m.has_half) ? hipErrorInvalidValue : launch_slices_t<false, false, false>(m, x, y, alpha, stream);
-    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
-    if (m.has_strays) return m.has_half ? launch_slices_t<true, true, true>(m, x, y, alpha, stream) : launch_slices_t<true, true, false>(m, x, y, alpha, stream);
-    return m.has_half ? launch_slices_t<true, false, true>(m, x, y, alpha, stream) : launch_slices_t<true, false, false>(m, x, y, alpha, stream);
+    if (!slice_geometry_ok(m, slice_lds_bytes(m))) return hipErrorInvalidValue;
+    return launch_slices_t<1>(m, x, y, alpha, stream);
 }
 
 // Plan classes of the multi-vector pass; spmv_t_width is where a class that a measurement shows no faster than single calls is narrowed.
@@ -619,31 +476,12 @@ int spmv_t_width(const SpmvDeviceMatrix& m, int64_t vecs) {
     return 1;
 }
 
-template <int NV>
-static hipError_t launch_spmv_t_width(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
-    const auto go = [&](auto kernel) {
-        const hipError_t e = raise_lds_limit<kernel()>();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel(), dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m, NV), stream, (const char*)m.words, m.hdr,
-                           m.groups, m.frags, x, y, alpha, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows);
-        return hipGetLastError();
-    };
-#define HISPMV_T_NV(L, S, H) go([] { return spmv_slices_t_nv_kernel<NV, L, S, H>; })
-    if (m.lds_floats <= 0) return HISPMV_T_NV(false, false, false);
-    if (m.has_strays) return m.has_half ? HISPMV_T_NV(true, true, true) : HISPMV_T_NV(true, true, false);
-    return m.has_half ? HISPMV_T_NV(true, false, true) : HISPMV_T_NV(true, false, false);
-#undef HISPMV_T_NV
-}
-
 hipError_t launch_spmv_t_nv(const SpmvDeviceMatrix& m, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
     (void)hipGetLastError();
     if (nv != 2 && nv != 4) return hipErrorInvalidValue;
     if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
-    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || spmv_t_width(m, nv) != nv)
-        return hipErrorInvalidValue;
-    if (m.lds_floats <= 0 && (m.has_strays || m.has_half)) return hipErrorInvalidValue;
-    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
-    return nv == 4 ? launch_spmv_t_width<4>(m, x, y, alpha, stream) : launch_spmv_t_width<2>(m, x, y, alpha, stream);
+    if (!slice_geometry_ok(m, slice_lds_bytes(m, nv)) || spmv_t_width(m, nv) != nv) return hipErrorInvalidValue;
+    return nv == 4 ? launch_slices_t<4>(m, x, y, alpha, stream) : launch_slices_t<2>(m, x, y, alpha, stream);
 }
 
 // Row blocks per column block: enough workgroups to fill the chip twice over (1024 in all) while a block keeps at least 16 rows,

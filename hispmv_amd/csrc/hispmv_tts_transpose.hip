@@ -1,7 +1,7 @@
 // hispmv_tts_transpose.hip -- the transposed product and the value gradient on the transposed tile stream (hispmv_tts_transpose.h).
-// Stands on its own like hispmv_transpose.hip and hispmv_value_grad.hip: the few helpers of the tile-stream format it needs (the slice
-// request, the row-end arithmetic of the forward kernel's phase B) are its own copies, so that hispmv_kernels.hip -- and with it every
-// forward kernel -- is untouched by this file.
+// The bit and load helpers, store_grad and the LDS limit of a launch it shares with the other four satellite files
+// (hispmv_slice_walk.h); the few helpers of the tile-stream format (the slice request, the row-end arithmetic of the forward kernel's
+// phase B) are its own text, as hispmv_kernels.hip keeps its own: no forward kernel is touched from here.
 //
 // One workgroup per tile (hispmv_tts.h), LDS [x rows of the tile: acc_floats][staging: one float per row-major slot of the block in
 // flight] -- the forward kernel's layout without the chunk tails.  Per block the forward kernel's two phases in the other order:
@@ -21,10 +21,7 @@
 // the metas and the value map only: grad[q - 1] = sum_v staging_v[slot] * x[v, col], one writer per entry.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <type_traits>
-
-#include "hispmv_format.h"
+#include "hispmv_slice_walk.h"
 #include "hispmv_tts_transpose.h"
 #include "hispmv_update.h"
 
@@ -32,32 +29,7 @@ namespace hispmv {
 
 namespace {
 
-#define HISPMV_TT_GLOBAL __attribute__((address_space(1)))
 constexpr int kChunkSlots = 1024;      // hispmv_tts.h: kTtsChunk (slots per row-major chunk, words per column-order slice)
-constexpr unsigned kNoAccess = 0xffffffffu;
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_TT_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_TT_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-// global_atomic_add_f32 without a return value (hispmv_transpose.hip: y_add)
-__device__ __forceinline__ void y_add(float* y, unsigned col, float v) { (void)atomicAdd(y + col, v); }
-// a dword through a buffer descriptor: an offset past the descriptor's bytes (kNoAccess among them) reads 0
-__device__ __forceinline__ float buffer_float(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return i2f((int)__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t float_buffer(const float* p, int n_floats) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, n_floats * 4, 0x00020000);
-}
 
 // A column-order slice as it arrives: 4 values and 4 metas per lane and step (the forward kernel's TtsSlice); the gradient requests
 // the metas alone (they begin 4096 B behind the values).
@@ -174,15 +146,6 @@ __device__ __forceinline__ void scatter_slice(const TtsSlice& w, int col_base, c
     }
 }
 
-// grad[q - 1] = alpha * s + beta * grad[q - 1] for a map word q that names an input entry; this thread is its only writer
-__device__ __forceinline__ void store_grad(float* grad, long long n, int q, float s, float alpha, float beta) {
-    if (q < 1 || (long long)q > n) return;
-    float* const p = grad + (q - 1);
-    float r = alpha * s;
-    if (beta != 0.0f) r = r + beta * *p;
-    *p = r;
-}
-
 // The gradient's column-order phase for one slice: per word the sum over the vectors of staging_v[slot] (= gy[v, row]) * x[v, col], x
 // gathered through a descriptor of the vector's `cols` floats, 8 gathers in flight per lane; stored through the slice's map chunk.
 template <int NV>
@@ -256,7 +219,7 @@ __device__ __forceinline__ void tts_t_tile(const TtsDeviceMatrix& M, const float
     int cbA = 0, cbB = 0;
     auto request = [&](Slice& w, int& cb, int slice) {
         tts_request(w, words, slice, lane);
-        cb = *(const HISPMV_TT_GLOBAL int*)(M.col_base + slice);
+        cb = *(const HISPMV_GLOBAL int*)(M.col_base + slice);
     };
     if (wave < blk.y) request(wA, cbA, blk.x + wave);
     load_tile_rows<NV>(M, in, rows0, tile_first_row(M, row0), n_rows, tid);
@@ -273,8 +236,8 @@ __device__ __forceinline__ void tts_t_tile(const TtsDeviceMatrix& M, const float
         if (b + 1 < n_blocks) nxt = load_int4(M.blocks + 2 * (size_t)(block_begin + b + 1));
         // ---- expand: row-major order ----------------------------------------------------------------------------------------
         for (int c = wave; c < n_chunks; c += n_waves) {
-            const int first = *(const HISPMV_TT_GLOBAL int*)((const int*)M.chunk_info + 2 * (size_t)(chunk_begin + c));
-            const unsigned ends = *(const HISPMV_TT_GLOBAL unsigned short*)(M.flags + (size_t)(chunk_begin + c) * 64 + lane);
+            const int first = *(const HISPMV_GLOBAL int*)((const int*)M.chunk_info + 2 * (size_t)(chunk_begin + c));
+            const unsigned ends = *(const HISPMV_GLOBAL unsigned short*)(M.flags + (size_t)(chunk_begin + c) * 64 + lane);
             expand_chunk<NV>(rows0, M.acc_floats, staging0, stage_stride, c, first, ends, n_rows, lane);
         }
         __syncthreads();
@@ -310,14 +273,6 @@ template <int NV>
 __global__ __launch_bounds__(1024) void value_grad_tts_kernel(TtsDeviceMatrix M, const int32_t* __restrict__ map, const float* __restrict__ gy,
                                                               const float* __restrict__ x, float* grad, long long n, float alpha, float beta) {
     tts_t_tile<NV, true>(M, gy, grad, x, map, n, alpha, beta, (int)blockIdx.x);
-}
-
-template <auto Kernel>
-hipError_t raise_lds_limit() {
-    static std::once_flag once;
-    static hipError_t status = hipSuccess;
-    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
-    return status;
 }
 
 // tts_nv_lds_bytes(m, nv, false) of hispmv_kernels.hip: per vector the accumulators, one staging area (the largest block of the matrix in

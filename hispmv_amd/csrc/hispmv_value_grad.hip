@@ -1,7 +1,8 @@
 // hispmv_value_grad.hip -- the kernels of the value gradient (hispmv_value_grad.h): grad[k] = alpha * sum_v gy[v, row_k] * x[v, col_k]
 // + beta * grad[k] for every entry k of the creation input, on the slice streams and dense layouts of loaded, updatable handles.
-// Stands on its own like hispmv_transpose.hip: the few decode helpers of the slice format it needs are its own copies, so that
-// hispmv_kernels.hip, hispmv_transpose.hip and hispmv_update.hip are untouched by this file.
+// What it needs of the slice format (the meta request, decode_metas, store_grad, the buffer loads, the launch
+// checks) it shares with the other four satellite files: hispmv_slice_walk.h.  hispmv_kernels.hip takes no part in that and keeps its
+// own text, so that no forward kernel is touched from here.
 //
 // Roles, against the forward slice kernel (hispmv_kernels.hip: slices_group / batched_group) and the transposed one (slices_group_t):
 //   forward                                  transposed                                 value gradient
@@ -15,94 +16,13 @@
 // word like every other entry and gets its gradient.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
-#include "hispmv_format.h"
+#include "hispmv_slice_walk.h"
 #include "hispmv_update.h"
 #include "hispmv_value_grad.h"
 
 namespace hispmv {
 
 namespace {
-
-#define HISPMV_G_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_G_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ uint2 load_words2(const uint2* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    const u2v v = __builtin_nontemporal_load((const HISPMV_G_GLOBAL u2v*)p);
-    return uint2{v.x, v.y};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_G_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-// a dword through a buffer descriptor: an offset past the descriptor's bytes (kNoAccess among them) reads 0
-constexpr unsigned kNoAccess = 0xffffffffu;
-__device__ __forceinline__ float buffer_float(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return i2f((int)__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t float_buffer(const float* p, int n_floats) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, n_floats * 4, 0x00020000);
-}
-
-// The metas of a slice as they arrive (hispmv_format.h): they begin at byte 4096 of a compact (2 KiB) and of a wide (4 KiB) slice; the
-// 4 KiB of values before them are not requested.  HALF (bf16 storage): the compact metas of step j, lane l are dwords 2 and 3 of the
-// 16-byte piece at (j * 64 + l) * 16; only those 8 bytes are requested, the bf16 values in dwords 0 and 1 are not.
-template <bool COMPACT> struct SliceMetas;
-template <> struct SliceMetas<true>  { uint2 m[kSliceSteps]; };
-template <> struct SliceMetas<false> { uint4 m[kSliceSteps]; };
-template <bool COMPACT, bool HALF = false>
-__device__ __forceinline__ void request_metas(SliceMetas<COMPACT>& s, const char* base, int lane) {
-    static_assert(COMPACT || !HALF, "only a compact group has a half form");
-    if constexpr (HALF) {
-        const uint2* pm = (const uint2*)(base + 8) + 2 * lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 128);
-    } else if constexpr (COMPACT) {
-        const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
-    } else {
-        const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
-    }
-}
-// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j
-template <bool COMPACT>
-__device__ __forceinline__ void decode_metas(const SliceMetas<COMPACT>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
-    if constexpr (COMPACT) {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            const unsigned a = s.m[j].x, b = s.m[j].y;
-            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
-            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
-            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
-            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
-    }
-}
-
-// grad[q - 1] = alpha * s + beta * grad[q - 1] for a map word q that names an input entry; this thread is its only writer
-__device__ __forceinline__ void store_grad(float* grad, long long n, int q, float s, float alpha, float beta) {
-    if (q < 1 || (long long)q > n) return;
-    float* const p = grad + (q - 1);
-    float r = alpha * s;
-    if (beta != 0.0f) r = r + beta * *p;
-    *p = r;
-}
 
 // The work of one workgroup on group `group` of a slice stream for a pass of NV vectors, for a group stored COMPACT (6 B per element),
 // HALF (a compact group of a bf16 handle, 4 B) or wide (8 B).  STRAYS: the plan has stray areas behind the window; whether THIS group uses them is bit 2 of its group word.
@@ -130,7 +50,9 @@ __device__ __forceinline__ void value_grad_group(
     // the columns of every slice's strays live behind the headers, 64 per slice, 0xffffffff = none
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
 
-    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the windows are staged
+    // the forward kernel's walk (rotated start, a wavefront takes every n_waves-th slice); the first request leaves before the windows are staged.
+    // GroupWalk and local_rows of hispmv_slice_walk.h hold this text for the other files; here it stays written out, because through
+    // them hipcc gave three of these kernels more SGPR spills and the compact NV = 4 ones a VGPR more
     const int rot = n_here == 0 ? 0 : (int)((unsigned long long)group * 29ull % (unsigned)n_here);
     int k_slice = wave;
     int local = k_slice < n_here ? (k_slice + rot >= n_here ? k_slice + rot - n_here : k_slice + rot) : n_here;
@@ -346,28 +268,18 @@ __global__ __launch_bounds__(256) void value_grad_dense_kernel(const float* __re
     }
 }
 
-template <auto Kernel>
-hipError_t raise_lds_limit() {
-    static std::once_flag once;
-    static hipError_t status = hipSuccess;
-    std::call_once(once, [] { status = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynLdsMax); });
-    return status;
-}
-
 template <int NV>
 hipError_t launch_value_grad_width(const SpmvDeviceMatrix& m, const int32_t* map, const float* gy, const float* x, float* grad, int64_t n, float alpha,
                                    float beta, hipStream_t stream) {
-    const auto go = [&](auto kernel) {
-        const hipError_t e = raise_lds_limit<kernel()>();
+    return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
+        constexpr auto kernel = value_grad_slices_kernel<NV, USE_LDS(), STRAYS(), HALF()>;
+        const hipError_t e = raise_lds_limit<kernel>();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel(), dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m, NV), stream, (const char*)m.words, m.hdr,
+        hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m, NV), stream, (const char*)m.words, m.hdr,
                            m.groups, m.frags, map, gy, x, grad, (long long)n, alpha, beta, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats,
                            m.cols, m.rows);
         return hipGetLastError();
-    };
-    if (m.lds_floats <= 0) return go([] { return value_grad_slices_kernel<NV, false, false, false>; });
-    if (m.has_strays) return m.has_half ? go([] { return value_grad_slices_kernel<NV, true, true, true>; }) : go([] { return value_grad_slices_kernel<NV, true, true, false>; });
-    return m.has_half ? go([] { return value_grad_slices_kernel<NV, true, false, true>; }) : go([] { return value_grad_slices_kernel<NV, true, false, false>; });
+    });
 }
 
 }  // namespace
@@ -378,12 +290,8 @@ hipError_t launch_value_grad(const SpmvDeviceMatrix& m, int nv, const int32_t* m
     if (nv != 1 && nv != 2 && nv != 4) return hipErrorInvalidValue;
     if (m.n_slices <= 0 || m.n_groups <= 0 || n <= 0) return hipSuccess;
     if (!map) return hipErrorInvalidValue;
-    if (m.lds_floats <= 0 && m.has_half) return hipErrorInvalidValue;          // half groups exist only in plans with a window
-    if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || slice_lds_bytes(m, nv) > (size_t)kDynLdsMax)
-        return hipErrorInvalidValue;
+    if (!slice_geometry_ok(m, slice_lds_bytes(m, nv))) return hipErrorInvalidValue;
     if ((int64_t)m.cols * nv >= (1 << 30) || (int64_t)m.rows * nv >= (1 << 30)) return hipErrorInvalidValue;
-    if (m.lds_floats <= 0 && m.has_strays) return hipErrorInvalidValue;        // stray slots exist only in plans with a window
-    if (m.has_strays && m.lds_floats < (m.block_threads / 64) * kStraySlots) return hipErrorInvalidValue;
     switch (nv) {
         case 4: return launch_value_grad_width<4>(m, map, gy, x, grad, n, alpha, beta, stream);
         case 2: return launch_value_grad_width<2>(m, map, gy, x, grad, n, alpha, beta, stream);
