@@ -19,8 +19,12 @@ transpose when that is a slice stream and through the atomics otherwise).  The u
 --wide-grad (implies --spmm) takes the value gradient through the wide-batch entry as well (sparse_linear(..., wide_grad=True)): the
 feature-major copies of x and grad_y serve all three products of a step.
 
+--bf16-activations (implies --spmm) keeps the activations bfloat16: x is drawn in fp32 and rounded once, y and grad_x are bf16
+(sparse_linear(..., spmm=True) on a bfloat16 x: FpgaHandle.spmm_device_bf16 / spmm_device_t_bf16), the loss is taken in fp32 on the
+widened y; bias and the values stay fp32, and the value gradient runs through the fp32 entries on widened copies.
+
     python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1] [--bf16]
-                                          [--companion] [--spmm] [--wide-grad]
+                                          [--companion] [--spmm] [--wide-grad] [--bf16-activations]
 """
 from __future__ import annotations
 
@@ -54,6 +58,8 @@ def train(a, r, c, start, teacher, storage: str) -> list:
         dev = torch.device("cuda", 0)
         gen = torch.Generator(device=dev).manual_seed(0)
         x = torch.randn((a.batch, a.cols), dtype=torch.float32, device=dev, generator=gen)
+        if a.bf16_activations:
+            x = x.to(torch.bfloat16)
         bias = torch.zeros(a.rows, dtype=torch.float32, device=dev)
         teacher_d, v = torch.from_numpy(teacher).to(dev), torch.from_numpy(start).to(dev).requires_grad_(True)
         torch.cuda.synchronize()
@@ -66,7 +72,7 @@ def train(a, r, c, start, teacher, storage: str) -> list:
                 target = sparse_linear(h, i, x, bias, values=teacher_d, spmm=a.spmm, wide_grad=a.wide_grad)
             for step in range(a.steps):
                 y = sparse_linear(h, i, x, bias, values=v, spmm=a.spmm, wide_grad=a.wide_grad)
-                loss = ((y - target) ** 2).mean() * a.rows
+                loss = ((y.float() - target.float()) ** 2).mean() * a.rows
                 loss.backward()
                 with torch.no_grad():
                     v -= a.lr * v.grad
@@ -93,8 +99,9 @@ def main() -> None:
     ap.add_argument("--companion", action="store_true", help="store the transpose with the handle: a deterministic backward pass, for its bytes")
     ap.add_argument("--spmm", action="store_true", help="forward and grad_x through the wide-batch entries (feature-major operands, lanes across vectors)")
     ap.add_argument("--wide-grad", action="store_true", help="the value gradient through the wide-batch entry as well (implies --spmm)")
+    ap.add_argument("--bf16-activations", action="store_true", help="bfloat16 x, y and grad_x through the bf16 wide-batch entries (implies --spmm)")
     a = ap.parse_args()
-    a.spmm = a.spmm or a.wide_grad
+    a.spmm = a.spmm or a.wide_grad or a.bf16_activations
 
     rng = np.random.default_rng(0)
     r, c = np.nonzero(rng.random((a.rows, a.cols)) < a.density)

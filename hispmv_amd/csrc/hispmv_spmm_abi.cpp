@@ -1,9 +1,11 @@
 // hispmv_spmm_abi.cpp -- the wide-batch entries of the C ABI (include/hispmv.h: hispmv_spmm_device, hispmv_spmm_device_t,
-// hispmv_spmm_info, hispmv_prep_spmm_tiles, hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_info) over the launchers of
-// hispmv_spmm.h and hispmv_spmm_grad.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
+// hispmv_spmm_info, hispmv_prep_spmm_tiles, hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_info, and the bf16-activation forms
+// hispmv_spmm_device_bf16, hispmv_spmm_device_t_bf16, hispmv_spmm_bf16_info, hispmv_prep_spmm_bf16_tiles) over the launchers of
+// hispmv_spmm.h, hispmv_spmm_bf16.h and hispmv_spmm_grad.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
 // nothing in it, so the other entry points are not touched.
 #include "hispmv_ctx.h"
 #include "hispmv_spmm.h"
+#include "hispmv_spmm_bf16.h"
 #include "hispmv_spmm_grad.h"
 
 using namespace hispmv;
@@ -137,6 +139,138 @@ HISPMV_API int hispmv_spmm_device_t(hispmv_ctx* c, int idx, const float* d_xt, i
                                            "; create it after hispmv_set_transposable(ctx, 3) (FpgaHandle.set_transposable(\"companion\"))");
     if (!t->loaded) return fail(c, HISPMV_ESTATE, "internal: the stored transpose is not loaded");
     return run_spmm(c, *t, "spmm_device_t", d_xt, num_vecs, ld_x, d_bias, bias_stride, d_yt, ld_y, alpha, beta, d_work, work_bytes, stream);
+}
+
+// ---- wide batch with bf16 activations (include/hispmv.h: hispmv_spmm_device_bf16; kernels: hispmv_spmm_bf16.hip) ----------------------
+namespace {
+
+// bytes of the workspace for tiles of 64 * vb vectors: the fp32 partials of the largest part, then -- more than one part -- the fp32 tile
+// accumulator the parts add into
+int64_t bf16_partials_of(const Matrix& t, int vb) {
+    int64_t n = 0;
+    for (auto& p : t.parts) n = std::max(n, spmm_bf16_work_bytes(p.dev, vb));
+    return n;
+}
+int64_t bf16_work_bytes_of(const Matrix& t, int vb) { return bf16_partials_of(t, vb) + (t.parts.size() > 1 ? spmm_bf16_acc_bytes(t.rows, vb) : 0); }
+
+int64_t pointer_align2(const void* p) {
+    const uintptr_t u = (uintptr_t)p;
+    return (u & 15) == 0 ? 16 : (u & 7) == 0 ? 8 : (u & 3) == 0 ? 4 : 2;
+}
+
+// run_spmm for 2-byte operands: the same checks in the same order, the same tiles-then-parts order of launches.  More than one part:
+// every part but the last stores fp32 into the tile accumulator (part 0 with the caller's beta * bias, a later one adding in place),
+// the last reads it as its bias and is the only one that rounds and stores to yt.
+int run_spmm_bf16(hispmv_ctx* c, const Matrix& t, const char* who, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias,
+                  int64_t bias_stride, uint16_t* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream) {
+    const std::string w(who);
+    if (num_vecs < 1) return fail(c, HISPMV_EINVAL, w + ": num_vecs must be at least 1");
+    if (num_vecs > 0x7fffffffLL) return fail(c, HISPMV_EINVAL, w + ": num_vecs must stay below 2^31");
+    if (ld_x < num_vecs || ld_y < num_vecs) return fail(c, HISPMV_EINVAL, w + ": ld_x and ld_y must be at least num_vecs");
+    if (!d_xt || !d_yt || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
+    if (d_xt == d_yt) return fail(c, HISPMV_EINVAL, w + ": xt and yt must not be the same matrix");
+    if (bias_stride != 0 && bias_stride != ld_y) return fail(c, HISPMV_EINVAL, w + ": bias_stride must be 0 (one fp32 bias[row] for all vectors) or ld_y");
+    if (beta != 0.0f && d_bias == (const void*)d_yt && bias_stride == 0) return fail(c, HISPMV_EINVAL, w + ": d_bias == d_yt needs bias_stride = ld_y");
+    if (((uintptr_t)d_xt | (uintptr_t)d_yt | (bias_stride != 0 ? (uintptr_t)d_bias : 0)) & 1)
+        return fail(c, HISPMV_EINVAL, w + ": bf16 device pointers must be 2-byte aligned");
+    if (((uintptr_t)d_work | (bias_stride == 0 ? (uintptr_t)d_bias : 0)) & 3)
+        return fail(c, HISPMV_EINVAL, w + ": the workspace and a shared fp32 bias must be 4-byte aligned");
+    // what hispmv_spmm_bf16_info reports for these leading dimensions (16-byte aligned pointers: the widest lanes, the largest workspace)
+    const int64_t need = bf16_work_bytes_of(t, spmm_bf16_tiles(t.cols, num_vecs, ld_x, ld_y, 16).vl_first);
+    if (work_bytes < need || (need > 0 && !d_work))
+        return fail(c, HISPMV_EINVAL, w + ": the workspace holds " + std::to_string(work_bytes) + " bytes, hispmv_spmm_bf16_info asks for " + std::to_string(need));
+    // every argument is accepted: from here on the call is one hispmv_synchronize waits for
+    if (stream) c->user_stream = (hipStream_t)stream;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SpmmBf16Operands a{};
+    a.xt = d_xt; a.yt = d_yt; a.work = (float*)d_work; a.ld_x = ld_x; a.ld_y = ld_y; a.n_vecs = (int)num_vecs;
+    const int caller_bias = bias_stride == 0 ? kBf16BiasShared : kBf16BiasMatrix;
+    if (alpha == 0.0f) {          // yt is exactly bf16(beta * bias); neither xt nor the matrix is read
+        a.bias = d_bias; a.bias_kind = caller_bias; a.alpha = 0.0f; a.beta = beta;
+        const hipError_t e = launch_spmm_bf16_bias(a, t.rows, s);
+        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_spmm_bf16_bias");
+    }
+    // a lane's VB halves must be one aligned access in every row of xt, yt and a bias laid out like yt; its fp32 partials go in two
+    // accesses of VB / 2 floats, which the same alignment of the workspace covers
+    int64_t align = std::min({pointer_align2(d_xt), pointer_align2(d_yt), pointer_align2(d_work)});
+    if (beta != 0.0f && bias_stride != 0) align = std::min(align, pointer_align2(d_bias));
+    size_t first = t.parts.size(), last = 0;          // the parts that hold slices (only a matrix without rows has a part without)
+    for (size_t q = 0; q < t.parts.size(); ++q)
+        if (t.parts[q].dev.n_slices > 0) { first = std::min(first, q); last = q; }
+    for (int64_t k = 0; k < num_vecs;) {
+        const int vb = spmm_bf16_vb(t.cols, num_vecs - k, ld_x, ld_y, align);
+        a.tile0 = (int)k;
+        a.acc = t.parts.size() > 1 ? (float*)((char*)d_work + bf16_partials_of(t, vb)) : nullptr;
+        for (size_t q = first; q <= last && q < t.parts.size(); ++q) {
+            const SpmvDeviceMatrix& d = t.parts[q].dev;
+            if (d.n_slices <= 0) continue;
+            if (q == first) { a.bias = d_bias; a.bias_kind = caller_bias; a.alpha = alpha; a.beta = beta; }
+            else { a.bias = nullptr; a.bias_kind = kBf16BiasAcc; a.alpha = alpha; a.beta = 1.0f; }
+            a.to_acc = q == last ? 0 : 1;
+            const hipError_t e = launch_spmm_bf16_part(d, vb, a, s);
+            if (e != hipSuccess) return hip_fail(c, e, "launch_spmm_bf16_part");
+        }
+        k += std::min<int64_t>(num_vecs - k, 64 * vb);
+    }
+    return HISPMV_OK;
+}
+
+}  // namespace
+
+HISPMV_API int hispmv_prep_spmm_bf16_tiles(int64_t cols, int64_t num_vecs, int64_t ld, int64_t align_bytes, int64_t out[4]) {
+    if (!out || cols < 1 || num_vecs < 1 || ld < 1 || align_bytes < 1) return HISPMV_EINVAL;
+    if (ld < num_vecs) return HISPMV_EINVAL;
+    const SpmmTiles t = spmm_bf16_tiles(cols, num_vecs, ld, ld, align_bytes);
+    out[0] = t.vl_first; out[1] = t.tiles; out[2] = t.last_vecs; out[3] = t.vl_last;
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_spmm_bf16_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t ld, int64_t out[8]) {
+    if (!c || !out || idx < 0 || idx >= (int)c->mats.size() || num_vecs < 1 || ld < num_vecs) return HISPMV_EINVAL;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    const Matrix& m = *c->mats[(size_t)idx];
+    if (!m.loaded) return HISPMV_OK;
+    const bool fwd = spmm_accepts(m);
+    const Matrix* t = spmm_companion(m);
+    out[0] = fwd ? 1 : 0; out[1] = t ? 1 : 0;
+    if (fwd) {
+        const SpmmTiles tl = spmm_bf16_tiles(m.cols, num_vecs, ld, ld, 16);
+        out[2] = tl.vl_first; out[3] = tl.tiles; out[4] = launches_of(m, tl.tiles); out[5] = bf16_work_bytes_of(m, tl.vl_first);
+    }
+    if (t) out[6] = bf16_work_bytes_of(*t, spmm_bf16_tiles(t->cols, num_vecs, ld, ld, 16).vl_first);
+    return HISPMV_OK;
+}
+
+HISPMV_API int hispmv_spmm_device_bf16(hispmv_ctx* c, int idx, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias, int64_t bias_stride,
+                                       uint16_t* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[(size_t)idx];
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmm_device_bf16 called before load_matrices");
+    if (m.dense)
+        return fail(c, HISPMV_ENOTSUP, "spmm_device_bf16: this is a dense handle; a wide batch against a dense W is a GEMM, which this library leaves to a GEMM library");
+    if (!spmm_accepts(m))
+        return fail(c, HISPMV_ENOTSUP, "spmm_device_bf16: this handle is a transposed tile stream, which has no wide-batch kernel; create it after "
+                                       "hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream");
+    return run_spmm_bf16(c, m, "spmm_device_bf16", d_xt, num_vecs, ld_x, d_bias, bias_stride, d_yt, ld_y, alpha, beta, d_work, work_bytes, stream);
+}
+
+HISPMV_API int hispmv_spmm_device_t_bf16(hispmv_ctx* c, int idx, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias, int64_t bias_stride,
+                                         uint16_t* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream) {
+    if (!c) return HISPMV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
+    Matrix& m = *c->mats[(size_t)idx];
+    if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmm_device_t_bf16 called before load_matrices");
+    const Matrix* t = spmm_companion(m);
+    if (!t)
+        return fail(c, HISPMV_ENOTSUP, std::string("spmm_device_t_bf16: the transposed wide batch runs over a stored transpose that is a slice stream, and this handle ") +
+                                           (m.companion ? "stores its transpose as a tile stream" : "has none") +
+                                           "; create it after hispmv_set_transposable(ctx, 3) (FpgaHandle.set_transposable(\"companion\"))");
+    if (!t->loaded) return fail(c, HISPMV_ESTATE, "internal: the stored transpose is not loaded");
+    return run_spmm_bf16(c, *t, "spmm_device_t_bf16", d_xt, num_vecs, ld_x, d_bias, bias_stride, d_yt, ld_y, alpha, beta, d_work, work_bytes, stream);
 }
 
 // ---- wide-batch value gradient (include/hispmv.h: hispmv_spmm_value_grad_device; kernels: hispmv_spmm_grad.hip) ---------------------

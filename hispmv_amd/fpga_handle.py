@@ -335,6 +335,38 @@ class FpgaHandle:
         return {"accepted": bool(out[0]), "accepted_t": bool(out[1]), "vl": int(out[2]), "tiles": int(out[3]), "launches": int(out[4]),
                 "work_bytes": int(out[5]), "work_bytes_t": int(out[6])}
 
+    def spmm_device_bf16(self, matrix_idx: int, d_xt: int, num_vecs: int, d_bias: int, d_yt: int, alpha: float = 1.0, beta: float = 0.0,
+                         ld_x=None, ld_y=None, bias_stride: int = 0, work: int = 0, work_bytes: int = 0, stream: int = 0) -> None:
+        """spmm_device with bf16 activations (hispmv_spmm_device_bf16): xt [cols, ld_x] and yt [rows, ld_y] hold bfloat16, ld in elements.
+        bias_stride 0: d_bias is an FP32 bias[rows]; ld_y: a BF16 matrix laid out like yt, which may be yt (in place).  Products and
+        sums are fp32 in the order of spmm_device; the finished value -- bit for bit what spmm_device stores for the widened operands --
+        is rounded once to bf16 (nearest, ties to even).  A lane owns up to 8 vectors, a tile is up to 512.  work_bytes >=
+        spmm_bf16_info(...)["work_bytes"].  Same handles, same exceptions as spmm_device."""
+        self._check(lib.hispmv_spmm_device_bf16(self._ctx, int(matrix_idx), C.c_void_p(d_xt), int(num_vecs), int(num_vecs if ld_x is None else ld_x),
+                                                C.c_void_p(d_bias), int(bias_stride), C.c_void_p(d_yt), int(num_vecs if ld_y is None else ld_y),
+                                                float(alpha), float(beta), C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def spmm_device_t_bf16(self, matrix_idx: int, d_xt: int, num_vecs: int, d_bias: int, d_yt: int, alpha: float = 1.0, beta: float = 0.0,
+                           ld_x=None, ld_y=None, bias_stride: int = 0, work: int = 0, work_bytes: int = 0, stream: int = 0) -> None:
+        """spmm_device_bf16 with A^T: xt is [rows, ld_x], yt [cols, ld_y], bfloat16 (hispmv_spmm_device_t_bf16); work_bytes >=
+        spmm_bf16_info(...)["work_bytes_t"].  Same handles, same exceptions as spmm_device_t."""
+        self._check(lib.hispmv_spmm_device_t_bf16(self._ctx, int(matrix_idx), C.c_void_p(d_xt), int(num_vecs), int(num_vecs if ld_x is None else ld_x),
+                                                  C.c_void_p(d_bias), int(bias_stride), C.c_void_p(d_yt), int(num_vecs if ld_y is None else ld_y),
+                                                  float(alpha), float(beta), C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def spmm_bf16_info(self, matrix_idx: int, num_vecs: int, ld=None) -> dict:
+        """{"accepted", "accepted_t", "vb", "tiles", "launches", "work_bytes", "work_bytes_t"} of spmm_device_bf16 / spmm_device_t_bf16 for
+        num_vecs vectors with ld_x = ld_y = ld (default num_vecs) and 16-byte aligned pointers (hispmv_spmm_bf16_info): the bf16 per lane
+        of the first tile, the vector tiles, the launches of a call with alpha != 0, the workspace bytes (valid for every alignment)."""
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_spmm_bf16_info(self._ctx, int(matrix_idx), int(num_vecs), int(num_vecs if ld is None else ld), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError("num_vecs must be at least 1 and ld at least num_vecs")
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "accepted_t": bool(out[1]), "vb": int(out[2]), "tiles": int(out[3]), "launches": int(out[4]),
+                "work_bytes": int(out[5]), "work_bytes_t": int(out[6])}
+
     def spmm_value_grad_device(self, matrix_idx: int, d_gyt: int, d_xt: int, num_vecs: int, d_grad: int, alpha: float = 1.0, beta: float = 0.0,
                                ld_gy=None, ld_x=None, stream: int = 0) -> None:
         """grad[k] = alpha * sum_v gyt[row_k, v] * xt[col_k, v] + beta * grad[k] for every entry k of the creation input of a loaded,

@@ -276,6 +276,17 @@ def spmm_tiles(cols: int, num_vecs: int, ld=None, align_bytes: int = 16) -> dict
     return {"vl": int(out[0]), "tiles": int(out[1]), "last_vecs": int(out[2]), "vl_last": int(out[3])}
 
 
+def spmm_bf16_tiles(cols: int, num_vecs: int, ld=None, align_bytes: int = 16) -> dict:
+    """The vector tiles of a wide call with bf16 activations (hispmv_prep_spmm_bf16_tiles), host-only: {"vb", "tiles", "last_vecs",
+    "vb_last"} for num_vecs vectors against a matrix of `cols` columns, leading dimension ld (default num_vecs, in elements), pointers
+    aligned to align_bytes.  A lane owns vb in {8, 4, 2, 1} bf16, a tile is 64 * vb vectors."""
+    out = (C.c_int64 * 4)()
+    rc = lib.hispmv_prep_spmm_bf16_tiles(int(cols), int(num_vecs), int(num_vecs if ld is None else ld), int(align_bytes), out)
+    if rc != HISPMV_OK:
+        raise ValueError("hispmv_prep_spmm_bf16_tiles: cols, num_vecs, ld and align_bytes must be at least 1, ld at least num_vecs")
+    return {"vb": int(out[0]), "tiles": int(out[1]), "last_vecs": int(out[2]), "vb_last": int(out[3])}
+
+
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 

@@ -21,7 +21,8 @@ stream the caller synchronises between torch's operations and the layer.
 
 ``spmm=True`` routes the forward product and grad_x through the wide-batch entries (FpgaHandle.spmm_device / spmm_device_t) on
 feature-major copies of the activations; ``wide_grad=True`` on top of it takes grad_values through the wide-batch value gradient
-(FpgaHandle.spmm_value_grad_device) on the same copies.  The default route is unchanged (see sparse_linear).
+(FpgaHandle.spmm_value_grad_device) on the same copies.  With ``spmm=True`` a bfloat16 ``x`` stays bfloat16 through both products
+(FpgaHandle.spmm_device_bf16 / spmm_device_t_bf16).  The default route is unchanged (see sparse_linear).
 
 The backward pass is differentiable once (no double backward).  The autograd graph keeps a reference to the handle, which keeps the
 object alive but not open: the handle must not be closed between forward and backward (a closed handle makes backward raise, it does
@@ -29,11 +30,12 @@ not launch).  torch is imported inside the functions, as in hispmv_amd/dist.py."
 from __future__ import annotations
 
 
-def _check_tensor(torch, t, name: str, last: int, dims) -> None:
+def _check_tensor(torch, t, name: str, last: int, dims, dtype=None) -> None:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch tensor")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, not {t.dtype}")
+    dtype = torch.float32 if dtype is None else dtype
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, not {t.dtype}")
     if not t.is_cuda:
         raise ValueError(f"{name} must be a device (cuda) tensor")
     if t.dim() not in dims or t.shape[-1] != last:
@@ -323,6 +325,113 @@ def _function_spmm_wide(torch):
     return SparseLinearSpmmWide
 
 
+def _function_spmm_bf16(torch):
+    fn = getattr(_function_spmm_bf16, "cached", None)
+    if fn is not None:
+        return fn
+
+    def feature_major(a, ld, dtype):
+        """[B, n] -> [n, ld] of `dtype` with the batch in the first B columns and zeros in the pad columns"""
+        B = a.shape[0]
+        if ld == B:
+            return a.t().to(dtype).contiguous()
+        at = torch.zeros((a.shape[1], ld), dtype=dtype, device=a.device)
+        at[:, :B] = a.t()
+        return at
+
+    def workspace(work_bytes, device):
+        return torch.empty((max(work_bytes, 4) + 3) // 4, dtype=torch.float32, device=device)
+
+    class SparseLinearSpmmBf16(torch.autograd.Function):
+        """sparse_linear with spmm=True and a bfloat16 x: forward through spmm_device_bf16 on a feature-major bf16 copy (ld = B rounded up
+        to 8), y bf16; grad_x bf16 through spmm_device_t_bf16 where the handle has a slice-stream companion, otherwise linear_device_t on
+        the widened grad_y, narrowed by torch.  bias is fp32, grad_bias = grad_y.float().sum(0).  `values` is the fp32 master copy:
+        its gradient goes through the unchanged fp32 entries on torch-widened copies of the saved activations and of grad_y --
+        spmm_value_grad_device on feature-major copies (ld = B rounded up to 4, as SparseLinearSpmmWide builds them) when `wide`,
+        value_grad_device otherwise -- so it has the bits of the fp32-activation call on the widened inputs.  Stream ordering as in
+        SparseLinearSpmm."""
+
+        @staticmethod
+        def forward(ctx, x, bias, values, handle, idx, rows, wide):
+            ctx.handle, ctx.idx, ctx.has_bias, ctx.has_values, ctx.wide = handle, idx, bias is not None, values is not None, wide
+            current = torch.cuda.current_stream(x.device)
+            stream = current.cuda_stream
+            B = x.shape[0]
+            ld = (B + 7) & ~7
+            info = handle.spmm_bf16_info(idx, B, ld)
+            v = values.contiguous() if values is not None else None
+            b = bias.contiguous() if bias is not None else None
+            xt = feature_major(x, ld, torch.bfloat16)
+            yt = torch.empty((rows, ld), dtype=torch.bfloat16, device=x.device)
+            work = workspace(info["work_bytes"], x.device)
+            if stream == 0:
+                current.synchronize()
+            if v is not None:
+                handle.update_values_device(idx, v.data_ptr(), v.numel(), stream)
+                ctx.n = v.numel()
+            handle.spmm_device_bf16(idx, xt.data_ptr(), B, b.data_ptr() if b is not None else 0, yt.data_ptr(), 1.0, 1.0 if b is not None else 0.0,
+                                    ld_x=ld, ld_y=ld, work=work.data_ptr(), work_bytes=info["work_bytes"], stream=stream)
+            if stream == 0:
+                handle.synchronize()
+            del xt, work, b, v
+            ctx.cols = x.shape[1]
+            if values is not None and values.requires_grad:          # x is kept for the value gradient only
+                ctx.save_for_backward(x.contiguous())
+            return yt[:, :B].t()
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_y):
+            grad_x = grad_bias = grad_values = None
+            handle, idx = ctx.handle, ctx.idx
+            current = torch.cuda.current_stream(grad_y.device)
+            stream = current.cuda_stream
+            B = grad_y.shape[0]
+            ld, ld4 = (B + 7) & ~7, (B + 3) & ~3
+            if ctx.has_bias and ctx.needs_input_grad[1]:
+                grad_bias = grad_y.float().sum(0)
+            want_x, want_v = ctx.needs_input_grad[0], ctx.has_values and ctx.needs_input_grad[2]
+            # torch's side first: everything the launches below read or write
+            info = handle.spmm_bf16_info(idx, B, ld) if want_x else None
+            wide_t = want_x and info["accepted_t"]
+            g = gt = gxt = gx32 = work = g32 = x32 = None
+            if wide_t:
+                gt = feature_major(grad_y, ld, torch.bfloat16)
+                gxt = torch.empty((ctx.cols, ld), dtype=torch.bfloat16, device=grad_y.device)
+                work = workspace(info["work_bytes_t"], grad_y.device)
+            elif want_x:
+                g = grad_y.float().contiguous()
+                gx32 = torch.empty((B, ctx.cols), dtype=torch.float32, device=grad_y.device)
+            if want_v:
+                (x,) = ctx.saved_tensors
+                if ctx.wide:
+                    g32, x32 = feature_major(grad_y, ld4, torch.float32), feature_major(x, ld4, torch.float32)
+                else:
+                    g32, x32 = (g if g is not None else grad_y.float().contiguous()), x.float()
+                grad_values = torch.empty((ctx.n,), dtype=torch.float32, device=grad_y.device)
+            if stream == 0 and (want_x or want_v):
+                current.synchronize()
+            if wide_t:
+                handle.spmm_device_t_bf16(idx, gt.data_ptr(), B, 0, gxt.data_ptr(), 1.0, 0.0, ld_x=ld, ld_y=ld, work=work.data_ptr(),
+                                          work_bytes=info["work_bytes_t"], stream=stream)
+                grad_x = gxt[:, :B].t()
+            elif want_x:
+                handle.linear_device_t(idx, g.data_ptr(), B, 0, gx32.data_ptr(), 1.0, 0.0, 0, stream)
+            if want_v and ctx.wide:
+                handle.spmm_value_grad_device(idx, g32.data_ptr(), x32.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, ld_gy=ld4, ld_x=ld4, stream=stream)
+            elif want_v:
+                handle.value_grad_device(idx, g32.data_ptr(), x32.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, stream)
+            if stream == 0 and (want_x or want_v):
+                handle.synchronize()
+            if gx32 is not None:
+                grad_x = gx32.to(torch.bfloat16)              # (on the default stream behind the wait above: gx32 is written)
+            del g, gt, work, g32, x32
+            return grad_x, grad_bias, grad_values, None, None, None, None
+
+    _function_spmm_bf16.cached = SparseLinearSpmmBf16
+    return SparseLinearSpmmBf16
+
+
 def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = False, wide_grad: bool = False):
     """y = A x (+ bias) for the loaded matrix `idx` of `handle` (an FpgaHandle): x is a float32 CUDA tensor [B, cols] or [cols] (made
     contiguous), the result [B, rows] (or [rows]); bias, if given, a float32 CUDA tensor [rows].  Differentiable in x and bias (grad_x =
@@ -368,6 +477,14 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     allows.  On torch's default stream every pass waits on the host after torch has built those copies and again behind the library's
     launches (the context's stream is not ordered with torch's kernels).
 
+    spmm=True with a bfloat16 x (CUDA, [B, cols] or [cols]): the activations stay bf16.  Forward builds a feature-major bf16 copy (leading
+    dimension B rounded up to 8, so that every batch takes the lane widths its size allows), multiplies through
+    FpgaHandle.spmm_device_bf16 and returns a bf16 [B, rows]: per element the fp32 value of the float32 route on x.float(), rounded once.
+    grad_x is bf16: through spmm_device_t_bf16 where the handle has a slice-stream companion, otherwise linear_device_t on the widened
+    grad_y, narrowed by torch.  bias stays a float32 [rows] tensor and grad_bias = grad_y.float().sum(0); `values` stays the float32
+    master copy, and its gradient goes through the unchanged fp32 gradient entries (wide_grad or not) on torch-widened copies of x and
+    grad_y: bit for bit the gradient of the float32 route on the widened tensors.  With spmm=False a bfloat16 x raises TypeError.
+
     wide_grad=False (default): nothing changes.  wide_grad=True needs spmm=True and `values` (otherwise ValueError, before any launch)
     and takes grad_values through FpgaHandle.spmm_value_grad_device: the forward pass saves the feature-major copy of x it built
     anyway (instead of x), the backward pass builds the feature-major grad_y once and uses it for spmm_device_t (where the handle has
@@ -380,7 +497,8 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     if wide_grad and values is None:
         raise ValueError("wide_grad=True needs values")
     info = handle.matrix_info(idx)
-    _check_tensor(torch, x, "x", info["cols"], (1, 2))
+    bf16 = spmm and isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16
+    _check_tensor(torch, x, "x", info["cols"], (1, 2), torch.bfloat16 if bf16 else torch.float32)
     if bias is not None:
         _check_tensor(torch, bias, "bias", info["rows"], (1,))
         if bias.device != x.device:
@@ -391,6 +509,9 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     if spmm and not handle.spmm_info(idx, 1)["accepted"]:
         raise NotImplementedError("sparse_linear(spmm=True) needs a loaded slice-stream handle (FpgaHandle.set_transposable(True) keeps a sparse "
                                   "handle one); tile-stream and dense handles have no wide-batch kernel")
+    if values is None and bf16:
+        y = _function_spmm_bf16(torch).apply(x.unsqueeze(0) if one else x, bias, None, handle, int(idx), info["rows"], False)
+        return y.squeeze(0) if one else y
     if values is None and spmm:
         y = _function_spmm(torch).apply(x.unsqueeze(0) if one else x, bias, None, handle, int(idx), info["rows"])
         return y.squeeze(0) if one else y
@@ -403,6 +524,9 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     _check_tensor(torch, values, "values", upd["n"], (1,))
     if values.device != x.device:
         raise ValueError("values must be on the device of x")
+    if bf16:
+        y = _function_spmm_bf16(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"], bool(wide_grad))
+        return y.squeeze(0) if one else y
     if spmm:
         fn = _function_spmm_wide(torch) if wide_grad else _function_spmm(torch)
         y = fn.apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"])

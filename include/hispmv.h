@@ -428,7 +428,8 @@ int hispmv_value_grad_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_ve
  *    work_bytes smaller than hispmv_spmm_info reports for (num_vecs, ld_x, ld_y), NULL d_xt or d_yt, NULL d_bias with beta != 0,
  *    d_xt == d_yt, d_bias == d_yt with bias_stride 0, a bad index -> HISPMV_EINVAL.
  * Out of scope: tile-stream and dense handles, a transposed wide product without a stored transpose, wide calls
- * inside hispmv_spmv_device_batch or the step kernel, sharding over devices, host-pointer variants, bf16 activations. */
+ * inside hispmv_spmv_device_batch or the step kernel, sharding over devices, host-pointer variants.  (bf16 activations:
+ * hispmv_spmm_device_bf16 below.) */
 int hispmv_spmm_device(hispmv_ctx* ctx, int matrix_idx, const float* d_xt, int64_t num_vecs, int64_t ld_x, const float* d_bias,
                        int64_t bias_stride, float* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
 int hispmv_spmm_device_t(hispmv_ctx* ctx, int matrix_idx, const float* d_xt, int64_t num_vecs, int64_t ld_x, const float* d_bias,
@@ -468,7 +469,7 @@ int hispmv_spmm_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, in
  *  - HANDLE STATE: the entry reads metas, slice headers, fragment tables, stray columns and the value map, and writes nothing but
  *    d_grad: it may overlap forward, transposed, wide and update calls on the same handle.
  * Out of scope: tile-stream and dense handles, gradients inside hispmv_spmv_device_batch or the step kernel, sharding over devices,
- * host-pointer variants, bf16 activations. */
+ * host-pointer variants, bf16 activations (the products take them: hispmv_spmm_device_bf16; the value gradients do not). */
 int hispmv_spmm_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gyt, int64_t ld_gy, const float* d_xt, int64_t ld_x,
                                   int64_t num_vecs, float* d_grad, float alpha, float beta, void* stream);
 /* out = {1 if hispmv_spmm_value_grad_device accepts the (loaded) handle, VL of the first tile, vector tiles, launches of a call with
@@ -482,6 +483,41 @@ int hispmv_spmm_value_grad_info(const hispmv_ctx* ctx, int matrix_idx, int64_t n
  * The last tile is masked per lane.  out = {VL of the first tile, tiles, vectors in the last tile, VL of the last tile}.  cols,
  * num_vecs, ld or align_bytes < 1, or ld < num_vecs -> HISPMV_EINVAL. */
 int hispmv_prep_spmm_tiles(int64_t cols, int64_t num_vecs, int64_t ld, int64_t align_bytes, int64_t out[4]);
+
+/* ---- wide batch with bf16 activations ---------------------------------------------------------------------------------------------
+ *   hispmv_spmm_device_bf16:    yt[r, v] = bf16(alpha * sum_k a_rk * xt[k, v] + beta * bias),      r < rows, v < num_vecs
+ *   hispmv_spmm_device_t_bf16:  the same with A^T: xt is [rows, ld_x], yt is [cols, ld_y]
+ * hispmv_spmm_device / hispmv_spmm_device_t with 2-byte operands: d_xt [cols, ld_x] and d_yt [rows, ld_y] hold bfloat16 (uint16_t: the
+ * upper half of the fp32), every other argument means what it means there.  The matrix values are the handle's (fp32 or bf16 storage),
+ * products and sums are fp32.  A lane owns VB = 8, 4, 2 or 1 consecutive vectors (one dwordx4, dwordx2, dword or 16-bit load per stored
+ * element): a tile is 64 * VB vectors, up to 512.  Asynchronous on `stream` (the stream rule above).
+ *  - BIAS: bias_stride == 0: d_bias is one vector of rows FP32 values, as in hispmv_spmm_device; bias_stride == ld_y: d_bias is a BF16
+ *    matrix laid out like d_yt and may BE d_yt (in place).  beta == 0 never reads d_bias.  alpha == 0 gives exactly bf16(beta * bias).
+ *  - ALIGNMENT: d_xt, d_yt and a matrix bias 2 bytes at least; d_work and a shared bias 4 bytes.  Less than 16 bytes may take a smaller VB.
+ *  - The elements num_vecs .. ld_y - 1 of a row of d_yt are not written.  ZERO SLOTS as in hispmv_spmm_device.
+ *  - BITS: widening a bf16 is exact, and the fp32 value of yt[r, v] before it is stored has the fixed order of hispmv_spmm_device: it is
+ *    bit for bit what hispmv_spmm_device stores for the widened operands (the bias widened), whatever num_vecs, the tile or VB.  It is
+ *    then rounded ONCE: nearest, ties to even; +-Inf stay; overflow becomes Inf; a NaN becomes a quiet NaN with its sign
+ *    (hispmv_update_values on a bf16 handle rounds by the same rule).  A handle of several parts does not round between them: the parts
+ *    add into an fp32 tile accumulator [rows, 64 * VB] in the workspace and the last part alone stores to d_yt.
+ *  - ACCEPTED, refused, and every error with its code and order: as hispmv_spmm_device / hispmv_spmm_device_t.  All before any launch.
+ *  - WORKSPACE: the bytes hispmv_spmm_bf16_info reports: the fp32 partial sums of hispmv_spmm_device for tiles of 64 * VB vectors, and
+ *    for a handle of more than one part the tile accumulator behind them.  The caller's; nothing is kept in the handle.
+ * Out of scope: bf16 activations for the value gradients, hispmv_linear_device* and the one-vector entries; tile-stream and dense
+ * handles; wide calls inside hispmv_spmv_device_batch or the step kernel; sharding over devices. */
+int hispmv_spmm_device_bf16(hispmv_ctx* ctx, int matrix_idx, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias,
+                            int64_t bias_stride, uint16_t* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
+int hispmv_spmm_device_t_bf16(hispmv_ctx* ctx, int matrix_idx, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias,
+                              int64_t bias_stride, uint16_t* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
+/* hispmv_spmm_info for the bf16 entries: out = {1 if hispmv_spmm_device_bf16 accepts the (loaded) handle, 1 if hispmv_spmm_device_t_bf16
+ * does, VB of the first vector tile, vector tiles, launches of a call with alpha != 0, work_bytes of hispmv_spmm_device_bf16, work_bytes of
+ * hispmv_spmm_device_t_bf16, 0} for ld_x = ld_y = ld and 16-byte aligned pointers; the workspace figures hold for every alignment. */
+int hispmv_spmm_bf16_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t ld, int64_t out[8]);
+/* The vector tiles of a wide call with bf16 activations (host-only).  Every tile takes the largest VB in {8, 4, 2} such that
+ *   (a) 64 * (VB / 2) < vectors left;   (b) cols * 64 * VB * 2 <= 8 MiB: VB 8 up to 8192 columns, VB 4 up to 16384, VB 2 up to 32768
+ *   (the bound of hispmv_prep_spmm_tiles in bytes, reused unmeasured);   (c) ld % VB == 0 and align_bytes % (2 * VB) == 0;
+ * otherwise VB = 1.  out = {VB of the first tile, tiles, vectors in the last tile, VB of the last tile}.  Errors as hispmv_prep_spmm_tiles. */
+int hispmv_prep_spmm_bf16_tiles(int64_t cols, int64_t num_vecs, int64_t ld, int64_t align_bytes, int64_t out[4]);
 
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */

@@ -15,7 +15,12 @@ keeps slice streams (HISPMV_FORMAT=slices), so that both wide entries accept it.
 not a difference.  `max_rel_diff` is the largest difference between (s) and (l) over all vectors, relative to the largest entry of
 (l).  Prints a table and one JSON line, and writes the line to --out.
 
+--bf16-activations measures something else on the same handles: (sb) spmm_device_bf16 beside (s), and (stb) spmm_device_t_bf16 beside
+(st), the fp32 entries on the widened values of the same bf16 operands, alternately, with B = 1024 added; `bits` says whether (sb) is
+bf16((s)) bit for bit.  The result goes to profiles/spmm_bf16_bench.json.
+
     python tools/spmm_bench.py [--rounds 5] [--reps 10] [--vecs 32,64,128,256,512] [--out profiles/spmm_bench.json]
+    python tools/spmm_bench.py --bf16-activations --out profiles/spmm_bf16_bench.json
 """
 from __future__ import annotations
 
@@ -100,14 +105,60 @@ def measure(torch, h, name, idx, W, B, rounds, reps):
                 range_us={k: [float(min(v)), float(max(v))] for k, v in t.items()}, max_rel_diff=diff, max_rel_diff_t=diff_t)
 
 
+def measure_bf16(torch, h, name, idx, B, rounds, reps):
+    """(s) spmm_device on fp32 activations against (sb) spmm_device_bf16 on the same values as bf16, and (st) against (stb) for the
+    transposed entries, alternately on one handle and one stream; ld = B.  `equal_bits`: (sb) is bf16((s)) bit for bit."""
+    dev = torch.device("cuda", 0)
+    info = h.matrix_info(idx)
+    rows, cols = info["rows"], info["cols"]
+    si, sb = h.spmm_info(idx, B), h.spmm_bf16_info(idx, B)
+    assert si["accepted"] and sb["accepted"], (name, si, sb)
+    stream = torch.cuda.Stream(device=dev)
+    s = stream.cuda_stream
+    with torch.cuda.stream(stream):
+        xt16 = (torch.rand((cols, B), dtype=torch.float32, device=dev) - 0.3).to(torch.bfloat16)
+        gt16 = (torch.rand((rows, B), dtype=torch.float32, device=dev) - 0.5).to(torch.bfloat16)
+        xt, gt = xt16.float(), gt16.float()
+        bias = torch.rand(rows, dtype=torch.float32, device=dev)
+        yt, yt16 = torch.empty((rows, B), dtype=torch.float32, device=dev), torch.empty((rows, B), dtype=torch.bfloat16, device=dev)
+        gxt, gxt16 = torch.empty((cols, B), dtype=torch.float32, device=dev), torch.empty((cols, B), dtype=torch.bfloat16, device=dev)
+        work = torch.empty(max(si["work_bytes"], si["work_bytes_t"], sb["work_bytes"], sb["work_bytes_t"], 4) // 4, dtype=torch.float32, device=dev)
+    calls = dict(
+        s=lambda: h.spmm_device(idx, xt.data_ptr(), B, bias.data_ptr(), yt.data_ptr(), 1.0, 1.0, work=work.data_ptr(), work_bytes=si["work_bytes"], stream=s),
+        sb=lambda: h.spmm_device_bf16(idx, xt16.data_ptr(), B, bias.data_ptr(), yt16.data_ptr(), 1.0, 1.0, work=work.data_ptr(), work_bytes=sb["work_bytes"], stream=s))
+    if si["accepted_t"]:
+        calls["st"] = lambda: h.spmm_device_t(idx, gt.data_ptr(), B, 0, gxt.data_ptr(), 1.0, 0.0, work=work.data_ptr(), work_bytes=si["work_bytes_t"], stream=s)
+        calls["stb"] = lambda: h.spmm_device_t_bf16(idx, gt16.data_ptr(), B, 0, gxt16.data_ptr(), 1.0, 0.0, work=work.data_ptr(), work_bytes=sb["work_bytes_t"], stream=s)
+    torch.cuda.synchronize()
+    t = {k: [] for k in calls}
+    with torch.cuda.stream(stream):
+        for f in calls.values():
+            time_calls(torch, stream, f, 3)
+        for _ in range(rounds):
+            for k, f in calls.items():
+                t[k].append(time_calls(torch, stream, f, reps))
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(yt16, yt.to(torch.bfloat16)) and ("st" not in calls or torch.equal(gxt16, gxt.to(torch.bfloat16))))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    rel = {k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()}
+    return dict(name=name, rows=rows, cols=cols, nnz=info["nnz"], B=B, block_threads=info["block_threads"], parts=info["col_tiles"], spmm_info=si, spmm_bf16_info=sb,
+                spmm_us=med["s"], spmm_bf16_us=med["sb"], speedup=med["s"] / med["sb"], spread=max(rel["s"], rel["sb"]),
+                spmm_t_us=med.get("st"), spmm_t_bf16_us=med.get("stb"), speedup_t=(med["st"] / med["stb"]) if "st" in med else None,
+                spread_t=max(rel["st"], rel["stb"]) if "st" in rel else None, range_us={k: [float(min(v)), float(max(v))] for k, v in t.items()}, equal_bits=equal)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--vecs", default="32,64,128,256,512")
     ap.add_argument("--out", default="")
+    ap.add_argument("--bf16-activations", action="store_true",
+                    help="measure spmm_device_bf16 / spmm_device_t_bf16 beside (s) / (st) on the same handle instead (B = 1024 added; profiles/spmm_bf16_bench.json)")
     a = ap.parse_args()
     vecs = [int(v) for v in a.vecs.split(",")]
+    if a.bf16_activations and a.vecs == ap.get_default("vecs"):
+        vecs.append(1024)
     os.environ["HISPMV_FORMAT"] = "slices"          # read when the context is created: handle and stored transpose stay slice streams
     import torch
     import pyhispmv
@@ -134,6 +185,9 @@ def main() -> None:
         assert all(t[1] >= 0 for t in todo), todo
         h.load_matrices()
         out = []
+        if a.bf16_activations:
+            out = [measure_bf16(torch, h, name, i, B, a.rounds, a.reps) for name, i, _w, _rows, _cols in todo for B in vecs]
+            todo = []
         for name, i, (r, c, v), rows, cols in todo:
             W = torch.zeros((rows, cols), dtype=torch.float32, device=dev)
             W.index_put_((torch.from_numpy(r.astype(np.int64)).to(dev), torch.from_numpy(c.astype(np.int64)).to(dev)), torch.from_numpy(v).to(dev), accumulate=True)
@@ -141,6 +195,17 @@ def main() -> None:
             del W
     finally:
         h.close()
+    if a.bf16_activations:
+        print(f"{'layer':44s} {'B':>4s} {'VL':>2s} {'VB':>2s} {'(s) us':>9s} {'(sb) us':>9s} {'s/sb':>5s} {'spread':>6s} {'(st) us':>9s} {'(stb) us':>9s} {'st/stb':>6s} {'spread':>6s} bits")
+        for q in out:
+            print(f"{q['name'][:44]:44s} {q['B']:4d} {q['spmm_info']['vl']:2d} {q['spmm_bf16_info']['vb']:2d} {q['spmm_us']:9.1f} {q['spmm_bf16_us']:9.1f} {q['speedup']:5.2f} "
+                  f"{q['spread']:6.2f} {q['spmm_t_us']:9.1f} {q['spmm_t_bf16_us']:9.1f} {q['speedup_t']:6.2f} {q['spread_t']:6.2f} {'equal' if q['equal_bits'] else 'DIFFER'}")
+        line = json.dumps({"spmm_bf16_bench": out, "rounds": a.rounds, "reps": a.reps, "device": torch.cuda.get_device_name(0)})
+        print(line)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(a.out).write_text(line + "\n")
+        return
     print(f"{'layer':44s} {'B':>3s} {'VL':>2s} {'tiles':>5s} {'(s) us':>9s} {'(s+) us':>9s} {'(l) us':>9s} {'l/s':>5s} {'l/s+':>5s} {'spread':>6s} {'(st) us':>9s} {'(lt) us':>9s} "
           f"{'lt/st':>5s} {'spread':>6s} {'(mm) us':>9s} {'diff':>8s}")
     for q in out:
