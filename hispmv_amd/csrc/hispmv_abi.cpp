@@ -230,22 +230,19 @@ int load_value_map(hispmv_ctx* c, Matrix& m, const std::vector<std::vector<Value
         m.allocs.push_back(dt);
         m.d_map = (int32_t*)dm; m.d_upd_table = (ValueChunkDev*)dt;
         HIP_TRY(c, hipMemcpyAsync(dt, tab.data(), tab.size() * sizeof(ValueChunkDev), hipMemcpyHostToDevice, c->stream));
-        hipError_t e = hipSuccess;
         if (bf16) {               // the map was read on the host (HostPart::value_map): a half slice holds no payloads
             for (const Matrix::Part& p : m.parts) {
                 if (p.value_map.size() != chunks[(size_t)(&p - m.parts.data())].size() * (size_t)kValueChunk) return fail(c, HISPMV_EINVAL, "internal: a part's host value map does not match its chunks");
                 if (!p.value_map.empty()) HIP_TRY(c, hipMemcpyAsync(m.d_map + p.map_chunk_base * kValueChunk, p.value_map.data(), p.value_map.size() * 4, hipMemcpyHostToDevice, c->stream));
             }
         } else {
-            e = launch_build_value_map(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->stream);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_build_value_map");
+            LAUNCH_TRY(c, launch_build_value_map, m.d_upd_table, (int64_t)tab.size(), m.d_map, c->stream);
         }
         int rc;
         if ((rc = ensure_vec(c, &c->d_upd, &c->cap_d_upd, m.upd_n)) != HISPMV_OK) return rc;
         if (m.upd_n > 0) HIP_TRY(c, hipMemcpyAsync(c->d_upd, m.upd_values.data(), (size_t)m.upd_n * 4, hipMemcpyHostToDevice, c->stream));
-        e = bf16 ? launch_update_values_bf16(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream)
-                 : launch_update_values(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_update_values");
+        LAUNCH_TRY_AS(c, "launch_update_values", bf16 ? launch_update_values_bf16(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream)
+                                                      : launch_update_values(m.d_upd_table, (int64_t)tab.size(), m.d_map, c->d_upd, m.upd_n, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`tab` and the values are host locals / released next)
     }
     for (Matrix::Part& p : m.parts) p.value_map = std::vector<int32_t>();
@@ -305,86 +302,90 @@ int launch_matrix(hispmv_ctx* c, Matrix& m, const float* d_x, const float* d_bia
         return spmv_batch_locked(c, 1, &idx, &d_x, &d_bias, &d_y, alpha, beta, s, idx >= kCompanionId);
     }
     if (m.dense) {
-        hipError_t e = launch_gemv(m.d_dense, m.rows, m.cols, d_x, d_bias, d_y, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_gemv");
+        LAUNCH_TRY(c, launch_gemv, m.d_dense, m.rows, m.cols, d_x, d_bias, d_y, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
         return HISPMV_OK;
     }
     if (m.format == 1) {
-        hipError_t e = launch_tts(m.parts[0].tdev, d_x, d_bias, d_y, alpha, beta, s);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_tts");
+        LAUNCH_TRY(c, launch_tts, m.parts[0].tdev, d_x, d_bias, d_y, alpha, beta, s);
         return HISPMV_OK;
     }
     for (size_t t = 0; t < m.parts.size(); ++t) {
         // column tile 0 computes alpha*A_0*x + beta*bias into y; tile t > 0 writes alpha*A_t*x into its partial vector
-        hipError_t e = (t == 0) ? launch_spmv(m.parts[t].dev, d_x, d_bias, d_y, alpha, beta, s, fixup_only)
-                                : launch_spmv(m.parts[t].dev, d_x, nullptr, m.d_ypart + (t - 1) * (size_t)kMaxBatch * m.rows, alpha, 0.0f, s, fixup_only);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_spmv");
+        if (t == 0) LAUNCH_TRY(c, launch_spmv, m.parts[t].dev, d_x, d_bias, d_y, alpha, beta, s, fixup_only);
+        else LAUNCH_TRY(c, launch_spmv, m.parts[t].dev, d_x, nullptr, m.d_ypart + (t - 1) * (size_t)kMaxBatch * m.rows, alpha, 0.0f, s, fixup_only);
     }
-    if (m.parts.size() > 1) {
-        hipError_t e = launch_merge_parts(d_y, m.d_ypart, (int)m.parts.size() - 1, (int64_t)kMaxBatch * m.rows, m.rows, 1, 0, 0, s);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_merge_parts");
-    }
+    if (m.parts.size() > 1) LAUNCH_TRY(c, launch_merge_parts, d_y, m.d_ypart, (int)m.parts.size() - 1, (int64_t)kMaxBatch * m.rows, m.rows, 1, 0, 0, s);
     return HISPMV_OK;
 }
 
-// `vecs` vectors with a shared bias (FpgaHandle::linear): the reference relaunches its kernel per vector
-// (fpga_handle.cpp:366-379); here up to 8 (dense) / 4 (sparse) vectors share one pass over the matrix when the plan allows.
-int launch_matrix_vectors(hispmv_ctx* c, Matrix& m, int64_t vecs, const float* d_x, const float* d_bias, float* d_y,
-                          float alpha, float beta, hipStream_t s, bool fixup_only) {
-    // (`linear` always takes the fix-up carry variant: one vector or many, every vector gets the same bits)
-    if (vecs == 1) return launch_matrix(c, m, d_x, d_bias, d_y, alpha, beta, s, fixup_only);
-    if (m.dense) {
-        hipError_t e = launch_gemv_batched(m.d_dense, m.rows, m.cols, vecs, d_x, d_bias, d_y, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_batched");
-        return HISPMV_OK;
+// ---- the forward pass plan: one width rule, one launch loop ---------------------------------------------------------------------------
+// Vectors of the next forward pass over `m` with `left` vectors to go: what launch_forward launches and hispmv_linear_info reports
+// (the transposed side: transposed_width).  Dense 8, 4, 2, 1.  A tile stream of one part without zero_fill: 4 or 2 vectors through
+// every pass over the words where the tiles are small enough, else up to kTtsMaxVectors in one launch, one after the other.  A slice
+// stream: what every part takes (spmv_batch_width), kMaxBatch at most.  Everything else one vector.  Two things differ by caller:
+//   slices_batched  false: a slice stream goes one vector per launch -- hispmv_linear_device with beta == 0 (the batched slice kernel's
+//                   tile 0 reads a bias); hispmv_linear has beta = 1, and the stored transpose takes the batched widths for every beta
+//   per_vector_bias the batched tile kernel takes one shared bias: such a call goes one vector per launch on a tile stream
+int forward_width(const Matrix& m, int64_t left, bool slices_batched, bool per_vector_bias) {
+    if (left < 2) return 1;
+    if (m.dense) return left >= 8 ? 8 : left >= 4 ? 4 : 2;
+    if (m.format == 1) {
+        if (m.parts.size() != 1 || m.parts[0].tdev.zero_fill || per_vector_bias) return 1;
+        const int nv = tts_batch_width(m.parts[0].tdev, left);
+        return nv >= 2 ? nv : (int)std::min<int64_t>(left, kTtsMaxVectors);
     }
-    if (m.format == 1) {          // transposed tile stream: up to 8 vectors per launch (same bits as a single-vector call each)
-        int64_t k = 0;
-        while (k < vecs) {
-            // 4 or 2 vectors through every pass over the words where the tiles are small enough; else up to 8 in one launch, one after the other
-            int nv = 1;
-            if (m.parts.size() == 1 && !m.parts[0].tdev.zero_fill) {
-                nv = tts_batch_width(m.parts[0].tdev, vecs - k);
-                if (nv < 2) nv = (int)std::min<int64_t>(vecs - k, kTtsMaxVectors);
-            }
-            if (nv >= 2) {
-                hipError_t e = launch_tts_batched(m.parts[0].tdev, nv, d_x + k * m.cols, d_bias, d_y + k * m.rows, alpha, beta, s);
-                if (e != hipSuccess) return hip_fail(c, e, "launch_tts_batched");
-            } else {
-                const int rc = launch_matrix(c, m, d_x + k * m.cols, d_bias, d_y + k * m.rows, alpha, beta, s);
-                if (rc != HISPMV_OK) return rc;
-            }
-            k += nv;
-        }
-        return HISPMV_OK;
-    }
-    int64_t k = 0;
-    while (k < vecs) {
-        int nv = beta != 0.0f ? kMaxBatch : 1;       // (linear always has beta = 1; the batched kernel's tile 0 reads a bias)
-        for (auto& p : m.parts) nv = std::min(nv, spmv_batch_width(p.dev, vecs - k));
+    if (!slices_batched) return 1;
+    int nv = kMaxBatch;
+    for (auto& p : m.parts) nv = std::min(nv, spmv_batch_width(p.dev, left));
+    return nv;
+}
+// ... of the next transposed pass (a handle without a stored transpose): launch loops, hispmv_linear_info, hispmv_value_grad_info
+int transposed_width(const Matrix& m, int64_t left) {
+    if (m.dense) return gemv_t_width(left);
+    if (m.format == 1) return tts_t_width(m.parts[0].tdev, left);      // (an accepted tile stream: one part)
+    int nv = kMaxBatch;
+    for (auto& p : m.parts) nv = std::min(nv, spmv_t_width(p.dev, left));
+    return nv;
+}
+
+// y_k = alpha * A * x_k + beta * bias_k for `vecs` vectors (x_k = d_x + k * cols, y_k = d_y + k * rows, bias_k = d_bias + k * bias_stride):
+// passes of forward_width vectors, every vector with the bits of a one-vector call.  The reference relaunches its kernel per vector
+// (FpgaHandle::linear, fpga_handle.cpp:366-379).  Serves hispmv_run_kernel and hispmv_linear, hispmv_linear_device (bias_stride 0) and,
+// over a stored transpose, the transposed entries.  fixup_only: the carry variant of a one-vector slice pass -- `linear` and the device
+// entries always take the fix-up one (one vector or many, every vector gets the same bits), hispmv_run_kernel the plan's own.
+// unbiased_batched: a slice stream takes its batched widths with beta == 0 too (the stored transpose; forward_width: slices_batched).
+int launch_forward(hispmv_ctx* c, Matrix& m, int64_t vecs, const float* d_x, const float* d_bias, int64_t bias_stride, float* d_y,
+                   float alpha, float beta, hipStream_t s, bool fixup_only, bool unbiased_batched = false) {
+    // A d_x off the 16-byte alignment takes one vector per pass (the same bits): the launches hispmv_spmv_device makes for such a
+    // pointer.  Single- and multi-vector kernels alike stage x with 16-byte global loads (stage_fragments, the dense and tile-stream
+    // bodies), so this does not align those loads -- the hardware executes them at any 4-byte address --; it keeps an unusual
+    // pointer off the batched passes, whose only stated condition is on cols (spmv_batch_width).
+    const bool batched = vecs > 1 && ((uintptr_t)d_x & 15) == 0;
+    const bool has_bias = beta != 0.0f;
+    for (int64_t k = 0; k < vecs;) {
+        const int nv = batched ? forward_width(m, vecs - k, has_bias || unbiased_batched, has_bias && bias_stride != 0) : 1;
         const float* xk = d_x + k * m.cols;
+        const float* bk = has_bias ? d_bias + k * bias_stride : nullptr;
         float* yk = d_y + k * m.rows;
-        if (nv < 2) {
-            int rc = launch_matrix(c, m, xk, d_bias, yk, alpha, beta, s, true);
+        if (batched && m.dense) {          // (a last pass of one vector too: the launch of launch_gemv)
+            LAUNCH_TRY(c, launch_gemv_batched, m.d_dense, m.rows, m.cols, nv, xk, bk, yk, alpha, beta, s, m.value_storage == HISPMV_VALUES_BF16);
+        } else if (nv < 2) {
+            const int rc = launch_matrix(c, m, xk, bk, yk, alpha, beta, s, fixup_only);
             if (rc != HISPMV_OK) return rc;
-            k += 1;
-            continue;
-        }
-        for (size_t t = 0; t < m.parts.size(); ++t) {
-            // tile 0: shared bias; tile t > 0: the nv partial vectors of that tile, no bias
-            hipError_t e = (t == 0) ? launch_spmv_batched(m.parts[t].dev, nv, xk, d_bias, 0, yk, alpha, beta, s)
-                                    : launch_spmv_batched(m.parts[t].dev, nv, xk, nullptr, 0, m.d_ypart + (t - 1) * (size_t)kMaxBatch * m.rows, alpha, 0.0f, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_batched");
-        }
-        if (m.parts.size() > 1) {
-            hipError_t e = launch_merge_parts(yk, m.d_ypart, (int)m.parts.size() - 1, (int64_t)kMaxBatch * m.rows, m.rows, nv, m.rows, m.rows, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_merge_parts");
+        } else if (m.format == 1) {
+            LAUNCH_TRY(c, launch_tts_batched, m.parts[0].tdev, nv, xk, bk, yk, alpha, beta, s);
+        } else {
+            for (size_t t = 0; t < m.parts.size(); ++t) {
+                // tile 0: the bias (shared, or one per vector); tile t > 0: the nv partial vectors of that tile, no bias
+                if (t == 0) LAUNCH_TRY(c, launch_spmv_batched, m.parts[t].dev, nv, xk, bk, (int)bias_stride, yk, alpha, beta, s);
+                else LAUNCH_TRY(c, launch_spmv_batched, m.parts[t].dev, nv, xk, nullptr, 0, m.d_ypart + (t - 1) * (size_t)kMaxBatch * m.rows, alpha, 0.0f, s);
+            }
+            if (m.parts.size() > 1) LAUNCH_TRY(c, launch_merge_parts, yk, m.d_ypart, (int)m.parts.size() - 1, (int64_t)kMaxBatch * m.rows, m.rows, nv, m.rows, m.rows, s);
         }
         k += nv;
     }
     return HISPMV_OK;
 }
-
 
 }  // namespace
 
@@ -396,10 +397,10 @@ HISPMV_API int hispmv_boundary_pack(hispmv_ctx* c, const float* const* d_last, c
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     if (n < 0 || (n > 0 && (!d_last || !d_mask || !d_send))) return fail(c, HISPMV_EINVAL, "bad boundary_pack arguments");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    const hipError_t e = launch_boundary_pack(d_last, d_mask, d_send, n, stream ? (hipStream_t)stream : c->stream);
-    return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_boundary_pack");
+    hipStream_t s;
+    if (const int rc = adopt_stream(c, stream, &s)) return rc;
+    LAUNCH_TRY(c, launch_boundary_pack, d_last, d_mask, d_send, n, s);
+    return HISPMV_OK;
 }
 
 HISPMV_API int hispmv_boundary_apply(hispmv_ctx* c, float* const* d_first, const float* d_recv, const float* d_weights, int32_t n,
@@ -407,10 +408,10 @@ HISPMV_API int hispmv_boundary_apply(hispmv_ctx* c, float* const* d_first, const
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     if (n < 0 || world < 1 || (n > 0 && (!d_first || !d_recv || !d_weights))) return fail(c, HISPMV_EINVAL, "bad boundary_apply arguments");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    const hipError_t e = launch_boundary_apply(d_first, d_recv, d_weights, n, world, stream ? (hipStream_t)stream : c->stream);
-    return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_boundary_apply");
+    hipStream_t s;
+    if (const int rc = adopt_stream(c, stream, &s)) return rc;
+    LAUNCH_TRY(c, launch_boundary_apply, d_first, d_recv, d_weights, n, world, s);
+    return HISPMV_OK;
 }
 
 HISPMV_API const char* hispmv_version(void) { return "hispmv-amd 0.2.0 gfx950"; }
@@ -988,7 +989,7 @@ HISPMV_API int hispmv_load_matrices(hispmv_ctx* c) {
 HISPMV_API int hispmv_select_matrix(hispmv_ctx* c, uint32_t idx) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    if (idx >= c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");   // fpga_handle.cpp:267-270
+    if (idx >= c->mats.size()) return idx_out_of_range(c);
     c->selected = (int)idx;
     return HISPMV_OK;
 }
@@ -1021,8 +1022,7 @@ static int run_host_vectors(hispmv_ctx* c, Matrix& m, const float* x, int64_t nu
         if (beta != 0.0f) std::memcpy(c->h_stage + nx, bias, bb);
         // (x and bias cross PCIe through a copy KERNEL that reads the pinned block: the DMA path costs ~10 us per call; HISPMV_HOST_Y=copy: as before)
         if (c->d_stage && (nx + nb) * (int64_t)sizeof(float) <= (1 << 20)) {
-            const hipError_t e = launch_fetch_vectors(c->d_stage, d_x, beta != 0.0f ? nx + nb : (int64_t)m.cols * num_vecs, c->stream);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_fetch_vectors");
+            LAUNCH_TRY(c, launch_fetch_vectors, c->d_stage, d_x, beta != 0.0f ? nx + nb : (int64_t)m.cols * num_vecs, c->stream);
         } else
             HIP_TRY(c, hipMemcpyAsync(d_x, c->h_stage, beta != 0.0f ? (size_t)nx * sizeof(float) + bb : bx, hipMemcpyHostToDevice, c->stream));
     } else {
@@ -1035,7 +1035,7 @@ static int run_host_vectors(hispmv_ctx* c, Matrix& m, const float* x, int64_t nu
     float* const h_y = staged ? c->h_stage + nx + nb : y;
     float* const d_y = (staged && c->d_stage) ? c->d_stage + nx + nb : c->d_y;
     HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    if ((rc = launch_matrix_vectors(c, m, num_vecs, d_x, d_bias, d_y, alpha, beta, c->stream, is_linear)) != HISPMV_OK) return rc;
+    if ((rc = launch_forward(c, m, num_vecs, d_x, d_bias, 0, d_y, alpha, beta, c->stream, is_linear)) != HISPMV_OK) return rc;
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     if (d_y == c->d_y) HIP_TRY(c, hipMemcpyAsync(h_y, c->d_y, by, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1057,9 +1057,9 @@ HISPMV_API int hispmv_run_kernel(hispmv_ctx* c, const float* x, const float* bia
 HISPMV_API int hispmv_linear(hispmv_ctx* c, int idx, const float* x, int64_t x_len, const float* bias, float* y_out) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-    Matrix& m = *c->mats[idx];
-    if (!m.loaded) return fail(c, HISPMV_ESTATE, "linear called before load_matrices");
+    Matrix* mp = nullptr;
+    if (const int rc = find_handle(c, idx, "linear", &mp)) return rc;
+    Matrix& m = *mp;
     if (!x || !bias || !y_out) return fail(c, HISPMV_EINVAL, "NULL vector");
     const int64_t num_vecs = x_len / m.cols;   // fpga_handle.cpp:336
     if (num_vecs <= 0) return fail(c, HISPMV_EINVAL, "x shorter than one input vector");
@@ -1070,13 +1070,12 @@ HISPMV_API int hispmv_spmv_device(hispmv_ctx* c, int idx, const float* d_x, cons
                                   float alpha, float beta, void* stream) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-    Matrix& m = *c->mats[idx];
-    if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device called before load_matrices");
+    Matrix* m = nullptr;
+    if (const int rc = find_handle(c, idx, "spmv_device", &m)) return rc;
     if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    return launch_matrix(c, m, d_x, d_bias, d_y, alpha, beta, stream ? (hipStream_t)stream : c->stream);
+    hipStream_t s;
+    if (const int rc = adopt_stream(c, stream, &s)) return rc;
+    return launch_matrix(c, *m, d_x, d_bias, d_y, alpha, beta, s);
 }
 
 // ---- transposed product (include/hispmv.h: hispmv_spmv_device_t; kernels: hispmv_transpose.hip) ---------------------------------
@@ -1114,22 +1113,9 @@ int refuse_tile_stream(hispmv_ctx* c, const Matrix& m, const char* who, const ch
 
 // ---- the stored transpose (include/hispmv.h: HISPMV_TRANSPOSABLE_COMPANION) ------------------------------------------------------------
 // The transposed entries of a handle that owns one run the FORWARD launches of `t` = *owner.companion (t.rows = owner.cols): no atomic,
-// per vector the bits of a one-vector hispmv_linear_device call on a handle made from the swapped input.  Its own launch routine:
-// launch_matrix_vectors and the behaviour of hispmv_linear_device are not touched.
+// per vector the bits of a one-vector hispmv_linear_device call on a handle made from the swapped input.  Widths and launch loop
+// are the forward ones (forward_width, launch_forward) with the batched slice widths for every beta.
 
-// Vectors of the next pass: the widths launch_matrix_vectors takes for beta != 0, for every beta.  per_vector_bias: the batched tile
-// kernel takes one shared bias, so such a call goes one vector per launch on a tile stream.
-int companion_width(const Matrix& t, int64_t left, bool per_vector_bias) {
-    if (left < 2) return 1;
-    if (t.format == 1) {
-        if (t.parts.size() != 1 || t.parts[0].tdev.zero_fill || per_vector_bias) return 1;
-        const int nv = tts_batch_width(t.parts[0].tdev, left);
-        return nv >= 2 ? nv : (int)std::min<int64_t>(left, kTtsMaxVectors);
-    }
-    int nv = kMaxBatch;
-    for (auto& p : t.parts) nv = std::min(nv, spmv_batch_width(p.dev, left));
-    return nv;
-}
 // Launches of one pass of nv vectors (alpha != 0).  A one-vector pass over a cut matrix is a batch call of one matrix (launch_matrix):
 // one grid per workgroup size (and stray class) among its parts, then its tail -- one launch where the merge applies the fix-ups itself.
 int64_t companion_pass_launches(const Matrix& t, int nv) {
@@ -1157,38 +1143,11 @@ int launch_companion(hispmv_ctx* c, Matrix& owner, int64_t vecs, const float* d_
                      float alpha, float beta, hipStream_t s) {
     Matrix& t = *owner.companion;
     if (!t.loaded) return fail(c, HISPMV_ESTATE, "internal: the stored transpose is not loaded");
-    if (alpha == 0.0f) {          // y is exactly beta * bias, per vector; neither x nor the matrix is read
-        const hipError_t e = launch_transpose_prologue(d_bias, d_y, t.rows, beta, s, vecs, bias_stride);
-        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_transpose_prologue");
+    if (alpha == 0.0f) {          // y is exactly beta * bias, per vector; neither x nor the matrix is read (hispmv_linear_device runs its kernels)
+        LAUNCH_TRY(c, launch_transpose_prologue, d_bias, d_y, t.rows, beta, s, vecs, bias_stride);
+        return HISPMV_OK;
     }
-    const bool has_bias = beta != 0.0f;
-    const bool one_by_one = ((uintptr_t)d_x & 15) != 0;       // (the rule of hispmv_linear_device: an unusual pointer stays off the batched passes)
-    for (int64_t k = 0; k < vecs;) {
-        const int nv = one_by_one ? 1 : companion_width(t, vecs - k, has_bias && bias_stride != 0);
-        const float* xk = d_x + k * t.cols;
-        const float* bk = has_bias ? d_bias + k * bias_stride : nullptr;
-        float* yk = d_y + k * t.rows;
-        if (nv < 2) {
-            const int rc = launch_matrix(c, t, xk, bk, yk, alpha, beta, s, true);
-            if (rc != HISPMV_OK) return rc;
-        } else if (t.format == 1) {
-            const hipError_t e = launch_tts_batched(t.parts[0].tdev, nv, xk, bk, yk, alpha, beta, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_tts_batched");
-        } else {
-            for (size_t q = 0; q < t.parts.size(); ++q) {
-                // part 0: the bias (shared, or one per vector); part q > 0: the nv partial vectors of that part, no bias
-                const hipError_t e = (q == 0) ? launch_spmv_batched(t.parts[q].dev, nv, xk, bk, (int)bias_stride, yk, alpha, beta, s)
-                                              : launch_spmv_batched(t.parts[q].dev, nv, xk, nullptr, 0, t.d_ypart + (q - 1) * (size_t)kMaxBatch * t.rows, alpha, 0.0f, s);
-                if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_batched");
-            }
-            if (t.parts.size() > 1) {
-                const hipError_t e = launch_merge_parts(yk, t.d_ypart, (int)t.parts.size() - 1, (int64_t)kMaxBatch * t.rows, t.rows, nv, t.rows, t.rows, s);
-                if (e != hipSuccess) return hip_fail(c, e, "launch_merge_parts");
-            }
-        }
-        k += nv;
-    }
-    return HISPMV_OK;
+    return launch_forward(c, t, vecs, d_x, d_bias, bias_stride, d_y, alpha, beta, s, true, true);
 }
 
 }  // namespace
@@ -1219,38 +1178,21 @@ HISPMV_API int hispmv_spmv_device_t(hispmv_ctx* c, int idx, const float* d_x, co
                                     float alpha, float beta, void* stream) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-    Matrix& m = *c->mats[idx];
-    if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device_t called before load_matrices");
+    Matrix* mp = nullptr;
+    if (const int rc = find_handle(c, idx, "spmv_device_t", &mp)) return rc;
+    Matrix& m = *mp;
     if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
     if (d_x == d_y) return fail(c, HISPMV_EINVAL, "spmv_device_t: x and y must not be the same vector");
-    if (m.companion) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        if (stream) c->user_stream = (hipStream_t)stream;
-        return launch_companion(c, m, 1, d_x, d_bias, 0, d_y, alpha, beta, stream ? (hipStream_t)stream : c->stream);
-    }
-    if (!transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!m.companion && !transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
+    hipStream_t s;
+    if (const int rc = adopt_stream(c, stream, &s)) return rc;
+    if (m.companion) return launch_companion(c, m, 1, d_x, d_bias, 0, d_y, alpha, beta, s);
     // y = beta * bias first, then every part of the matrix adds alpha * A_t^T * x into it: no partial vectors, no merge
-    hipError_t e = launch_transpose_prologue(d_bias, d_y, m.cols, beta, s);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
+    LAUNCH_TRY(c, launch_transpose_prologue, d_bias, d_y, m.cols, beta, s);
     if (alpha == 0.0f) return HISPMV_OK;          // y is exactly beta * bias
-    if (m.dense) {
-        e = launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, d_x, d_y, alpha, s);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_t");
-        return HISPMV_OK;
-    }
-    if (m.format == 1) {          // an accepted tile stream: one launch, no carries, no fix-up
-        e = launch_tts_t(m.parts[0].tdev, 1, d_x, d_y, alpha, s);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_tts_t");
-        return HISPMV_OK;
-    }
-    for (auto& p : m.parts) {
-        e = launch_spmv_t(p.dev, d_x, d_y, alpha, s);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_t");
-    }
+    if (m.dense) LAUNCH_TRY(c, launch_gemv_t, m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, d_x, d_y, alpha, s);
+    else if (m.format == 1) LAUNCH_TRY(c, launch_tts_t, m.parts[0].tdev, 1, d_x, d_y, alpha, s);      // an accepted tile stream: one launch, no carries, no fix-up
+    else for (auto& p : m.parts) LAUNCH_TRY(c, launch_spmv_t, p.dev, d_x, d_y, alpha, s);
     return HISPMV_OK;
 }
 
@@ -1260,45 +1202,24 @@ namespace {
 // The checks both entries share, all before any device call; on success *out is the handle.  in_len / out_len: floats per vector.
 int linear_device_target(hispmv_ctx* c, int idx, const float* d_x, int64_t num_vecs, const float* d_bias, const float* d_y, float beta,
                          const char* who, Matrix** out) {
-    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-    Matrix& m = *c->mats[idx];
-    if (!m.loaded) return fail(c, HISPMV_ESTATE, std::string(who) + " called before load_matrices");
+    if (const int rc = find_handle(c, idx, who, out)) return rc;
+    const Matrix& m = **out;
     if (num_vecs < 1) return fail(c, HISPMV_EINVAL, std::string(who) + ": num_vecs must be at least 1");
     if (!d_x || !d_y || (beta != 0.0f && !d_bias)) return fail(c, HISPMV_EINVAL, "NULL device vector");
     if (d_x == d_y) return fail(c, HISPMV_EINVAL, std::string(who) + ": x and y must not be the same vectors");
     if ((int64_t)m.rows * num_vecs >= (1LL << 30) || (int64_t)m.cols * num_vecs >= (1LL << 30))
         return fail(c, HISPMV_EINVAL, std::string(who) + ": rows * num_vecs and cols * num_vecs must stay below 2^30 floats; split the batch");
-    *out = &m;
     return HISPMV_OK;
 }
 
-// The passes of a forward call with beta != 0: widest pass and number of passes.  A COPY of the width choices of
-// launch_matrix_vectors (above) and launch_gemv_batched (hispmv_kernels.hip), which launch as they choose and report nothing: whoever
-// changes a width there changes it here.  (The transposed side has one function, transposed_width, for launch loop and report.)
-void forward_passes(const Matrix& m, int64_t vecs, int64_t& widest, int64_t& passes) {
-    widest = 0; passes = 0;
+// The passes of a forward call with beta != 0 and a shared bias on an aligned d_x, walked along forward_width: widest pass, number of
+// passes and -- `launches` given, m a stored transpose -- their launches.
+void forward_passes(const Matrix& m, int64_t vecs, int64_t& widest, int64_t& passes, int64_t* launches = nullptr) {
     for (int64_t k = 0; k < vecs;) {
-        int64_t nv = 1;
-        if (vecs == 1) nv = 1;
-        else if (m.dense) nv = vecs - k >= 8 ? 8 : vecs - k >= 4 ? 4 : vecs - k >= 2 ? 2 : 1;
-        else if (m.format == 1) {
-            if (m.parts.size() == 1 && !m.parts[0].tdev.zero_fill) {
-                nv = tts_batch_width(m.parts[0].tdev, vecs - k);
-                if (nv < 2) nv = std::min<int64_t>(vecs - k, kTtsMaxVectors);
-            }
-        } else {
-            nv = kMaxBatch;
-            for (auto& p : m.parts) nv = std::min<int64_t>(nv, spmv_batch_width(p.dev, vecs - k));
-        }
-        widest = std::max(widest, nv); passes += 1; k += nv;
+        const int nv = forward_width(m, vecs - k, true, false);
+        widest = std::max<int64_t>(widest, nv); passes += 1; k += nv;
+        if (launches) *launches += companion_pass_launches(m, nv);
     }
-}
-int transposed_width(const Matrix& m, int64_t left) {
-    if (m.dense) return gemv_t_width(left);
-    if (m.format == 1) return tts_t_width(m.parts[0].tdev, left);      // (an accepted tile stream: one part)
-    int nv = kMaxBatch;
-    for (auto& p : m.parts) nv = std::min(nv, spmv_t_width(p.dev, left));
-    return nv;
 }
 
 }  // namespace
@@ -1309,11 +1230,8 @@ HISPMV_API int hispmv_linear_info(const hispmv_ctx* c, int idx, int64_t num_vecs
     for (int i = 0; i < 5; ++i) out[i] = 0;
     if (!m.loaded) return HISPMV_OK;
     forward_passes(m, num_vecs, out[0], out[1]);
-    if (m.companion) {          // the passes of launch_companion with a shared bias and an aligned d_x
-        for (int64_t k = 0; k < num_vecs;) {
-            const int nv = companion_width(*m.companion, num_vecs - k, false);
-            out[2] = std::max<int64_t>(out[2], nv); out[3] += 1; out[4] += companion_pass_launches(*m.companion, nv); k += nv;
-        }
+    if (m.companion) {          // the passes of launch_companion
+        forward_passes(*m.companion, num_vecs, out[2], out[3], &out[4]);
         return HISPMV_OK;
     }
     if (!transposable_handle(m)) return HISPMV_OK;
@@ -1336,22 +1254,9 @@ HISPMV_API int hispmv_linear_device(hispmv_ctx* c, int idx, const float* d_x, in
     Matrix* mp = nullptr;
     const int rc = linear_device_target(c, idx, d_x, num_vecs, d_bias, d_y, beta, "linear_device", &mp);
     if (rc != HISPMV_OK) return rc;
-    Matrix& m = *mp;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    // A d_x off the 16-byte alignment takes one vector per pass (the same bits): the launches hispmv_spmv_device makes for such a
-    // pointer.  Single- and multi-vector kernels alike stage x with 16-byte global loads (stage_fragments, the dense and tile-stream
-    // bodies), so this does not align those loads -- the hardware executes them at any 4-byte address --; it keeps an unusual
-    // pointer off the batched passes, whose only stated condition is on cols (spmv_batch_width).
-    if (((uintptr_t)d_x & 15) != 0 && num_vecs > 1) {
-        for (int64_t k = 0; k < num_vecs; ++k) {
-            const int r1 = launch_matrix_vectors(c, m, 1, d_x + k * m.cols, d_bias, d_y + k * m.rows, alpha, beta, s, true);
-            if (r1 != HISPMV_OK) return r1;
-        }
-        return HISPMV_OK;
-    }
-    return launch_matrix_vectors(c, m, num_vecs, d_x, d_bias, d_y, alpha, beta, s, true);
+    hipStream_t s;
+    if (const int r = adopt_stream(c, stream, &s)) return r;
+    return launch_forward(c, *mp, num_vecs, d_x, d_bias, 0, d_y, alpha, beta, s, true);
 }
 
 HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, int64_t num_vecs, const float* d_bias, int64_t bias_stride,
@@ -1365,35 +1270,25 @@ HISPMV_API int hispmv_linear_device_t(hispmv_ctx* c, int idx, const float* d_x, 
     if (bias_stride != 0 && bias_stride != m.cols) return fail(c, HISPMV_EINVAL, "linear_device_t: bias_stride must be 0 (one bias for all vectors) or cols");
     if (beta != 0.0f && d_bias == d_y && bias_stride == 0 && num_vecs > 1)
         return fail(c, HISPMV_EINVAL, "linear_device_t: d_bias == d_y needs bias_stride = cols (a shared bias would be overwritten by vector 0)");
-    if (m.companion) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        if (stream) c->user_stream = (hipStream_t)stream;
-        return launch_companion(c, m, num_vecs, d_x, d_bias, bias_stride, d_y, alpha, beta, stream ? (hipStream_t)stream : c->stream);
-    }
-    if (!transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!m.companion && !transposable_handle(m)) return refuse_tile_stream(c, m, "spmv_device_t", "transposed product");
+    hipStream_t s;
+    if (const int r = adopt_stream(c, stream, &s)) return r;
+    if (m.companion) return launch_companion(c, m, num_vecs, d_x, d_bias, bias_stride, d_y, alpha, beta, s);
     // ONE prologue for all vectors, then passes of the widest width that fits (4, 2, 1; dense 8, 4, 2, 1)
-    hipError_t e = launch_transpose_prologue(d_bias, d_y, m.cols, beta, s, num_vecs, bias_stride);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
+    LAUNCH_TRY(c, launch_transpose_prologue, d_bias, d_y, m.cols, beta, s, num_vecs, bias_stride);
     if (alpha == 0.0f) return HISPMV_OK;          // y is exactly beta * bias, per vector
     for (int64_t k = 0; k < num_vecs;) {
         const int nv = transposed_width(m, num_vecs - k);
         const float* xk = d_x + k * m.rows;
         float* yk = d_y + k * m.cols;
+        // (a pass of several vectors reports under the one-vector launcher's name)
         if (m.dense) {
-            e = nv == 1 ? launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, xk, yk, alpha, s)
-                        : launch_gemv_t_nv(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, nv, xk, yk, alpha, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_gemv_t");
+            LAUNCH_TRY_AS(c, "launch_gemv_t", nv == 1 ? launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, xk, yk, alpha, s)
+                                                   : launch_gemv_t_nv(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, nv, xk, yk, alpha, s));
         } else if (m.format == 1) {
-            e = launch_tts_t(m.parts[0].tdev, nv, xk, yk, alpha, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_tts_t");
+            LAUNCH_TRY(c, launch_tts_t, m.parts[0].tdev, nv, xk, yk, alpha, s);
         } else {
-            for (auto& p : m.parts) {
-                e = nv == 1 ? launch_spmv_t(p.dev, xk, yk, alpha, s) : launch_spmv_t_nv(p.dev, nv, xk, yk, alpha, s);
-                if (e != hipSuccess) return hip_fail(c, e, "launch_spmv_t");
-            }
+            for (auto& p : m.parts) LAUNCH_TRY_AS(c, "launch_spmv_t", nv == 1 ? launch_spmv_t(p.dev, xk, yk, alpha, s) : launch_spmv_t_nv(p.dev, nv, xk, yk, alpha, s));
         }
         k += nv;
     }
@@ -1435,9 +1330,9 @@ HISPMV_API int hispmv_value_grad_device(hispmv_ctx* c, int idx, const float* d_g
                                         float alpha, float beta, void* stream) {
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
-    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-    Matrix& m = *c->mats[idx];
-    if (!m.loaded) return fail(c, HISPMV_ESTATE, "value_grad_device called before load_matrices");
+    Matrix* mp = nullptr;
+    if (const int rc = find_handle(c, idx, "value_grad_device", &mp)) return rc;
+    Matrix& m = *mp;
     if (!m.updatable) return fail(c, HISPMV_ESTATE, "value_grad_device: handle was not created with value updates on (hispmv_set_value_updates)");
     if (!value_grad_accepts(m)) return refuse_tile_stream(c, m, "value_grad_device", "value-gradient kernel");
     if (num_vecs < 1) return fail(c, HISPMV_EINVAL, "value_grad_device: num_vecs must be at least 1");
@@ -1446,21 +1341,12 @@ HISPMV_API int hispmv_value_grad_device(hispmv_ctx* c, int idx, const float* d_g
     if ((int64_t)m.rows * num_vecs >= (1LL << 30) || (int64_t)m.cols * num_vecs >= (1LL << 30))
         return fail(c, HISPMV_EINVAL, "value_grad_device: rows * num_vecs and cols * num_vecs must stay below 2^30 floats; split the batch");
     if (m.upd_n == 0) return HISPMV_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    hipError_t e;
-    if (alpha == 0.0f) {          // grad = beta * grad exactly, gy and x not read: the elementwise launch of the transposed prologue, in place
-        constexpr int64_t kPiece = 1LL << 29;
-        for (int64_t at = 0; at < m.upd_n; at += kPiece) {
-            e = launch_transpose_prologue(d_grad + at, d_grad + at, (int32_t)std::min(kPiece, m.upd_n - at), beta, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_transpose_prologue");
-        }
-        return HISPMV_OK;
-    }
+    hipStream_t s;
+    if (const int rc = adopt_stream(c, stream, &s)) return rc;
+    if (alpha == 0.0f) return scale_in_place(c, d_grad, m.upd_n, beta, s);          // grad = beta * grad exactly, gy and x not read
     if (m.dense) {                // all vectors in one launch
-        e = launch_value_grad_dense(m.rows, m.cols, num_vecs, d_gy, d_x, d_grad, alpha, beta, s);
-        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_value_grad_dense");
+        LAUNCH_TRY(c, launch_value_grad_dense, m.rows, m.cols, num_vecs, d_gy, d_x, d_grad, alpha, beta, s);
+        return HISPMV_OK;
     }
     // passes of the widest width that fits (4, 2, 1: the rule of hispmv_linear_device_t); the first stores alpha * s_0 + beta * grad,
     // every later one grad + alpha * s_p
@@ -1468,13 +1354,11 @@ HISPMV_API int hispmv_value_grad_device(hispmv_ctx* c, int idx, const float* d_g
         const int nv = transposed_width(m, num_vecs - k);
         if (m.format == 1) {
             const Matrix::Part& p = m.parts[0];
-            e = launch_tts_value_grad(p.tdev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
-                                      k == 0 ? beta : 1.0f, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_tts_value_grad");
+            LAUNCH_TRY(c, launch_tts_value_grad, p.tdev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
+                       k == 0 ? beta : 1.0f, s);
         } else for (auto& p : m.parts) {
-            e = launch_value_grad(p.dev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
-                                  k == 0 ? beta : 1.0f, s);
-            if (e != hipSuccess) return hip_fail(c, e, "launch_value_grad");
+            LAUNCH_TRY(c, launch_value_grad, p.dev, nv, m.d_map + p.map_chunk_base * kValueChunk, d_gy + k * m.rows, d_x + k * m.cols, d_grad, m.upd_n, alpha,
+                       k == 0 ? beta : 1.0f, s);
         }
         k += nv;
     }
@@ -1568,13 +1452,12 @@ namespace {
 
 // The checks both update entries share; on success *out is the handle.
 int update_target(hispmv_ctx* c, int idx, const float* values, int64_t n, Matrix** out) {
-    if (idx < 0 || idx >= (int)c->mats.size()) return fail(c, HISPMV_EINVAL, "Matrix idx out of range");
-    Matrix& m = *c->mats[idx];
+    if (const int rc = find_handle(c, idx, nullptr, out)) return rc;      // (this entry asks for `updatable` before `loaded`)
+    const Matrix& m = **out;
     if (!m.updatable) return fail(c, HISPMV_ESTATE, "handle was not created with value updates on (hispmv_set_value_updates)");
     if (!m.loaded) return fail(c, HISPMV_ESTATE, "update_values called before load_matrices");
     if (n != m.upd_n) return fail(c, HISPMV_EINVAL, "update_values: n is not the number of values the handle was created with");
     if (n > 0 && !values) return fail(c, HISPMV_EINVAL, "update_values: values is NULL");
-    *out = &m;
     return HISPMV_OK;
 }
 
@@ -1583,16 +1466,15 @@ int issue_update(hispmv_ctx* c, Matrix& m, const float* d_values, hipStream_t s)
     if (m.upd_n == 0) return HISPMV_OK;
     const bool bf16 = m.value_storage == HISPMV_VALUES_BF16;
     if (m.dense && bf16) {
-        const hipError_t e = launch_update_dense_bf16((uint16_t*)m.d_dense, d_values, m.upd_n, s);
-        return e == hipSuccess ? HISPMV_OK : hip_fail(c, e, "launch_update_dense_bf16");
+        LAUNCH_TRY(c, launch_update_dense_bf16, (uint16_t*)m.d_dense, d_values, m.upd_n, s);
+        return HISPMV_OK;
     }
     if (m.dense) {
         HIP_TRY(c, hipMemcpyAsync(m.d_dense, d_values, (size_t)m.upd_n * 4, hipMemcpyDeviceToDevice, s));
         return HISPMV_OK;
     }
-    const hipError_t e = bf16 ? launch_update_values_bf16(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s)
-                              : launch_update_values(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_update_values");
+    LAUNCH_TRY_AS(c, "launch_update_values", bf16 ? launch_update_values_bf16(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s)
+                                                  : launch_update_values(m.d_upd_table, m.map_slots / kValueChunk, m.d_map, d_values, m.upd_n, s));
     return m.companion ? issue_update(c, *m.companion, d_values, s) : HISPMV_OK;      // the stored transpose: the same values through its own map
 }
 
@@ -1626,7 +1508,7 @@ HISPMV_API int hispmv_update_values_device(hispmv_ctx* c, int idx, const float* 
     Matrix* m = nullptr;
     const int rc = update_target(c, idx, d_values, n, &m);
     if (rc != HISPMV_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (stream) c->user_stream = (hipStream_t)stream;
-    return issue_update(c, *m, d_values, stream ? (hipStream_t)stream : c->stream);
+    hipStream_t s;
+    if (const int r = adopt_stream(c, stream, &s)) return r;
+    return issue_update(c, *m, d_values, s);
 }

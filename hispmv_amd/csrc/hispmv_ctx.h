@@ -262,6 +262,40 @@ std::string& prep_error();
         hipError_t e_ = (call);                                          \
         if (e_ != hipSuccess) return ::hispmv::hip_fail((c), e_, #call); \
     } while (0)
+// ... for the library's own launchers: LAUNCH_TRY(c, launch_spmv, args...) calls launch_spmv(args...) and reports a failure as
+// "launch_spmv: <HIP's text>"; LAUNCH_TRY_AS where the call is an expression, or is reported under another launcher's name
+#define LAUNCH_TRY_AS(c, name, call)                                      \
+    do {                                                                  \
+        hipError_t e_ = (call);                                           \
+        if (e_ != hipSuccess) return ::hispmv::hip_fail((c), e_, (name)); \
+    } while (0)
+#define LAUNCH_TRY(c, launcher, ...) LAUNCH_TRY_AS(c, #launcher, launcher(__VA_ARGS__))
+
+// The preamble of the entries that take a handle index and a stream (hispmv_abi.cpp, hispmv_spmm_abi.cpp, hispmv_batch.cpp).
+inline int idx_out_of_range(hispmv_ctx* c) { return fail(c, HISPMV_EINVAL, "Matrix idx out of range"); }   // fpga_handle.cpp:267-270
+// *out = handle `idx`, refused when out of range or -- `who` given -- not loaded.  who == nullptr: an entry that checks something
+// else before the loaded state checks that itself.
+inline int find_handle(hispmv_ctx* c, int idx, const char* who, Matrix** out) {
+    if (idx < 0 || idx >= (int)c->mats.size()) return idx_out_of_range(c);
+    *out = c->mats[(size_t)idx].get();
+    if (who && !(*out)->loaded) return fail(c, HISPMV_ESTATE, std::string(who) + " called before load_matrices");
+    return HISPMV_OK;
+}
+// Called behind an entry's last argument check: every argument is accepted, from here on the call is one hispmv_synchronize waits
+// for.  *s = the stream to launch on (`stream` NULL = the context's).
+inline int adopt_stream(hispmv_ctx* c, void* stream, hipStream_t* s) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (stream) c->user_stream = (hipStream_t)stream;
+    *s = stream ? (hipStream_t)stream : c->stream;
+    return HISPMV_OK;
+}
+// d_v = beta * d_v exactly, in place (the value gradients with alpha == 0): the elementwise launch of the transposed prologue, in
+// pieces whose length an int32 holds
+inline int scale_in_place(hispmv_ctx* c, float* d_v, int64_t n, float beta, hipStream_t s) {
+    constexpr int64_t kPiece = 1LL << 29;
+    for (int64_t at = 0; at < n; at += kPiece) LAUNCH_TRY(c, launch_transpose_prologue, d_v + at, d_v + at, (int32_t)std::min(kPiece, n - at), beta, s);
+    return HISPMV_OK;
+}
 
 // Every device / pinned allocation of the library is released through these: a failing free (a pointer freed twice, a
 // pointer the runtime does not know) is counted, and hispmv_free_failures() lets a test read the count.

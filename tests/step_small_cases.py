@@ -144,7 +144,7 @@ def tts_widths(tts, cols):
 
 
 def linear_passes(tts, cols, vecs, xlds_on):
-    """The passes of a `linear` call of `vecs` vectors (launch_matrix_vectors + tts_batch_width): [(vectors, x in the LDS)]."""
+    """The passes of a `linear` call of `vecs` vectors (forward_width + tts_batch_width): [(vectors, x in the LDS)]."""
     out, k = [], 0
     while k < vecs:
         left, nv, lds = vecs - k, 1, False
