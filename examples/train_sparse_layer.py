@@ -23,8 +23,12 @@ feature-major copies of x and grad_y serve all three products of a step.
 (sparse_linear(..., spmm=True) on a bfloat16 x: FpgaHandle.spmm_device_bf16 / spmm_device_t_bf16), the loss is taken in fp32 on the
 widened y; bias and the values stay fp32, and the value gradient runs through the fp32 entries on widened copies.
 
+--bf16-wide-grad (implies --bf16-activations) takes the value gradient on the bf16 activations as well (sparse_linear(...,
+wide_grad="bf16"): FpgaHandle.spmm_value_grad_device_bf16): the bf16 feature-major copies of x and grad_y serve all three products of a
+step and no fp32 copy of an activation is made; the gradient itself stays fp32.
+
     python examples/train_sparse_layer.py [--rows 2048] [--cols 1024] [--density 0.05] [--batch 64] [--steps 10] [--lr 0.1] [--bf16]
-                                          [--companion] [--spmm] [--wide-grad] [--bf16-activations]
+                                          [--companion] [--spmm] [--wide-grad] [--bf16-activations] [--bf16-wide-grad]
 """
 from __future__ import annotations
 
@@ -100,8 +104,12 @@ def main() -> None:
     ap.add_argument("--spmm", action="store_true", help="forward and grad_x through the wide-batch entries (feature-major operands, lanes across vectors)")
     ap.add_argument("--wide-grad", action="store_true", help="the value gradient through the wide-batch entry as well (implies --spmm)")
     ap.add_argument("--bf16-activations", action="store_true", help="bfloat16 x, y and grad_x through the bf16 wide-batch entries (implies --spmm)")
+    ap.add_argument("--bf16-wide-grad", action="store_true", help="the value gradient on the bf16 activations too (implies --bf16-activations)")
     a = ap.parse_args()
+    a.bf16_activations = a.bf16_activations or a.bf16_wide_grad
     a.spmm = a.spmm or a.wide_grad or a.bf16_activations
+    if a.bf16_wide_grad:
+        a.wide_grad = "bf16"
 
     rng = np.random.default_rng(0)
     r, c = np.nonzero(rng.random((a.rows, a.cols)) < a.density)

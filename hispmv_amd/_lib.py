@@ -111,6 +111,8 @@ SIGNATURES = {
     "hispmv_prep_spmm_bf16_tiles": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i64p]),
     "hispmv_spmm_value_grad_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int64, _p, C.c_float, C.c_float, _p]),
     "hispmv_spmm_value_grad_info": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, _i64p]),
+    "hispmv_spmm_value_grad_device_bf16": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int64, _p, C.c_float, C.c_float, _p]),
+    "hispmv_spmm_value_grad_bf16_info": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, _i64p]),
     "hispmv_prep_spmm_tiles": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i64p]),
     "hispmv_prep_vector_widths": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),

@@ -1,12 +1,14 @@
 // hispmv_spmm_abi.cpp -- the wide-batch entries of the C ABI (include/hispmv.h: hispmv_spmm_device, hispmv_spmm_device_t,
 // hispmv_spmm_info, hispmv_prep_spmm_tiles, hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_info, and the bf16-activation forms
-// hispmv_spmm_device_bf16, hispmv_spmm_device_t_bf16, hispmv_spmm_bf16_info, hispmv_prep_spmm_bf16_tiles) over the launchers of
-// hispmv_spmm.h, hispmv_spmm_bf16.h and hispmv_spmm_grad.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
+// hispmv_spmm_device_bf16, hispmv_spmm_device_t_bf16, hispmv_spmm_bf16_info, hispmv_prep_spmm_bf16_tiles,
+// hispmv_spmm_value_grad_device_bf16, hispmv_spmm_value_grad_bf16_info) over the launchers of
+// hispmv_spmm.h, hispmv_spmm_bf16.h, hispmv_spmm_grad.h and hispmv_spmm_grad_bf16.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
 // nothing in it, so the other entry points are not touched.
 #include "hispmv_ctx.h"
 #include "hispmv_spmm.h"
 #include "hispmv_spmm_bf16.h"
 #include "hispmv_spmm_grad.h"
+#include "hispmv_spmm_grad_bf16.h"
 
 using namespace hispmv;
 
@@ -238,7 +240,8 @@ HISPMV_API int hispmv_spmm_device_t_bf16(hispmv_ctx* c, int idx, const uint16_t*
     return run_spmm_bf16(c, *t, "spmm_device_t_bf16", d_xt, num_vecs, ld_x, d_bias, bias_stride, d_yt, ld_y, alpha, beta, d_work, work_bytes, stream);
 }
 
-// ---- wide-batch value gradient (include/hispmv.h: hispmv_spmm_value_grad_device; kernels: hispmv_spmm_grad.hip) ---------------------
+// ---- wide-batch value gradient (include/hispmv.h: hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_device_bf16; kernels:
+// hispmv_spmm_grad.hip, hispmv_spmm_grad_bf16.hip) ------------------------------------------------------------------------------------
 namespace {
 
 // launches of one vector tile: one per part that holds slices (none for a handle without entries)
@@ -249,55 +252,83 @@ int64_t grad_launches_of(const Matrix& m) {
     return n;
 }
 
-}  // namespace
-
-HISPMV_API int hispmv_spmm_value_grad_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t ld, int64_t out[4]) {
+// bf16 operands take the product's bf16 rule as it stands (spmm_bf16_tiles); its 8 MiB of rule (b) was measured for neither bf16 kernel
+int value_grad_info(bool bf16, const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t ld, int64_t out[4]) {
     if (!c || !out || idx < 0 || idx >= (int)c->mats.size() || num_vecs < 1 || ld < num_vecs) return HISPMV_EINVAL;
     for (int i = 0; i < 4; ++i) out[i] = 0;
     const Matrix& m = *c->mats[(size_t)idx];
     if (!m.loaded || !m.updatable || !spmm_accepts(m)) return HISPMV_OK;
-    const SpmmTiles tl = spmm_tiles(m.cols, num_vecs, ld, ld, 16);
+    const SpmmTiles tl = tiles_of(bf16, m.cols, num_vecs, ld, ld, 16);
     out[0] = 1; out[1] = tl.vl_first; out[2] = tl.tiles; out[3] = grad_launches_of(m) * tl.tiles;
     return HISPMV_OK;
 }
 
-HISPMV_API int hispmv_spmm_value_grad_device(hispmv_ctx* c, int idx, const float* d_gyt, int64_t ld_gy, const float* d_xt, int64_t ld_x, int64_t num_vecs,
-                                             float* d_grad, float alpha, float beta, void* stream) {
+// One call of either entry; Half = uint16_t for bf16 operands, float otherwise.  Checks, order and return codes are the same; the
+// operands' alignment, the tile rule and the launcher differ.
+template <class Half>
+int run_value_grad(hispmv_ctx* c, int idx, const char* who, const Half* d_gyt, int64_t ld_gy, const Half* d_xt, int64_t ld_x, int64_t num_vecs, float* d_grad,
+                   float alpha, float beta, void* stream) {
+    constexpr bool bf16 = sizeof(Half) == 2;
     if (!c) return HISPMV_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     Matrix* mp = nullptr;
-    if (const int rc = find_handle(c, idx, "spmm_value_grad_device", &mp)) return rc;
+    if (const int rc = find_handle(c, idx, who, &mp)) return rc;
     Matrix& m = *mp;
+    const std::string w(who);
     if (m.dense)
-        return fail(c, HISPMV_ENOTSUP, "spmm_value_grad_device: this is a dense handle; the value gradient of a dense W over a wide batch is a GEMM (gyt * xt^T), "
-                                       "which this library leaves to a GEMM library");
-    if (!spmm_accepts(m)) return refuse_tile_stream(c, "spmm_value_grad_device");
-    if (!m.updatable) return fail(c, HISPMV_ESTATE, "spmm_value_grad_device: handle was not created with value updates on (hispmv_set_value_updates)");
-    const std::string w("spmm_value_grad_device");
+        return fail(c, HISPMV_ENOTSUP, w + ": this is a dense handle; the value gradient of a dense W over a wide batch is a GEMM (gyt * xt^T), "
+                                           "which this library leaves to a GEMM library");
+    if (!spmm_accepts(m)) return refuse_tile_stream(c, who);
+    if (!m.updatable) return fail(c, HISPMV_ESTATE, w + ": handle was not created with value updates on (hispmv_set_value_updates)");
     if (num_vecs < 1) return fail(c, HISPMV_EINVAL, w + ": num_vecs must be at least 1");
     if (num_vecs > 0x7fffffffLL) return fail(c, HISPMV_EINVAL, w + ": num_vecs must stay below 2^31");
     if (ld_gy < num_vecs || ld_x < num_vecs) return fail(c, HISPMV_EINVAL, w + ": ld_gy and ld_x must be at least num_vecs");
     if (!d_gyt || !d_xt || (m.upd_n > 0 && !d_grad)) return fail(c, HISPMV_EINVAL, "NULL device vector");
-    if (d_grad && ((const float*)d_grad == d_gyt || (const float*)d_grad == d_xt)) return fail(c, HISPMV_EINVAL, w + ": grad must not be gyt or xt");
-    if (((uintptr_t)d_gyt | (uintptr_t)d_xt | (uintptr_t)d_grad) & 3) return fail(c, HISPMV_EINVAL, w + ": device pointers must be 4-byte aligned");
+    if (d_grad && ((const void*)d_grad == (const void*)d_gyt || (const void*)d_grad == (const void*)d_xt)) return fail(c, HISPMV_EINVAL, w + ": grad must not be gyt or xt");
+    if constexpr (!bf16) {
+        if (((uintptr_t)d_gyt | (uintptr_t)d_xt | (uintptr_t)d_grad) & 3) return fail(c, HISPMV_EINVAL, w + ": device pointers must be 4-byte aligned");
+    } else {
+        if (((uintptr_t)d_gyt | (uintptr_t)d_xt) & 1) return fail(c, HISPMV_EINVAL, w + ": bf16 device pointers must be 2-byte aligned");
+        if ((uintptr_t)d_grad & 3) return fail(c, HISPMV_EINVAL, w + ": grad must be 4-byte aligned");
+    }
     if (m.upd_n == 0) return HISPMV_OK;
     hipStream_t s;
     if (const int rc = adopt_stream(c, stream, &s)) return rc;
     if (alpha == 0.0f) return scale_in_place(c, d_grad, m.upd_n, beta, s);          // grad = beta * grad exactly, gyt and xt not read
     // Vector tiles one after the other -- the first with the caller's beta, every later one adding in place -- and inside a tile the
     // parts one after the other, each with its own chunks of the value map: every input entry lives in exactly one slot over all
-    // parts, so a part writes only its own entries.  A lane's VL floats must be one aligned load in every row of gyt and xt.
+    // parts, so a part writes only its own entries.  A lane's VL floats (VB halves) must be one aligned load in every row of gyt and xt.
     const int64_t align = std::min(pointer_align(d_gyt), pointer_align(d_xt));
-    SpmmGradOperands a{};
+    std::conditional_t<bf16, SpmmGradBf16Operands, SpmmGradOperands> a{};
     a.gyt = d_gyt; a.xt = d_xt; a.grad = d_grad; a.ld_gy = ld_gy; a.ld_x = ld_x; a.n = m.upd_n; a.n_vecs = (int)num_vecs; a.alpha = alpha;
     for (int64_t k = 0; k < num_vecs;) {
-        const int vl = spmm_vl(m.cols, num_vecs - k, ld_x, ld_gy, align);
+        const int vl = bf16 ? spmm_bf16_vb(m.cols, num_vecs - k, ld_x, ld_gy, align) : spmm_vl(m.cols, num_vecs - k, ld_x, ld_gy, align);
         a.tile0 = (int)k; a.beta = k == 0 ? beta : 1.0f;
         for (auto& p : m.parts) {
             if (p.dev.n_slices <= 0) continue;
-            LAUNCH_TRY(c, launch_spmm_grad_part, p.dev, vl, m.d_map + p.map_chunk_base * kValueChunk, a, s);
+            if constexpr (bf16) { LAUNCH_TRY(c, launch_spmm_grad_bf16_part, p.dev, vl, m.d_map + p.map_chunk_base * kValueChunk, a, s); }
+            else { LAUNCH_TRY(c, launch_spmm_grad_part, p.dev, vl, m.d_map + p.map_chunk_base * kValueChunk, a, s); }
         }
         k += std::min<int64_t>(num_vecs - k, 64 * vl);
     }
     return HISPMV_OK;
+}
+
+}  // namespace
+
+HISPMV_API int hispmv_spmm_value_grad_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t ld, int64_t out[4]) {
+    return value_grad_info(false, c, idx, num_vecs, ld, out);
+}
+HISPMV_API int hispmv_spmm_value_grad_bf16_info(const hispmv_ctx* c, int idx, int64_t num_vecs, int64_t ld, int64_t out[4]) {
+    return value_grad_info(true, c, idx, num_vecs, ld, out);
+}
+
+HISPMV_API int hispmv_spmm_value_grad_device(hispmv_ctx* c, int idx, const float* d_gyt, int64_t ld_gy, const float* d_xt, int64_t ld_x, int64_t num_vecs,
+                                             float* d_grad, float alpha, float beta, void* stream) {
+    return run_value_grad<float>(c, idx, "spmm_value_grad_device", d_gyt, ld_gy, d_xt, ld_x, num_vecs, d_grad, alpha, beta, stream);
+}
+
+HISPMV_API int hispmv_spmm_value_grad_device_bf16(hispmv_ctx* c, int idx, const uint16_t* d_gyt, int64_t ld_gy, const uint16_t* d_xt, int64_t ld_x, int64_t num_vecs,
+                                                  float* d_grad, float alpha, float beta, void* stream) {
+    return run_value_grad<uint16_t>(c, idx, "spmm_value_grad_device_bf16", d_gyt, ld_gy, d_xt, ld_x, num_vecs, d_grad, alpha, beta, stream);
 }

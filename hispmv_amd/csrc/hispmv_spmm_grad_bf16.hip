@@ -1,37 +1,68 @@
-// hispmv_spmm_grad.hip -- the kernels of the wide-batch value gradient (hispmv_spmm_grad.h): grad[k] = alpha * sum_v gyt[row_k, v] *
-// xt[col_k, v] + beta * grad[k] on the slice stream of a loaded, updatable handle, operands feature-major.  What it needs of the slice
-// format (the meta request, decode_metas, store_grad, the launch checks) it shares with the other satellite
-// files: hispmv_slice_walk.h; the sum over the lanes it shares with hispmv_spmm_grad_bf16.hip: hispmv_lane_tree.h.  hispmv_kernels.hip takes no part in that and keeps its own text, so that no forward kernel is touched from here.
+// hispmv_spmm_grad_bf16.hip -- the kernels of the wide-batch value gradient with bf16 activations (hispmv_spmm_grad_bf16.h):
+// spmm_grad_group of hispmv_spmm_grad.hip with 2-byte gyt and xt.  The seventh satellite on hispmv_slice_walk.h; the lane tree is the one
+// of the fp32 kernel (hispmv_lane_tree.h).  No other kernel file is touched from here.
 //
-// Roles, against the wide-batch product (hispmv_spmm.hip: spmm_group) and the value gradient of 4 vectors (hispmv_value_grad.hip):
-//   wide-batch product                          value gradient (4-2-1)                     wide-batch value gradient
-//   a lane owns VL vectors                      a lane owns 16 elements of the slice       a lane owns VL vectors
-//   values and metas of a slice                 the metas only                             the metas only
-//   window words hold COLUMN NUMBERS            x window staged per vector                 window words hold column numbers
-//   a lane sums a row sequentially              16 products per lane, summed over vectors  VL products per lane and element, then the sum
-//                                                                                          over the 64 lanes: a butterfly over 64 elements
-//   carry + fix-up launch for cut rows          none                                       none: every element is independent
-// An explicit zero of the input has a map word like every other entry and gets its gradient; a slot whose map word is 0 (fillers,
-// row extensions, padding) writes nothing.
+// What is kept from hispmv_spmm_grad.hip: grid, groups and walk; metas only, never values; column numbers in the LDS window; stray areas;
+// in-bounds loads without a branch (row 0 or column 0 for an element without a place, lane 0's address for a lane past the batch); the
+// PRODUCT mask; the asm volatile that forms the lane sum where it is written; the next-slice request before the last step; store_grad
+// through the value map, plain stores, one writer per entry.
+// What differs:
+//   a lane owns VB = 8, 4, 2 or 1 bf16 of a row: one dwordx4, dwordx2, dword or 16-bit load per element for xt and per row for gyt.  The
+//   gathered halves and the row of gyt requested one row end ahead stay PACKED (VB / 2 dwords) until they are used; they are widened
+//   exactly (bits << 16, bits & 0xffff0000) in front of the products.
+//   VB 8 gathers in halves of a lane's elements (two 16-byte elements per gather), as fp32 VL 4 does; VB <= 4 gathers all four.
+// load_packed and widen are a second copy of those of hispmv_spmm_bf16.hip, which stays as it is: a shared header would have meant an
+// edit of that file.
 #include <hip/hip_runtime.h>
 
 #include "hispmv_slice_walk.h"
 #include "hispmv_lane_tree.h"
-#include "hispmv_spmm_grad.h"
+#include "hispmv_spmm_grad_bf16.h"
 #include "hispmv_update.h"
 
 namespace hispmv {
 
 namespace {
 
+// the VB bf16 of a lane as packed dwords: element 2d in the low half of dword d, 2d + 1 in the high half (VB 1: the low half of d[0])
+template <int VB> constexpr int kPacked = VB >= 2 ? VB / 2 : 1;
+template <int VB> __device__ __forceinline__ void load_packed(const uint16_t* p, unsigned (&d)[kPacked<VB>]) {
+    if constexpr (VB == 8) {
+        typedef unsigned u4v __attribute__((ext_vector_type(4)));
+        const u4v q = *(const HISPMV_GLOBAL u4v*)p;
+        d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
+    } else if constexpr (VB == 4) {
+        typedef unsigned u2v __attribute__((ext_vector_type(2)));
+        const u2v q = *(const HISPMV_GLOBAL u2v*)p;
+        d[0] = q.x; d[1] = q.y;
+    } else if constexpr (VB == 2) {
+        d[0] = *(const HISPMV_GLOBAL unsigned*)p;
+    } else {
+        d[0] = *(const HISPMV_GLOBAL uint16_t*)p;
+    }
+}
+// exact: a bf16 is the upper half of its fp32
+template <int VB> __device__ __forceinline__ void widen(const unsigned (&d)[kPacked<VB>], float (&x)[VB]) {
+    if constexpr (VB == 1) {
+        x[0] = i2f((int)(d[0] << 16));
+    } else {
+#pragma unroll
+        for (int i = 0; i < VB / 2; ++i) {
+            x[2 * i] = i2f((int)(d[i] << 16));
+            x[2 * i + 1] = i2f((int)(d[i] & 0xffff0000u));
+        }
+    }
+}
+
 // The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
 // LDS: the forward launch's window of lds_floats words (the wavefronts' stray areas are its last words), holding column numbers.
-template <int VL, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
-__device__ __forceinline__ void spmm_grad_group(
+template <int VB, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
+__device__ __forceinline__ void spmm_grad_bf16_group(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const int32_t* __restrict__ map,
-    const SpmmGradOperands& a, long long n_slices, int group_slices, int lds_floats, int cols, int rows, long long group, int4 g) {
+    const SpmmGradBf16Operands& a, long long n_slices, int group_slices, int lds_floats, int cols, int rows, long long group, int4 g) {
     extern __shared__ unsigned colwin[];
     constexpr int kE = kSliceSteps * kLaneElems;
+    constexpr int NP = kPacked<VB>;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
     // the forward kernel's walk; the first request leaves before the window is filled
     auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
@@ -48,19 +79,19 @@ __device__ __forceinline__ void spmm_grad_group(
     }
     if (USE_LDS) fill_column_window(colwin, frags, g, wk.in_lds, lds_floats, wk.win_floats, lane, wave, n_waves);
 
-    // A lane past the batch reads the floats of lane 0 (always inside the row).  keep[i]: the lane's vector i is below n_vecs; the
-    // PRODUCT of every other one is masked to +0, so that neither a pad float of gyt nor one of xt (NaN, say) gets into a sum.
-    const int lane_vec = a.tile0 + lane * VL;
-    const unsigned lane_bytes = lane_vec < a.n_vecs ? (unsigned)(lane * VL * 4) : 0u;      // (a uniform row address + these 32 bits: one scalar-base load)
-    const float* const xtile = a.xt + a.tile0;
-    const float* const gtile = a.gyt + a.tile0;
-    bool keep[VL];
+    // A lane past the batch reads the halves of lane 0 (always inside the row).  keep[i]: the lane's vector i is below n_vecs; the
+    // PRODUCT of every other one is masked to +0, so that neither a pad half of gyt nor one of xt (NaN, say) gets into a sum.
+    const int lane_vec = a.tile0 + lane * VB;
+    const unsigned lane_bytes = lane_vec < a.n_vecs ? (unsigned)(lane * VB * 2) : 0u;      // (a uniform row address + these 32 bits: one scalar-base load)
+    const uint16_t* const xtile = a.xt + a.tile0;
+    const uint16_t* const gtile = a.gyt + a.tile0;
+    bool keep[VB];
 #pragma unroll
-    for (int i = 0; i < VL; ++i) keep[i] = lane_vec + i < a.n_vecs;
-    // gyt[row, the lane's vectors]; a row past the matrix (elements of padding behind the last row) reads row 0: its map word is 0
-    const auto load_gy = [&](float (&d)[VL], int row) {
+    for (int i = 0; i < VB; ++i) keep[i] = lane_vec + i < a.n_vecs;
+    // gyt[row, the lane's vectors], packed; a row past the matrix (elements of padding behind the last row) reads row 0: its map word is 0
+    const auto load_gy = [&](unsigned (&d)[NP], int row) {
         const int rc = (row >= 0 && row < rows) ? row : 0;
-        load_vl<VL>((const float*)((const char*)(gtile + (size_t)rc * (size_t)a.ld_gy) + lane_bytes), d);
+        load_packed<VB>((const uint16_t*)((const char*)(gtile + (size_t)rc * (size_t)a.ld_gy) + lane_bytes), d);
     };
 
     while (wk.live()) {
@@ -68,8 +99,13 @@ __device__ __forceinline__ void spmm_grad_group(
         // passed so far in the slice, in stream order (the decode of value_grad_group)
         int row = __builtin_amdgcn_readfirstlane(h.x);
         const long long cur = wk.cur();
-        float gy[VL], gy_next[VL];      // of `row` and of row + 1, requested one row end ahead
-        load_gy(gy, row);
+        float gy[VB];                   // of `row`, widened
+        unsigned gy_next[NP];           // of row + 1, requested one row end ahead, packed until it becomes gy
+        {
+            unsigned d[NP];
+            load_gy(d, row);
+            widen<VB>(d, gy);
+        }
         load_gy(gy_next, row + 1);
         unsigned c[kE];
         decode_metas<COMPACT>(w, c);
@@ -83,31 +119,32 @@ __device__ __forceinline__ void spmm_grad_group(
                                                   [&](unsigned col, int) { return col < (unsigned)cols; });
 
         // the 1024 elements in stream order: step j, lane L, element k.  The meta of an element is wave-uniform (readlane); every lane
-        // gathers its VL floats of that column's row of xt.  The gathers carry no branch: an element without a column reads row 0 of
+        // gathers its VB halves of that column's row of xt.  The gathers carry no branch: an element without a column reads row 0 of
         // xt (its sum is dropped at the store: its map word is 0).
-        // NK elements per gather: the four of a lane, or -- VL 4, 16 bytes per lane and element -- its two halves one after the other
-        constexpr int NK = VL == 4 ? kLaneElems / 2 : kLaneElems;
-        struct Gathered { unsigned m[NK]; float x[NK][VL]; };
+        // NK elements per gather: the four of a lane, or -- VB 8, 16 bytes per lane and element -- its two halves one after the other
+        constexpr int NK = VB == 8 ? kLaneElems / 2 : kLaneElems;
+        struct Gathered { unsigned m[NK]; unsigned x[NK][NP]; };
         const auto gather = [&](Gathered& q, int j, int L, int k0) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 q.m[k] = (unsigned)__builtin_amdgcn_readlane((int)meta[4 * j + k0 + k], L);
-                load_vl<VL>((const float*)((const char*)(xtile + (size_t)(q.m[k] < kSkipMeta ? q.m[k] >> 1 : 0u) * (size_t)a.ld_x) + lane_bytes), q.x[k]);
+                load_packed<VB>((const uint16_t*)((const char*)(xtile + (size_t)(q.m[k] < kSkipMeta ? q.m[k] >> 1 : 0u) * (size_t)a.ld_x) + lane_bytes), q.x[k]);
             }
         };
         // -> the lane's partial of each of the four elements; behind a row end (wave-uniform) gyt of the next row
         const auto consume = [&](const Gathered& q, float (&p)[kLaneElems], int k0) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
+                float x[VB];
+                widen<VB>(q.x[k], x);
                 float s = 0.0f;
 #pragma unroll
-                for (int i = 0; i < VL; ++i) s = s + (keep[i] ? gy[i] * q.x[k][i] : 0.0f);
-                asm volatile("" : "+v"(s));      // the sum is formed HERE: left alone, hipcc sinks the products below the row-end branches and keeps every gathered float live
+                for (int i = 0; i < VB; ++i) s = s + (keep[i] ? gy[i] * x[i] : 0.0f);
+                asm volatile("" : "+v"(s));      // the sum is formed HERE: left alone, hipcc sinks the products below the row-end branches and keeps every gathered half live
                 p[k0 + k] = s;
                 if (q.m[k] & 1u) {
                     row += 1;
-#pragma unroll
-                    for (int i = 0; i < VL; ++i) gy[i] = gy_next[i];
+                    widen<VB>(gy_next, gy);
                     load_gy(gy_next, row + 1);
                 }
             }
@@ -129,7 +166,7 @@ __device__ __forceinline__ void spmm_grad_group(
                     request_metas<COMPACT, HALF>(w, wk.slice(), lane);
                 }
             }
-            if constexpr (VL < 4) {
+            if constexpr (NK == kLaneElems) {
                 Gathered qa, qb;
                 gather(qa, j, 0, 0);
 #pragma unroll 1
@@ -170,33 +207,33 @@ __device__ __forceinline__ void spmm_grad_group(
 }
 
 // HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
-template <int VL, bool USE_LDS, bool STRAYS, bool HALF>
-__global__ __launch_bounds__(1024) void spmm_grad_slices_kernel(
+template <int VB, bool USE_LDS, bool STRAYS, bool HALF>
+__global__ __launch_bounds__(1024) void spmm_grad_bf16_slices_kernel(
     const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
-    const int32_t* __restrict__ map, SpmmGradOperands a, long long n_slices, int group_slices, int lds_floats, int cols, int rows) {
+    const int32_t* __restrict__ map, SpmmGradBf16Operands a, long long n_slices, int group_slices, int lds_floats, int cols, int rows) {
     const long long group = (long long)blockIdx.x;
     if constexpr (USE_LDS) {
         const int4 g = load_int4(groups + group);
         const int gw = __builtin_amdgcn_readfirstlane(g.w);
         if constexpr (HALF) {
             if (gw & kGroupHalf) {
-                spmm_grad_group<VL, true, true, STRAYS, true>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+                spmm_grad_bf16_group<VB, true, true, STRAYS, true>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
                 return;
             }
         }
         if (gw & kGroupCompact)
-            spmm_grad_group<VL, true, true, STRAYS, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+            spmm_grad_bf16_group<VB, true, true, STRAYS, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
         else
-            spmm_grad_group<VL, true, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+            spmm_grad_bf16_group<VB, true, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
     } else {
-        spmm_grad_group<VL, false, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, int4{0, 0, 0, 0});
+        spmm_grad_bf16_group<VB, false, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, int4{0, 0, 0, 0});
     }
 }
 
-template <int VL>
-hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+template <int VB>
+hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const SpmmGradBf16Operands& a, hipStream_t stream) {
     return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
-        constexpr auto kernel = spmm_grad_slices_kernel<VL, USE_LDS(), STRAYS(), HALF()>;
+        constexpr auto kernel = spmm_grad_bf16_slices_kernel<VB, USE_LDS(), STRAYS(), HALF()>;
         const hipError_t e = raise_lds_limit<kernel>();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
@@ -207,18 +244,21 @@ hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const Sp
 
 }  // namespace
 
-hipError_t launch_spmm_grad_part(const SpmvDeviceMatrix& m, int vl, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+hipError_t launch_spmm_grad_bf16_part(const SpmvDeviceMatrix& m, int vb, const int32_t* map, const SpmmGradBf16Operands& a, hipStream_t stream) {
     (void)hipGetLastError();
     if (m.n_slices <= 0 || m.n_groups <= 0 || a.n <= 0) return hipSuccess;
     if (!map) return hipErrorInvalidValue;
     if (!slice_geometry_ok(m, (size_t)m.lds_floats * 4)) return hipErrorInvalidValue;
     if (m.rows <= 0 || m.cols <= 0) return hipErrorInvalidValue;          // (rows 0 and columns 0 of gyt and xt are read for elements without a place)
     if (!a.gyt || !a.xt || !a.grad || a.n_vecs < 1 || a.tile0 < 0 || a.tile0 >= a.n_vecs || a.ld_x < a.n_vecs || a.ld_gy < a.n_vecs) return hipErrorInvalidValue;
-    switch (vl) {
+    if (vb != 8 && vb != 4 && vb != 2 && vb != 1) return hipErrorInvalidValue;
+    // a lane's vb halves are one aligned load that ends inside the row: the tile rule's (c), checked where the loads are issued
+    if (a.tile0 % vb || a.ld_x % vb || a.ld_gy % vb || ((uintptr_t)a.gyt | (uintptr_t)a.xt) % (uintptr_t)(2 * vb)) return hipErrorInvalidValue;
+    switch (vb) {
+        case 8: return launch_slices<8>(m, map, a, stream);
         case 4: return launch_slices<4>(m, map, a, stream);
         case 2: return launch_slices<2>(m, map, a, stream);
-        case 1: return launch_slices<1>(m, map, a, stream);
-        default: return hipErrorInvalidValue;
+        default: return launch_slices<1>(m, map, a, stream);
     }
 }
 

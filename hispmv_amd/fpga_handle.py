@@ -393,6 +393,29 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range")
         return {"accepted": bool(out[0]), "vl": int(out[1]), "tiles": int(out[2]), "launches": int(out[3])}
 
+    def spmm_value_grad_device_bf16(self, matrix_idx: int, d_gyt: int, d_xt: int, num_vecs: int, d_grad: int, alpha: float = 1.0, beta: float = 0.0,
+                                    ld_gy=None, ld_x=None, stream: int = 0) -> None:
+        """spmm_value_grad_device with bfloat16 gyt [rows, ld_gy] and xt [cols, ld_x] (hispmv_spmm_value_grad_device_bf16); grad, alpha and
+        beta stay float32.  A lane owns 8, 4, 2 or 1 vectors (prep.spmm_bf16_tiles with the smaller alignment of the two operands), a
+        tile is up to 512 vectors.  Widening is exact and the order of the sum is that of spmm_value_grad_device: where both take the
+        same lane width and tiles, the bits are those of spmm_value_grad_device on the widened operands.  Operands 2-byte aligned, grad
+        4-byte.  Same handles, same exceptions as spmm_value_grad_device."""
+        self._check(lib.hispmv_spmm_value_grad_device_bf16(self._ctx, int(matrix_idx), C.c_void_p(d_gyt), int(num_vecs if ld_gy is None else ld_gy),
+                                                           C.c_void_p(d_xt), int(num_vecs if ld_x is None else ld_x), int(num_vecs), C.c_void_p(d_grad),
+                                                           float(alpha), float(beta), C.c_void_p(stream)))
+
+    def spmm_value_grad_bf16_info(self, matrix_idx: int, num_vecs: int, ld=None) -> dict:
+        """{"accepted", "vb", "tiles", "launches"} of spmm_value_grad_device_bf16 for num_vecs vectors with ld_gy = ld_x = ld (default
+        num_vecs) and 16-byte aligned pointers (hispmv_spmm_value_grad_bf16_info): the bf16 per lane of the first tile, the vector tiles,
+        the launches of a call with alpha != 0 (one per tile and part that holds slices); zeros for a handle it does not accept."""
+        out = (C.c_int64 * 4)()
+        rc = lib.hispmv_spmm_value_grad_bf16_info(self._ctx, int(matrix_idx), int(num_vecs), int(num_vecs if ld is None else ld), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError("num_vecs must be at least 1 and ld at least num_vecs")
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "vb": int(out[1]), "tiles": int(out[2]), "launches": int(out[3])}
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

@@ -22,7 +22,8 @@ stream the caller synchronises between torch's operations and the layer.
 ``spmm=True`` routes the forward product and grad_x through the wide-batch entries (FpgaHandle.spmm_device / spmm_device_t) on
 feature-major copies of the activations; ``wide_grad=True`` on top of it takes grad_values through the wide-batch value gradient
 (FpgaHandle.spmm_value_grad_device) on the same copies.  With ``spmm=True`` a bfloat16 ``x`` stays bfloat16 through both products
-(FpgaHandle.spmm_device_bf16 / spmm_device_t_bf16).  The default route is unchanged (see sparse_linear).
+(FpgaHandle.spmm_device_bf16 / spmm_device_t_bf16), and ``wide_grad="bf16"`` keeps the value gradient on the bf16 copies as well
+(FpgaHandle.spmm_value_grad_device_bf16).  The default route is unchanged (see sparse_linear).
 
 The backward pass is differentiable once (no double backward).  The autograd graph keeps a reference to the handle, which keeps the
 object alive but not open: the handle must not be closed between forward and backward (a closed handle makes backward raise, it does
@@ -348,8 +349,10 @@ def _function_spmm_bf16(torch):
         the widened grad_y, narrowed by torch.  bias is fp32, grad_bias = grad_y.float().sum(0).  `values` is the fp32 master copy:
         its gradient goes through the unchanged fp32 entries on torch-widened copies of the saved activations and of grad_y --
         spmm_value_grad_device on feature-major copies (ld = B rounded up to 4, as SparseLinearSpmmWide builds them) when `wide`,
-        value_grad_device otherwise -- so it has the bits of the fp32-activation call on the widened inputs.  Stream ordering as in
-        SparseLinearSpmm."""
+        value_grad_device otherwise -- so it has the bits of the fp32-activation call on the widened inputs.  `wide` == "bf16": the value
+        gradient stays on 2-byte operands too (spmm_value_grad_device_bf16): forward saves the bf16 feature-major xt it built anyway (not
+        x), backward builds the bf16 feature-major grad_y once, for spmm_device_t_bf16 (where accepted) and for the value gradient, and no
+        fp32 copy of an activation is made.  Stream ordering as in SparseLinearSpmm."""
 
         @staticmethod
         def forward(ctx, x, bias, values, handle, idx, rows, wide):
@@ -373,10 +376,10 @@ def _function_spmm_bf16(torch):
                                     ld_x=ld, ld_y=ld, work=work.data_ptr(), work_bytes=info["work_bytes"], stream=stream)
             if stream == 0:
                 handle.synchronize()
-            del xt, work, b, v
             ctx.cols = x.shape[1]
-            if values is not None and values.requires_grad:          # x is kept for the value gradient only
-                ctx.save_for_backward(x.contiguous())
+            if values is not None and values.requires_grad:          # x (or, "bf16", the feature-major copy) is kept for the value gradient only
+                ctx.save_for_backward(xt if wide == "bf16" else x.contiguous())
+            del xt, work, b, v
             return yt[:, :B].t()
 
         @staticmethod
@@ -394,15 +397,20 @@ def _function_spmm_bf16(torch):
             # torch's side first: everything the launches below read or write
             info = handle.spmm_bf16_info(idx, B, ld) if want_x else None
             wide_t = want_x and info["accepted_t"]
-            g = gt = gxt = gx32 = work = g32 = x32 = None
+            half_v = want_v and ctx.wide == "bf16"
+            g = gt = gxt = gx32 = work = g32 = x32 = xt = None
+            if wide_t or half_v:
+                gt = feature_major(grad_y, ld, torch.bfloat16)          # ONE copy, for both products
             if wide_t:
-                gt = feature_major(grad_y, ld, torch.bfloat16)
                 gxt = torch.empty((ctx.cols, ld), dtype=torch.bfloat16, device=grad_y.device)
                 work = workspace(info["work_bytes_t"], grad_y.device)
             elif want_x:
                 g = grad_y.float().contiguous()
                 gx32 = torch.empty((B, ctx.cols), dtype=torch.float32, device=grad_y.device)
-            if want_v:
+            if half_v:
+                (xt,) = ctx.saved_tensors
+                grad_values = torch.empty((ctx.n,), dtype=torch.float32, device=grad_y.device)
+            elif want_v:
                 (x,) = ctx.saved_tensors
                 if ctx.wide:
                     g32, x32 = feature_major(grad_y, ld4, torch.float32), feature_major(x, ld4, torch.float32)
@@ -417,7 +425,9 @@ def _function_spmm_bf16(torch):
                 grad_x = gxt[:, :B].t()
             elif want_x:
                 handle.linear_device_t(idx, g.data_ptr(), B, 0, gx32.data_ptr(), 1.0, 0.0, 0, stream)
-            if want_v and ctx.wide:
+            if half_v:
+                handle.spmm_value_grad_device_bf16(idx, gt.data_ptr(), xt.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, ld_gy=ld, ld_x=ld, stream=stream)
+            elif want_v and ctx.wide:
                 handle.spmm_value_grad_device(idx, g32.data_ptr(), x32.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, ld_gy=ld4, ld_x=ld4, stream=stream)
             elif want_v:
                 handle.value_grad_device(idx, g32.data_ptr(), x32.data_ptr(), B, grad_values.data_ptr(), 1.0, 0.0, stream)
@@ -425,7 +435,7 @@ def _function_spmm_bf16(torch):
                 handle.synchronize()
             if gx32 is not None:
                 grad_x = gx32.to(torch.bfloat16)              # (on the default stream behind the wait above: gx32 is written)
-            del g, gt, work, g32, x32
+            del g, gt, work, g32, x32, xt
             return grad_x, grad_bias, grad_values, None, None, None, None
 
     _function_spmm_bf16.cached = SparseLinearSpmmBf16
@@ -490,12 +500,23 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     anyway (instead of x), the backward pass builds the feature-major grad_y once and uses it for spmm_device_t (where the handle has
     a slice-stream companion) and for the value gradient, which then reads the slice stream once per tile of up to 256 vectors
     instead of once per 4.  y and grad_x keep the bits of spmm=True; grad_values is deterministic, but its bits are not those of
-    value_grad_device and depend on the batch size (the sums go lane by lane, then over the lanes as a pairwise tree)."""
+    value_grad_device and depend on the batch size (the sums go lane by lane, then over the lanes as a pairwise tree).
+
+    wide_grad="bf16": a third state, for a bfloat16 x (it needs one, spmm=True and `values`; otherwise, or for any state other than
+    False, True and "bf16", ValueError before any launch).  y and grad_x are those of wide_grad=True; grad_values goes through
+    FpgaHandle.spmm_value_grad_device_bf16 on the bf16 feature-major copies: forward saves the copy of x it built anyway (leading
+    dimension B rounded up to 8), backward builds the copy of grad_y once, for spmm_device_t_bf16 and for the value gradient, and no
+    float32 copy of an activation is made.  grad_values is float32 and deterministic; a lane owns up to 8 vectors, so its bits are
+    those of wide_grad=True only where both entries take the same lane width and tiles."""
     import torch
+    if not (isinstance(wide_grad, bool) or (isinstance(wide_grad, str) and wide_grad == "bf16")):
+        raise ValueError('wide_grad must be False, True or "bf16"')
     if wide_grad and not spmm:
         raise ValueError("wide_grad=True needs spmm=True")
     if wide_grad and values is None:
         raise ValueError("wide_grad=True needs values")
+    if wide_grad == "bf16" and not (isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16):
+        raise ValueError('wide_grad="bf16" needs a bfloat16 x')
     info = handle.matrix_info(idx)
     bf16 = spmm and isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16
     _check_tensor(torch, x, "x", info["cols"], (1, 2), torch.bfloat16 if bf16 else torch.float32)
@@ -525,7 +546,7 @@ def sparse_linear(handle, idx: int, x, bias=None, values=None, spmm: bool = Fals
     if values.device != x.device:
         raise ValueError("values must be on the device of x")
     if bf16:
-        y = _function_spmm_bf16(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"], bool(wide_grad))
+        y = _function_spmm_bf16(torch).apply(x.unsqueeze(0) if one else x, bias, values, handle, int(idx), info["rows"], wide_grad)
         return y.squeeze(0) if one else y
     if spmm:
         fn = _function_spmm_wide(torch) if wide_grad else _function_spmm(torch)

@@ -469,7 +469,7 @@ int hispmv_spmm_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, in
  *  - HANDLE STATE: the entry reads metas, slice headers, fragment tables, stray columns and the value map, and writes nothing but
  *    d_grad: it may overlap forward, transposed, wide and update calls on the same handle.
  * Out of scope: tile-stream and dense handles, gradients inside hispmv_spmv_device_batch or the step kernel, sharding over devices,
- * host-pointer variants, bf16 activations (the products take them: hispmv_spmm_device_bf16; the value gradients do not). */
+ * host-pointer variants.  bf16 activations: hispmv_spmm_value_grad_device_bf16. */
 int hispmv_spmm_value_grad_device(hispmv_ctx* ctx, int matrix_idx, const float* d_gyt, int64_t ld_gy, const float* d_xt, int64_t ld_x,
                                   int64_t num_vecs, float* d_grad, float alpha, float beta, void* stream);
 /* out = {1 if hispmv_spmm_value_grad_device accepts the (loaded) handle, VL of the first tile, vector tiles, launches of a call with
@@ -503,8 +503,9 @@ int hispmv_prep_spmm_tiles(int64_t cols, int64_t num_vecs, int64_t ld, int64_t a
  *  - ACCEPTED, refused, and every error with its code and order: as hispmv_spmm_device / hispmv_spmm_device_t.  All before any launch.
  *  - WORKSPACE: the bytes hispmv_spmm_bf16_info reports: the fp32 partial sums of hispmv_spmm_device for tiles of 64 * VB vectors, and
  *    for a handle of more than one part the tile accumulator behind them.  The caller's; nothing is kept in the handle.
- * Out of scope: bf16 activations for the value gradients, hispmv_linear_device* and the one-vector entries; tile-stream and dense
- * handles; wide calls inside hispmv_spmv_device_batch or the step kernel; sharding over devices. */
+ * Out of scope: bf16 activations for hispmv_value_grad_device (the wide-batch value gradient takes them: hispmv_spmm_value_grad_device_bf16
+ * below), hispmv_linear_device* and the one-vector entries; tile-stream and dense handles; wide calls inside hispmv_spmv_device_batch or
+ * the step kernel; sharding over devices. */
 int hispmv_spmm_device_bf16(hispmv_ctx* ctx, int matrix_idx, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias,
                             int64_t bias_stride, uint16_t* d_yt, int64_t ld_y, float alpha, float beta, void* d_work, int64_t work_bytes, void* stream);
 int hispmv_spmm_device_t_bf16(hispmv_ctx* ctx, int matrix_idx, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias,
@@ -518,6 +519,28 @@ int hispmv_spmm_bf16_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vec
  *   (the bound of hispmv_prep_spmm_tiles in bytes, reused unmeasured);   (c) ld % VB == 0 and align_bytes % (2 * VB) == 0;
  * otherwise VB = 1.  out = {VB of the first tile, tiles, vectors in the last tile, VB of the last tile}.  Errors as hispmv_prep_spmm_tiles. */
 int hispmv_prep_spmm_bf16_tiles(int64_t cols, int64_t num_vecs, int64_t ld, int64_t align_bytes, int64_t out[4]);
+/* ---- wide-batch value gradient with bf16 activations -----------------------------------------------------------------------------
+ *   grad[k] = alpha * sum_{v < num_vecs} gyt[row_k, v] * xt[col_k, v] + beta * grad[k]
+ * hispmv_spmm_value_grad_device with 2-byte operands: d_gyt [rows, ld_gy] and d_xt [cols, ld_x] hold bfloat16 (uint16_t: the upper half
+ * of the fp32); d_grad, alpha and beta are fp32 and every other argument means what it means there.  A lane owns VB = 8, 4, 2 or 1
+ * consecutive vectors (one dwordx4, dwordx2, dword or 16-bit load per stored element and per row of gyt): a tile is 64 * VB vectors, up
+ * to 512.  The pad halves num_vecs .. ld - 1 of a row are never used (they may hold NaN).  Asynchronous on `stream`.
+ *  - TILES: the rule of hispmv_prep_spmm_bf16_tiles with ld_x, ld_gy and align_bytes the smaller alignment of d_gyt and d_xt (its 8 MiB
+ *    bound is reused, unmeasured for this kernel); the first tile stores alpha * s + beta * grad, every later one grad + alpha * s.
+ *    Inside a tile the parts of the handle run one after the other.  No workspace, no second launch, no atomics, nothing kept in the handle.
+ *  - BITS: widening a bf16 is exact.  The sum s of an entry over one tile: the VB products of a lane ascending from +0, every product and
+ *    add unfused, the product of a vector >= num_vecs replaced by +0; then the pairwise tree over the 64 lanes.  Where a tile has
+ *    VB <= 4 and the same boundaries as a tile of hispmv_spmm_value_grad_device, its bits are those of that entry on the widened operands.
+ *    Two identical calls give identical bits.
+ *  - ALIGNMENT: d_gyt and d_xt 2 bytes at least, d_grad 4 bytes.  Less than 16 bytes may take a smaller VB.
+ *  - ACCEPTED, refused, and every error with its code and order: as hispmv_spmm_value_grad_device.  alpha == 0: exactly beta * grad,
+ *    the operands not read; a handle without entries: HISPMV_OK without a launch.
+ * Out of scope: bf16 operands for hispmv_value_grad_device, a bf16 d_grad, tile-stream and dense handles. */
+int hispmv_spmm_value_grad_device_bf16(hispmv_ctx* ctx, int matrix_idx, const uint16_t* d_gyt, int64_t ld_gy, const uint16_t* d_xt, int64_t ld_x,
+                                       int64_t num_vecs, float* d_grad, float alpha, float beta, void* stream);
+/* hispmv_spmm_value_grad_info for the bf16 entry: out = {accepted, VB of the first tile, vector tiles, launches = tiles * parts that hold
+ * slices (0 for a handle without entries)} for ld_gy = ld_x = ld and 16-byte aligned pointers.  Errors as hispmv_spmm_value_grad_info. */
+int hispmv_spmm_value_grad_bf16_info(const hispmv_ctx* ctx, int matrix_idx, int64_t num_vecs, int64_t ld, int64_t out[4]);
 
 /* Time `reps` back-to-back launches of matrix_idx on the context stream with HIP events
  * (kernel-only, the reference's convention: spmv-helper.cpp:1030-1035).  Returns ms per launch. */

@@ -15,6 +15,17 @@ streams (HISPMV_FORMAT=slices).
 and one JSON line, and writes the line to --out.
 
     python tools/spmm_value_grad_bench.py [--rounds 5] [--reps 10] [--vecs 16,32,64,128,256] [--out profiles/spmm_value_grad_bench.json]
+
+--bf16-activations measures the entry with bf16 operands instead, same layers and method, --vecs 16,32,64,128,256,512,1024 by default:
+  (w)   spmm_value_grad_device        on the widened fp32 feature-major operands, ld = B rounded up to 4 -- the yardstick: code the bf16
+                                      entry does not touch
+  (wb)  spmm_value_grad_device_bf16   on the bf16 feature-major operands, ld = B rounded up to 8
+  (wb4) the same with both operands moved by 8 bytes: alignment 8 caps the lanes at VB 4, so where (wb) runs one VB 8 tile this runs two
+        VB 4 tiles on the same data
+  (c)   the two torch copies that sparse_linear(wide_grad="bf16") saves: gy, x bf16 [B, n] -> fp32 feature-major [n, ld]
+`max_rel_diff` is then (wb) against (w) on all entries.
+
+    python tools/spmm_value_grad_bench.py --bf16-activations [--out profiles/spmm_value_grad_bf16_bench.json]
 """
 from __future__ import annotations
 
@@ -95,14 +106,75 @@ def measure(torch, h, name, idx, r, c, B, rounds, reps):
                 range_us={k: [float(min(v)), float(max(v))] for k, v in t.items()}, max_rel_diff=diff, max_rel_diff_torch=diff_torch)
 
 
+def measure_bf16(torch, h, name, idx, B, rounds, reps):
+    dev = torch.device("cuda", 0)
+    info = h.matrix_info(idx)
+    rows, cols, n = info["rows"], info["cols"], h.value_update_info(idx)["n"]
+    ld4, ld8 = (B + 3) & ~3, (B + 7) & ~7
+    wi, bi = h.spmm_value_grad_info(idx, B, ld4), h.spmm_value_grad_bf16_info(idx, B, ld8)
+    assert wi["accepted"] and bi["accepted"], (name, wi, bi)
+    stream = torch.cuda.Stream(device=dev)
+    s = stream.cuda_stream
+
+    def feature_major(a, ld, dtype, lead=0):
+        """[B, n] -> [n, ld] of dtype behind `lead` elements, pad columns zero"""
+        flat = torch.zeros(lead + a.shape[1] * ld, dtype=dtype, device=dev)
+        at = flat[lead:].view(a.shape[1], ld)
+        at[:, :B] = a.t()
+        return flat, at
+
+    with torch.cuda.stream(stream):
+        x = (torch.rand((B, cols), dtype=torch.float32, device=dev) - 0.3).to(torch.bfloat16)
+        gy = (torch.rand((B, rows), dtype=torch.float32, device=dev) - 0.5).to(torch.bfloat16)
+        _, xt32 = feature_major(x, ld4, torch.float32)
+        _, gt32 = feature_major(gy, ld4, torch.float32)
+        _, xt16 = feature_major(x, ld8, torch.bfloat16)
+        _, gt16 = feature_major(gy, ld8, torch.bfloat16)
+        xo, xt16o = feature_major(x, ld8, torch.bfloat16, lead=4)
+        go, gt16o = feature_major(gy, ld8, torch.bfloat16, lead=4)
+        assert xt16.data_ptr() % 16 == 0 and gt16.data_ptr() % 16 == 0 and xt16o.data_ptr() % 16 == 8 and gt16o.data_ptr() % 16 == 8
+        grad_w = torch.empty(n, dtype=torch.float32, device=dev)
+        grad_b = torch.empty(n, dtype=torch.float32, device=dev)
+        grad_o = torch.empty(n, dtype=torch.float32, device=dev)
+    keep = {}
+
+    def copies():
+        keep["c"] = (feature_major(gy, ld4, torch.float32), feature_major(x, ld4, torch.float32))
+
+    calls = dict(w=lambda: h.spmm_value_grad_device(idx, gt32.data_ptr(), xt32.data_ptr(), B, grad_w.data_ptr(), 1.0, 0.0, ld_gy=ld4, ld_x=ld4, stream=s),
+                 wb=lambda: h.spmm_value_grad_device_bf16(idx, gt16.data_ptr(), xt16.data_ptr(), B, grad_b.data_ptr(), 1.0, 0.0, ld_gy=ld8, ld_x=ld8, stream=s),
+                 wb4=lambda: h.spmm_value_grad_device_bf16(idx, gt16o.data_ptr(), xt16o.data_ptr(), B, grad_o.data_ptr(), 1.0, 0.0, ld_gy=ld8, ld_x=ld8, stream=s),
+                 c=copies)
+    torch.cuda.synchronize()
+    t = {k: [] for k in calls}
+    with torch.cuda.stream(stream):
+        for f in calls.values():
+            time_calls(torch, stream, f, 3)
+        for _ in range(rounds):
+            for k, f in calls.items():
+                t[k].append(time_calls(torch, stream, f, reps))
+    torch.cuda.synchronize()
+    scale = grad_w.abs().max().clamp_min(1e-30)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    rel = {k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()}
+    from hispmv_amd import prep
+    return dict(name=name, rows=rows, cols=cols, nnz=info["nnz"], B=B, ld_fp32=ld4, ld_bf16=ld8, block_threads=info["block_threads"], lds_bytes=info["lds_bytes"],
+                parts=info["col_tiles"], fp32_info=wi, bf16_info=bi, bf16_tiles_align8=prep.spmm_bf16_tiles(cols, B, ld8, 8),
+                wide_us=med["w"], wide_bf16_us=med["wb"], wide_bf16_align8_us=med["wb4"], copies_us=med["c"],
+                wb_over_w=med["wb"] / med["w"], wb_over_wb4=med["wb"] / med["wb4"], wb_over_w_plus_c=med["wb"] / (med["w"] + med["c"]),
+                spread=max(rel.values()), spread_of=rel, range_us={k: [float(min(v)), float(max(v))] for k, v in t.items()},
+                max_rel_diff=float((grad_b - grad_w).abs().max() / scale), max_rel_diff_align8=float((grad_o - grad_w).abs().max() / scale))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--vecs", default="16,32,64,128,256")
+    ap.add_argument("--vecs", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--bf16-activations", action="store_true", help="measure spmm_value_grad_device_bf16 against the fp32 entry on the widened operands")
     a = ap.parse_args()
-    vecs = [int(v) for v in a.vecs.split(",")]
+    vecs = [int(v) for v in (a.vecs or ("16,32,64,128,256,512,1024" if a.bf16_activations else "16,32,64,128,256")).split(",")]
     os.environ["HISPMV_FORMAT"] = "slices"          # read when the context is created: the handles stay slice streams
     import torch
     import pyhispmv
@@ -131,11 +203,27 @@ def main() -> None:
         h.load_matrices()
         out = []
         for name, i, (r, c, _v) in todo:
+            if a.bf16_activations:
+                out += [measure_bf16(torch, h, name, i, B, a.rounds, a.reps) for B in vecs]
+                continue
             dr, dc = torch.from_numpy(r.astype(np.int64)).to(dev), torch.from_numpy(c.astype(np.int64)).to(dev)
             out += [measure(torch, h, name, i, dr, dc, B, a.rounds, a.reps) for B in vecs]
             del dr, dc
     finally:
         h.close()
+    if a.bf16_activations:
+        print(f"{'layer':44s} {'B':>4s} {'VL':>2s} {'tiles':>5s} {'VB':>2s} {'tiles':>5s} {'(w) us':>9s} {'(wb) us':>9s} {'(wb4) us':>9s} {'(c) us':>9s} {'wb/w':>5s} {'wb/wb4':>6s} "
+              f"{'wb/(w+c)':>8s} {'spread':>6s} {'diff':>8s}")
+        for q in out:
+            wi, bi = q["fp32_info"], q["bf16_info"]
+            print(f"{q['name'][:44]:44s} {q['B']:4d} {wi['vl']:2d} {wi['tiles']:5d} {bi['vb']:2d} {bi['tiles']:5d} {q['wide_us']:9.1f} {q['wide_bf16_us']:9.1f} "
+                  f"{q['wide_bf16_align8_us']:9.1f} {q['copies_us']:9.1f} {q['wb_over_w']:5.2f} {q['wb_over_wb4']:6.2f} {q['wb_over_w_plus_c']:8.2f} {q['spread']:6.2f} {q['max_rel_diff']:8.1e}")
+        line = json.dumps({"spmm_value_grad_bf16_bench": out, "rounds": a.rounds, "reps": a.reps, "device": torch.cuda.get_device_name(0)})
+        print(line)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(a.out).write_text(line + "\n")
+        return
     print(f"{'layer':44s} {'B':>3s} {'VL':>2s} {'tiles':>5s} {'(w) us':>9s} {'(w+) us':>9s} {'(g) us':>9s} {'(f) us':>9s} {'(t) us':>9s} {'w/g':>5s} {'w/f':>5s} {'t/w':>5s} "
           f"{'t/w+':>5s} {'spread':>6s} {'diff':>8s}")
     for q in out:
