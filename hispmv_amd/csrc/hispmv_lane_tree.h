@@ -1,6 +1,5 @@
-// hispmv_lane_tree.h -- the sum over the 64 lanes of a wavefront, 64 elements at a time: what the two wide-batch value-gradient kernel
-// files (hispmv_spmm_grad.hip: fp32 operands, hispmv_spmm_grad_bf16.hip: bf16 operands) share beyond hispmv_slice_walk.h.  Device code
-// only; include it behind hispmv_slice_walk.h (f2i, i2f).
+// hispmv_lane_tree.h -- the sum over the 64 lanes of a wavefront, 64 elements at a time, of the wide-batch value-gradient kernels
+// (hispmv_spmm_grad.hip, fp32 and bf16 operands alike).  Device code only; include it behind hispmv_slice_walk.h (f2i, i2f).
 #pragma once
 #include <hip/hip_runtime.h>
 

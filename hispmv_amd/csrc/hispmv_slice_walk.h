@@ -1,9 +1,9 @@
 // hispmv_slice_walk.h -- what the satellite kernel files share: hispmv_transpose.hip, hispmv_value_grad.hip, hispmv_tts_transpose.hip,
-// hispmv_spmm.hip, hispmv_spmm_grad.hip and (written on it from the start) hispmv_spmm_bf16.hip, and nobody else.
+// hispmv_spmm.hip and hispmv_spmm_grad.hip (the last two through hispmv_wide_lanes.h as well, which sits on this file), and nobody else.
 // The bit and load helpers, the slice of a stream as it arrives and its
 // decode, the walk of a wavefront over the slices of its group (GroupWalk, local_rows, the column-number window), and the few host
 // helpers of their launches (the LDS limit, the geometry checks, the (USE_LDS, STRAYS, HALF) choice).  A change of the slice format is
-// made here once for all of them.  (What stays written out in the first five files, and why: DESIGN.md 2.14.)
+// made here once for all of them.  (What stays written out in the five files, and why: DESIGN.md 2.14.)
 //
 // hispmv_kernels.hip does NOT include this file and keeps its own text of all of it: a shared body function has cost the step kernel
 // registers before, and nothing in here may move a forward kernel's instructions.  Everything sits in an unnamed namespace:

@@ -2,13 +2,11 @@
 // hispmv_spmm_info, hispmv_prep_spmm_tiles, hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_info, and the bf16-activation forms
 // hispmv_spmm_device_bf16, hispmv_spmm_device_t_bf16, hispmv_spmm_bf16_info, hispmv_prep_spmm_bf16_tiles,
 // hispmv_spmm_value_grad_device_bf16, hispmv_spmm_value_grad_bf16_info) over the launchers of
-// hispmv_spmm.h, hispmv_spmm_bf16.h, hispmv_spmm_grad.h and hispmv_spmm_grad_bf16.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
+// hispmv_spmm.h and hispmv_spmm_grad.h.  A translation unit of its own: the entries read a loaded handle's device tables and keep
 // nothing in it, so the other entry points are not touched.
 #include "hispmv_ctx.h"
 #include "hispmv_spmm.h"
-#include "hispmv_spmm_bf16.h"
 #include "hispmv_spmm_grad.h"
-#include "hispmv_spmm_grad_bf16.h"
 
 using namespace hispmv;
 
@@ -129,7 +127,7 @@ int run_spmm(hispmv_ctx* c, const Matrix& t, const char* who, const float* d_xt,
     return HISPMV_OK;
 }
 
-// run_spmm for 2-byte operands (kernels: hispmv_spmm_bf16.hip): the same tiles-then-parts order of launches.  More than one part:
+// run_spmm for 2-byte operands (the same kernels over uint16_t): the same tiles-then-parts order of launches.  More than one part:
 // every part but the last stores fp32 into the tile accumulator (part 0 with the caller's beta * bias, a later one adding in place),
 // the last reads it as its bias and is the only one that rounds and stores to yt.
 int run_spmm_bf16(hispmv_ctx* c, const Matrix& t, const char* who, const uint16_t* d_xt, int64_t num_vecs, int64_t ld_x, const void* d_bias,
@@ -241,7 +239,7 @@ HISPMV_API int hispmv_spmm_device_t_bf16(hispmv_ctx* c, int idx, const uint16_t*
 }
 
 // ---- wide-batch value gradient (include/hispmv.h: hispmv_spmm_value_grad_device, hispmv_spmm_value_grad_device_bf16; kernels:
-// hispmv_spmm_grad.hip, hispmv_spmm_grad_bf16.hip) ------------------------------------------------------------------------------------
+// hispmv_spmm_grad.hip) ---------------------------------------------------------------------------------------------------------------
 namespace {
 
 // launches of one vector tile: one per part that holds slices (none for a handle without entries)

@@ -1,21 +1,27 @@
 // hispmv_spmm_grad.hip -- the kernels of the wide-batch value gradient (hispmv_spmm_grad.h): grad[k] = alpha * sum_v gyt[row_k, v] *
-// xt[col_k, v] + beta * grad[k] on the slice stream of a loaded, updatable handle, operands feature-major.  What it needs of the slice
-// format (the meta request, decode_metas, store_grad, the launch checks) it shares with the other satellite
-// files: hispmv_slice_walk.h; the sum over the lanes it shares with hispmv_spmm_grad_bf16.hip: hispmv_lane_tree.h.  hispmv_kernels.hip takes no part in that and keeps its own text, so that no forward kernel is touched from here.
+// xt[col_k, v] + beta * grad[k] on the slice stream of a loaded, updatable handle, operands feature-major, fp32 or bf16: one text over
+// the activation type T.  What it needs of the slice format (the meta request, decode_metas, store_grad, the launch checks) it shares
+// with the other satellite files: hispmv_slice_walk.h; a lane's elements as they are loaded and widened: hispmv_wide_lanes.h; the sum
+// over the lanes: hispmv_lane_tree.h.  hispmv_kernels.hip takes no part in that and keeps its own text, so that no forward kernel is
+// touched from here.
 //
 // Roles, against the wide-batch product (hispmv_spmm.hip: spmm_group) and the value gradient of 4 vectors (hispmv_value_grad.hip):
 //   wide-batch product                          value gradient (4-2-1)                     wide-batch value gradient
-//   a lane owns VL vectors                      a lane owns 16 elements of the slice       a lane owns VL vectors
+//   a lane owns V vectors                       a lane owns 16 elements of the slice       a lane owns V vectors
 //   values and metas of a slice                 the metas only                             the metas only
 //   window words hold COLUMN NUMBERS            x window staged per vector                 window words hold column numbers
-//   a lane sums a row sequentially              16 products per lane, summed over vectors  VL products per lane and element, then the sum
+//   a lane sums a row sequentially              16 products per lane, summed over vectors  V products per lane and element, then the sum
 //                                                                                          over the 64 lanes: a butterfly over 64 elements
 //   carry + fix-up launch for cut rows          none                                       none: every element is independent
 // An explicit zero of the input has a map word like every other entry and gets its gradient; a slot whose map word is 0 (fillers,
 // row extensions, padding) writes nothing.
+// A lane owns V = 4, 2 or 1 floats, or 8, 4, 2 or 1 bf16, of a row: one dwordx4, dwordx2, dword or 16-bit load per element for xt and per
+// row for gyt.  bf16: the gathered halves and the row of gyt requested one row end ahead stay PACKED (V / 2 dwords) until they are used;
+// they are widened exactly (bits << 16, bits & 0xffff0000) in front of the products.
 #include <hip/hip_runtime.h>
 
 #include "hispmv_slice_walk.h"
+#include "hispmv_wide_lanes.h"
 #include "hispmv_lane_tree.h"
 #include "hispmv_spmm_grad.h"
 #include "hispmv_update.h"
@@ -26,12 +32,15 @@ namespace {
 
 // The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
 // LDS: the forward launch's window of lds_floats words (the wavefronts' stray areas are its last words), holding column numbers.
-template <int VL, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
+template <class T, int V, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
 __device__ __forceinline__ void spmm_grad_group(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const int32_t* __restrict__ map,
-    const SpmmGradOperands& a, long long n_slices, int group_slices, int lds_floats, int cols, int rows, long long group, int4 g) {
+    const SpmmGradOperandsOf<T>& a, long long n_slices, int group_slices, int lds_floats, int cols, int rows, long long group, int4 g) {
     extern __shared__ unsigned colwin[];
     constexpr int kE = kSliceSteps * kLaneElems;
+    using Lanes = WideLanes<T, V>;
+    using Word = typename Lanes::Word;      // a lane's V elements as loaded: NP floats, or NP packed dwords
+    constexpr int NP = Lanes::NP;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
     // the forward kernel's walk; the first request leaves before the window is filled
     auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
@@ -48,19 +57,19 @@ __device__ __forceinline__ void spmm_grad_group(
     }
     if (USE_LDS) fill_column_window(colwin, frags, g, wk.in_lds, lds_floats, wk.win_floats, lane, wave, n_waves);
 
-    // A lane past the batch reads the floats of lane 0 (always inside the row).  keep[i]: the lane's vector i is below n_vecs; the
-    // PRODUCT of every other one is masked to +0, so that neither a pad float of gyt nor one of xt (NaN, say) gets into a sum.
-    const int lane_vec = a.tile0 + lane * VL;
-    const unsigned lane_bytes = lane_vec < a.n_vecs ? (unsigned)(lane * VL * 4) : 0u;      // (a uniform row address + these 32 bits: one scalar-base load)
-    const float* const xtile = a.xt + a.tile0;
-    const float* const gtile = a.gyt + a.tile0;
-    bool keep[VL];
+    // A lane past the batch reads the elements of lane 0 (always inside the row).  keep[i]: the lane's vector i is below n_vecs; the
+    // PRODUCT of every other one is masked to +0, so that neither a pad element of gyt nor one of xt (NaN, say) gets into a sum.
+    const int lane_vec = a.tile0 + lane * V;
+    const unsigned lane_bytes = lane_vec < a.n_vecs ? (unsigned)(lane * V * sizeof(T)) : 0u;      // (a uniform row address + these 32 bits: one scalar-base load)
+    const T* const xtile = a.xt + a.tile0;
+    const T* const gtile = a.gyt + a.tile0;
+    bool keep[V];
 #pragma unroll
-    for (int i = 0; i < VL; ++i) keep[i] = lane_vec + i < a.n_vecs;
-    // gyt[row, the lane's vectors]; a row past the matrix (elements of padding behind the last row) reads row 0: its map word is 0
-    const auto load_gy = [&](float (&d)[VL], int row) {
+    for (int i = 0; i < V; ++i) keep[i] = lane_vec + i < a.n_vecs;
+    // gyt[row, the lane's vectors], as loaded; a row past the matrix (elements of padding behind the last row) reads row 0: its map word is 0
+    const auto load_gy = [&](Word (&d)[NP], int row) {
         const int rc = (row >= 0 && row < rows) ? row : 0;
-        load_vl<VL>((const float*)((const char*)(gtile + (size_t)rc * (size_t)a.ld_gy) + lane_bytes), d);
+        Lanes::load((const T*)((const char*)(gtile + (size_t)rc * (size_t)a.ld_gy) + lane_bytes), d);
     };
 
     while (wk.live()) {
@@ -68,8 +77,13 @@ __device__ __forceinline__ void spmm_grad_group(
         // passed so far in the slice, in stream order (the decode of value_grad_group)
         int row = __builtin_amdgcn_readfirstlane(h.x);
         const long long cur = wk.cur();
-        float gy[VL], gy_next[VL];      // of `row` and of row + 1, requested one row end ahead
-        load_gy(gy, row);
+        float gy[V];                    // of `row`, widened
+        Word gy_next[NP];               // of row + 1, requested one row end ahead, as loaded until it becomes gy
+        {
+            Word d[NP];
+            load_gy(d, row);
+            Lanes::widen(d, gy);
+        }
         load_gy(gy_next, row + 1);
         unsigned c[kE];
         decode_metas<COMPACT>(w, c);
@@ -83,31 +97,32 @@ __device__ __forceinline__ void spmm_grad_group(
                                                   [&](unsigned col, int) { return col < (unsigned)cols; });
 
         // the 1024 elements in stream order: step j, lane L, element k.  The meta of an element is wave-uniform (readlane); every lane
-        // gathers its VL floats of that column's row of xt.  The gathers carry no branch: an element without a column reads row 0 of
+        // gathers its V elements of that column's row of xt.  The gathers carry no branch: an element without a column reads row 0 of
         // xt (its sum is dropped at the store: its map word is 0).
-        // NK elements per gather: the four of a lane, or -- VL 4, 16 bytes per lane and element -- its two halves one after the other
-        constexpr int NK = VL == 4 ? kLaneElems / 2 : kLaneElems;
-        struct Gathered { unsigned m[NK]; float x[NK][VL]; };
+        // NK elements per gather: the four of a lane, or -- 16 bytes per lane and element: VL 4, VB 8 -- its two halves one after the other
+        constexpr int NK = Lanes::kWholeLoad ? kLaneElems / 2 : kLaneElems;
+        struct Gathered { unsigned m[NK]; Word x[NK][NP]; };
         const auto gather = [&](Gathered& q, int j, int L, int k0) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 q.m[k] = (unsigned)__builtin_amdgcn_readlane((int)meta[4 * j + k0 + k], L);
-                load_vl<VL>((const float*)((const char*)(xtile + (size_t)(q.m[k] < kSkipMeta ? q.m[k] >> 1 : 0u) * (size_t)a.ld_x) + lane_bytes), q.x[k]);
+                Lanes::load((const T*)((const char*)(xtile + (size_t)(q.m[k] < kSkipMeta ? q.m[k] >> 1 : 0u) * (size_t)a.ld_x) + lane_bytes), q.x[k]);
             }
         };
         // -> the lane's partial of each of the four elements; behind a row end (wave-uniform) gyt of the next row
         const auto consume = [&](const Gathered& q, float (&p)[kLaneElems], int k0) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
+                float x[V];
+                Lanes::widen(q.x[k], x);
                 float s = 0.0f;
 #pragma unroll
-                for (int i = 0; i < VL; ++i) s = s + (keep[i] ? gy[i] * q.x[k][i] : 0.0f);
-                asm volatile("" : "+v"(s));      // the sum is formed HERE: left alone, hipcc sinks the products below the row-end branches and keeps every gathered float live
+                for (int i = 0; i < V; ++i) s = s + (keep[i] ? gy[i] * x[i] : 0.0f);
+                asm volatile("" : "+v"(s));      // the sum is formed HERE: left alone, hipcc sinks the products below the row-end branches and keeps every gathered element live
                 p[k0 + k] = s;
                 if (q.m[k] & 1u) {
                     row += 1;
-#pragma unroll
-                    for (int i = 0; i < VL; ++i) gy[i] = gy_next[i];
+                    Lanes::widen(gy_next, gy);
                     load_gy(gy_next, row + 1);
                 }
             }
@@ -129,7 +144,7 @@ __device__ __forceinline__ void spmm_grad_group(
                     request_metas<COMPACT, HALF>(w, wk.slice(), lane);
                 }
             }
-            if constexpr (VL < 4) {
+            if constexpr (NK == kLaneElems) {
                 Gathered qa, qb;
                 gather(qa, j, 0, 0);
 #pragma unroll 1
@@ -170,33 +185,33 @@ __device__ __forceinline__ void spmm_grad_group(
 }
 
 // HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
-template <int VL, bool USE_LDS, bool STRAYS, bool HALF>
+template <class T, int V, bool USE_LDS, bool STRAYS, bool HALF>
 __global__ __launch_bounds__(1024) void spmm_grad_slices_kernel(
     const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
-    const int32_t* __restrict__ map, SpmmGradOperands a, long long n_slices, int group_slices, int lds_floats, int cols, int rows) {
+    const int32_t* __restrict__ map, SpmmGradOperandsOf<T> a, long long n_slices, int group_slices, int lds_floats, int cols, int rows) {
     const long long group = (long long)blockIdx.x;
     if constexpr (USE_LDS) {
         const int4 g = load_int4(groups + group);
         const int gw = __builtin_amdgcn_readfirstlane(g.w);
         if constexpr (HALF) {
             if (gw & kGroupHalf) {
-                spmm_grad_group<VL, true, true, STRAYS, true>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+                spmm_grad_group<T, V, true, true, STRAYS, true>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
                 return;
             }
         }
         if (gw & kGroupCompact)
-            spmm_grad_group<VL, true, true, STRAYS, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+            spmm_grad_group<T, V, true, true, STRAYS, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
         else
-            spmm_grad_group<VL, true, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
+            spmm_grad_group<T, V, true, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, g);
     } else {
-        spmm_grad_group<VL, false, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, int4{0, 0, 0, 0});
+        spmm_grad_group<T, V, false, false, false, false>(words, hdr, frags, map, a, n_slices, group_slices, lds_floats, cols, rows, group, int4{0, 0, 0, 0});
     }
 }
 
-template <int VL>
-hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+template <class T, int V>
+hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const SpmmGradOperandsOf<T>& a, hipStream_t stream) {
     return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
-        constexpr auto kernel = spmm_grad_slices_kernel<VL, USE_LDS(), STRAYS(), HALF()>;
+        constexpr auto kernel = spmm_grad_slices_kernel<T, V, USE_LDS(), STRAYS(), HALF()>;
         const hipError_t e = raise_lds_limit<kernel>();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), (size_t)m.lds_floats * 4, stream, (const char*)m.words, m.hdr,
@@ -205,21 +220,37 @@ hipError_t launch_slices(const SpmvDeviceMatrix& m, const int32_t* map, const Sp
     });
 }
 
-}  // namespace
-
-hipError_t launch_spmm_grad_part(const SpmvDeviceMatrix& m, int vl, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+// The checks of either entry, then the kernel of lanes of v elements of T.
+template <class T>
+hipError_t launch_part(const SpmvDeviceMatrix& m, int v, const int32_t* map, const SpmmGradOperandsOf<T>& a, hipStream_t stream) {
     (void)hipGetLastError();
     if (m.n_slices <= 0 || m.n_groups <= 0 || a.n <= 0) return hipSuccess;
     if (!map) return hipErrorInvalidValue;
     if (!slice_geometry_ok(m, (size_t)m.lds_floats * 4)) return hipErrorInvalidValue;
     if (m.rows <= 0 || m.cols <= 0) return hipErrorInvalidValue;          // (rows 0 and columns 0 of gyt and xt are read for elements without a place)
     if (!a.gyt || !a.xt || !a.grad || a.n_vecs < 1 || a.tile0 < 0 || a.tile0 >= a.n_vecs || a.ld_x < a.n_vecs || a.ld_gy < a.n_vecs) return hipErrorInvalidValue;
-    switch (vl) {
-        case 4: return launch_slices<4>(m, map, a, stream);
-        case 2: return launch_slices<2>(m, map, a, stream);
-        case 1: return launch_slices<1>(m, map, a, stream);
-        default: return hipErrorInvalidValue;
+    if (v != 1 && v != 2 && v != 4 && (v != 8 || sizeof(T) != 2)) return hipErrorInvalidValue;
+    // A lane's v elements are one aligned load that ends inside the row: the tile rule's (c), checked where the loads are issued.  It
+    // refuses no call of the C ABI, fp32 or bf16: v comes from that rule with these leading dimensions and the smaller alignment of
+    // the two addresses, and tile0 is a sum of earlier tiles of 64 * v' vectors with v' a multiple of v ((a) only narrows as the batch runs out).
+    if (a.tile0 % v || a.ld_x % v || a.ld_gy % v || ((uintptr_t)a.gyt | (uintptr_t)a.xt) % (uintptr_t)(sizeof(T) * v)) return hipErrorInvalidValue;
+    switch (v) {
+        case 4: return launch_slices<T, 4>(m, map, a, stream);
+        case 2: return launch_slices<T, 2>(m, map, a, stream);
+        case 1: return launch_slices<T, 1>(m, map, a, stream);
+        default:
+            if constexpr (sizeof(T) == 2) return launch_slices<T, 8>(m, map, a, stream);
+            return hipErrorInvalidValue;
     }
+}
+
+}  // namespace
+
+hipError_t launch_spmm_grad_part(const SpmvDeviceMatrix& m, int vl, const int32_t* map, const SpmmGradOperands& a, hipStream_t stream) {
+    return launch_part<float>(m, vl, map, a, stream);
+}
+hipError_t launch_spmm_grad_bf16_part(const SpmvDeviceMatrix& m, int vb, const int32_t* map, const SpmmGradBf16Operands& a, hipStream_t stream) {
+    return launch_part<uint16_t>(m, vb, map, a, stream);
 }
 
 }  // namespace hispmv

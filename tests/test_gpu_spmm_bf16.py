@@ -1,4 +1,4 @@
-"""The wide-batch product with bf16 activations (hispmv_spmm_device_bf16; hispmv_spmm_bf16.hip) on loaded slice-stream handles, at the
+"""The wide-batch product with bf16 activations (hispmv_spmm_device_bf16; hispmv_spmm.hip) on loaded slice-stream handles, at the
 small shapes of tests/step_small_cases.py, one matrix per code path: no window (256 threads, the nnz = 0 matrix as well), a long chain
 (fix-up launch), a compact 256-thread window, wide groups, 1024 threads, stray slots, the two parts of a stray split and eight column
 parts (the fp32 tile accumulator), half groups; and, since those 1024-thread matrices are too wide for more than VB 2, the same plans

@@ -1,4 +1,4 @@
-"""The wide-batch value gradient with bf16 activations (hispmv_spmm_value_grad_device_bf16; hispmv_spmm_grad_bf16.hip) and
+"""The wide-batch value gradient with bf16 activations (hispmv_spmm_value_grad_device_bf16; hispmv_spmm_grad.hip) and
 sparse_linear(..., spmm=True, wide_grad="bf16"), at the small shapes of tests/step_small_cases.py with the plan classes, the Ctx and the
 helpers of tests/test_gpu_spmm_value_grad.py.
 

@@ -1,4 +1,4 @@
-"""The tile rule of the wide-batch product with bf16 activations (hispmv_prep_spmm_bf16_tiles; hispmv_spmm_bf16.h), host-only.
+"""The tile rule of the wide-batch product with bf16 activations (hispmv_prep_spmm_bf16_tiles; hispmv_spmm.h), host-only.
 
 Every tile takes the largest VB in {8, 4, 2} with (a) 64 * (VB / 2) < vectors left, (b) cols * 64 * VB * 2 <= 8 MiB, (c) ld % VB == 0 and
 align_bytes % (2 * VB) == 0, otherwise VB 1; a tile is 64 * VB vectors.  The library's answer is compared with the restatement below
