@@ -1,0 +1,74 @@
+"""Solves a generated symmetric positive definite system with CG and a generated least-squares problem with CGLS on loaded handles
+(hispmv_amd.solvers), and prints iterations and residuals next to the fp64 residuals computed on the host.
+
+    python examples/solve_check.py [--grid 64] [--rtol 1e-6]
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+
+def laplacian_coo(m):
+    """The 5-point Laplacian of an m x m grid as COO triplets."""
+    k = np.arange(m * m)
+    i, j = k // m, k % m
+    r, c, v = [k], [k], [np.full(m * m, 4.0)]
+    for ok, off in ((i > 0, -m), (i < m - 1, m), (j > 0, -1), (j < m - 1, 1)):
+        r.append(k[ok]); c.append(k[ok] + off); v.append(np.full(int(ok.sum()), -1.0))
+    return np.concatenate(r), np.concatenate(c), np.concatenate(v).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--rtol", type=float, default=1e-6)
+    args = ap.parse_args()
+    import torch
+    import pyhispmv
+    from hispmv_amd import solvers
+
+    rng = np.random.default_rng(0)
+    n = args.grid * args.grid
+    r, c, v = laplacian_coo(args.grid)
+    rows, cols, nnz = 3000, 1200, 40000
+    lr, lc = rng.integers(0, rows, nnz), rng.integers(0, cols, nnz)
+    lv = rng.uniform(-1, 1, nnz).astype(np.float32)
+
+    h = pyhispmv.FpgaHandle("solve.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
+    spd = h.create_sparse_handle(r, c, v, n, n)
+    h.set_transposable("companion")          # CGLS multiplies by A^T: a stored transpose keeps that product free of atomics
+    ls = h.create_sparse_handle(lr, lc, lv, rows, cols)
+    h.load_matrices()
+
+    dev = torch.device("cuda", 0)
+    b = rng.uniform(-1, 1, n).astype(np.float32)
+    x, info = solvers.cg(h, spd, torch.from_numpy(b).to(dev), rtol=args.rtol)
+    x64 = x.cpu().numpy().astype(np.float64)
+    Ax = np.bincount(r, weights=v.astype(np.float64) * x64[c], minlength=n)
+    true = np.linalg.norm(b - Ax) / np.linalg.norm(b)
+    print(f"CG    {n} x {n}: {info['status']}, {info['iterations']} iterations, {info['products']} products, "
+          f"recursive residual {info['relres']:.3e}, true {true:.3e}")
+    assert info["status"] == "CONVERGED" and true < 100 * args.rtol
+
+    b = rng.uniform(-1, 1, rows).astype(np.float32)
+    x, info = solvers.cgls(h, ls, torch.from_numpy(b).to(dev), rtol=args.rtol)
+    x64 = x.cpu().numpy().astype(np.float64)
+    res = b - np.bincount(lr, weights=lv.astype(np.float64) * x64[lc], minlength=rows)
+    atr = np.bincount(lc, weights=lv.astype(np.float64) * res[lr], minlength=cols)
+    atb = np.bincount(lc, weights=lv.astype(np.float64) * b.astype(np.float64)[lr], minlength=cols)
+    true = np.linalg.norm(atr) / np.linalg.norm(atb)
+    print(f"CGLS  {rows} x {cols}: {info['status']}, {info['iterations']} iterations, {info['products']} products, "
+          f"|A^T r| / |A^T b| recursive {info['relres']:.3e}, true {true:.3e}, |r| / |b| {np.linalg.norm(res) / np.linalg.norm(b):.3f}")
+    assert info["status"] == "CONVERGED" and true < 100 * args.rtol
+    h.close()
+    print("solve_check ok")
+
+
+if __name__ == "__main__":
+    main()

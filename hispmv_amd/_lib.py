@@ -35,6 +35,12 @@ HISPMV_TRANSPOSABLE_SLICES = 1
 HISPMV_TRANSPOSABLE_KEEP_FORMAT = 2
 HISPMV_TRANSPOSABLE_COMPANION = 3
 
+HISPMV_KRYLOV_CG = 0
+HISPMV_KRYLOV_BICGSTAB = 1
+HISPMV_KRYLOV_CGLS = 2
+KRYLOV_SOLVERS = {"cg": HISPMV_KRYLOV_CG, "bicgstab": HISPMV_KRYLOV_BICGSTAB, "cgls": HISPMV_KRYLOV_CGLS}
+KRYLOV_STATUS = ("CONVERGED", "MAX_ITERS", "BREAKDOWN", "IN_FLIGHT")
+
 
 class MatrixInfo(C.Structure):
     _fields_ = [
@@ -48,6 +54,10 @@ class MatrixInfo(C.Structure):
         ("format", C.c_int32), ("tts_lines_per_gather", C.c_float), ("tile_kind", C.c_int32),
         ("batch_group_slices", C.c_int32),
     ]
+
+
+class KrylovResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("relres", C.c_double), ("products", C.c_int64)]
 
 
 _p = C.c_void_p
@@ -114,6 +124,13 @@ SIGNATURES = {
     "hispmv_spmm_value_grad_device_bf16": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int64, _p, C.c_float, C.c_float, _p]),
     "hispmv_spmm_value_grad_bf16_info": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, _i64p]),
     "hispmv_prep_spmm_tiles": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i64p]),
+    "hispmv_prep_krylov_groups": (C.c_int, [C.c_int64, _i64p]),
+    "hispmv_krylov_info": (C.c_int, [_p, C.c_int, C.c_int, _i64p]),
+    "hispmv_dot_device": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, C.c_int64, _p]),
+    "hispmv_cg_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
+    "hispmv_bicgstab_device": (C.c_int, [_p, C.c_int, _p, _p, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
+    "hispmv_cgls_device": (C.c_int, [_p, C.c_int, _p, _p, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
+    "hispmv_krylov_status": (C.c_int, [_p, _p, _p, C.POINTER(KrylovResult)]),
     "hispmv_prep_vector_widths": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),

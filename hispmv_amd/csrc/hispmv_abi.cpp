@@ -1088,7 +1088,7 @@ HISPMV_API int hispmv_set_transposable(hispmv_ctx* c, int enable) {
     return HISPMV_OK;
 }
 
-namespace {
+namespace hispmv {          // (declared in hispmv_ctx.h: hispmv_krylov_abi.cpp refuses what hispmv_spmv_device_t refuses)
 
 // A tile-stream handle the transposed and gradient entries accept (hispmv_tts_transpose.h): created in state _KEEP_FORMAT, one part,
 // stream words for every row -- the standard and the small geometry.
@@ -1110,6 +1110,10 @@ int refuse_tile_stream(hispmv_ctx* c, const Matrix& m, const char* who, const ch
                                        "; create it after hispmv_set_transposable(ctx, 1) (FpgaHandle.set_transposable(True)) so that it keeps the slice stream, or after "
                                        "hispmv_set_transposable(ctx, 2) (FpgaHandle.set_transposable(\"keep_format\")) so that the tile stream itself is accepted");
 }
+
+}  // namespace hispmv
+
+namespace {
 
 // ---- the stored transpose (include/hispmv.h: HISPMV_TRANSPOSABLE_COMPANION) ------------------------------------------------------------
 // The transposed entries of a handle that owns one run the FORWARD launches of `t` = *owner.companion (t.rows = owner.cols): no atomic,

@@ -310,6 +310,10 @@ template <class T> void host_free(T*& p) {
 }
 
 int check_device_error(hispmv_ctx* c);      // hispmv_abi.cpp
+// the transposed entries accept the (loaded) handle itself -- dense, a slice stream, a tile stream kept for them -- and, where they do
+// not, the HISPMV_ENOTSUP they answer with (hispmv_abi.cpp)
+bool transposable_handle(const Matrix& m);
+int refuse_tile_stream(hispmv_ctx* c, const Matrix& m, const char* who, const char* what);
 void free_batch_plans(hispmv_ctx* c);       // hispmv_batch.cpp
 int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float* const* d_x, const float* const* d_bias,
                       float* const* d_y, float alpha, float beta, hipStream_t s, bool companions = false);

@@ -1,0 +1,512 @@
+// hispmv_krylov.hip -- the vector kernels of the Krylov layer (hispmv_krylov.h; include/hispmv.h: hispmv_dot_device, hispmv_cg_device,
+// hispmv_bicgstab_device, hispmv_cgls_device).  Pure streams: a workgroup of 256 threads takes chunks of 1024 elements, chunk g, g + G,
+// ... ascending for workgroup g of G = krylov_groups(n); a thread owns 4 consecutive floats of a chunk (one 16-byte access where that
+// vector is 16-byte aligned and the chunk is whole, 4-byte accesses otherwise).  Vector arithmetic is fp32 and unfused
+// (-ffp-contract=off); every scalar is fp64, computed by every workgroup itself from the same partials, hence with the same bits, and
+// rounded once to fp32 before it meets a vector.  No atomics, no tickets: a dot product's partials are summed by the NEXT kernel.
+#include <hip/hip_runtime.h>
+
+#include "hispmv_krylov.h"
+
+namespace hispmv {
+namespace {
+
+// zero, infinite or NaN: no denominator
+__device__ __forceinline__ bool bad(double d) { return !(d != 0.0 && fabs(d) <= 1.7976931348623157e308); }
+__device__ __forceinline__ bool finite_d(double d) { return fabs(d) <= 1.7976931348623157e308; }
+
+// the vector at p is 16-byte aligned (i is a multiple of 4): decided per vector, so one 4-byte-aligned operand of the caller's does
+// not take the 16-byte accesses from the others of the pass
+__device__ __forceinline__ bool aligned16(const float* p) { return ((uintptr_t)p & 15) == 0; }
+// v[0 .. m) = p[i .. i + m), the rest +0
+__device__ __forceinline__ void ld4(const float* p, int64_t i, int m, float v[4]) {
+    if (aligned16(p) && m == 4) {
+        const float4 f = *reinterpret_cast<const float4*>(p + i);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = j < m ? p[i + j] : 0.0f;
+}
+__device__ __forceinline__ void st4(float* p, int64_t i, int m, const float v[4]) {
+    if (aligned16(p) && m == 4) {
+        *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < m) p[i + j] = v[j];
+}
+// the 4 products of a thread, exact in fp64, summed ascending from +0
+__device__ __forceinline__ double dot4(const float a[4], const float b[4], int m) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < m) s += (double)a[j] * (double)b[j];
+    return s;
+}
+
+// The pairwise tree over the 256 threads: v[t] += v[t + 128], then + 64, 32, ... 1; every thread returns v[0].
+__device__ double block_sum(double v, double* sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    if (t < 128) sh[t] += sh[t + 128];
+    __syncthreads();
+    if (t < 64) {
+        double w = sh[t] + sh[t + 64];
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) w += __shfl_down(w, s, 64);
+        if (t == 0) sh[0] = w;
+    }
+    __syncthreads();
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+// The sum of `groups` <= 1024 partials: thread t adds part[4t .. 4t + 3] ascending from +0, then the tree.
+__device__ double sum_partials(const double* part, int64_t groups, double* sh) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = 4 * (int64_t)threadIdx.x + j;
+        if (i < groups) s += part[i];
+    }
+    return block_sum(s, sh);
+}
+__device__ __forceinline__ const double* slot_of(const KrylovStep& k, int slot) { return k.parts + (int64_t)slot * kKrylovMaxGroups; }
+__device__ __forceinline__ double* slot_out(const KrylovStep& k, int slot) { return k.parts + (int64_t)slot * kKrylovMaxGroups; }
+__device__ __forceinline__ int64_t groups_of(int64_t n) {
+    const int64_t c = (n + kKrylovChunk - 1) / kKrylovChunk;
+    return c < kKrylovMaxGroups ? c : kKrylovMaxGroups;
+}
+__device__ __forceinline__ void load_state(const double* s_in, double S[kKrylovState]) {
+#pragma unroll
+    for (int i = 0; i < kKrylovState; ++i) S[i] = s_in[i];
+}
+__device__ __forceinline__ void store_state(double* s_out, const double S[kKrylovState]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kKrylovState; ++i) s_out[i] = S[i];
+    }
+}
+__device__ __forceinline__ bool frozen(const double S[kKrylovState]) { return S[kKsDone] != 0.0 || S[kKsBreakdown] != 0.0; }
+
+// f(i, m) for every chunk of this workgroup, ascending: i = the thread's first element, m = how many of its 4 lie below n
+template <class F>
+__device__ __forceinline__ void for_chunks(int64_t n, F&& f) {
+    const int64_t chunks = (n + kKrylovChunk - 1) / kKrylovChunk;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t i = c * kKrylovChunk + 4 * (int64_t)threadIdx.x;
+        const int64_t left = n - i;
+        f(i, left >= 4 ? 4 : left > 0 ? (int)left : 0);
+    }
+}
+
+__global__ __launch_bounds__(kKrylovThreads) void krylov_dot_kernel(const float* a, const float* b, int64_t n, double* part) {
+    __shared__ double sh[kKrylovThreads];
+    double acc = 0.0;
+    for_chunks(n, [&](int64_t i, int m) {
+        float va[4], vb[4];
+        ld4(a, i, m, va);
+        ld4(b, i, m, vb);
+        acc += dot4(va, vb, m);
+    });
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kKrylovThreads) void krylov_dot_finish_kernel(const double* part, int64_t groups, double* out) {
+    __shared__ double sh[kKrylovThreads];
+    const double s = sum_partials(part, groups, sh);
+    if (threadIdx.x == 0) out[0] = s;
+}
+
+// The first kernel of a solve, behind the products that give src (the residual; CGLS: A^T of it): the scalar block from nothing.
+__global__ __launch_bounds__(kKrylovThreads) void krylov_init_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+#pragma unroll
+    for (int i = 0; i < kKrylovState; ++i) S[i] = 0.0;
+    const double b2 = sum_partials(slot_of(k, kSlotB2), groups_of(k.n2), sh);
+    const double bb = k.slot_bb == kSlotB2 ? b2 : sum_partials(slot_of(k, k.slot_bb), groups_of(k.n), sh);
+    S[kKsB2] = b2; S[kKsBb] = bb; S[kKsProducts] = k.products; S[kKsAlpha] = 1.0; S[kKsOmega] = 1.0;
+    const bool zero_x = b2 == 0.0;
+    if (zero_x) S[kKsDone] = 1.0;
+    else if (bad(bb) || !finite_d(b2)) S[kKsBreakdown] = 1.0;
+    store_state(k.s_out, S);
+    double acc_rr = 0.0, acc_rz = 0.0;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float r[4], z[4];
+        ld4(k.r, i, m, r);
+        if (k.minv) {
+            float d[4];
+            ld4(k.minv, i, m, d);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = d[j] * r[j];
+            acc_rz += dot4(r, z, m);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = r[j];
+        }
+        acc_rr += dot4(r, r, m);
+        st4(k.p, i, m, z);
+        if (k.rhat) st4(k.rhat, i, m, r);
+        if (zero_x) {
+            const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            st4(k.x, i, m, zero);
+        }
+    });
+    const double rr = block_sum(acc_rr, sh);
+    if (threadIdx.x == 0) slot_out(k, kSlotRr)[blockIdx.x] = rr;
+    if (k.minv) {
+        const double rz = block_sum(acc_rz, sh);
+        if (threadIdx.x == 0) slot_out(k, kSlotRho)[blockIdx.x] = rz;
+    }
+}
+
+// The dot pass behind a product.  first: rr and rho of the initial residual still lie in their partials (over n2 elements); they are
+// summed here and the stopping rule sees the initial residual.
+__global__ __launch_bounds__(kKrylovThreads) void krylov_step_dot_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    if (k.first && !frozen(S)) {
+        const double rr = sum_partials(slot_of(k, kSlotRr), groups_of(k.n2), sh);
+        const double rho = k.slot_rho == kSlotRr ? rr : sum_partials(slot_of(k, k.slot_rho), groups_of(k.n2), sh);
+        S[kKsRr] = rr; S[kKsRho] = rho;
+        if (rr <= k.tol2 * S[kKsBb]) S[kKsDone] = 1.0;
+    }
+    store_state(k.s_out, S);
+    double acc1 = 0.0, acc2 = 0.0;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float a[4], b[4];
+        ld4(k.a1, i, m, a);
+        ld4(k.b1, i, m, b);
+        acc1 += dot4(a, b, m);
+        if (k.a2) {
+            ld4(k.a2, i, m, a);
+            ld4(k.b2, i, m, b);
+            acc2 += dot4(a, b, m);
+        }
+    });
+    const double s1 = block_sum(acc1, sh);
+    if (threadIdx.x == 0) slot_out(k, k.slot1)[blockIdx.x] = s1;
+    if (k.a2) {
+        const double s2 = block_sum(acc2, sh);
+        if (threadIdx.x == 0) slot_out(k, k.slot2)[blockIdx.x] = s2;
+    }
+}
+
+// CG: alpha = rho / (p, q); x += alpha p; r -= alpha q; the partials of (r, r) and, with minv, of (r, minv r)
+__global__ __launch_bounds__(kKrylovThreads) void krylov_cg_update_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    bool act = false;
+    float a32 = 0.0f;
+    if (!frozen(S)) {
+        const double den = sum_partials(slot_of(k, kSlotDen), groups_of(k.n), sh);
+        S[kKsDen] = den;
+        if (bad(den) || !finite_d(S[kKsRho])) S[kKsBreakdown] = 1.0;
+        else {
+            const double alpha = S[kKsRho] / den;
+            S[kKsAlpha] = alpha; S[kKsIters] += 1.0;
+            a32 = (float)alpha;
+            act = true;
+        }
+    }
+    store_state(k.s_out, S);
+    if (!act) return;
+    double acc_rr = 0.0, acc_rz = 0.0;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float x[4], p[4], r[4], q[4];
+        ld4(k.x, i, m, x);
+        ld4(k.p, i, m, p);
+        ld4(k.r, i, m, r);
+        ld4(k.q, i, m, q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ap = a32 * p[j];
+            x[j] = x[j] + ap;
+            const float aq = a32 * q[j];
+            r[j] = r[j] - aq;
+        }
+        st4(k.x, i, m, x);
+        st4(k.r, i, m, r);
+        acc_rr += dot4(r, r, m);
+        if (k.minv) {
+            float d[4], z[4];
+            ld4(k.minv, i, m, d);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = d[j] * r[j];
+            acc_rz += dot4(r, z, m);
+        }
+    });
+    const double rr = block_sum(acc_rr, sh);
+    if (threadIdx.x == 0) slot_out(k, kSlotRr)[blockIdx.x] = rr;
+    if (k.minv) {
+        const double rz = block_sum(acc_rz, sh);
+        if (threadIdx.x == 0) slot_out(k, kSlotRho)[blockIdx.x] = rz;
+    }
+}
+
+// CG and CGLS: the stopping rule on the new rr, then beta = rho' / rho; p = z + beta p with z = minv r (or r; CGLS: s)
+__global__ __launch_bounds__(kKrylovThreads) void krylov_direction_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    bool act = false;
+    float b32 = 0.0f;
+    if (!frozen(S)) {
+        const double rr = sum_partials(slot_of(k, kSlotRr), groups_of(k.n), sh);
+        const double rho = k.slot_rho == kSlotRr ? rr : sum_partials(slot_of(k, k.slot_rho), groups_of(k.n), sh);
+        S[kKsRr] = rr;
+        if (rr <= k.tol2 * S[kKsBb]) { S[kKsDone] = 1.0; S[kKsRho] = rho; }
+        else if (bad(S[kKsRho]) || !finite_d(rho)) S[kKsBreakdown] = 1.0;
+        else {
+            b32 = (float)(rho / S[kKsRho]);
+            S[kKsRho] = rho;
+            act = true;
+        }
+    }
+    store_state(k.s_out, S);
+    if (!act) return;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float r[4], p[4];
+        ld4(k.r, i, m, r);
+        ld4(k.p, i, m, p);
+        if (k.minv) {
+            float d[4];
+            ld4(k.minv, i, m, d);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = d[j] * r[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float bp = b32 * p[j];
+            p[j] = r[j] + bp;
+        }
+        st4(k.p, i, m, p);
+    });
+}
+
+// CGLS: alpha = rho / (q, q); x += alpha p over n elements; r -= alpha q over n2
+__global__ __launch_bounds__(kKrylovThreads) void krylov_cgls_update_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    bool act = false;
+    float a32 = 0.0f;
+    if (!frozen(S)) {
+        const double den = sum_partials(slot_of(k, kSlotDen), groups_of(k.n2), sh);
+        S[kKsDen] = den;
+        if (bad(den) || !finite_d(S[kKsRho])) S[kKsBreakdown] = 1.0;
+        else {
+            const double alpha = S[kKsRho] / den;
+            S[kKsAlpha] = alpha; S[kKsIters] += 1.0;
+            a32 = (float)alpha;
+            act = true;
+        }
+    }
+    store_state(k.s_out, S);
+    if (!act) return;
+    const int64_t nmax = k.n > k.n2 ? k.n : k.n2;
+    for_chunks(nmax, [&](int64_t i, int) {
+        const int mx = k.n - i >= 4 ? 4 : k.n - i > 0 ? (int)(k.n - i) : 0;
+        const int mr = k.n2 - i >= 4 ? 4 : k.n2 - i > 0 ? (int)(k.n2 - i) : 0;
+        if (mx > 0) {
+            float x[4], p[4];
+            ld4(k.x, i, mx, x);
+            ld4(k.p, i, mx, p);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float ap = a32 * p[j];
+                x[j] = x[j] + ap;
+            }
+            st4(k.x, i, mx, x);
+        }
+        if (mr > 0) {
+            float r[4], q[4];
+            ld4(k.r, i, mr, r);
+            ld4(k.q, i, mr, q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float aq = a32 * q[j];
+                r[j] = r[j] - aq;
+            }
+            st4(k.r, i, mr, r);
+        }
+    });
+}
+
+// BiCGSTAB: alpha = rho / (rhat, v); s = r - alpha v, stored over r; the partials of (s, s)
+__global__ __launch_bounds__(kKrylovThreads) void krylov_bicg_s_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    bool act = false;
+    float a32 = 0.0f;
+    if (!frozen(S)) {
+        const double den = sum_partials(slot_of(k, kSlotDen), groups_of(k.n), sh);
+        S[kKsDen] = den;
+        if (bad(den) || bad(S[kKsRho])) S[kKsBreakdown] = 1.0;
+        else {
+            const double alpha = S[kKsRho] / den;
+            S[kKsAlpha] = alpha;
+            a32 = (float)alpha;
+            act = true;
+        }
+    }
+    store_state(k.s_out, S);
+    if (!act) return;
+    double acc = 0.0;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float r[4], v[4];
+        ld4(k.r, i, m, r);
+        ld4(k.q, i, m, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float av = a32 * v[j];
+            r[j] = r[j] - av;
+        }
+        st4(k.r, i, m, r);
+        acc += dot4(r, r, m);
+    });
+    const double ss = block_sum(acc, sh);
+    if (threadIdx.x == 0) slot_out(k, kSlotSs)[blockIdx.x] = ss;
+}
+
+// BiCGSTAB: (s, s) within the tolerance: x += alpha p and done.  Otherwise omega = (t, s) / (t, t); x += alpha p; x += omega s;
+// r = s - omega t; the partials of (r, r) and (rhat, r)
+__global__ __launch_bounds__(kKrylovThreads) void krylov_bicg_x_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    int act = 0;          // 1 the half step, 2 the whole
+    const float a32 = (float)S[kKsAlpha];
+    float w32 = 0.0f;
+    if (!frozen(S)) {
+        const int64_t g = groups_of(k.n);
+        const double ss = sum_partials(slot_of(k, kSlotSs), g, sh);
+        const double ts = sum_partials(slot_of(k, kSlotTs), g, sh);
+        const double tt = sum_partials(slot_of(k, kSlotTt), g, sh);
+        S[kKsTs] = ts; S[kKsTt] = tt;
+        if (ss <= k.tol2 * S[kKsBb]) {
+            S[kKsRr] = ss; S[kKsDone] = 1.0; S[kKsIters] += 1.0;
+            act = 1;
+        } else if (bad(tt) || bad(ts / tt)) S[kKsBreakdown] = 1.0;
+        else {
+            const double omega = ts / tt;
+            S[kKsOmega] = omega; S[kKsIters] += 1.0;
+            w32 = (float)omega;
+            act = 2;
+        }
+    }
+    store_state(k.s_out, S);
+    if (!act) return;
+    double acc_rr = 0.0, acc_rho = 0.0;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float x[4], p[4];
+        ld4(k.x, i, m, x);
+        ld4(k.p, i, m, p);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ap = a32 * p[j];
+            x[j] = x[j] + ap;
+        }
+        if (act == 2) {
+            float s[4], t[4], h[4];
+            ld4(k.r, i, m, s);
+            ld4(k.t, i, m, t);
+            ld4(k.rhat, i, m, h);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float ws = w32 * s[j];
+                x[j] = x[j] + ws;
+                const float wt = w32 * t[j];
+                s[j] = s[j] - wt;
+            }
+            st4(k.r, i, m, s);
+            acc_rr += dot4(s, s, m);
+            acc_rho += dot4(h, s, m);
+        }
+        st4(k.x, i, m, x);
+    });
+    if (act != 2) return;
+    const double rr = block_sum(acc_rr, sh);
+    if (threadIdx.x == 0) slot_out(k, kSlotRr)[blockIdx.x] = rr;
+    const double rho = block_sum(acc_rho, sh);
+    if (threadIdx.x == 0) slot_out(k, kSlotRho)[blockIdx.x] = rho;
+}
+
+// BiCGSTAB: the stopping rule on the new rr, then beta = (rho' / rho) (alpha / omega); p = r + beta (p - omega v)
+__global__ __launch_bounds__(kKrylovThreads) void krylov_bicg_p_kernel(KrylovStep k) {
+    __shared__ double sh[kKrylovThreads];
+    double S[kKrylovState];
+    load_state(k.s_in, S);
+    bool act = false;
+    float b32 = 0.0f;
+    const float w32 = (float)S[kKsOmega];
+    if (!frozen(S)) {
+        const int64_t g = groups_of(k.n);
+        const double rr = sum_partials(slot_of(k, kSlotRr), g, sh);
+        const double rho = sum_partials(slot_of(k, kSlotRho), g, sh);
+        S[kKsRr] = rr;
+        const double beta = (rho / S[kKsRho]) * (S[kKsAlpha] / S[kKsOmega]);
+        if (rr <= k.tol2 * S[kKsBb]) { S[kKsDone] = 1.0; S[kKsRho] = rho; }
+        else if (!finite_d(beta)) S[kKsBreakdown] = 1.0;
+        else {
+            b32 = (float)beta;
+            S[kKsRho] = rho;
+            act = true;
+        }
+    }
+    store_state(k.s_out, S);
+    if (!act) return;
+    for_chunks(k.n, [&](int64_t i, int m) {
+        float r[4], p[4], v[4];
+        ld4(k.r, i, m, r);
+        ld4(k.p, i, m, p);
+        ld4(k.q, i, m, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float wv = w32 * v[j];
+            const float d = p[j] - wv;
+            const float bd = b32 * d;
+            p[j] = r[j] + bd;
+        }
+        st4(k.p, i, m, p);
+    });
+}
+
+unsigned grid_of(int64_t n) {
+    const int64_t g = krylov_groups(n);
+    return (unsigned)(g > 0 ? g : 1);
+}
+}  // namespace
+
+hipError_t launch_krylov_dot(const float* a, const float* b, int64_t n, double* part, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(krylov_dot_kernel, dim3(grid_of(n)), dim3(kKrylovThreads), 0, s, a, b, n, part);
+    return hipGetLastError();
+}
+hipError_t launch_krylov_dot_finish(const double* part, int64_t groups, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(krylov_dot_finish_kernel, dim3(1), dim3(kKrylovThreads), 0, s, part, groups, out);
+    return hipGetLastError();
+}
+
+#define KRYLOV_LAUNCH(kernel, n_)                                                              \
+    hipLaunchKernelGGL(kernel, dim3(grid_of(n_)), dim3(kKrylovThreads), 0, s, k);                  \
+    return hipGetLastError();
+
+hipError_t launch_krylov_init(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_init_kernel, k.n) }
+hipError_t launch_krylov_step_dot(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_step_dot_kernel, k.n) }
+hipError_t launch_krylov_cg_update(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_cg_update_kernel, k.n) }
+hipError_t launch_krylov_direction(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_direction_kernel, k.n) }
+hipError_t launch_krylov_cgls_update(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_cgls_update_kernel, (k.n > k.n2 ? k.n : k.n2)) }
+hipError_t launch_krylov_bicg_s(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_bicg_s_kernel, k.n) }
+hipError_t launch_krylov_bicg_x(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_bicg_x_kernel, k.n) }
+hipError_t launch_krylov_bicg_p(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_bicg_p_kernel, k.n) }
+
+}  // namespace hispmv

@@ -416,6 +416,65 @@ class FpgaHandle:
             raise IndexError("Matrix idx out of range")
         return {"accepted": bool(out[0]), "vb": int(out[1]), "tiles": int(out[2]), "launches": int(out[3])}
 
+    # -- Krylov solvers (hispmv_krylov_abi.cpp; hispmv_amd.solvers wraps these for torch tensors) -----------------------------------
+    def krylov_info(self, matrix_idx: int, solver: str) -> dict:
+        """{"accepted", "work_bytes", "launches_per_iteration", "products_per_iteration", "products_t_per_iteration", "r_offset",
+        "x_len", "b_len"} of `solver` ("cg", "bicgstab", "cgls") on a handle (hispmv_krylov_info): the workspace a solve needs, the
+        vector kernels and the products of one iteration, where the workspace keeps the residual; zeros for a handle it refuses."""
+        if solver not in _lib.KRYLOV_SOLVERS:
+            raise ValueError('solver must be "cg", "bicgstab" or "cgls"')
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_krylov_info(self._ctx, int(matrix_idx), _lib.KRYLOV_SOLVERS[solver], out)
+        if rc != _lib.HISPMV_OK:
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "work_bytes": int(out[1]), "launches_per_iteration": int(out[2]), "products_per_iteration": int(out[3]),
+                "products_t_per_iteration": int(out[4]), "r_offset": int(out[5]), "x_len": int(out[6]), "b_len": int(out[7])}
+
+    @staticmethod
+    def _krylov_result(res) -> dict:
+        return {"status": _lib.KRYLOV_STATUS[res.status], "iterations": int(res.iterations), "relres": float(res.relres), "products": int(res.products)}
+
+    def dot_device(self, n: int, d_a: int, d_b: int, d_out: int, work: int, work_bytes: int, stream: int = 0) -> None:
+        """*d_out (a float64 in device memory) = sum a[i] * b[i] of two float32 device vectors, exact products summed in fp64 in an order
+        that depends on n alone (hispmv_dot_device; include/hispmv.h writes the order down).  Asynchronous on `stream`.  `work` points
+        at work_bytes >= 8 * prep.krylov_groups(n) bytes, 16-byte aligned; a and b need 4-byte alignment only."""
+        self._check(lib.hispmv_dot_device(self._ctx, int(n), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out), C.c_void_p(work), int(work_bytes),
+                                          C.c_void_p(stream)))
+
+    def cg_device(self, matrix_idx: int, d_b: int, d_x: int, d_minv: int = 0, rtol: float = 1e-6, max_iters: int = 1000, check_every: int = 8,
+                  work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """Preconditioned CG on device pointers (hispmv_cg_device): d_x holds the initial guess and then the solution, d_minv is 0 or
+        the inverse diagonal.  Returns {"status", "iterations", "relres", "products"}; with check_every = 0 the call returns at once
+        with status "IN_FLIGHT" and krylov_status reads the outcome.  A handle that is not square, a bad rtol / max_iters /
+        check_every or a short, missing or misaligned workspace raises ValueError, a call before load_matrices AssertionError."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_cg_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(d_minv), float(rtol), int(max_iters),
+                                         int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
+        return self._krylov_result(res)
+
+    def bicgstab_device(self, matrix_idx: int, d_b: int, d_x: int, rtol: float = 1e-6, max_iters: int = 1000, check_every: int = 8,
+                        work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """BiCGSTAB for a square handle, forward products only (hispmv_bicgstab_device); arguments, result and exceptions as cg_device."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_bicgstab_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), C.c_void_p(d_x), float(rtol), int(max_iters),
+                                               int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
+        return self._krylov_result(res)
+
+    def cgls_device(self, matrix_idx: int, d_b: int, d_x: int, rtol: float = 1e-6, max_iters: int = 1000, check_every: int = 8,
+                    work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """CGLS, min ||b - A x|| for any shape, one forward and one transposed product per iteration (hispmv_cgls_device).  A handle
+        spmv_device_t refuses raises its NotImplementedError before anything is launched; otherwise as cg_device."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_cgls_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), C.c_void_p(d_x), float(rtol), int(max_iters),
+                                           int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
+        return self._krylov_result(res)
+
+    def krylov_status(self, work: int, stream: int = 0) -> dict:
+        """Waits for `stream` and reads the outcome of the check_every = 0 solve that ran on it with workspace `work` (hispmv_krylov_status)."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_krylov_status(self._ctx, C.c_void_p(work), C.c_void_p(stream), C.byref(res)))
+        return self._krylov_result(res)
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

@@ -287,6 +287,15 @@ def spmm_bf16_tiles(cols: int, num_vecs: int, ld=None, align_bytes: int = 16) ->
     return {"vb": int(out[0]), "tiles": int(out[1]), "last_vecs": int(out[2]), "vb_last": int(out[3])}
 
 
+def krylov_groups(n: int) -> int:
+    """The workgroups of a pass of the Krylov layer over n elements, which are the fp64 partials of a dot product: chunks of 1024
+    elements, at most 1024 workgroups, workgroup g taking chunks g, g + groups, ...  The rule of hispmv_prep_krylov_groups, restated
+    here (tests compare the two): the order of a dot product's sum depends on n through it alone."""
+    if n < 0:
+        raise ValueError("krylov_groups: n must not be negative")
+    return min((int(n) + 1023) // 1024, 1024)
+
+
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 

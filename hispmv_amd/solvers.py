@@ -1,0 +1,78 @@
+"""Krylov solvers on loaded handles, for torch tensors: ``cg``, ``bicgstab`` and ``cgls`` over FpgaHandle.cg_device /
+bicgstab_device / cgls_device (include/hispmv.h: hispmv_cg_device ...).  The products are the launches of spmv_device / spmv_device_t;
+everything between two products runs in the library's fused vector kernels with every scalar on the device, and the host looks at the
+residual every ``check_every`` iterations only.  There is no torch fallback: the loops exist in the library or not at all.
+
+Streams: the launches go to torch's current stream by its handle.  Inside ``with torch.cuda.stream(torch.cuda.Stream()):`` everything
+-- the torch kernels that made b, x0 and minv, the solve, whatever reads x afterwards -- is ordered on one real stream and nothing
+waits.  torch's DEFAULT stream has the handle 0, which the library reads as "the context's own stream" (include/hispmv.h: the stream
+rule), a stream that is not ordered with torch's kernels on the default stream.  There the solvers order the two themselves: they wait
+on the host for the default stream before the first launch (b, x0, minv and the copy of x0 were written there), and a call with
+``check_every > 0`` waits for the context's stream before it returns, so the x it returns is ready for torch.  A ``check_every = 0``
+call on the default stream returns with the solve in flight on the context's stream: x must not be read, and b and minv not
+overwritten, before ``handle.krylov_status(info["work"].data_ptr(), 0)`` or ``handle.synchronize()`` has returned."""
+from __future__ import annotations
+
+import torch
+
+
+def _vector(t, name: str, n: int):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+        raise TypeError(f"{name} must be a contiguous 1-D float32 CUDA tensor")
+    if t.numel() != n:
+        raise ValueError(f"{name} holds {t.numel()} elements, the handle needs {n}")
+    return t
+
+
+def workspace(handle, idx: int, solver: str, device) -> torch.Tensor:
+    """A workspace tensor for `solver` on handle `idx` (krylov_info's work_bytes; torch allocations are 16-byte aligned)."""
+    info = handle.krylov_info(idx, solver)
+    if not info["accepted"]:
+        return torch.empty(0, dtype=torch.uint8, device=device)          # the entry itself says why it refuses
+    return torch.empty(info["work_bytes"], dtype=torch.uint8, device=device)
+
+
+def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, check_every: int, work):
+    m = handle.matrix_info(idx)
+    b = _vector(b, "b", m["rows"])
+    x = torch.zeros(m["cols"], dtype=torch.float32, device=b.device) if x0 is None else _vector(x0, "x0", m["cols"]).clone()
+    if minv is not None:
+        minv = _vector(minv, "minv", m["rows"])
+    if max_iters is None:
+        max_iters = 2 * max(m["rows"], m["cols"])
+    if work is None:
+        work = workspace(handle, idx, solver, b.device)
+    current = torch.cuda.current_stream(b.device)
+    stream = current.cuda_stream
+    if stream == 0:          # torch's default stream: the library launches on the context's own stream (module docstring)
+        current.synchronize()
+    kw = dict(rtol=rtol, max_iters=max_iters, check_every=check_every, work=work.data_ptr(), work_bytes=work.numel() * work.element_size(), stream=stream)
+    if solver == "cg":
+        info = handle.cg_device(idx, b.data_ptr(), x.data_ptr(), 0 if minv is None else minv.data_ptr(), **kw)
+    elif solver == "bicgstab":
+        info = handle.bicgstab_device(idx, b.data_ptr(), x.data_ptr(), **kw)
+    else:
+        info = handle.cgls_device(idx, b.data_ptr(), x.data_ptr(), **kw)
+    if stream == 0 and check_every > 0:
+        handle.synchronize()
+    info["work"] = work          # check_every = 0: handle.krylov_status(info["work"].data_ptr(), stream) reads the outcome
+    return x, info
+
+
+def cg(handle, idx: int, b, x0=None, *, minv=None, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+    """Solves A x = b for the symmetric positive definite handle `idx` by (diagonally preconditioned) CG on torch's current stream.
+    b, x0 and minv (the inverse diagonal, optional) are float32 CUDA vectors; returns (x, info) with info = {"status", "iterations",
+    "relres", "products", "work"}.  max_iters defaults to twice the dimension; check_every = 0 enqueues exactly max_iters iterations
+    and returns without waiting (status "IN_FLIGHT")."""
+    return _solve("cg", handle, idx, b, x0, minv, rtol, max_iters, check_every, work)
+
+
+def bicgstab(handle, idx: int, b, x0=None, *, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+    """Solves A x = b for a square, non-symmetric handle by BiCGSTAB (forward products only); arguments and result as `cg`."""
+    return _solve("bicgstab", handle, idx, b, x0, None, rtol, max_iters, check_every, work)
+
+
+def cgls(handle, idx: int, b, x0=None, *, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+    """min ||b - A x|| for a handle of any shape by CGLS, stopping on ||A^T r|| <= rtol ||A^T b||; the handle must be one spmv_device_t
+    accepts (create it under set_transposable(...)); arguments and result as `cg`."""
+    return _solve("cgls", handle, idx, b, x0, None, rtol, max_iters, check_every, work)

@@ -17,7 +17,9 @@ stream: forward and backward each wait on the host for the default stream before
 optimiser step) and for the context's stream after them (FpgaHandle.synchronize), so the natural loop ``v -= lr * v.grad`` is correct
 there, at the price of two host waits per pass.  Inside ``with torch.cuda.stream(torch.cuda.Stream()):`` everything is ordered on one
 real stream and nothing waits (examples/train_sparse_layer.py).  Without ``values`` the layer adds no wait, as before: on the default
-stream the caller synchronises between torch's operations and the layer.
+stream the caller synchronises between torch's operations and the layer.  One exception: a non-contiguous ``x`` or ``bias`` is copied
+inside the forward pass, on torch's current stream, where no caller can stand between the copy and the launch; on the default stream
+the forward pass waits for that copy itself.
 
 ``spmm=True`` routes the forward product and grad_x through the wide-batch entries (FpgaHandle.spmm_device / spmm_device_t) on
 feature-major copies of the activations; ``wide_grad=True`` on top of it takes grad_values through the wide-batch value gradient
@@ -52,10 +54,14 @@ def _function(torch):
         @staticmethod
         def forward(ctx, x, bias, handle, idx, rows):
             ctx.handle, ctx.idx, ctx.has_bias = handle, idx, bias is not None
-            stream = torch.cuda.current_stream(x.device).cuda_stream
+            current = torch.cuda.current_stream(x.device)
+            stream = current.cuda_stream
+            copied = not x.is_contiguous() or (bias is not None and not bias.is_contiguous())
             x = x.contiguous()
             y = torch.empty((x.shape[0], rows), dtype=torch.float32, device=x.device)
             b = bias.contiguous() if bias is not None else None
+            if copied and stream == 0:        # the copies above ran on torch's default stream, which the context's stream does not wait for
+                current.synchronize()
             handle.linear_device(idx, x.data_ptr(), x.shape[0], b.data_ptr() if b is not None else 0, y.data_ptr(), 1.0,
                                  1.0 if b is not None else 0.0, stream)
             ctx.cols = x.shape[1]

@@ -560,6 +560,94 @@ int hispmv_boundary_pack(hispmv_ctx* ctx, const float* const* d_last, const floa
 int hispmv_boundary_apply(hispmv_ctx* ctx, float* const* d_first, const float* d_recv, const float* d_weights, int32_t n, int32_t world,
                           void* stream);
 
+/* ---- Krylov solvers on loaded handles (no counterpart in the reference, which multiplies only) -----------------------------------
+ * A x = b solved on the device: the products are exactly the launches of hispmv_spmv_device / hispmv_spmv_device_t (the first with
+ * alpha = -1, beta = 1, bias = b for the residual r = b - A x, every later one with alpha = 1, beta = 0), and everything between two
+ * products runs in fused vector kernels that keep every scalar on the device.  The host looks at the result every check_every
+ * iterations, or never.  The workspace is the caller's (hispmv_krylov_info: work_bytes, 16-byte aligned); nothing is kept in the
+ * handle or the context.  ONE solve per handle may be in flight: the handle's carries and partial vectors belong to its products.
+ *
+ * THE DOT PRODUCT (a, b) of two fp32 vectors of n elements.  The product of two floats is exact in fp64; the sums are fp64 in an order
+ * that depends on n alone -- not on the device, the stream or the run.  With C = ceil(n / 1024) chunks of 1024 elements and
+ * G = min(C, 1024) workgroups (hispmv_prep_krylov_groups):
+ *   - thread t (0 .. 255) of chunk c owns elements 1024 c + 4 t + j, j = 0 .. 3; s(c, t) = ((((+0 + a0 b0) + a1 b1) + a2 b2) + a3 b3),
+ *     elements at or beyond n left out (adding +0 in their place gives the same bits);
+ *   - workgroup g takes chunks g, g + G, g + 2 G, ... ascending: acc(g, t) = ((+0 + s(g, t)) + s(g + G, t)) + ...;
+ *   - TREE over the 256 values v[t]: v[t] += v[t + 128] for t < 128, then v[t] += v[t + 64] for t < 64, then 32, 16, 8, 4, 2, 1;
+ *     partial(g) = v[0];
+ *   - the result is the same scheme over the partials: u[t] = ((((+0 + partial(4 t)) + partial(4 t + 1)) + partial(4 t + 2)) +
+ *     partial(4 t + 3)), partials at or beyond G left out, then TREE over u.
+ * Every kernel that needs a dot product's value sums the partials itself, in every workgroup, so all readers hold the same bits and
+ * no atomic, ticket or launch of its own is spent on a scalar.
+ *
+ * THE UPDATES.  A scalar (alpha, beta, omega) is computed in fp64 with IEEE division from such sums and rounded ONCE to fp32 (nearest
+ * even) before it meets a vector.  Vector arithmetic is fp32 and unfused, one rounding per operation:
+ *   CG         q = A p; alpha = rho / (p, q); x = x + alpha32 * p; r = r - alpha32 * q; z = minv * r (or r); rho' = (r, z);
+ *              beta = rho' / rho; p = z + beta32 * p.  Start: r = b - A x, p = z.
+ *   BiCGSTAB   v = A p; alpha = rho / (rhat, v); s = r - alpha32 * v; t = A s; omega = (t, s) / (t, t); x = x + alpha32 * p;
+ *              x = x + omega32 * s; r = s - omega32 * t; rho' = (rhat, r); beta = (rho' / rho) * (alpha / omega);
+ *              p = r + beta32 * (p - omega32 * v).  Start: rhat = p = r = b - A x.  (s, s) within the tolerance ends the solve on the
+ *              half step x = x + alpha32 * p.
+ *   CGLS       q = A p; alpha = gamma / (q, q); x = x + alpha32 * p; r = r - alpha32 * q; s = A^T r; gamma' = (s, s);
+ *              beta = gamma' / gamma; p = s + beta32 * p.  Start: r = b - A x, p = s = A^T r.
+ * STOPPING is decided on the device: the kernel that finishes an iteration compares rr <= (rtol * rtol) * bb in fp64, rr = (r, r) and
+ * bb = (b, b) -- CGLS: rr = (s, s), bb = (A^T b, A^T b) -- and sets `done`; from the next launch on every update is a no-op (the
+ * products still run, their results are ignored).  x, iterations and relres are therefore those of the FIRST iteration that met the
+ * tolerance, whatever check_every is.  A denominator ((p, q), (rhat, v), (t, t), (q, q), rho, omega, CGLS: bb) that is zero or not
+ * finite sets `breakdown` before the update that would use it, and the updates freeze the same way: x stays the last good iterate.
+ * b == 0 gives x = 0, CONVERGED, 0 iterations -- and, where the host looks (check_every > 0), no product.
+ *
+ * check_every = k > 0: after every k iterations the scalar block is copied to pinned memory (hipMemcpyAsync), the stream is
+ * synchronised, and the loop ends on done, breakdown or max_iters; the call returns with *result filled.  check_every = 0: exactly
+ * max_iters iterations are enqueued and the call returns without synchronising, *result = {HISPMV_KRYLOV_IN_FLIGHT, 0, 0, products
+ * enqueued}; hispmv_krylov_status reads the outcome later.  Between checks the loop adds no allocation, synchronous copy or
+ * synchronisation to what the product launches do. */
+#define HISPMV_KRYLOV_CG        0
+#define HISPMV_KRYLOV_BICGSTAB  1
+#define HISPMV_KRYLOV_CGLS      2
+#define HISPMV_KRYLOV_CONVERGED 0
+#define HISPMV_KRYLOV_MAX_ITERS 1
+#define HISPMV_KRYLOV_BREAKDOWN 2
+#define HISPMV_KRYLOV_IN_FLIGHT 3
+typedef struct hispmv_krylov_result {
+    int32_t status;         /* HISPMV_KRYLOV_CONVERGED, _MAX_ITERS, _BREAKDOWN (_IN_FLIGHT: a check_every = 0 call that has returned) */
+    int32_t iterations;     /* updates of x applied */
+    double relres;          /* sqrt(rr / bb), from the recursive residual */
+    int64_t products;       /* products issued, forward and transposed */
+} hispmv_krylov_result;
+/* The rule on the host (no device needed): *groups = min(ceil(n / 1024), 1024), the workgroups of a pass over n elements and the fp64
+ * partials of a dot product.  n < 0 -> HISPMV_EINVAL. */
+int hispmv_prep_krylov_groups(int64_t n, int64_t* groups);
+/* out = {accepted, work_bytes, launches_per_iteration (vector kernels), products_per_iteration, products_t_per_iteration, byte offset
+ * of the residual r in the workspace, elements of x, elements of b} for `solver` (HISPMV_KRYLOV_CG, ...) on this handle; zeros for a
+ * handle the solver does not accept (not loaded, not square for CG and BiCGSTAB, refused by hispmv_spmv_device_t for CGLS). */
+int hispmv_krylov_info(const hispmv_ctx* ctx, int matrix_idx, int solver, int64_t out[8]);
+/* *d_out (a double in device memory, 8-byte aligned) = (a, b) in the order above; asynchronous on `stream`.  d_a and d_b need 4-byte
+ * alignment (16-byte aligned operands are read in 16-byte accesses, same bits); work_bytes >= 8 * groups, 16-byte aligned. */
+int hispmv_dot_device(hispmv_ctx* ctx, int64_t n, const float* d_a, const float* d_b, double* d_out, void* d_work, int64_t work_bytes,
+                      void* stream);
+/* Preconditioned CG for a symmetric positive definite handle.  d_x[cols] holds the initial guess on entry and the solution on return;
+ * d_minv is NULL or the inverse diagonal (z = minv * r elementwise).  Every handle hispmv_spmv_device accepts is accepted (a bf16
+ * handle solves the system of its rounded values).  HISPMV_EINVAL before any launch: a handle that is not square, rtol < 0,
+ * max_iters < 1 or > 2^30 (the launches of a check_every = 0 call are counted in 64 bits, but nobody waits for more), check_every < 0,
+ * a workspace that is NULL, too small or not 16-byte aligned.  d_b, d_x, d_minv: 4-byte aligned; each vector that is 16-byte aligned
+ * is read and written in 16-byte accesses, the others in 4-byte ones, same bits.
+ * Cost outside the loop: a call with check_every > 0 allocates and frees its 128 pinned bytes itself (hipHostMalloc / hipHostFree, both
+ * of which synchronise the device) and looks at (b, b) once before the first product; check_every = 0 does neither. */
+int hispmv_cg_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float* d_x, const float* d_minv, double rtol, int64_t max_iters,
+                     int64_t check_every, void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result);
+/* BiCGSTAB for square, non-symmetric systems; the forward product only, two per iteration.  Arguments and errors as for CG. */
+int hispmv_bicgstab_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float* d_x, double rtol, int64_t max_iters, int64_t check_every,
+                           void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result);
+/* CGLS: min || b - A x || for any rows x cols, b[rows], x[cols]; stops on || A^T r || <= rtol * || A^T b ||; one forward and one
+ * transposed product per iteration (three products before the first).  Accepts what hispmv_spmv_device_t accepts and refuses the rest
+ * as it does (HISPMV_ENOTSUP, its message) before any launch, d_x untouched.  Over a stored transpose the solve is bit-reproducible;
+ * over the atomic transposed path it is not.  A^T b == 0 with b != 0 is a breakdown. */
+int hispmv_cgls_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float* d_x, double rtol, int64_t max_iters, int64_t check_every,
+                       void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result);
+/* Synchronises `stream` and reads the outcome of a check_every = 0 solve that ran on it out of its workspace. */
+int hispmv_krylov_status(hispmv_ctx* ctx, const void* d_work, void* stream, hispmv_krylov_result* result);
+
 /* ---- getters (HiSpmvHandle getters, spmv-helper.cpp:752-810) ------------------------------------ */
 typedef struct hispmv_matrix_info {
     int32_t rows, cols;
