@@ -547,7 +547,7 @@ int spmv_batch_locked(hispmv_ctx* c, int32_t n, const int32_t* idx, const float*
                       float* const* d_y, float alpha, float beta, hipStream_t s, bool companions) {
     if (n < 0 || (n > 0 && (!idx || !d_x || !d_y || (beta != 0.0f && !d_bias)))) return fail(c, HISPMV_EINVAL, "NULL argument");
     for (int i = 0; i < n; ++i) {
-        if (!c->has_matrix(idx[i], companions)) return idx_out_of_range(c);      // (companions: the stored transpose of a handle, hispmv_abi.cpp)
+        if (!c->has_matrix(idx[i], companions)) return idx_out_of_range(c);      // (companions: the stored transpose of a handle, hispmv_launch.cpp: launch_matrix)
         const Matrix& m = c->matrix(idx[i]);
         if (!m.loaded) return fail(c, HISPMV_ESTATE, "spmv_device_batch called before load_matrices");
         if (!d_x[i] || !d_y[i] || (beta != 0.0f && !d_bias[i])) return fail(c, HISPMV_EINVAL, "NULL device vector");

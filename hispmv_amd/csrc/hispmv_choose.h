@@ -1,9 +1,9 @@
 // hispmv_choose.h -- per-matrix FORMAT AND TILING CHOICE: slice stream or transposed tile stream, column tiles, band tiles.
 // The MI355X analogue of the reference's per-matrix configuration search (automation_tool/src/dse.py:23-95 picks the
 // hardware configuration per matrix from its row statistics; tileAndPad spmv-helper.cpp:242-263 decides the tiling).
-// Host-only code (no HIP): the loader (hispmv_abi.cpp) calls choose_format() for every sparse handle, the host-only entry
+// Host-only code (no HIP): the loader (hispmv_create.cpp: make_sparse) calls choose_format() for every sparse handle, the host-only entry
 // hispmv_prep_choose_format() exposes the same decision to tests on a CPU-only box, tools/sanitize_host.sh runs it under
-// ASan/UBSan.  Until round 3 this logic lived inside hispmv_abi.cpp (compiled by hipcc, reachable only with a device).
+// ASan/UBSan.  Until round 3 this logic lived inside the C ABI file (compiled by hipcc, reachable only with a device).
 #pragma once
 #include <cstdint>
 #include <functional>

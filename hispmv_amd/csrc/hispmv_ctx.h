@@ -1,8 +1,15 @@
 // hispmv_ctx.h -- the context and matrix objects behind the C ABI (include/hispmv.h), shared by the translation units of the
-// library's host side: hispmv_abi.cpp (context, handles, upload, single launches), hispmv_batch.cpp (hispmv_spmv_device_batch:
-// launch tables, lanes, HIP-graph replay) and hispmv_prep_abi.cpp (the host-only hispmv_prep_* entries).  MI355X counterpart of
-// the reference's FpgaHandle (pyhispmv/include/fpga_handle.h:9-74), which owns the XRT device, the per-channel matrix arena and
-// the kernel run object.  Internal header: nothing here is part of the ABI.
+// library's host side.  MI355X counterpart of the reference's FpgaHandle (pyhispmv/include/fpga_handle.h:9-74), which owns the XRT
+// device, the per-channel matrix arena and the kernel run object.  Internal header: nothing here is part of the ABI.  Which file
+// holds what:
+//   hispmv_abi.cpp         error reporting, hispmv_create / _destroy, arena, version, synchronize, the hispmv_set_* switches, the
+//                          boundary kernels' entries and every *_info getter that only reads Matrix fields
+//   hispmv_create.cpp      the four hispmv_create_*_handle* entries: creation checks, make_sparse (byte accounting), registration
+//   hispmv_load.cpp        hispmv_load_matrices: every device allocation and upload of a handle, the value map, free_matrix_device
+//   hispmv_launch.cpp      the forward pass plan, the host-vector path, the transposed and stored-transpose entries, the value
+//                          gradient, the value updates, and the getters that walk the pass plan (linear / value_grad / transpose _info)
+//   hispmv_batch.cpp       hispmv_spmv_device_batch: launch tables, lanes, HIP-graph replay
+//   hispmv_spmm_abi.cpp    the wide-batch entries;  hispmv_krylov_abi.cpp  the solvers;  hispmv_prep_abi.cpp  the host-only hispmv_prep_*
 #pragma once
 #include "../../include/hispmv.h"
 
@@ -96,7 +103,7 @@ struct Matrix {
     // (rows and cols exchanged, same entry order) under the same switches, without a batch layout.  Not in the context's handle list:
     // `index` of a companion is kCompanionId + its owner's index, the id a cached batch plan keys on (hispmv_ctx::matrix).  The
     // owner's device_bytes and prep_seconds include the companion's; every value update writes both; the transposed entries run the
-    // companion's forward launches (hispmv_abi.cpp: launch_companion).
+    // companion's forward launches (hispmv_launch.cpp: launch_companion).
     std::unique_ptr<Matrix> companion;
     std::vector<void*> allocs;
 };
@@ -271,7 +278,7 @@ std::string& prep_error();
     } while (0)
 #define LAUNCH_TRY(c, launcher, ...) LAUNCH_TRY_AS(c, #launcher, launcher(__VA_ARGS__))
 
-// The preamble of the entries that take a handle index and a stream (hispmv_abi.cpp, hispmv_spmm_abi.cpp, hispmv_batch.cpp).
+// The preamble of the entries that take a handle index and a stream (hispmv_launch.cpp, hispmv_spmm_abi.cpp, hispmv_batch.cpp).
 inline int idx_out_of_range(hispmv_ctx* c) { return fail(c, HISPMV_EINVAL, "Matrix idx out of range"); }   // fpga_handle.cpp:267-270
 // *out = handle `idx`, refused when out of range or -- `who` given -- not loaded.  who == nullptr: an entry that checks something
 // else before the loaded state checks that itself.
@@ -310,6 +317,12 @@ template <class T> void host_free(T*& p) {
 }
 
 int check_device_error(hispmv_ctx* c);      // hispmv_abi.cpp
+// *p holds at least n floats afterwards (the context's device vectors: d_x, d_y, d_upd; hispmv_abi.cpp)
+int ensure_vec(hispmv_ctx* c, float** p, int64_t* cap, int64_t n);
+// hispmv_load.cpp: releases what a load allocated (the stored transpose's too); what one layout of a slice part costs on the device,
+// for make_sparse (hispmv_create.cpp)
+void free_matrix_device(Matrix& m);
+int64_t slice_layout_device_bytes(const SliceStream& st, const LaunchPlan& plan, const DeviceStream& ds);
 // the transposed entries accept the (loaded) handle itself -- dense, a slice stream, a tile stream kept for them -- and, where they do
 // not, the HISPMV_ENOTSUP they answer with (hispmv_abi.cpp)
 bool transposable_handle(const Matrix& m);

@@ -621,7 +621,7 @@ __device__ __forceinline__ void slices_group(
             // (Resolving the row in its own iteration made every wavefront wait for its left neighbour's scan each
             // round: lockstep.  One iteration of slack removes most of it, yet on long per-wave chunks a wavefront that
             // runs ahead still waits for the slower ones, and the variant itself is ~5 us slower than the fix-up
-            // variant's main kernel on PFlow_742 -- so large matrices keep the fix-up launch, hispmv_abi.cpp.)
+            // variant's main kernel on PFlow_742 -- so large matrices keep the fix-up launch, hispmv_load.cpp: choose_carry_variant.)
             if (pend_slice >= 0) {
                 const float chain = lookback_chain(lb, mbox, first, pend_slice, pend_len, lane);
                 if (lane == 0) {
@@ -1348,7 +1348,7 @@ hipError_t launch_spmv(SpmvDeviceMatrix& m_in, const float* x, const float* bias
             m.launches++;
         }
         // stray slots and half groups (bf16 value storage) exist only in plans with a window, stray slots never with
-        // look-back (hispmv_abi.cpp); a handle with half groups takes the kernel of its own that reads them
+        // look-back (hispmv_load.cpp); a handle with half groups takes the kernel of its own that reads them
         const bool window = m.lds_floats > 0;
         e = with_bools({beta != 0.0f, window, m.lookback, window && !m.lookback && m.has_strays, window && m.has_half},
                        [&](auto HAS_BETA, auto USE_LDS, auto LOOKBACK, auto STRAYS, auto HALF) {
@@ -2061,7 +2061,7 @@ hipError_t launch_tts_multi(const TtsEntry* entries, int n, const uint8_t* item_
     size_t lds = 0;
     for (int i = 0; i < n; ++i) {
         const TtsDeviceMatrix& m = entries[i].m;
-        if (tts_x_in_lds(m, 1) != xlds) return hipErrorInvalidValue;      // (one class per launch: hispmv_abi.cpp)
+        if (tts_x_in_lds(m, 1) != xlds) return hipErrorInvalidValue;      // (one class per launch: hispmv_batch.cpp)
         if (m.zero_fill != m0.zero_fill || m.threads != m0.threads) return hipErrorInvalidValue;
         lds = std::max(lds, xlds ? tts_nv_lds_bytes(m, 1, true) : tts_tile_lds_bytes(m));
     }
@@ -2333,7 +2333,7 @@ hipError_t launch_gemv_batched(const float* W, int32_t rows, int32_t cols, int64
 }
 
 // ---------------------------------------------------------------------------
-// A batch call replayed as a HIP graph (hispmv_abi.cpp) with another alpha: alpha is a by-value argument of every kernel of
+// A batch call replayed as a HIP graph (hispmv_batch.cpp) with another alpha: alpha is a by-value argument of every kernel of
 // the call, so the instantiated graph is patched in place -- hipGraphExecKernelNodeSetParams on each of its kernel nodes --
 // instead of being captured and instantiated again (a solver that changes alpha every step would pay an instantiation
 // per step).  `graph` is the captured graph the executable was instantiated from (its node handles address the

@@ -301,7 +301,7 @@ hipError_t raise_lds_limit() {
 // What every slice launch checks of a plan before it starts a grid of m.n_groups workgroups with lds_bytes of dynamic LDS.
 inline bool slice_geometry_ok(const SpmvDeviceMatrix& m, size_t lds_bytes) {
     if (m.n_groups > 0x7fffffffLL || m.block_threads < 64 || m.block_threads > 1024 || (m.block_threads & 63) || lds_bytes > (size_t)kDynLdsMax) return false;
-    // stray slots and half groups exist only in plans with a window (hispmv_abi.cpp)
+    // stray slots and half groups exist only in plans with a window (hispmv_load.cpp)
     if (m.lds_floats <= 0 && (m.has_strays || m.has_half)) return false;
     return !m.has_strays || m.lds_floats >= (m.block_threads / 64) * kStraySlots;
 }

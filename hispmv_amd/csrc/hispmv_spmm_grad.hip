@@ -46,7 +46,7 @@ __device__ __forceinline__ void spmm_grad_group(
     auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
     const bool strays = wk.strays;
     unsigned* const stray_area = colwin + wk.win_floats + wave * kStraySlots;
-    // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
+    // the columns of every slice's strays live behind the headers (hispmv_load.cpp: upload_slice_layout), 64 per slice, 0xffffffff = none
     const unsigned* const stray_cols = (const unsigned*)(hdr + n_slices);
 
     SliceMetas<COMPACT> w;

@@ -57,7 +57,7 @@ __device__ __forceinline__ void slices_group_t(
     const bool in_lds = wk.in_lds, strays = wk.strays;
     const int win_floats = wk.win_floats;
     float* const stray_area = xs + win_floats + wave * kStraySlots;
-    // the columns of every slice's strays live behind the headers (hispmv_abi.cpp), 64 per slice, 0xffffffff = none
+    // the columns of every slice's strays live behind the headers (hispmv_load.cpp: upload_slice_layout), 64 per slice, 0xffffffff = none
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
 
     SliceRaw<COMPACT, HALF> w;

@@ -440,7 +440,7 @@ def test_csr_with_unsorted_rows_and_null_arrays(fpga):
 
 
 def test_batch_tables_survive_the_first_host_vector_call(pyhispmv_mod):
-    """Regression (round 1, hispmv_abi.cpp run_host_vectors): the first staged run_kernel / linear of a context grew the
+    """Regression (round 1, hispmv_launch.cpp run_host_vectors): the first staged run_kernel / linear of a context grew the
     pinned staging block and, through a stray line, freed the device tables of earlier hispmv_spmv_device_batch calls
     without forgetting them -- the next batch call with the same arguments launched on freed memory.  Sequence: batch,
     first host-vector call (grows the stage), a few small device allocations that would reuse the freed fragments and
@@ -670,7 +670,7 @@ def oracle_linear(case, v, W, x, b):
 @pytest.mark.parametrize("mode", ["direct", "copy"])
 def test_host_vector_path_direct_and_copied_y(pyhispmv_mod, mode, monkeypatch):
     """run_kernel / linear from host buffers: by default x and bias reach the device through a fetch kernel that reads the pinned
-    staging block and y is written straight into that block (no DMA copies: hispmv_abi.cpp run_host_vectors); HISPMV_HOST_Y=copy keeps
+    staging block and y is written straight into that block (no DMA copies: hispmv_launch.cpp run_host_vectors); HISPMV_HOST_Y=copy keeps
     the copies.  Both give the bits of the device entry point -- for a slice stream with cut rows (the tail's read-modify-writes of y
     cross PCIe), a matrix in two column parts (partial vector + merge), a dense handle, 5 vectors per linear call, beta = 0, and a
     matrix whose vectors are too large for the staging block (> 8 MB: plain copies in both modes)."""
