@@ -1,7 +1,8 @@
 """Solves a generated symmetric positive definite system with CG and a generated least-squares problem with CGLS on loaded handles
-(hispmv_amd.solvers), and prints iterations and residuals next to the fp64 residuals computed on the host.
+(hispmv_amd.solvers), and prints iterations and residuals next to the fp64 residuals computed on the host.  --rhs M also solves the
+SPD system for M right-hand sides in one call (solvers.cg_multi) and prints iterations and the true residual of every column.
 
-    python examples/solve_check.py [--grid 64] [--rtol 1e-6]
+    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M]
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--rtol", type=float, default=1e-6)
+    ap.add_argument("--rhs", type=int, default=0, help="also solve the SPD system for this many right-hand sides in one call")
     args = ap.parse_args()
     import torch
     import pyhispmv
@@ -44,6 +46,9 @@ def main():
     spd = h.create_sparse_handle(r, c, v, n, n)
     h.set_transposable("companion")          # CGLS multiplies by A^T: a stored transpose keeps that product free of atomics
     ls = h.create_sparse_handle(lr, lc, lv, rows, cols)
+    if args.rhs > 0:
+        h.set_transposable(True)             # the multi solves run over spmm_device, which takes slice streams: keep that format
+        spd_wide = h.create_sparse_handle(r, c, v, n, n)
     h.load_matrices()
 
     dev = torch.device("cuda", 0)
@@ -55,6 +60,18 @@ def main():
     print(f"CG    {n} x {n}: {info['status']}, {info['iterations']} iterations, {info['products']} products, "
           f"recursive residual {info['relres']:.3e}, true {true:.3e}")
     assert info["status"] == "CONVERGED" and true < 100 * args.rtol
+
+    if args.rhs > 0:          # smoother columns stop earlier; each column has its own count and is frozen while the others go on
+        t = (np.arange(n) + 0.5) / n
+        B = np.stack([np.sin(np.pi * (j + 1) * t) if j % 2 else rng.uniform(-1, 1, n) for j in range(args.rhs)], axis=1).astype(np.float32)
+        X, info = solvers.cg_multi(h, spd_wide, torch.from_numpy(B).to(dev), rtol=args.rtol)
+        X64 = X.cpu().numpy().astype(np.float64)
+        print(f"CG    {n} x {n}, {args.rhs} right-hand sides in one call: {info['products']} products")
+        for j in range(args.rhs):
+            Ax = np.bincount(r, weights=v.astype(np.float64) * X64[c, j], minlength=n)
+            true = np.linalg.norm(B[:, j] - Ax) / np.linalg.norm(B[:, j])
+            print(f"  column {j:3d}: {info['status'][j]}, {info['iterations'][j]} iterations, recursive residual {info['relres'][j]:.3e}, true {true:.3e}")
+            assert info["status"][j] == "CONVERGED"          # (a smooth column's true fp32 residual stalls near cond(A) * 2^-24, above the recursive one)
 
     b = rng.uniform(-1, 1, rows).astype(np.float32)
     x, info = solvers.cgls(h, ls, torch.from_numpy(b).to(dev), rtol=args.rtol)

@@ -131,6 +131,14 @@ SIGNATURES = {
     "hispmv_bicgstab_device": (C.c_int, [_p, C.c_int, _p, _p, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
     "hispmv_cgls_device": (C.c_int, [_p, C.c_int, _p, _p, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
     "hispmv_krylov_status": (C.c_int, [_p, _p, _p, C.POINTER(KrylovResult)]),
+    "hispmv_prep_krylov_multi": (C.c_int, [C.c_int64, C.c_int64, _i64p]),
+    "hispmv_krylov_multi_info": (C.c_int, [_p, C.c_int, C.c_int, C.c_int64, _i64p]),
+    "hispmv_dot_multi_device": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int64, _p]),
+    "hispmv_cg_multi_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int64, _p, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p,
+                                         C.POINTER(KrylovResult)]),
+    "hispmv_bicgstab_multi_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p,
+                                               C.POINTER(KrylovResult)]),
+    "hispmv_krylov_multi_status": (C.c_int, [_p, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
     "hispmv_prep_vector_widths": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),

@@ -475,6 +475,62 @@ class FpgaHandle:
         self._check(lib.hispmv_krylov_status(self._ctx, C.c_void_p(work), C.c_void_p(stream), C.byref(res)))
         return self._krylov_result(res)
 
+    # -- several right-hand sides (hispmv_krylov_multi_abi.cpp; hispmv_amd.solvers.cg_multi / bicgstab_multi wrap these) ------------
+    def krylov_multi_info(self, matrix_idx: int, solver: str, num_vecs: int) -> dict:
+        """{"accepted", "work_bytes", "launches_per_iteration", "products_per_iteration", "ld", "r_offset", "n", "groups"} of `solver` ("cg",
+        "bicgstab") for num_vecs right-hand sides on a handle (hispmv_krylov_multi_info): the workspace, the vector kernels and the
+        spmm_device calls of one iteration, the leading dimension of the workspace's vectors and where R lies; zeros for a handle the
+        entries refuse."""
+        if solver not in ("cg", "bicgstab"):
+            raise ValueError('solver must be "cg" or "bicgstab"')
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_krylov_multi_info(self._ctx, int(matrix_idx), _lib.KRYLOV_SOLVERS[solver], int(num_vecs), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError("num_vecs must be at least 1 (and at most 2^20)")
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "work_bytes": int(out[1]), "launches_per_iteration": int(out[2]), "products_per_iteration": int(out[3]),
+                "ld": int(out[4]), "r_offset": int(out[5]), "n": int(out[6]), "groups": int(out[7])}
+
+    def dot_multi_device(self, n: int, num_vecs: int, d_a: int, d_b: int, d_out: int, work: int, work_bytes: int, ld_a=None, ld_b=None,
+                         stream: int = 0) -> None:
+        """d_out[v] (float64, device) = sum_i a[i, v] * b[i, v] for the num_vecs columns of two feature-major float32 operands [n, ld]
+        (hispmv_dot_multi_device): every column in the order of dot_device for n.  `work` points at work_bytes >= 8 * groups * ld of
+        prep.krylov_multi(n, num_vecs), 16-byte aligned; n <= 2^20."""
+        self._check(lib.hispmv_dot_multi_device(self._ctx, int(n), int(num_vecs), C.c_void_p(d_a), int(num_vecs if ld_a is None else ld_a), C.c_void_p(d_b),
+                                                int(num_vecs if ld_b is None else ld_b), C.c_void_p(d_out), C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def cg_multi_device(self, matrix_idx: int, d_b: int, d_x: int, num_vecs: int, d_minv: int = 0, ld_b=None, ld_x=None, rtol: float = 1e-6,
+                        max_iters: int = 1000, check_every: int = 8, work: int = 0, work_bytes: int = 0, stream: int = 0) -> list:
+        """num_vecs independent preconditioned CG solves that share their launches (hispmv_cg_multi_device): d_b is [n, ld_b], d_x
+        [n, ld_x] (initial guesses, then the solutions), d_minv 0 or ONE inverse diagonal for all columns.  Column v is bit for bit
+        cg_device's arithmetic over spmm_device's products, with its own stopping and breakdown.  Returns the list of the columns'
+        {"status", "iterations", "relres", "products"}; check_every = 0 returns at once with every status "IN_FLIGHT" and
+        krylov_multi_status reads the outcome.  Exceptions as cg_device; a tile-stream or dense handle raises spmm_device's
+        NotImplementedError."""
+        res = (_lib.KrylovResult * int(max(num_vecs, 1)))()
+        self._check(lib.hispmv_cg_multi_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), int(num_vecs if ld_b is None else ld_b), C.c_void_p(d_x),
+                                               int(num_vecs if ld_x is None else ld_x), int(num_vecs), C.c_void_p(d_minv), float(rtol), int(max_iters),
+                                               int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), res))
+        return [self._krylov_result(r) for r in res]
+
+    def bicgstab_multi_device(self, matrix_idx: int, d_b: int, d_x: int, num_vecs: int, ld_b=None, ld_x=None, rtol: float = 1e-6,
+                              max_iters: int = 1000, check_every: int = 8, work: int = 0, work_bytes: int = 0, stream: int = 0) -> list:
+        """num_vecs independent BiCGSTAB solves that share their launches (hispmv_bicgstab_multi_device); arguments, result and
+        exceptions as cg_multi_device."""
+        res = (_lib.KrylovResult * int(max(num_vecs, 1)))()
+        self._check(lib.hispmv_bicgstab_multi_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), int(num_vecs if ld_b is None else ld_b), C.c_void_p(d_x),
+                                                     int(num_vecs if ld_x is None else ld_x), int(num_vecs), float(rtol), int(max_iters),
+                                                     int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), res))
+        return [self._krylov_result(r) for r in res]
+
+    def krylov_multi_status(self, work: int, num_vecs: int, stream: int = 0) -> list:
+        """Waits for `stream` and reads the columns' outcomes of the check_every = 0 multi solve that ran on it with workspace `work`
+        (hispmv_krylov_multi_status)."""
+        res = (_lib.KrylovResult * int(max(num_vecs, 1)))()
+        self._check(lib.hispmv_krylov_multi_status(self._ctx, C.c_void_p(work), int(num_vecs), C.c_void_p(stream), res))
+        return [self._krylov_result(r) for r in res]
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

@@ -296,6 +296,17 @@ def krylov_groups(n: int) -> int:
     return min((int(n) + 1023) // 1024, 1024)
 
 
+def krylov_multi(n: int, num_vecs: int) -> dict:
+    """The layout rule of the multi-right-hand-side Krylov entries (hispmv_prep_krylov_multi), host-only: {"groups", "ld", "state_bytes",
+    "partial_bytes"} for num_vecs columns of n rows -- one workgroup and one fp64 partial per chunk of 1024 rows (n <= 2^20, so the
+    order of a column's dot product is that of krylov_groups(n)), the workspace's leading dimension (num_vecs rounded up to 4), the
+    bytes of the columns' scalar blocks and of the partials; the residual R lies behind the two."""
+    out = (C.c_int64 * 4)()
+    if lib.hispmv_prep_krylov_multi(int(n), int(num_vecs), out) != HISPMV_OK:
+        raise ValueError("hispmv_prep_krylov_multi: 0 <= n <= 2^20 and 1 <= num_vecs <= 2^20")
+    return {"groups": int(out[0]), "ld": int(out[1]), "state_bytes": int(out[2]), "partial_bytes": int(out[3])}
+
+
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 

@@ -10,7 +10,10 @@ rule), a stream that is not ordered with torch's kernels on the default stream. 
 on the host for the default stream before the first launch (b, x0, minv and the copy of x0 were written there), and a call with
 ``check_every > 0`` waits for the context's stream before it returns, so the x it returns is ready for torch.  A ``check_every = 0``
 call on the default stream returns with the solve in flight on the context's stream: x must not be read, and b and minv not
-overwritten, before ``handle.krylov_status(info["work"].data_ptr(), 0)`` or ``handle.synchronize()`` has returned."""
+overwritten, before ``handle.krylov_status(info["work"].data_ptr(), 0)`` or ``handle.synchronize()`` has returned.
+
+Several right-hand sides: ``cg_multi`` and ``bicgstab_multi`` solve the columns of B [n, m] as m independent solves that share their
+launches (FpgaHandle.cg_multi_device / bicgstab_multi_device over spmm_device's products); same streams, same rule."""
 from __future__ import annotations
 
 import torch
@@ -32,6 +35,19 @@ def workspace(handle, idx: int, solver: str, device) -> torch.Tensor:
     return torch.empty(info["work_bytes"], dtype=torch.uint8, device=device)
 
 
+def _launch(handle, device, check_every: int, call):
+    """call(stream) on torch's current stream under the stream rule of the module docstring: on the default stream wait for torch
+    before the first launch and, where the call itself looks at the result (check_every > 0), for the context's stream behind it."""
+    current = torch.cuda.current_stream(device)
+    stream = current.cuda_stream
+    if stream == 0:          # torch's default stream: the library launches on the context's own stream (module docstring)
+        current.synchronize()
+    info = call(stream)
+    if stream == 0 and check_every > 0:
+        handle.synchronize()
+    return info
+
+
 def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, check_every: int, work):
     m = handle.matrix_info(idx)
     b = _vector(b, "b", m["rows"])
@@ -42,19 +58,15 @@ def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, c
         max_iters = 2 * max(m["rows"], m["cols"])
     if work is None:
         work = workspace(handle, idx, solver, b.device)
-    current = torch.cuda.current_stream(b.device)
-    stream = current.cuda_stream
-    if stream == 0:          # torch's default stream: the library launches on the context's own stream (module docstring)
-        current.synchronize()
-    kw = dict(rtol=rtol, max_iters=max_iters, check_every=check_every, work=work.data_ptr(), work_bytes=work.numel() * work.element_size(), stream=stream)
-    if solver == "cg":
-        info = handle.cg_device(idx, b.data_ptr(), x.data_ptr(), 0 if minv is None else minv.data_ptr(), **kw)
-    elif solver == "bicgstab":
-        info = handle.bicgstab_device(idx, b.data_ptr(), x.data_ptr(), **kw)
-    else:
-        info = handle.cgls_device(idx, b.data_ptr(), x.data_ptr(), **kw)
-    if stream == 0 and check_every > 0:
-        handle.synchronize()
+
+    def call(stream):
+        kw = dict(rtol=rtol, max_iters=max_iters, check_every=check_every, work=work.data_ptr(), work_bytes=work.numel() * work.element_size(), stream=stream)
+        if solver == "cg":
+            return handle.cg_device(idx, b.data_ptr(), x.data_ptr(), 0 if minv is None else minv.data_ptr(), **kw)
+        if solver == "bicgstab":
+            return handle.bicgstab_device(idx, b.data_ptr(), x.data_ptr(), **kw)
+        return handle.cgls_device(idx, b.data_ptr(), x.data_ptr(), **kw)
+    info = _launch(handle, b.device, check_every, call)
     info["work"] = work          # check_every = 0: handle.krylov_status(info["work"].data_ptr(), stream) reads the outcome
     return x, info
 
@@ -76,3 +88,63 @@ def cgls(handle, idx: int, b, x0=None, *, rtol: float = 1e-6, max_iters=None, ch
     """min ||b - A x|| for a handle of any shape by CGLS, stopping on ||A^T r|| <= rtol ||A^T b||; the handle must be one spmv_device_t
     accepts (create it under set_transposable(...)); arguments and result as `cg`."""
     return _solve("cgls", handle, idx, b, x0, None, rtol, max_iters, check_every, work)
+
+
+# ---- several right-hand sides -------------------------------------------------------------------------------------------------------
+def _columns(t, name: str, n: int, m=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+        raise TypeError(f"{name} must be a 2-D float32 CUDA tensor [n, m]")
+    if t.shape[0] != n or t.shape[1] < 1 or (m is not None and t.shape[1] != m):
+        raise ValueError(f"{name} is {tuple(t.shape)}, the handle needs [{n}, {'m >= 1' if m is None else m}]")
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name} must be row-major: stride(1) == 1 and stride(0) >= m (a narrowed view of a wider tensor is fine)")
+    return t
+
+
+def workspace_multi(handle, idx: int, solver: str, num_vecs: int, device) -> torch.Tensor:
+    """A workspace tensor for `solver` with num_vecs right-hand sides on handle `idx` (krylov_multi_info's work_bytes)."""
+    info = handle.krylov_multi_info(idx, solver, num_vecs)
+    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+
+
+def _solve_multi(solver: str, handle, idx: int, B, X0, minv, rtol: float, max_iters, check_every: int, work):
+    import numpy as np
+    mi = handle.matrix_info(idx)
+    n = mi["rows"]
+    B = _columns(B, "B", n)
+    m = B.shape[1]
+    X = torch.zeros(mi["cols"], m, dtype=torch.float32, device=B.device) if X0 is None else _columns(X0, "X0", mi["cols"], m).contiguous().clone()
+    if minv is not None:
+        minv = _vector(minv, "minv", n)
+    if max_iters is None:
+        max_iters = 2 * max(mi["rows"], mi["cols"])
+    if work is None:
+        work = workspace_multi(handle, idx, solver, m, B.device)
+    ld_b = B.stride(0) if n > 1 else m
+
+    def call(stream):
+        kw = dict(ld_b=ld_b, ld_x=m, rtol=rtol, max_iters=max_iters, check_every=check_every, work=work.data_ptr(),
+                  work_bytes=work.numel() * work.element_size(), stream=stream)
+        if solver == "cg":
+            return handle.cg_multi_device(idx, B.data_ptr(), X.data_ptr(), m, 0 if minv is None else minv.data_ptr(), **kw)
+        return handle.bicgstab_multi_device(idx, B.data_ptr(), X.data_ptr(), m, **kw)
+    res = _launch(handle, B.device, check_every, call)
+    info = {"status": [r["status"] for r in res], "iterations": np.array([r["iterations"] for r in res], np.int32),
+            "relres": np.array([r["relres"] for r in res], np.float64), "products": res[0]["products"],
+            "work": work}          # check_every = 0: handle.krylov_multi_status(info["work"].data_ptr(), m, stream) reads the outcome
+    return X, info
+
+
+def cg_multi(handle, idx: int, B, X0=None, *, minv=None, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+    """Solves A x_v = b_v for the m columns of B [n, m] by m independent (diagonally preconditioned) CG solves that share their
+    launches, on torch's current stream (FpgaHandle.cg_multi_device): column v is bit for bit what `cg` computes over spmm_device's
+    products, with its own iteration count, stopping and breakdown.  B is a float32 CUDA tensor with stride(1) == 1 and stride(0) >= m
+    (a narrowed view of a wider tensor is allowed); X0 [n, m] the initial guesses; minv ONE inverse diagonal for all columns.  Returns
+    (X, info), X contiguous [n, m], info = {"status": list, "iterations": int array, "relres": float array, "products", "work"}.
+    Streams as in the module docstring; a check_every = 0 call is read with handle.krylov_multi_status(info["work"].data_ptr(), m, stream)."""
+    return _solve_multi("cg", handle, idx, B, X0, minv, rtol, max_iters, check_every, work)
+
+
+def bicgstab_multi(handle, idx: int, B, X0=None, *, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+    """m independent BiCGSTAB solves for a square, non-symmetric handle that share their launches; arguments and result as `cg_multi`."""
+    return _solve_multi("bicgstab", handle, idx, B, X0, None, rtol, max_iters, check_every, work)

@@ -648,6 +648,64 @@ int hispmv_cgls_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float*
 /* Synchronises `stream` and reads the outcome of a check_every = 0 solve that ran on it out of its workspace. */
 int hispmv_krylov_status(hispmv_ctx* ctx, const void* d_work, void* stream, hispmv_krylov_result* result);
 
+/* ---- Krylov solvers for several right-hand sides ------------------------------------------------------------------------------------
+ * num_vecs INDEPENDENT solves A x_v = b_v that share their launches: column v has its own scalars, iteration count, stopping and
+ * breakdown.  This is not block CG: no Krylov space is shared.  Operands are feature-major like hispmv_spmm_device: d_B is [n, ld_b],
+ * d_X is [n, ld_x], row-major, ld >= num_vecs >= 1, pointers 4-byte aligned.  d_X holds the initial guesses on entry and the solutions
+ * on return; the floats num_vecs .. ld_x - 1 of a row of d_X are never written, the pads of d_B never read.  d_minv is NULL or ONE
+ * inverse diagonal minv[n] for all columns; rtol, max_iters and check_every are shared too.
+ *
+ * THE ARITHMETIC OF COLUMN v IS THAT OF THE SINGLE-VECTOR ENTRIES ABOVE with the product of hispmv_spmm_device in place of
+ * hispmv_spmv_device's: the dot products in the order of hispmv_dot_device for that n, fp64 scalars rounded once, fp32 unfused vector
+ * arithmetic, the update formulas, the stopping rule rr <= rtol^2 * bb and the denominators that set `breakdown` of the CG and
+ * BiCGSTAB paragraphs.  b_v == 0 gives x_v = 0, CONVERGED, 0 iterations.  x_v, iterations_v and relres_v therefore depend neither on
+ * check_every nor on the other columns, their number, ld, or the column's position (hispmv_spmm_device's bits of a vector do not
+ * either); an Inf or NaN in b_v or in x_v's initial guess breaks column v down and no other.  From the launch after a column is done
+ * or broken down every update of it is a no-op; the products still compute it and are ignored; the other columns go on.
+ * To keep the order of a dot product a function of n alone with lanes running across columns, n <= 1024 * 1024: every workgroup owns
+ * exactly one chunk of 1024 rows and G = ceil(n / 1024).  A larger n -> HISPMV_EINVAL.
+ *
+ * PRODUCTS: hispmv_spmm_device, called like any caller does.  The residual is one call with alpha = -1, beta = 1 in place on R (B
+ * copied into it), every later product has alpha = 1, beta = 0; results[v].products counts these calls and is the same for every
+ * column.  WORKSPACE (hispmv_krylov_multi_info: work_bytes, 16-byte aligned), laid out by the rule of hispmv_prep_krylov_multi: the
+ * columns' scalar blocks (128 bytes each, twice), the partials [slot][G][ldw], the solver's vectors [n, ldw] with ldw = num_vecs
+ * rounded up to 4 -- 16-byte aligned, so the products may take VL 4 --, then the workspace hispmv_spmm_info sizes for (num_vecs, ldw).
+ * Nothing is kept in the handle or the context.
+ *
+ * check_every = k > 0: every k iterations ONE asynchronous copy of the columns' scalar blocks (128 * num_vecs bytes) to a pinned
+ * buffer of the call's own and one synchronise; the loop ends when EVERY column is done or broken down, or at max_iters.  Before the
+ * first product one look at the (b_v, b_v) (8 * num_vecs bytes): all zero -> X = 0 and no product.  check_every = 0: everything is
+ * enqueued, nothing synchronises, every results[v] is HISPMV_KRYLOV_IN_FLIGHT and hispmv_krylov_multi_status reads the outcome.
+ *
+ * ACCEPTED: what hispmv_spmm_device accepts, square: a loaded slice-stream handle, all group kinds and parts, fp32 or bf16 storage.  A
+ * tile-stream or dense handle -> hispmv_spmm_device's code and message; not square -> HISPMV_EINVAL, the "square" message above;
+ * num_vecs < 1, ld < num_vecs, rtol < 0, max_iters < 1, check_every < 0, a workspace that is NULL, short or not 16-byte aligned, a bad
+ * index -> HISPMV_EINVAL; not loaded -> HISPMV_ESTATE.  All before any launch, d_X untouched.
+ * Out of scope: CGLS and any transposed multi solve, true block-Krylov methods, per-column rtol or preconditioners, n > 2^20, bf16
+ * vectors, tile-stream and dense handles, solves inside hispmv_spmv_device_batch or the step kernel, sharding over devices, HIP-graph
+ * capture, dot products fused into the product's stores. */
+/* The layout rule on the host (no device needed): out = {G = ceil(n / 1024), ldw = num_vecs rounded up to 4, bytes of the scalar
+ * blocks and the (b, b) row = 2 * 128 * ldw + 8 * ldw, bytes of the partials = 8 slots * G * ldw * 8}; R lies behind the two.
+ * n < 0, n > 2^20, num_vecs < 1 or > 2^20 -> HISPMV_EINVAL. */
+int hispmv_prep_krylov_multi(int64_t n, int64_t num_vecs, int64_t out[4]);
+/* out = {accepted, work_bytes, vector kernels per iteration, hispmv_spmm_device calls per iteration, leading dimension of the
+ * workspace's vectors, byte offset of R in the workspace, n, G} for `solver` (HISPMV_KRYLOV_CG or _BICGSTAB) and num_vecs columns;
+ * zeros for a handle the entries do not accept. */
+int hispmv_krylov_multi_info(const hispmv_ctx* ctx, int matrix_idx, int solver, int64_t num_vecs, int64_t out[8]);
+/* d_out[v] = (a[:, v], b[:, v]), v < num_vecs, each in the order of hispmv_dot_device for n; d_a is [n, ld_a], d_b is [n, ld_b], 4-byte
+ * aligned, pads never read; d_out 8-byte aligned; work_bytes >= 8 * G * ldw, 16-byte aligned.  n <= 2^20.  Asynchronous on `stream`. */
+int hispmv_dot_multi_device(hispmv_ctx* ctx, int64_t n, int64_t num_vecs, const float* d_a, int64_t ld_a, const float* d_b, int64_t ld_b,
+                            double* d_out, void* d_work, int64_t work_bytes, void* stream);
+/* results: num_vecs of them. */
+int hispmv_cg_multi_device(hispmv_ctx* ctx, int matrix_idx, const float* d_B, int64_t ld_b, float* d_X, int64_t ld_x, int64_t num_vecs,
+                           const float* d_minv, double rtol, int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes,
+                           void* stream, hispmv_krylov_result* results);
+int hispmv_bicgstab_multi_device(hispmv_ctx* ctx, int matrix_idx, const float* d_B, int64_t ld_b, float* d_X, int64_t ld_x, int64_t num_vecs,
+                                 double rtol, int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes, void* stream,
+                                 hispmv_krylov_result* results);
+/* Synchronises `stream` and reads the outcome of a check_every = 0 multi solve of num_vecs columns out of its workspace. */
+int hispmv_krylov_multi_status(hispmv_ctx* ctx, const void* d_work, int64_t num_vecs, void* stream, hispmv_krylov_result* results);
+
 /* ---- getters (HiSpmvHandle getters, spmv-helper.cpp:752-810) ------------------------------------ */
 typedef struct hispmv_matrix_info {
     int32_t rows, cols;
