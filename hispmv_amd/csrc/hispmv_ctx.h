@@ -9,7 +9,9 @@
 //   hispmv_launch.cpp      the forward pass plan, the host-vector path, the transposed and stored-transpose entries, the value
 //                          gradient, the value updates, and the getters that walk the pass plan (linear / value_grad / transpose _info)
 //   hispmv_batch.cpp       hispmv_spmv_device_batch: launch tables, lanes, HIP-graph replay
-//   hispmv_spmm_abi.cpp    the wide-batch entries;  hispmv_krylov_abi.cpp  the solvers;  hispmv_prep_abi.cpp  the host-only hispmv_prep_*
+//   hispmv_spmm_abi.cpp    the wide-batch entries;  hispmv_prep_abi.cpp  the host-only hispmv_prep_*
+//   hispmv_krylov_abi.cpp, hispmv_krylov_multi_abi.cpp   the solvers for one and for several right-hand sides: each its entries, its
+//                          workspace layout and its backend of hispmv_krylov_solve.h, which holds their checks and the one solve loop
 #pragma once
 #include "../../include/hispmv.h"
 

@@ -1,6 +1,7 @@
 // hispmv_krylov.h -- launchers of the Krylov layer's vector kernels (hispmv_krylov.hip): the fixed-order fp64 dot product of fp32
-// vectors and the fused updates of CG, BiCGSTAB and CGLS that keep every scalar on the device.  The solver loops and the workspace
-// layout are hispmv_krylov_abi.cpp's; the arithmetic and the order of every sum are written down in include/hispmv.h.
+// vectors and the fused updates of CG, BiCGSTAB and CGLS that keep every scalar on the device.  The workspace layout is
+// hispmv_krylov_abi.cpp's, the solve loop hispmv_krylov_solve.h's, the scalar rules hispmv_krylov_scalar.h's; the arithmetic and the
+// order of every sum are written down in include/hispmv.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

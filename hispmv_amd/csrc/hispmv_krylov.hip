@@ -3,17 +3,15 @@
 // ... ascending for workgroup g of G = krylov_groups(n); a thread owns 4 consecutive floats of a chunk (one 16-byte access where that
 // vector is 16-byte aligned and the chunk is whole, 4-byte accesses otherwise).  Vector arithmetic is fp32 and unfused
 // (-ffp-contract=off); every scalar is fp64, computed by every workgroup itself from the same partials, hence with the same bits, and
-// rounded once to fp32 before it meets a vector.  No atomics, no tickets: a dot product's partials are summed by the NEXT kernel.
+// rounded once to fp32 before it meets a vector.  No atomics, no tickets: a dot product's partials are summed by the NEXT kernel,
+// which hands the sums to the scalar rule of hispmv_krylov_scalar.h: the arithmetic of every scalar is written there.
 #include <hip/hip_runtime.h>
 
 #include "hispmv_krylov.h"
+#include "hispmv_krylov_scalar.h"
 
 namespace hispmv {
 namespace {
-
-// zero, infinite or NaN: no denominator
-__device__ __forceinline__ bool bad(double d) { return !(d != 0.0 && fabs(d) <= 1.7976931348623157e308); }
-__device__ __forceinline__ bool finite_d(double d) { return fabs(d) <= 1.7976931348623157e308; }
 
 // the vector at p is 16-byte aligned (i is a multiple of 4): decided per vector, so one 4-byte-aligned operand of the caller's does
 // not take the 16-byte accesses from the others of the pass
@@ -90,7 +88,6 @@ __device__ __forceinline__ void store_state(double* s_out, const double S[kKrylo
         for (int i = 0; i < kKrylovState; ++i) s_out[i] = S[i];
     }
 }
-__device__ __forceinline__ bool frozen(const double S[kKrylovState]) { return S[kKsDone] != 0.0 || S[kKsBreakdown] != 0.0; }
 
 // f(i, m) for every chunk of this workgroup, ascending: i = the thread's first element, m = how many of its 4 lie below n
 template <class F>
@@ -126,14 +123,10 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_dot_finish_kernel(const
 __global__ __launch_bounds__(kKrylovThreads) void krylov_init_kernel(KrylovStep k) {
     __shared__ double sh[kKrylovThreads];
     double S[kKrylovState];
-#pragma unroll
-    for (int i = 0; i < kKrylovState; ++i) S[i] = 0.0;
     const double b2 = sum_partials(slot_of(k, kSlotB2), groups_of(k.n2), sh);
     const double bb = k.slot_bb == kSlotB2 ? b2 : sum_partials(slot_of(k, k.slot_bb), groups_of(k.n), sh);
-    S[kKsB2] = b2; S[kKsBb] = bb; S[kKsProducts] = k.products; S[kKsAlpha] = 1.0; S[kKsOmega] = 1.0;
-    const bool zero_x = b2 == 0.0;
-    if (zero_x) S[kKsDone] = 1.0;
-    else if (bad(bb) || !finite_d(b2)) S[kKsBreakdown] = 1.0;
+    bool zero_x = false;
+    krylov_rule_init(S, b2, bb, k.products, zero_x);
     store_state(k.s_out, S);
     double acc_rr = 0.0, acc_rz = 0.0;
     for_chunks(k.n, [&](int64_t i, int m) {
@@ -174,8 +167,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_step_dot_kernel(KrylovS
     if (k.first && !frozen(S)) {
         const double rr = sum_partials(slot_of(k, kSlotRr), groups_of(k.n2), sh);
         const double rho = k.slot_rho == kSlotRr ? rr : sum_partials(slot_of(k, k.slot_rho), groups_of(k.n2), sh);
-        S[kKsRr] = rr; S[kKsRho] = rho;
-        if (rr <= k.tol2 * S[kKsBb]) S[kKsDone] = 1.0;
+        krylov_rule_first(S, rr, rho, k.tol2);
     }
     store_state(k.s_out, S);
     double acc1 = 0.0, acc2 = 0.0;
@@ -207,14 +199,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_cg_update_kernel(Krylov
     float a32 = 0.0f;
     if (!frozen(S)) {
         const double den = sum_partials(slot_of(k, kSlotDen), groups_of(k.n), sh);
-        S[kKsDen] = den;
-        if (bad(den) || !finite_d(S[kKsRho])) S[kKsBreakdown] = 1.0;
-        else {
-            const double alpha = S[kKsRho] / den;
-            S[kKsAlpha] = alpha; S[kKsIters] += 1.0;
-            a32 = (float)alpha;
-            act = true;
-        }
+        act = krylov_rule_alpha<false>(S, den, a32);
     }
     store_state(k.s_out, S);
     if (!act) return;
@@ -261,14 +246,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_direction_kernel(Krylov
     if (!frozen(S)) {
         const double rr = sum_partials(slot_of(k, kSlotRr), groups_of(k.n), sh);
         const double rho = k.slot_rho == kSlotRr ? rr : sum_partials(slot_of(k, k.slot_rho), groups_of(k.n), sh);
-        S[kKsRr] = rr;
-        if (rr <= k.tol2 * S[kKsBb]) { S[kKsDone] = 1.0; S[kKsRho] = rho; }
-        else if (bad(S[kKsRho]) || !finite_d(rho)) S[kKsBreakdown] = 1.0;
-        else {
-            b32 = (float)(rho / S[kKsRho]);
-            S[kKsRho] = rho;
-            act = true;
-        }
+        act = krylov_rule_direction(S, rr, rho, k.tol2, b32);
     }
     store_state(k.s_out, S);
     if (!act) return;
@@ -300,14 +278,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_cgls_update_kernel(Kryl
     float a32 = 0.0f;
     if (!frozen(S)) {
         const double den = sum_partials(slot_of(k, kSlotDen), groups_of(k.n2), sh);
-        S[kKsDen] = den;
-        if (bad(den) || !finite_d(S[kKsRho])) S[kKsBreakdown] = 1.0;
-        else {
-            const double alpha = S[kKsRho] / den;
-            S[kKsAlpha] = alpha; S[kKsIters] += 1.0;
-            a32 = (float)alpha;
-            act = true;
-        }
+        act = krylov_rule_alpha<false>(S, den, a32);
     }
     store_state(k.s_out, S);
     if (!act) return;
@@ -349,14 +320,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_bicg_s_kernel(KrylovSte
     float a32 = 0.0f;
     if (!frozen(S)) {
         const double den = sum_partials(slot_of(k, kSlotDen), groups_of(k.n), sh);
-        S[kKsDen] = den;
-        if (bad(den) || bad(S[kKsRho])) S[kKsBreakdown] = 1.0;
-        else {
-            const double alpha = S[kKsRho] / den;
-            S[kKsAlpha] = alpha;
-            a32 = (float)alpha;
-            act = true;
-        }
+        act = krylov_rule_alpha<true>(S, den, a32);
     }
     store_state(k.s_out, S);
     if (!act) return;
@@ -391,17 +355,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_bicg_x_kernel(KrylovSte
         const double ss = sum_partials(slot_of(k, kSlotSs), g, sh);
         const double ts = sum_partials(slot_of(k, kSlotTs), g, sh);
         const double tt = sum_partials(slot_of(k, kSlotTt), g, sh);
-        S[kKsTs] = ts; S[kKsTt] = tt;
-        if (ss <= k.tol2 * S[kKsBb]) {
-            S[kKsRr] = ss; S[kKsDone] = 1.0; S[kKsIters] += 1.0;
-            act = 1;
-        } else if (bad(tt) || bad(ts / tt)) S[kKsBreakdown] = 1.0;
-        else {
-            const double omega = ts / tt;
-            S[kKsOmega] = omega; S[kKsIters] += 1.0;
-            w32 = (float)omega;
-            act = 2;
-        }
+        act = krylov_rule_bicg_omega(S, ss, ts, tt, k.tol2, w32);
     }
     store_state(k.s_out, S);
     if (!act) return;
@@ -452,15 +406,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_bicg_p_kernel(KrylovSte
         const int64_t g = groups_of(k.n);
         const double rr = sum_partials(slot_of(k, kSlotRr), g, sh);
         const double rho = sum_partials(slot_of(k, kSlotRho), g, sh);
-        S[kKsRr] = rr;
-        const double beta = (rho / S[kKsRho]) * (S[kKsAlpha] / S[kKsOmega]);
-        if (rr <= k.tol2 * S[kKsBb]) { S[kKsDone] = 1.0; S[kKsRho] = rho; }
-        else if (!finite_d(beta)) S[kKsBreakdown] = 1.0;
-        else {
-            b32 = (float)beta;
-            S[kKsRho] = rho;
-            act = true;
-        }
+        act = krylov_rule_bicg_beta(S, rr, rho, k.tol2, b32);
     }
     store_state(k.s_out, S);
     if (!act) return;

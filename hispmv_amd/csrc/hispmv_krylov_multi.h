@@ -1,7 +1,7 @@
 // hispmv_krylov_multi.h -- launchers of the multi-right-hand-side Krylov kernels (hispmv_krylov_multi.hip): the vector kernels of
 // hispmv_krylov.h over num_vecs independent columns of feature-major operands [n, ld], lanes across columns.  Column v computes what
 // the single-vector kernels compute for a vector of n elements, bit for bit: the same scalar block (KrylovScalar), the same partial
-// arrays (KrylovSlot), the same order of every sum (include/hispmv.h).  The loops and the workspace are hispmv_krylov_multi_abi.cpp's.
+// arrays (KrylovSlot), the same order of every sum (include/hispmv.h).  The workspace is hispmv_krylov_multi_abi.cpp's, the loop hispmv_krylov_solve.h's.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -11,20 +11,18 @@
 // run over the row lanes, through LDS and wavefront shuffles.  The sum over the G <= 1024 partials of a column is the same tree with leaf t = partials
 // 4 t .. 4 t + 3, and every workgroup sums the partials of ITS columns itself: no finish launch, no atomics, no tickets, no waiting.
 //
-// PER COLUMN: a scalar block (KrylovScalar) with its own done and breakdown.  One thread per column runs the scalar code of the
-// single-vector kernel; a frozen column's updates are no-ops and its loads are skipped where all 4 columns of a thread are frozen.
+// PER COLUMN: a scalar block (KrylovScalar) with its own done and breakdown.  One thread per column runs the scalar rule the
+// single-vector kernel runs (hispmv_krylov_scalar.h); a frozen column's updates are no-ops and its loads are skipped where all 4 columns of a thread are frozen.
 // Vector arithmetic is fp32 and unfused (-ffp-contract=off), scalars are fp64 rounded once.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
 #include "hispmv_krylov_multi.h"
+#include "hispmv_krylov_scalar.h"
 
 namespace hispmv {
 namespace {
-
-__device__ __forceinline__ bool bad(double d) { return !(d != 0.0 && fabs(d) <= 1.7976931348623157e308); }
-__device__ __forceinline__ bool finite_d(double d) { return fabs(d) <= 1.7976931348623157e308; }
 
 // the widest access every row of an operand [n, ld] at p allows a lane of 4 columns: 4, 2 or 1 floats
 __device__ __forceinline__ int width_of(const void* p, int64_t ld) {
@@ -185,7 +183,7 @@ template <int CLB>
 __device__ __forceinline__ bool load_frozen(const Geo<CLB>& g, const KrylovMultiStep& K, Shared& sh, bool lm[4]) {
     if (g.tid < Geo<CLB>::TW) {
         const int c = g.col0 + g.tid;
-        sh.frz[g.tid] = c < K.m ? (K.s_in[(int64_t)c * kKrylovState + kKsDone] != 0.0 || K.s_in[(int64_t)c * kKrylovState + kKsBreakdown] != 0.0) : 1;
+        sh.frz[g.tid] = c < K.m ? frozen(K.s_in + (int64_t)c * kKrylovState) : 1;
         sh.act[g.tid] = 0; sh.f1[g.tid] = 0.0f; sh.f2[g.tid] = 0.0f;
     }
     __syncthreads();
@@ -210,7 +208,6 @@ __device__ __forceinline__ void scalar_phase(const Geo<CLB>& g, const KrylovMult
     }
     __syncthreads();
 }
-__device__ __forceinline__ bool frozen(const double* S) { return S[kKsDone] != 0.0 || S[kKsBreakdown] != 0.0; }
 
 // f(row, off) for the rows of leaf t that lie below n; off = row * ldw + the lane's first column
 template <int CLB, class F>
@@ -275,9 +272,7 @@ __global__ __launch_bounds__(kKrylovThreads) void km_init_kernel(KrylovMultiStep
     K.s_in = nullptr;
     scalar_phase(g, K, [&](int lc, double* S) {
         const double b2 = sh.sum[Geo<CLB>::at(0, lc)];
-        S[kKsB2] = b2; S[kKsBb] = b2; S[kKsProducts] = K.products; S[kKsAlpha] = 1.0; S[kKsOmega] = 1.0;
-        if (b2 == 0.0) { S[kKsDone] = 1.0; sh.act[lc] = 1; }
-        else if (bad(b2)) S[kKsBreakdown] = 1.0;
+        krylov_rule_init(S, b2, b2, K.products, sh.act[lc]);
     });
     bool zx[4], any_zx = false;
 #pragma unroll
@@ -341,8 +336,7 @@ __global__ __launch_bounds__(kKrylovThreads) void km_step_dot_kernel(KrylovMulti
         if (!K.first || frozen(S)) return;
         const double rr = sh.sum[Geo<CLB>::at(0, lc)];
         const double rho = same ? rr : sh.sum[Geo<CLB>::at(1, lc)];
-        S[kKsRr] = rr; S[kKsRho] = rho;
-        if (rr <= K.tol2 * S[kKsBb]) S[kKsDone] = 1.0;
+        krylov_rule_first(S, rr, rho, K.tol2);
     });
     double acc[8];
 #pragma unroll
@@ -380,13 +374,8 @@ __global__ __launch_bounds__(kKrylovThreads) void km_cg_update_kernel(KrylovMult
     scalar_phase(g, K, [&](int lc, double* S) {
         if (frozen(S)) return;
         const double den = sh.sum[Geo<CLB>::at(0, lc)];
-        S[kKsDen] = den;
-        if (bad(den) || !finite_d(S[kKsRho])) S[kKsBreakdown] = 1.0;
-        else {
-            const double alpha = S[kKsRho] / den;
-            S[kKsAlpha] = alpha; S[kKsIters] += 1.0;
-            sh.f1[lc] = (float)alpha; sh.act[lc] = 1;
-        }
+        float a32;
+        if (krylov_rule_alpha<false>(S, den, a32)) { sh.f1[lc] = a32; sh.act[lc] = 1; }
     });
     bool act[4], any_act = false;
     float a32[4];
@@ -448,14 +437,8 @@ __global__ __launch_bounds__(kKrylovThreads) void km_direction_kernel(KrylovMult
         if (frozen(S)) return;
         const double rr = sh.sum[Geo<CLB>::at(0, lc)];
         const double rho = same ? rr : sh.sum[Geo<CLB>::at(1, lc)];
-        S[kKsRr] = rr;
-        if (rr <= K.tol2 * S[kKsBb]) { S[kKsDone] = 1.0; S[kKsRho] = rho; }
-        else if (bad(S[kKsRho]) || !finite_d(rho)) S[kKsBreakdown] = 1.0;
-        else {
-            sh.f1[lc] = (float)(rho / S[kKsRho]);
-            S[kKsRho] = rho;
-            sh.act[lc] = 1;
-        }
+        float b32;
+        if (krylov_rule_direction(S, rr, rho, K.tol2, b32)) { sh.f1[lc] = b32; sh.act[lc] = 1; }
     });
     bool act[4], any_act = false;
     float b32[4];
@@ -496,13 +479,8 @@ __global__ __launch_bounds__(kKrylovThreads) void km_bicg_s_kernel(KrylovMultiSt
     scalar_phase(g, K, [&](int lc, double* S) {
         if (frozen(S)) return;
         const double den = sh.sum[Geo<CLB>::at(0, lc)];
-        S[kKsDen] = den;
-        if (bad(den) || bad(S[kKsRho])) S[kKsBreakdown] = 1.0;
-        else {
-            const double alpha = S[kKsRho] / den;
-            S[kKsAlpha] = alpha;
-            sh.f1[lc] = (float)alpha; sh.act[lc] = 1;
-        }
+        float a32;
+        if (krylov_rule_alpha<true>(S, den, a32)) { sh.f1[lc] = a32; sh.act[lc] = 1; }
     });
     bool act[4], any_act = false;
     float a32[4];
@@ -545,16 +523,10 @@ __global__ __launch_bounds__(kKrylovThreads) void km_bicg_x_kernel(KrylovMultiSt
         sh.f1[lc] = (float)S[kKsAlpha];
         if (frozen(S)) return;
         const double ss = sh.sum[Geo<CLB>::at(0, lc)], ts = sh.sum[Geo<CLB>::at(1, lc)], tt = sh.sum[Geo<CLB>::at(2, lc)];
-        S[kKsTs] = ts; S[kKsTt] = tt;
-        if (ss <= K.tol2 * S[kKsBb]) {
-            S[kKsRr] = ss; S[kKsDone] = 1.0; S[kKsIters] += 1.0;
-            sh.act[lc] = 1;
-        } else if (bad(tt) || bad(ts / tt)) S[kKsBreakdown] = 1.0;
-        else {
-            const double omega = ts / tt;
-            S[kKsOmega] = omega; S[kKsIters] += 1.0;
-            sh.f2[lc] = (float)omega; sh.act[lc] = 2;
-        }
+        float w32;
+        const int act = krylov_rule_bicg_omega(S, ss, ts, tt, K.tol2, w32);
+        if (act) sh.act[lc] = act;
+        if (act == 2) sh.f2[lc] = w32;
     });
     int act[4];          // 1 the half step, 2 the whole
     bool any_act = false, any_whole = false;
@@ -623,15 +595,7 @@ __global__ __launch_bounds__(kKrylovThreads) void km_bicg_p_kernel(KrylovMultiSt
         sh.f2[lc] = (float)S[kKsOmega];
         if (frozen(S)) return;
         const double rr = sh.sum[Geo<CLB>::at(0, lc)], rho = sh.sum[Geo<CLB>::at(1, lc)];
-        S[kKsRr] = rr;
-        const double beta = (rho / S[kKsRho]) * (S[kKsAlpha] / S[kKsOmega]);
-        if (rr <= K.tol2 * S[kKsBb]) { S[kKsDone] = 1.0; S[kKsRho] = rho; }
-        else if (!finite_d(beta)) S[kKsBreakdown] = 1.0;
-        else {
-            sh.f1[lc] = (float)beta;
-            S[kKsRho] = rho;
-            sh.act[lc] = 1;
-        }
+        if (krylov_rule_bicg_beta(S, rr, rho, K.tol2, sh.f1[lc])) sh.act[lc] = 1;
     });
     bool act[4], any_act = false;
     float b32[4], w32[4];

@@ -17,7 +17,7 @@ Systems: the small tridiagonal system of the tests (n = 4099) and stand-ins of h
 (the stand-ins carry random values; the diagonal makes them systems a Krylov method can be timed on -- "spd" rows are the symmetric
 part's positive definite kind, not symmetrised).  CGLS runs over a stored transpose (set_transposable("companion")).
 
-    python tools/krylov_bench.py [--iters 48] [--rounds 5] [--out profiles/krylov_bench.json]
+    python tools/krylov_bench.py [--iters 48] [--rounds 5] [--systems a,b] [--out profiles/krylov_bench.json]
 """
 from __future__ import annotations
 
@@ -118,6 +118,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=48)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--systems", default="")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "krylov_bench.json"))
     args = ap.parse_args()
     import torch
@@ -125,8 +126,11 @@ def main():
     from hispmv_amd import solvers
     dev = torch.device("cuda", 0)
     K = args.iters
+    only = set(filter(None, args.systems.split(",")))
     results = []
     for name, n, r, c, v in systems():
+        if only and name not in only:
+            continue
         h = pyhispmv.FpgaHandle("bench.xclbin", 0, 24, 1, 1, 2, 5, True, False, True)
         h.set_transposable("companion")
         idx = h.create_sparse_handle(r, c, v, n, n)

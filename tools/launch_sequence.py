@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The kernel launches of a fixed list of multi-vector calls, to compare two builds of the library launch for launch.
+"""The kernel launches of a fixed list of multi-vector and Krylov calls, to compare two builds of the library launch for launch.
 
     rocprofv3 --kernel-trace --output-format csv -d A -- python tools/launch_sequence.py run      # HISPMV_LIB = the one build
     rocprofv3 --kernel-trace --output-format csv -d B -- python tools/launch_sequence.py run      # ... the other, a process of its own
@@ -9,7 +9,13 @@
   linear_device    on a one-part slice stream, a slice stream of 8 column parts, a tile stream and a dense handle;
   linear_device_t  on handles whose stored transpose is a one-part slice stream, 8 column parts and a tile stream;
                    both for B in 1, 2, 3, 5, 9, beta 0 and 1, d_x aligned and moved by one float, _t with a shared and a per-vector bias;
-  spmm_device, spmm_device_t and their bf16 forms (5 and 130 vectors), value_grad_device on a slice stream and a dense handle.
+  spmm_device, spmm_device_t and their bf16 forms (5 and 130 vectors), value_grad_device on a slice stream and a dense handle;
+  the Krylov layer on tridiagonal systems of n = 1025 (two chunks, a one-element tail) and 4099: cg_device without and with minv,
+                   bicgstab_device, cgls_device over a stored transpose, and cg_multi_device without and with minv and
+                   bicgstab_multi_device for 5 and 65 right-hand sides (a second column tile of one column), each with rtol = 0 and
+                   (max_iters, check_every) = (4, 0), (4, 3) -- a look inside the loop and one behind it -- and (3, 3) -- the last look
+                   is the loop's; every entry once with b = 0 and check_every = 3 (the early return: no product); dot_device and
+                   dot_multi_device at n = 1025.
 It asserts that every handle got the kind it is listed under.  `compare` reads the kernel traces (the CSV columns tools/trace_seq.py
 reads), keeps the library's kernels in dispatch order and compares (kernel name, grid, workgroup, LDS bytes) line by line; exit
 status 1 on a difference."""
@@ -56,6 +62,18 @@ def uniform(rows, cols, nnz, seed, heavy_row=None):
 
 def T(m):
     return dict(m, rows=m["cols"], cols=m["rows"], r=m["c"], c=m["r"])
+
+
+def tridiag(n):
+    """2.5 on the diagonal, -1 beside it: the system of tests/krylov_model.py"""
+    i = np.arange(n, dtype=np.int32)
+    return dict(rows=n, cols=n, r=np.concatenate([i, i[1:], i[:-1]]), c=np.concatenate([i, i[:-1], i[1:]]),
+                v=np.concatenate([np.full(n, 2.5), np.full(2 * (n - 1), -1.0)]).astype(np.float32))
+
+
+KRYLOV_NS = (1025, 4099)
+KRYLOV_MS = (5, 65)
+KRYLOV_LOOPS = ((4, 0), (4, 3), (3, 3))          # (max_iters, check_every)
 
 
 def run():
@@ -157,6 +175,62 @@ def run():
     assert info["tile_stream"]["format"] == 1 and info["tile_stream"]["col_tiles"] == 1 and ci["format"] == 1 and ci["parts"] == 1, (info, ci)
     linear_calls(h, k["tile_stream"], info["tile_stream"], False)
     linear_calls(h, k["stored"], info["stored"], True)
+    h.close()
+
+    # ---- the Krylov layer: square slice streams for CG and BiCGSTAB, single and multi, and one with a stored transpose for CGLS
+    def make_krylov(h):
+        k = {("square", n): sparse(h, tridiag(n)) for n in KRYLOV_NS}
+        h.set_transposable("companion")
+        k.update({("stored", n): sparse(h, tridiag(n)) for n in KRYLOV_NS})
+        return k
+    h, k = context(SLICES, make_krylov)
+
+    def device(a):
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+
+    def workspace(nbytes):
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    for n in KRYLOV_NS:
+        mmax = max(KRYLOV_MS)
+        host = np.random.default_rng(1).uniform(-1, 1, n * mmax)
+        bs = {"b": device(host), "0": device(np.zeros(n * mmax))}
+        minv, x = device(np.full(n, 0.4)), device(np.zeros(n * mmax))
+        singles = [("cg", h.cg_device, ("square", n), {}), ("cg", h.cg_device, ("square", n), dict(d_minv=minv.data_ptr())),
+                   ("bicgstab", h.bicgstab_device, ("square", n), {}), ("cgls", h.cgls_device, ("stored", n), {})]
+        multis = [("cg", h.cg_multi_device, {}), ("cg", h.cg_multi_device, dict(d_minv=minv.data_ptr())), ("bicgstab", h.bicgstab_multi_device, {})]
+
+        def solve(call, idx, work, loops, b, **kw):
+            for max_iters, check_every in loops:
+                x.zero_()
+                torch.cuda.synchronize()
+                call(idx, bs[b].data_ptr(), x.data_ptr(), rtol=0.0, max_iters=max_iters, check_every=check_every, work=work.data_ptr(),
+                     work_bytes=work.numel(), **kw)
+                h.synchronize()
+        for solver, call, key, kw in singles:
+            info = h.krylov_info(k[key], solver)
+            assert info["accepted"], (solver, key, info)
+            work = workspace(info["work_bytes"])
+            solve(call, k[key], work, KRYLOV_LOOPS, "b", **kw)
+            if not kw:
+                solve(call, k[key], work, ((4, 3),), "0")
+        for m in KRYLOV_MS:
+            for solver, call, kw in multis:
+                info = h.krylov_multi_info(k["square", n], solver, m)
+                assert info["accepted"], (solver, m, info)
+                work = workspace(info["work_bytes"])
+                solve(call, k["square", n], work, KRYLOV_LOOPS, "b", num_vecs=m, **kw)
+                if not kw and m == KRYLOV_MS[0]:
+                    solve(call, k["square", n], work, ((4, 3),), "0", num_vecs=m)
+    n = KRYLOV_NS[0]
+    out, work = torch.zeros(max(KRYLOV_MS), dtype=torch.float64, device=dev), workspace(8 * 2 * 68)          # 2 chunks x ld 68
+    for m in (0,) + KRYLOV_MS:          # 0: dot_device
+        a = device(np.random.default_rng(2).uniform(-1, 1, n * max(m, 1)))
+        torch.cuda.synchronize()
+        if m:
+            h.dot_multi_device(n, m, a.data_ptr(), a.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel())
+        else:
+            h.dot_device(n, a.data_ptr(), a.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel())
+        h.synchronize()
     h.close()
     print("launch_sequence: all calls issued")
 
