@@ -1,8 +1,10 @@
 """Solves a generated symmetric positive definite system with CG and a generated least-squares problem with CGLS on loaded handles
 (hispmv_amd.solvers), and prints iterations and residuals next to the fp64 residuals computed on the host.  --rhs M also solves the
 SPD system for M right-hand sides in one call (solvers.cg_multi) and prints iterations and the true residual of every column.
+--gmres also solves a convection-diffusion system on the same grid (Peclet number 1000, strongly non-normal) with restarted GMRES
+(solvers.gmres, --restart M) and with BiCGSTAB under the same budget of products, and prints both outcomes.
 
-    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M]
+    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]]
 """
 from __future__ import annotations
 
@@ -25,11 +27,24 @@ def laplacian_coo(m):
     return np.concatenate(r), np.concatenate(c), np.concatenate(v).astype(np.float32)
 
 
+def convdiff_coo(m, pe=1000.0):
+    """Convection-diffusion on an m x m grid by central differences, convection along the fast index, as COO triplets."""
+    k = np.arange(m * m)
+    i, j = k // m, k % m
+    a = pe / (m + 1) / 2
+    r, c, v = [k], [k], [np.full(m * m, 4.0)]
+    for ok, off, val in ((i > 0, -m, -1.0), (i < m - 1, m, -1.0), (j > 0, -1, -(1 + a)), (j < m - 1, 1, -(1 - a))):
+        r.append(k[ok]); c.append(k[ok] + off); v.append(np.full(int(ok.sum()), val))
+    return np.concatenate(r), np.concatenate(c), np.concatenate(v).astype(np.float32)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--rtol", type=float, default=1e-6)
     ap.add_argument("--rhs", type=int, default=0, help="also solve the SPD system for this many right-hand sides in one call")
+    ap.add_argument("--gmres", action="store_true", help="also solve a convection-diffusion system with restarted GMRES and with BiCGSTAB")
+    ap.add_argument("--restart", type=int, default=10, help="basis vectors of a GMRES cycle, 1 .. 64")
     args = ap.parse_args()
     import torch
     import pyhispmv
@@ -49,6 +64,9 @@ def main():
     if args.rhs > 0:
         h.set_transposable(True)             # the multi solves run over spmm_device, which takes slice streams: keep that format
         spd_wide = h.create_sparse_handle(r, c, v, n, n)
+    if args.gmres:
+        gr, gc, gv = convdiff_coo(args.grid)
+        cd = h.create_sparse_handle(gr, gc, gv, n, n)
     h.load_matrices()
 
     dev = torch.device("cuda", 0)
@@ -72,6 +90,18 @@ def main():
             true = np.linalg.norm(B[:, j] - Ax) / np.linalg.norm(B[:, j])
             print(f"  column {j:3d}: {info['status'][j]}, {info['iterations'][j]} iterations, recursive residual {info['relres'][j]:.3e}, true {true:.3e}")
             assert info["status"][j] == "CONVERGED"          # (a smooth column's true fp32 residual stalls near cond(A) * 2^-24, above the recursive one)
+
+    if args.gmres:          # one product per inner iteration and a residual that cannot grow inside a cycle, against two products per
+        b = rng.uniform(-1, 1, n).astype(np.float32)          # iteration and no such promise
+        tb = torch.from_numpy(b).to(dev)
+        budget = 20 * args.grid
+        for name, (x, info) in (("GMRES", solvers.gmres(h, cd, tb, restart=args.restart, rtol=10 * args.rtol, max_iters=budget)),
+                                ("BiCGSTAB", solvers.bicgstab(h, cd, tb, rtol=10 * args.rtol, max_iters=budget // 2))):
+            x64 = x.cpu().numpy().astype(np.float64)
+            true = np.linalg.norm(b - np.bincount(gr, weights=gv.astype(np.float64) * x64[gc], minlength=n)) / np.linalg.norm(b)
+            print(f"{name:8s} {n} x {n}, convection-diffusion: {info['status']}, {info['iterations']} iterations, {info['products']} products, "
+                  f"recursive residual {info['relres']:.3e}, true {true:.3e}")
+            assert name != "GMRES" or (info["status"] == "CONVERGED" and true < 1000 * args.rtol)
 
     b = rng.uniform(-1, 1, rows).astype(np.float32)
     x, info = solvers.cgls(h, ls, torch.from_numpy(b).to(dev), rtol=args.rtol)

@@ -40,6 +40,7 @@ HISPMV_KRYLOV_BICGSTAB = 1
 HISPMV_KRYLOV_CGLS = 2
 KRYLOV_SOLVERS = {"cg": HISPMV_KRYLOV_CG, "bicgstab": HISPMV_KRYLOV_BICGSTAB, "cgls": HISPMV_KRYLOV_CGLS}
 KRYLOV_STATUS = ("CONVERGED", "MAX_ITERS", "BREAKDOWN", "IN_FLIGHT")
+HISPMV_GMRES_MAX_RESTART = 64
 
 
 class MatrixInfo(C.Structure):
@@ -139,6 +140,10 @@ SIGNATURES = {
     "hispmv_bicgstab_multi_device": (C.c_int, [_p, C.c_int, _p, C.c_int64, _p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p,
                                                C.POINTER(KrylovResult)]),
     "hispmv_krylov_multi_status": (C.c_int, [_p, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
+    "hispmv_prep_gmres": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _i64p]),
+    "hispmv_gmres_info": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i64p]),
+    "hispmv_dot_basis_device": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_int64, _p, _p, _p, C.c_int64, _p]),
+    "hispmv_gmres_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
     "hispmv_prep_vector_widths": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),

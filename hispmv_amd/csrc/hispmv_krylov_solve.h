@@ -1,5 +1,6 @@
 // hispmv_krylov_solve.h -- what the single-vector and the multi-right-hand-side Krylov entries share on the host
-// (hispmv_krylov_abi.cpp, hispmv_krylov_multi_abi.cpp; included by these two only): the solver tables, the bookkeeping of the two scalar
+// (hispmv_krylov_abi.cpp, hispmv_krylov_multi_abi.cpp; hispmv_gmres_abi.cpp takes the checks, KrylovBlocks and KrylovSolve and has a
+// loop of its own): the solver tables, the bookkeeping of the two scalar
 // blocks, the argument checks with their texts, the owner of the pinned buffer, and krylov_run, THE order of launches of a solve.  A
 // backend (the Solve struct of either file) derives from KrylovSolve and supplies its vectors, its products, its launchers and how it
 // looks at the device and writes results; the workspace layouts stay beside their backend.

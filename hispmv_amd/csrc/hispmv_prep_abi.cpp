@@ -3,6 +3,7 @@
 // HiSpmvHandle::getPreparedMtx (common/src/spmv-helper.cpp:800-802).  (hispmv_prep_from_coo_device is the one entry here that
 // touches the GPU.)
 #include "hispmv_ctx.h"
+#include "hispmv_gmres.h"
 
 using namespace hispmv;
 
@@ -369,4 +370,13 @@ HISPMV_API const void* hispmv_prep_value_array(const hispmv_prep* p, int which) 
         case 4: return p->vl_kinds.data();
         default: return nullptr;
     }
+}
+
+// The workspace rule of restarted GMRES (hispmv_gmres.h: gmres_layout), which hispmv_gmres_info and hispmv_gmres_device follow.
+HISPMV_API int hispmv_prep_gmres(int64_t n, int64_t restart, int with_minv, int64_t out[8]) {
+    if (!out || n < 0 || restart < 1 || restart > kGmresMaxRestart) return HISPMV_EINVAL;
+    const GmresLayout l = gmres_layout(n, restart, with_minv != 0);
+    out[0] = l.work_bytes; out[1] = l.off_v; out[2] = l.stride; out[3] = l.groups; out[4] = kGmresDotTile;
+    out[5] = kGmresLaunchesInner; out[6] = kGmresLaunchesCycle; out[7] = restart + 1;
+    return HISPMV_OK;
 }

@@ -531,6 +531,38 @@ class FpgaHandle:
         self._check(lib.hispmv_krylov_multi_status(self._ctx, C.c_void_p(work), int(num_vecs), C.c_void_p(stream), res))
         return [self._krylov_result(r) for r in res]
 
+    # -- restarted GMRES (hispmv_gmres_abi.cpp; hispmv_amd.solvers.gmres wraps these) --------------------------------------------------
+    def gmres_info(self, matrix_idx: int, restart: int = 30, with_minv: bool = False) -> dict:
+        """{"accepted", "work_bytes", "launches_per_iteration", "launches_per_cycle", "products_per_iteration", "v_offset", "stride",
+        "n"} of GMRES(restart) on a handle (hispmv_gmres_info): the workspace, the vector kernels of an inner iteration and of a cycle
+        besides, where the workspace keeps the basis and how many floats lie between two basis vectors; zeros for a handle that is not
+        loaded or not square."""
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_gmres_info(self._ctx, int(matrix_idx), int(restart), int(bool(with_minv)), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError(f"restart must be 1 .. {_lib.HISPMV_GMRES_MAX_RESTART}")
+            raise IndexError("Matrix idx out of range")
+        return {"accepted": bool(out[0]), "work_bytes": int(out[1]), "launches_per_iteration": int(out[2]), "launches_per_cycle": int(out[3]),
+                "products_per_iteration": int(out[4]), "v_offset": int(out[5]), "stride": int(out[6]), "n": int(out[7])}
+
+    def dot_basis_device(self, n: int, k: int, d_V: int, d_w: int, d_out: int, work: int, work_bytes: int, ld_v=None, stream: int = 0) -> None:
+        """d_out[i] (float64, device) = (V_i, w) for the k <= 65 float32 vectors V_i = d_V + i * ld_v (default ld_v = n) and w, each
+        value bit for bit dot_device's (hispmv_dot_basis_device).  `work` points at work_bytes >= 8 * k * prep.krylov_groups(n) bytes,
+        16-byte aligned.  Asynchronous on `stream`."""
+        self._check(lib.hispmv_dot_basis_device(self._ctx, int(n), int(k), C.c_void_p(d_V), int(n if ld_v is None else ld_v), C.c_void_p(d_w),
+                                                C.c_void_p(d_out), C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def gmres_device(self, matrix_idx: int, d_b: int, d_x: int, d_minv: int = 0, restart: int = 30, rtol: float = 1e-6, max_iters: int = 1000,
+                     check_every: int = 8, work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """Restarted GMRES(restart) for a square handle, one product per inner iteration (hispmv_gmres_device); d_minv is 0 or an
+        inverse diagonal used as a right preconditioner; max_iters counts inner iterations.  Result and exceptions as cg_device; a
+        restart outside 1 .. 64 raises ValueError."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_gmres_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(d_minv), int(restart), float(rtol),
+                                            int(max_iters), int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
+        return self._krylov_result(res)
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

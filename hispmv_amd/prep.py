@@ -307,6 +307,18 @@ def krylov_multi(n: int, num_vecs: int) -> dict:
     return {"groups": int(out[0]), "ld": int(out[1]), "state_bytes": int(out[2]), "partial_bytes": int(out[3])}
 
 
+def gmres(n: int, restart: int, with_minv: bool = False) -> dict:
+    """The workspace rule of restarted GMRES (hispmv_prep_gmres), host-only: {"work_bytes", "v_offset", "stride", "groups", "dot_tile",
+    "launches_per_iteration", "launches_per_cycle", "basis_vectors"} for a system of n unknowns -- the bytes a solve needs, where the
+    basis lies and how many floats apart its vectors are, the partials of a dot product, how many basis vectors one pass of the
+    multi-dot kernel accumulates per thread, the vector kernels of an inner iteration and of a cycle besides, and restart + 1."""
+    out = (C.c_int64 * 8)()
+    if lib.hispmv_prep_gmres(int(n), int(restart), int(bool(with_minv)), out) != HISPMV_OK:
+        raise ValueError("hispmv_prep_gmres: n >= 0 and 1 <= restart <= 64")
+    keys = ("work_bytes", "v_offset", "stride", "groups", "dot_tile", "launches_per_iteration", "launches_per_cycle", "basis_vectors")
+    return dict(zip(keys, (int(x) for x in out)))
+
+
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 

@@ -13,7 +13,9 @@ call on the default stream returns with the solve in flight on the context's str
 overwritten, before ``handle.krylov_status(info["work"].data_ptr(), 0)`` or ``handle.synchronize()`` has returned.
 
 Several right-hand sides: ``cg_multi`` and ``bicgstab_multi`` solve the columns of B [n, m] as m independent solves that share their
-launches (FpgaHandle.cg_multi_device / bicgstab_multi_device over spmm_device's products); same streams, same rule."""
+launches (FpgaHandle.cg_multi_device / bicgstab_multi_device over spmm_device's products); same streams, same rule.
+
+Restarted GMRES: ``gmres`` (FpgaHandle.gmres_device) for square non-symmetric systems, one product per inner iteration."""
 from __future__ import annotations
 
 import torch
@@ -88,6 +90,36 @@ def cgls(handle, idx: int, b, x0=None, *, rtol: float = 1e-6, max_iters=None, ch
     """min ||b - A x|| for a handle of any shape by CGLS, stopping on ||A^T r|| <= rtol ||A^T b||; the handle must be one spmv_device_t
     accepts (create it under set_transposable(...)); arguments and result as `cg`."""
     return _solve("cgls", handle, idx, b, x0, None, rtol, max_iters, check_every, work)
+
+
+def workspace_gmres(handle, idx: int, restart: int, with_minv: bool, device) -> torch.Tensor:
+    """A workspace tensor for GMRES(restart) on handle `idx` (gmres_info's work_bytes)."""
+    info = handle.gmres_info(idx, restart, with_minv)
+    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+
+
+def gmres(handle, idx: int, b, x0=None, *, minv=None, restart: int = 30, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+    """Solves A x = b for a square, non-symmetric handle by restarted GMRES(restart) on torch's current stream: one product per inner
+    iteration, the basis orthogonalised by two passes of classical Gram-Schmidt in the library's fused kernels.  minv is an optional
+    inverse diagonal used as a right preconditioner; max_iters counts inner iterations (default twice the dimension); result and
+    streams as `cg`."""
+    m = handle.matrix_info(idx)
+    b = _vector(b, "b", m["rows"])
+    x = torch.zeros(m["cols"], dtype=torch.float32, device=b.device) if x0 is None else _vector(x0, "x0", m["cols"]).clone()
+    if minv is not None:
+        minv = _vector(minv, "minv", m["rows"])
+    if max_iters is None:
+        max_iters = 2 * max(m["rows"], m["cols"])
+    if work is None:
+        work = workspace_gmres(handle, idx, restart, minv is not None, b.device)
+
+    def call(stream):
+        return handle.gmres_device(idx, b.data_ptr(), x.data_ptr(), 0 if minv is None else minv.data_ptr(), restart=restart, rtol=rtol,
+                                   max_iters=max_iters, check_every=check_every, work=work.data_ptr(),
+                                   work_bytes=work.numel() * work.element_size(), stream=stream)
+    info = _launch(handle, b.device, check_every, call)
+    info["work"] = work          # check_every = 0: handle.krylov_status(info["work"].data_ptr(), stream) reads the outcome
+    return x, info
 
 
 # ---- several right-hand sides -------------------------------------------------------------------------------------------------------

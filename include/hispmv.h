@@ -706,6 +706,62 @@ int hispmv_bicgstab_multi_device(hispmv_ctx* ctx, int matrix_idx, const float* d
 /* Synchronises `stream` and reads the outcome of a check_every = 0 multi solve of num_vecs columns out of its workspace. */
 int hispmv_krylov_multi_status(hispmv_ctx* ctx, const void* d_work, int64_t num_vecs, void* stream, hispmv_krylov_result* results);
 
+/* ---- Restarted GMRES(m) on loaded handles ---------------------------------------------------------------------------------------------
+ * A x = b for a square, non-symmetric handle with ONE product per inner iteration and a residual that never grows inside a cycle.
+ * The products are hispmv_spmv_device's launches, written straight into the basis; everything between two products is a pass over
+ * the basis in four vector kernels.  Arguments, errors, the stream rule and "ONE solve per handle in flight" are hispmv_cg_device's,
+ * plus restart = m, 1 .. HISPMV_GMRES_MAX_RESTART.  d_minv is NULL or an inverse diagonal used as a RIGHT preconditioner:
+ * A diag(minv) u = b, x = diag(minv) u; the residual the stopping rule sees stays that of A x = b.
+ *
+ * THE ARITHMETIC.  Every dot product is hispmv_dot_device's for n.  Scalars are fp64 with IEEE / and sqrt, unfused; a scalar is
+ * rounded ONCE to fp32 before it meets a vector; vector arithmetic is fp32, one rounding per operation.  bb = (b, b), tol2 = rtol^2.
+ * START OF A CYCLE of m = min(restart, iterations left) columns: r = b - A x (the product with alpha -1, beta 1, bias b, into basis
+ *   slot 0); rr = (r, r); rr not finite: breakdown; else rr <= tol2 * bb: done (b == 0 gives x = 0, CONVERGED, 0 iterations, as in CG);
+ *   else beta = sqrt(rr), v_0 = f32(1 / beta) * r in place, g_res[0] = beta, cols = 0.
+ * INNER STEP j: z = minv * v_j (or v_j); w = A z, written into basis slot j + 1.  CGS2: h1_i = (v_i, w) for i <= j; then
+ *   w = w - f32(h1_i) * v_i for i ascending (t = h32 * v is rounded before w = w - t); h2_i = (v_i, w); the same subtraction with h2;
+ *   h_i = h1_i + h2_i; ww = (w, w); hn = sqrt(ww).  A h1_i, h2_i or ww that is not finite sets breakdown in the kernel that sums it,
+ *   before that kernel writes a vector.  The earlier rotations, i < j ascending: t = c_i h_i + s_i h_{i+1};
+ *   h_{i+1} = c_i h_{i+1} - s_i h_i; h_i = t.  The new one: d = sqrt(h_j h_j + hn hn); d zero or not finite: breakdown; else
+ *   c_j = h_j / d, s_j = hn / d, R[i][j] = h_i (i < j), R[j][j] = d, g_fin[j] = c_j g_res[j], g_res[j+1] = -(s_j g_res[j]).  Then
+ *   cols = j + 1, iterations += 1, rr = g_res[j+1]^2; rr <= tol2 * bb: done (a lucky breakdown hn == 0 lands here); else
+ *   v_{j+1} = f32(1 / hn) * w in place.
+ * CLOSE OF A CYCLE, acting once and only if cols > 0: back substitution in fp64, i descending: s = g_fin[i]; for k = i + 1 .. cols - 1
+ *   ascending s = s - R[i][k] y_k; y_i = s / R[i][i].  u = f32(y_0) * v_0, then u = u + f32(y_i) * v_i for i ascending;
+ *   x = x + minv * u (or x + u); cols = 0.
+ * FREEZE: after done or breakdown every kernel copies the scalar block and writes no vector (the products still run and are ignored);
+ * the close still applies the cols columns completed before, so iterations counts exactly the columns that entered x.
+ * relres = sqrt(rr / bb), from the recomputed residual at a restart and from |g_res| inside a cycle.  products of a check_every = 0
+ * call = cycles + max_iters.  The host looks every check_every inner iterations, counted across cycles, and once at the end; the close
+ * of the cycle a look finds ended is enqueued and waited for before the call returns, so x, iterations and relres do not depend on
+ * check_every.  Between looks the loop adds no allocation, synchronous copy or synchronisation.
+ *
+ * WORKSPACE (hispmv_gmres_info: work_bytes, 16-byte aligned; the rule is hispmv_prep_gmres's): the two 128-byte scalar blocks of the
+ * other solvers first -- rr, bb, b2, iterations, done, breakdown and products keep their slots, slot 13 holds j and slot 14 cols,
+ * and the last kernel of a check_every = 0 call writes block 0, so hispmv_krylov_status reads a GMRES workspace unchanged -- then
+ * c, s, g_fin, g_res, h1, h (66 doubles each), R (64 x 64 doubles, row-major), the partials, the restart + 1 basis vectors
+ * (ceil(n / 4) * 4 floats apart) and, with minv, one vector z.  No kernel reads a word one of its own workgroups writes: g_fin and
+ * g_res are two arrays for that reason, and only workgroup 0 writes the Givens data and the block.
+ * Out of scope: several right-hand sides, flexible or left preconditioning, restart above 64, dot products fused into the product's
+ * stores, HIP-graph capture, sharding over devices, fp64 vectors. */
+#define HISPMV_GMRES_MAX_RESTART 64
+/* The workspace rule on the host (no device needed): out = {work_bytes, byte offset of the basis V, floats between two basis vectors,
+ * groups (hispmv_prep_krylov_groups(n)), dot_tile (basis vectors one pass of the multi-dot kernel accumulates per thread), vector
+ * kernels per inner iteration, vector kernels per cycle besides, basis vectors held (restart + 1)}.  n < 0 or restart outside
+ * 1 .. 64 -> HISPMV_EINVAL. */
+int hispmv_prep_gmres(int64_t n, int64_t restart, int with_minv, int64_t out[8]);
+/* out = {accepted, work_bytes, launches per inner iteration, launches per cycle besides, products per inner iteration (1), byte offset
+ * of V, vector stride in floats, n}; zeros for a handle that is not loaded or not square. */
+int hispmv_gmres_info(const hispmv_ctx* ctx, int matrix_idx, int64_t restart, int with_minv, int64_t out[8]);
+/* d_out[i] = (V_i, w), i < k <= 65, V_i = d_V + i * ld_v: each value bit for bit hispmv_dot_device(n, V_i, w), all from one pass that
+ * loads w once per dot_tile basis vectors.  Operands 4-byte aligned (16-byte accesses per vector where that vector is 16-byte
+ * aligned), d_out 8-byte aligned, work_bytes >= 8 * k * groups, 16-byte aligned.  Asynchronous on `stream`. */
+int hispmv_dot_basis_device(hispmv_ctx* ctx, int64_t n, int64_t k, const float* d_V, int64_t ld_v, const float* d_w, double* d_out,
+                            void* d_work, int64_t work_bytes, void* stream);
+int hispmv_gmres_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float* d_x, const float* d_minv, int64_t restart, double rtol,
+                        int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes, void* stream,
+                        hispmv_krylov_result* result);
+
 /* ---- getters (HiSpmvHandle getters, spmv-helper.cpp:752-810) ------------------------------------ */
 typedef struct hispmv_matrix_info {
     int32_t rows, cols;
