@@ -224,9 +224,9 @@ static int build_batch_plan_with(hispmv_ctx* c, hispmv_ctx::BatchPlan& plan, int
                     const size_t one = slice_lds_bytes(*d);
                     lds = std::max(lds, d->block_threads == 256 ? 4 * one : one);
                     strays = strays || d->has_strays;
-                    // a handle with half groups (bf16 value storage): spmv_step_kernel has no body that reads them.  By default the call
-                    // runs as separate grids (what HISPMV_STEP_KERNEL=0 does); under hispmv_set_step_half / HISPMV_STEP_HALF=1 it
-                    // qualifies and the launch takes spmv_step_half_kernel (opt-in, with the measurements)
+                    // a handle with half groups (bf16 value storage): spmv_step_kernel<., HALF = 0> has no body that reads them.  By default
+                    // the call runs as separate grids (what HISPMV_STEP_KERNEL=0 does); under hispmv_set_step_half / HISPMV_STEP_HALF=1 it
+                    // qualifies and the launch takes spmv_step_kernel<., HALF = 1> (opt-in, with the measurements)
                     ok = ok && (c->step_half || !d->has_half);
                     half = half || d->has_half;
                 }
@@ -716,7 +716,7 @@ HISPMV_API int hispmv_batch_call_info(hispmv_ctx* c, int64_t out[4]) {
     return HISPMV_OK;
 }
 
-// The switch of spmv_step_half_kernel (include/hispmv.h).  No device call: the state is part of a cached batch plan's key, so a call issued
+// The switch of spmv_step_kernel<., HALF = 1> (include/hispmv.h).  No device call: the state is part of a cached batch plan's key, so a call issued
 // after the setter finds (or builds) the plan of the new state, and the plans of the other state stay valid for the work that is in flight.
 HISPMV_API int hispmv_set_step_half(hispmv_ctx* c, int enable) {
     if (!c) return HISPMV_EINVAL;

@@ -132,7 +132,7 @@ struct hispmv_ctx {
     // and tiles as items of ONE queue drawn by one persistent workgroup per CU.  HISPMV_STEP_KERNEL=0: the grids of rounds 1 - 4 on two lanes.
     bool step_kernel = true;
     // hispmv_set_step_half / HISPMV_STEP_HALF=1 (opt-in): a call with half groups (bf16 value storage) qualifies for the step kernel too and
-    // runs spmv_step_half_kernel; off, such a call runs as grids.  Part of the key of a cached batch plan.
+    // runs spmv_step_kernel<., HALF = 1>; off, such a call runs as grids.  Part of the key of a cached batch plan.
     bool step_half = false;
     int step_order = 0;          // HISPMV_STEP_ORDER: 0 = kinds mixed in proportion, long items first (default); 1 = longest first (lpt); 2 = grid order
     bool batch_graphs = false;   // HISPMV_BATCH_GRAPH=1: two-stream batch calls captured into a HIP graph and replayed (the default until round 4;
@@ -197,7 +197,7 @@ struct hispmv_ctx {
         int step_workgroups = 0;
         size_t step_lds = 0;
         bool step_strays = false;
-        bool step_half = false;                         //   some slice part has half groups: spmv_step_half_kernel
+        bool step_half = false;                         //   some slice part has half groups: spmv_step_kernel<., HALF = 1>
         int lane = 0;                                   // main launches: 0 = the caller's stream, k > 0 = side stream k - 1
         bool in_lane = false;                           // kind 5 (HISPMV_LANE_TAILS): the tail of ONE lane's matrices, enqueued on that lane's stream before the join
         int64_t weight = 0;                             // main launches: device bytes of the matrices in the grid

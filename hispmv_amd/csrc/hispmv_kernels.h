@@ -181,7 +181,7 @@ hipError_t launch_tts_multi(const TtsEntry* entries, int n, const uint8_t* item_
 // kind 0 = group `index` of slice_table[entry] (a 1024-thread plan), 1 = groups index .. index + 3 of a 256-thread plan, 2 = tile
 // `index` of tts_table[entry] (standard geometry, x gathered through the cache).  d_sync: two zeroed words the kernel rearms itself.
 // `strays`: some slice part has stray slots.  `half`: some slice part has half groups (bf16 value storage) -- the launch takes
-// spmv_step_half_kernel, whose slice items know the half, compact and wide bodies; without it, spmv_step_kernel as ever.
+// spmv_step_kernel<., HALF = 1>, whose slice items know the half, compact and wide bodies; without it, the HALF = 0 instantiation as ever.
 struct StepArgs { const MultiEntry* slice_table; const TtsEntry* tts_table; const int2* items; unsigned* sync; unsigned n_items; float alpha; int pad, ticket_word; };
 hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_tts_table, const void* d_items, unsigned n_items,
                             unsigned* d_sync, int workgroups, size_t lds_bytes, bool strays, bool half, float alpha, hipStream_t stream);

@@ -20,6 +20,7 @@
 
 #include "hispmv_format.h"
 #include "hispmv_kernels.h"
+#include "hispmv_slice_decode.h"      // f2i / i2f, the stream loads, lanes_below, SliceRaw, request_slice, decode_metas: one text for every kernel file
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -69,11 +70,8 @@ struct WgTrace {
 #endif
 
 // ---------------------------------------------------------------------------
-// wave64 helpers
+// wave64 helpers (f2i, i2f and lanes_below: hispmv_slice_decode.h)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-
 // Segmented inclusive scan over the 64 lanes, Kogge-Stone on (head flag F, value v):
 //   (F1,v1) o (F2,v2) = (F1|F2, F2 ? v2 : v1+v2)
 // CTRL/ROWMASK select the DPP source; lanes without a source read the identity (0,0).
@@ -120,10 +118,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 constexpr int kTtsChunkSlots = 1024;   // hispmv_tts.h: kTtsChunk
 constexpr int kLookbackSpinMax = 1 << 22;   // ~seconds; a wait this long means a lost launch, not contention
-
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-}
 
 // Sum of the carries the `chain_len` slices before `cur` published for this launch (lane k polls granule
 // cur - chain_len + k, k += 64; fixed summation order).  Bounded wait: an expired poll sets *lb.err.
@@ -184,28 +178,9 @@ __device__ __forceinline__ float lookback_chain(const LookbackArgs& lb, lds_u64*
 //            y = alpha*total + beta*bias stores; the partial sum left open goes to carry[slice] (fix-up launch) or to
 //            the look-back mailbox/granule.
 // ---------------------------------------------------------------------------
-// One 16-byte / 8-byte piece of the packed stream.  The stream is read exactly once per launch: the non-temporal
-// hint keeps it from evicting x, y and the fragment tables from L2 (measured: -5..8 % kernel time on
-// PFlow_742, soc-Pokec and mouse_gene).
-// Every pointer is cast to the GLOBAL address space first: the multi-matrix kernel takes its pointers from a table in
-// memory, where hipcc cannot tell global from LDS and would emit FLAT loads -- those count on lgkmcnt as well and return
-// out of order, so every wait for an LDS gather would also wait for the prefetch of the next slice.
-#define HISPMV_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ uint2 load_words2(const uint2* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    const u2v v = __builtin_nontemporal_load((const HISPMV_GLOBAL u2v*)p);
-    return uint2{v.x, v.y};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
+// The pieces of the packed stream (load_words, load_words2), the table entries (load_int4), the slice as it arrives (SliceRaw,
+// request_slice) and its metas in wide form (decode_metas) are hispmv_slice_decode.h's.  The loads below are this file's own; like
+// those, they cast every pointer to the GLOBAL address space first (why: there).
 __device__ __forceinline__ float4 load_float4(const float4* p) {
     typedef float f4v __attribute__((ext_vector_type(4)));
     const f4v v = *(const HISPMV_GLOBAL f4v*)p;
@@ -218,34 +193,7 @@ __device__ __forceinline__ int2 load_int2(const int2* p) {
     return int2{v.x, v.y};
 }
 
-// A slice as it arrives: per step 4 values and 4 metas per lane (compact: 4 x u16 in a uint2; wide: 4 x u32).
-// HALF (bf16 value storage, hispmv_format.h): per step ONE 16-byte piece per lane, {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16}.
-template <bool COMPACT, bool HALF = false> struct SliceRaw;
-template <> struct SliceRaw<true>  { uint4 v[kSliceSteps]; uint2 m[kSliceSteps]; };
-template <> struct SliceRaw<false> { uint4 v[kSliceSteps]; uint4 m[kSliceSteps]; };
-template <> struct SliceRaw<true, true> { uint4 q[kSliceSteps]; };
-template <bool COMPACT, bool HALF = false>
-__device__ __forceinline__ void request_slice(SliceRaw<COMPACT, HALF>& s, const char* base, int lane) {
-    if constexpr (HALF) {
-        const uint4* pq = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.q[j] = load_words(pq + j * 64);
-    } else {
-    const uint4* pv = (const uint4*)base + lane;
-#pragma unroll
-    for (int j = 0; j < kSliceSteps; ++j) s.v[j] = load_words(pv + j * 64);
-    if constexpr (COMPACT) {
-        const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
-    } else {
-        const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
-    }
-    }
-}
-// the fp32 bits of the four values of step j: as stored, or -- half slice -- the bf16 halves of a dword widened (one VALU operation each)
+// the fp32 bits of the four values of step j of a slice (SliceRaw): as stored, or -- half slice -- the bf16 halves of a dword widened (one VALU operation each)
 template <bool COMPACT, bool HALF>
 __device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, int j, float (&v)[kLaneElems]) {
     if constexpr (HALF) {
@@ -253,24 +201,6 @@ __device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, i
         v[2] = i2f((int)(s.q[j].y << 16)); v[3] = i2f((int)(s.q[j].y & 0xffff0000u));
     } else {
         v[0] = i2f((int)s.v[j].x); v[1] = i2f((int)s.v[j].y); v[2] = i2f((int)s.v[j].z); v[3] = i2f((int)s.v[j].w);
-    }
-}
-// -> metas in wide form (rowEnd<<31 | window index or column), c[4*j + k] = element k of the lane in step j
-template <bool COMPACT, bool HALF = false>
-__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
-    if constexpr (COMPACT) {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            unsigned a, b;
-            if constexpr (HALF) { a = s.q[j].z; b = s.q[j].w; } else { a = s.m[j].x; b = s.m[j].y; }
-            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
-            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
-            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
-            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
     }
 }
 
@@ -361,7 +291,7 @@ struct SubBlock {
 // The work of one workgroup on group `group` of a matrix (the body of the slice kernels below), for a group stored
 // COMPACT (6 B per element) or wide (8 B): two instantiations, chosen per group by slices_body.
 // HALF (with COMPACT): the compact slice with bf16 values, 4 B per element (hispmv_format.h) -- like STRAYS a template parameter that
-// only the instantiations of launches with such a group carry (spmv_slices_half_kernel and its siblings below).
+// only the instantiations of launches with such a group carry (the HALF != 0 instantiations of spmv_slices_kernel and its siblings below).
 template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool COMPACT, bool STRAYS = false, bool HALF = false>
 __device__ __forceinline__ void slices_group(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
@@ -757,8 +687,7 @@ __device__ __forceinline__ void slices_body(
                                                        lds_floats, ytile_floats, cols, rows, lb, group, int4{0, 0, 0, 0}, sb);
     }
 }
-// HALF: 0 = no half groups in the launch; 1 = half, compact and wide groups (a multi-matrix grid with a bf16 handle in it);
-// 2 = half and wide groups only (ONE bf16 handle: it has no compact group that is not half, the compact body stays out)
+// ... with the whole workgroup on the group
 template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false, int HALF = 0>
 __device__ __forceinline__ void slices_body(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
@@ -769,26 +698,18 @@ __device__ __forceinline__ void slices_body(
                                                      lds_floats, ytile_floats, cols, rows, lb, group, SubBlock::whole());
 }
 
-template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false>
+// HALF (slices_body's; in every kernel below that has it): a handle with half groups (bf16 value storage) takes the HALF != 0
+// instantiation -- here HALF = 2, and USE_LDS: half groups are compact groups, such a plan always has a window.  The extra template
+// parameter leaves the HALF = 0 instantiations, which every handle without half groups runs, instruction for instruction as they were;
+// a shared body function between two kernels does not (it has cost spmv_slices_multi_kernel<false> 2 VGPRs: DESIGN.md 2.25).
+template <bool HAS_BETA, bool USE_LDS, bool LOOKBACK, bool STRAYS = false, int HALF = 0>
 __global__ __launch_bounds__(1024) void spmv_slices_kernel(
     const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups,
     const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
     float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
     int lds_floats, int ytile_floats, int cols, int rows, LookbackArgs lb) {
-    slices_body<HAS_BETA, USE_LDS, LOOKBACK, STRAYS>(words, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
-                                             lds_floats, ytile_floats, cols, rows, lb, (long long)blockIdx.x);
-}
-
-// The same for a handle with HALF groups (bf16 value storage): a kernel of its own, so that handles without them run exactly the
-// instantiations above.  Half groups are compact groups: such a plan always has a window (USE_LDS).
-template <bool HAS_BETA, bool LOOKBACK, bool STRAYS>
-__global__ __launch_bounds__(1024) void spmv_slices_half_kernel(
-    const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups,
-    const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
-    float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
-    int lds_floats, int ytile_floats, int cols, int rows, LookbackArgs lb) {
-    slices_body<HAS_BETA, true, LOOKBACK, STRAYS, 2>(words, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
-                                                        lds_floats, ytile_floats, cols, rows, lb, (long long)blockIdx.x);
+    slices_body<HAS_BETA, USE_LDS, LOOKBACK, STRAYS, HALF>(words, hdr, groups, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices,
+                                                           lds_floats, ytile_floats, cols, rows, lb, (long long)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -798,7 +719,8 @@ __global__ __launch_bounds__(1024) void spmv_slices_half_kernel(
 // SpMVs -- the 20 matrices of the benchmark set, the heads of a model -- then share launch ramps and tails instead of
 // paying 6-20 us of launch latency each.  All matrices of a launch have the same workgroup size.
 // ---------------------------------------------------------------------------
-template <bool STRAYS>
+// HALF = 1: a part of the launch has half groups (bf16 value storage) -- the bodies that know half, compact and wide groups.
+template <bool STRAYS, int HALF = 0>
 __global__ __launch_bounds__(1024) void spmv_slices_multi_kernel(const MultiEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
     int k = 0;
 #pragma unroll 1
@@ -818,40 +740,11 @@ __global__ __launch_bounds__(1024) void spmv_slices_multi_kernel(const MultiEntr
     // beta is per entry: the first column tile of a matrix applies beta*bias, its other tiles write alpha*A_t*x into the
     // handle's partial vectors (no bias read) -- both kinds share the grid, a workgroup runs one of the two bodies
     if (t.beta != 0.0f)
-        slices_body<true, true, false, STRAYS>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, alpha, t.beta,
-                                       t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
+        slices_body<true, true, false, STRAYS, HALF>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, alpha, t.beta,
+                                                     t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
     else
-        slices_body<false, true, false, STRAYS>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, alpha, 0.0f,
-                                        t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
-    WGT_END(blockDim.x == 1024 ? 1 : 2, e, group);
-}
-// ... when a part of the launch has half groups (bf16 value storage).  The same text with the HALF bodies -- a kernel of its own and not a
-// shared body function: called through one, spmv_slices_multi_kernel<false> came out with 93 VGPRs instead of 91.
-template <bool STRAYS>
-__global__ __launch_bounds__(1024) void spmv_slices_multi_half_kernel(const MultiEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
-    int k = 0;
-#pragma unroll 1
-    while (k + 1 < prefix.n && (long long)blockIdx.x >= prefix.begin[k + 1]) ++k;
-    long long group = (long long)blockIdx.x - prefix.begin[k];
-    int e = prefix.first[k];
-    const int tiles = prefix.tiles[k];
-    if (tiles > 1) {              // XCD-pinned column tiles (hispmv_kernels.h): tile from the block's index mod 8
-        const int per = 8 / tiles, res = (int)(group & 7);
-        e += res / per;
-        group = (group >> 3) * per + (res % per);
-    }
-    const MultiEntry t = table[e];
-    if (group * t.group_slices >= t.n_slices) return;      // (a pinned tile with fewer groups than its siblings)
-    WGT_BEGIN();
-    const LookbackArgs lb{};
-    // beta is per entry: the first column tile of a matrix applies beta*bias, its other tiles write alpha*A_t*x into the
-    // handle's partial vectors (no bias read) -- both kinds share the grid, a workgroup runs one of the two bodies
-    if (t.beta != 0.0f)
-        slices_body<true, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, alpha, t.beta,
-                                       t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
-    else
-        slices_body<false, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, alpha, 0.0f,
-                                        t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
+        slices_body<false, true, false, STRAYS, HALF>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, alpha, 0.0f,
+                                                      t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group);
     WGT_END(blockDim.x == 1024 ? 1 : 2, e, group);
 }
 // Fix-up of all matrices of a multi launch: thread blocks are concatenated the same way.
@@ -1127,13 +1020,24 @@ __device__ __forceinline__ void batched_group(
     }
 }
 
-template <bool HAS_BETA, bool USE_LDS, int NV>
+// HALF: a handle with half groups (bf16 value storage; always with a window)
+template <bool HAS_BETA, bool USE_LDS, int NV, bool HALF = false>
 __global__ __launch_bounds__(1024) void spmv_slices_batched_kernel(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
     const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
     float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
     int lds_floats, int ytile_floats, int cols, int rows, int bias_stride) {
-    if constexpr (USE_LDS) {
+    if constexpr (HALF) {
+        static_assert(USE_LDS, "half groups exist only in plans with a window");
+        const int4 g = load_int4(groups + blockIdx.x);
+        const int kind = __builtin_amdgcn_readfirstlane(g.w);
+        if ((kind & kGroupHalf) != 0)
+            batched_group<HAS_BETA, true, NV, true, true>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
+                                                          ytile_floats, cols, rows, bias_stride, g);
+        else      // (a bf16 handle has no compact group that is not half: two bodies, not three)
+            batched_group<HAS_BETA, true, NV, false>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
+                                                     ytile_floats, cols, rows, bias_stride, g);
+    } else if constexpr (USE_LDS) {
         const int4 g = load_int4(groups + blockIdx.x);
         if (__builtin_amdgcn_readfirstlane(g.w) != 0)
             batched_group<HAS_BETA, true, NV, true>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
@@ -1145,23 +1049,6 @@ __global__ __launch_bounds__(1024) void spmv_slices_batched_kernel(
         batched_group<HAS_BETA, false, NV, false>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
                                                   ytile_floats, cols, rows, bias_stride, int4{0, 0, 0, 0});
     }
-}
-
-// ... of a handle with half groups (bf16 value storage)
-template <bool HAS_BETA, int NV>
-__global__ __launch_bounds__(1024) void spmv_slices_batched_half_kernel(
-    const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ groups,
-    const int4* __restrict__ frags, const float* __restrict__ x, const float* bias, float* y,
-    float* __restrict__ carry, float alpha, float beta, long long n_slices, int group_slices,
-    int lds_floats, int ytile_floats, int cols, int rows, int bias_stride) {
-    const int4 g = load_int4(groups + blockIdx.x);
-    const int kind = __builtin_amdgcn_readfirstlane(g.w);
-    if ((kind & kGroupHalf) != 0)
-        batched_group<HAS_BETA, true, NV, true, true>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
-                                                      ytile_floats, cols, rows, bias_stride, g);
-    else      // (a bf16 handle has no compact group that is not half: two bodies, not three)
-        batched_group<HAS_BETA, true, NV, false>(stream, hdr, frags, x, bias, y, carry, alpha, beta, n_slices, group_slices, lds_floats,
-                                                 ytile_floats, cols, rows, bias_stride, g);
 }
 
 // Fix-up for rows shared between slices: y[row] += alpha * (carry[first] + ... + carry[first+len-1]),
@@ -1348,13 +1235,13 @@ hipError_t launch_spmv(SpmvDeviceMatrix& m_in, const float* x, const float* bias
             m.launches++;
         }
         // stray slots and half groups (bf16 value storage) exist only in plans with a window, stray slots never with
-        // look-back (hispmv_load.cpp); a handle with half groups takes the kernel of its own that reads them
+        // look-back (hispmv_load.cpp); a handle with half groups takes the HALF = 2 instantiation, which reads them
         const bool window = m.lds_floats > 0;
         e = with_bools({beta != 0.0f, window, m.lookback, window && !m.lookback && m.has_strays, window && m.has_half},
                        [&](auto HAS_BETA, auto USE_LDS, auto LOOKBACK, auto STRAYS, auto HALF) {
             const size_t lds = slice_lds_bytes(m, 1, LOOKBACK());
             if constexpr ((STRAYS() && (LOOKBACK() || !USE_LDS())) || (HALF() && !USE_LDS())) return hipErrorInvalidValue;
-            else if constexpr (HALF()) return launch_slice_grid<spmv_slices_half_kernel<HAS_BETA(), LOOKBACK(), STRAYS()>>(m, lds, x, bias, y, alpha, beta, stream, lb);
+            else if constexpr (HALF()) return launch_slice_grid<spmv_slices_kernel<HAS_BETA(), true, LOOKBACK(), STRAYS(), 2>>(m, lds, x, bias, y, alpha, beta, stream, lb);
             else return launch_slice_grid<spmv_slices_kernel<HAS_BETA(), USE_LDS(), LOOKBACK(), STRAYS()>>(m, lds, x, bias, y, alpha, beta, stream, lb);
         });
         if (e != hipSuccess || m.lookback) return e;
@@ -1388,7 +1275,7 @@ hipError_t launch_spmv_batched(SpmvDeviceMatrix& m, int nv, const float* x, cons
             return with_bools({beta != 0.0f, window, window && m.has_half}, [&](auto HAS_BETA, auto USE_LDS, auto HALF) {
                 const size_t lds = slice_lds_bytes(m, NV);
                 if constexpr (HALF() && !USE_LDS()) return hipErrorInvalidValue;
-                else if constexpr (HALF()) return launch_slice_grid<spmv_slices_batched_half_kernel<HAS_BETA(), NV>>(m, lds, x, bias, y, alpha, beta, stream, bias_stride);
+                else if constexpr (HALF()) return launch_slice_grid<spmv_slices_batched_kernel<HAS_BETA(), true, NV, true>>(m, lds, x, bias, y, alpha, beta, stream, bias_stride);
                 else return launch_slice_grid<spmv_slices_batched_kernel<HAS_BETA(), USE_LDS(), NV>>(m, lds, x, bias, y, alpha, beta, stream, bias_stride);
             });
         });
@@ -1407,7 +1294,7 @@ hipError_t launch_spmv_multi(const SpmvDeviceMatrix* const* parts, int n, const 
     const int threads = parts[0]->block_threads;
     size_t lds = 0;
     bool strays = false;          // (a launch with a stray-slot part takes the instantiation that fetches them; hispmv_batch.cpp keeps such parts in grids of their own)
-    bool half = false;            // (... and one with a half group -- bf16 value storage -- the kernel that reads them)
+    bool half = false;            // (... and one with a half group -- bf16 value storage -- the HALF = 1 instantiation, which reads them)
     for (int i = 0; i < n; ++i) {
         const SpmvDeviceMatrix& m = *parts[i];
         if (m.block_threads != threads || m.n_groups < 0) return hipErrorInvalidValue;
@@ -1419,8 +1306,7 @@ hipError_t launch_spmv_multi(const SpmvDeviceMatrix* const* parts, int n, const 
     const long long g = pinned_prefix(px, n, item_tiles, n_items, 8, [&](int e) { return parts[e]->n_slices > 0 ? (long long)parts[e]->n_groups : 0LL; });
     if (g < 0 || g > 0x7fffffffLL) return hipErrorInvalidValue;
     return with_bools({half, strays}, [&](auto HALF, auto STRAYS) {
-        if constexpr (HALF()) return launch_multi<spmv_slices_multi_half_kernel<STRAYS()>, kDynLdsMax>(g, threads, lds, stream, d_table, px, alpha);
-        else return launch_multi<spmv_slices_multi_kernel<STRAYS()>, kDynLdsMax>(g, threads, lds, stream, d_table, px, alpha);
+        return launch_multi<spmv_slices_multi_kernel<STRAYS(), HALF() ? 1 : 0>, kDynLdsMax>(g, threads, lds, stream, d_table, px, alpha);
     });
 }
 
@@ -1837,7 +1723,12 @@ __device__ __forceinline__ T load_const(const T* p) {
 //   * one launch on the caller's stream: no fork to / join from a side stream in front of the tail launch.
 // The last workgroup to leave resets the counters (self-cleaning: graph replays and plain launches alike, no host state).
 // ---------------------------------------------------------------------------
-template <bool STRAYS>        // some slice part of the call has stray slots: the instantiation that fetches them (it serves parts without them too)
+// STRAYS: some slice part of the call has stray slots -- the instantiation that fetches them (it serves parts without them too).
+// HALF = 1: some slice part of the call has half groups (bf16 value storage; opt-in: hispmv_set_step_half) -- the slice items run the
+// bodies that know half, compact and wide groups (fp32 handles share the queue with bf16 ones); tiles run the same body either way: a
+// bf16 tile stream keeps 32-bit slots.  A template parameter and not a shared body function: calls without half groups run the
+// HALF = 0 instantiations, instruction for instruction what they were before HALF existed (profiles/kernels_once_kernel_identity.txt).
+template <bool STRAYS, int HALF = 0>
 __global__ __launch_bounds__(1024) void spmv_step_kernel(StepArgs args) {
     // the ticket's LDS word: the LAST four bytes of the dynamic LDS, behind everything the items use.  (As a static __shared__ variable
     // it was placed FIRST and pushed the dynamic LDS to offset 4: every 16-byte LDS access of the bodies -- window staging, the tiles'
@@ -1888,84 +1779,15 @@ __global__ __launch_bounds__(1024) void spmv_step_kernel(StepArgs args) {
             const MultiEntry t = load_const(a.slice_table + entry);
             const LookbackArgs lb{};
             // kind 0: the workgroup is the group's; kind 1: four groups of a 256-thread plan, wavefronts 4q .. 4q+3 take group index + q
-            const SubBlock sb = kind == 0 ? SubBlock{wave, 16, 0, (int)(tid & 63)} : SubBlock{wave & 3, 4, (wave >> 2) * (t.lds_floats + 4 * t.ytile_floats), (int)(tid & 63)};
-            const long long group = kind == 0 ? index : index + (wave >> 2);
-            if (t.beta != 0.0f)
-                slices_body<true, true, false, STRAYS>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, a.alpha, t.beta,
-                                                       t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
-            else
-                slices_body<false, true, false, STRAYS>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, a.alpha, 0.0f,
-                                                        t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
-            if (tid == 0) s_next = next;
-        }
-        // the item's LDS is free and the next ticket visible behind this barrier
-#ifdef HISPMV_WG_TRACE
-        WGT_END(kind == 2 ? 3 : kind == 0 ? 1 : 2, entry, index);        // (contains the barrier)
-#else
-        __syncthreads();
-#endif
-    }
-    // every workgroup draws exactly one ticket past the end; the last one out rearms the queue for the next launch
-    if (threadIdx.x == 0) {
-        unsigned* const sync = ((const __attribute__((address_space(4))) StepArgs*)__builtin_amdgcn_kernarg_segment_ptr())->sync;
-        const unsigned done = __hip_atomic_fetch_add(sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (done == gridDim.x - 1) {
-            __hip_atomic_store(sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-// ... when a slice part of the call has half groups (bf16 value storage; opt-in: hispmv_set_step_half).  The same text with the HALF = 1
-// bodies in its slice items (half, compact and wide: fp32 handles share the queue with bf16 ones); tiles run the same body -- a bf16
-// tile stream keeps 32-bit slots.  A kernel of its own, neither a template parameter of spmv_step_kernel nor a shared body function:
-// calls without half groups run exactly the instantiations above (profiles/step_half_kernel_identity.txt).
-template <bool STRAYS>
-__global__ __launch_bounds__(1024) void spmv_step_half_kernel(StepArgs args) {
-    extern __shared__ float step_lds[];      // the ticket's LDS word: the last four bytes of the dynamic LDS (see spmv_step_kernel)
-    unsigned& s_next = *(unsigned*)(step_lds + args.ticket_word);
-    if (threadIdx.x == 0) s_next = __hip_atomic_fetch_add(args.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-#pragma unroll 1
-    for (;;) {
-        // nothing of the queue lives in registers across an item: the arguments are read again from the kernel-argument segment
-        typedef const __attribute__((address_space(4))) StepArgs* KernArgs;
-        KernArgs ap = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ap));
-        const StepArgs a{ap->slice_table, ap->tts_table, ap->items, ap->sync, ap->n_items, ap->alpha, 0, ap->ticket_word};
-        unsigned& s_next = *(unsigned*)(step_lds + a.ticket_word);
-        const unsigned it = s_next;
-        if (it >= a.n_items) break;
-        __syncthreads();                    // every thread has read the ticket: its slot may take the next one
-        unsigned next = 0;                  // the NEXT item's ticket is drawn first thing
-        if (threadIdx.x == 0) next = __hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int2 item = load_const(a.items + __builtin_amdgcn_readfirstlane((int)it));
-        const unsigned kind = (unsigned)__builtin_amdgcn_readfirstlane(item.x) & 3u;
-        const int entry = (int)((unsigned)__builtin_amdgcn_readfirstlane(item.x) >> 8);
-        const long long index = (long long)(unsigned)__builtin_amdgcn_readfirstlane(item.y);
-        unsigned tid = threadIdx.x;         // the thread index, opaque per item
-        asm volatile("" : "+v"(tid));
-        const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-        WGT_BEGIN();
-        if (kind == 2) {
-            // a tile: the next ticket is parked in the LDS BEFORE the tile starts (no register to hold it across the body)
-            if (tid == 0) s_next = next;
-            const TtsEntry e = load_const(a.tts_table + entry);
-            if (e.beta != 0.0f) tts_tile_body<true>(e.m, e.x, e.bias, e.y, a.alpha, e.beta, (int)index, tid);
-            else tts_tile_body<false>(e.m, e.x, e.y, e.y, a.alpha, 0.0f, (int)index, tid);
-        } else {
-            // slice groups: the next ticket stays in flight while the item runs and is consumed behind it
-            const MultiEntry t = load_const(a.slice_table + entry);
-            const LookbackArgs lb{};
-            // kind 0: the workgroup is the group's; kind 1: four groups of a 256-thread plan, wavefronts 4q .. 4q+3 take group index + q
             // (a sub-block past the part's last group: the empty group of slices_body -- the wide body, one barrier like the others)
             const SubBlock sb = kind == 0 ? SubBlock{wave, 16, 0, (int)(tid & 63)} : SubBlock{wave & 3, 4, (wave >> 2) * (t.lds_floats + 4 * t.ytile_floats), (int)(tid & 63)};
             const long long group = kind == 0 ? index : index + (wave >> 2);
             if (t.beta != 0.0f)
-                slices_body<true, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, a.alpha, t.beta,
-                                                          t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
+                slices_body<true, true, false, STRAYS, HALF>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.bias, t.y, t.carry, a.alpha, t.beta,
+                                                             t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
             else
-                slices_body<false, true, false, STRAYS, 1>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, a.alpha, 0.0f,
-                                                           t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
+                slices_body<false, true, false, STRAYS, HALF>((const char*)t.words, t.hdr, t.groups, t.frags, t.x, t.y, t.y, t.carry, a.alpha, 0.0f,
+                                                              t.n_slices, t.group_slices, t.lds_floats, t.ytile_floats, t.cols, t.rows, lb, group, sb);
             if (tid == 0) s_next = next;
         }
         // the item's LDS is free and the next ticket visible behind this barrier
@@ -1985,7 +1807,6 @@ __global__ __launch_bounds__(1024) void spmv_step_half_kernel(StepArgs args) {
         }
     }
 }
-
 // LDS of the NV-vector / x-in-LDS kernels: per vector the accumulators, one staging area (largest block of the matrix), 64
 // tails and -- xlds -- a copy of x
 static size_t tts_nv_lds_bytes(const TtsDeviceMatrix& m, int nv, bool xlds) {
@@ -2086,8 +1907,7 @@ hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_t
     if (lds_bytes > kLdsPerCu) return hipErrorInvalidValue;
     const StepArgs a{d_slice_table, d_tts_table, (const int2*)d_items, d_sync, n_items, alpha, 0, (int)(ticket_byte / 4)};
     return with_bools({strays, half}, [&](auto STRAYS, auto HALF) {
-        if constexpr (HALF()) return launch<spmv_step_half_kernel<STRAYS()>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
-        else return launch<spmv_step_kernel<STRAYS()>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
+        return launch<spmv_step_kernel<STRAYS(), HALF() ? 1 : 0>, kLdsPerCu>(dim3((unsigned)workgroups), dim3(1024), lds_bytes, stream, a);
     });
 }
 
@@ -2098,10 +1918,21 @@ hipError_t launch_spmv_step(const MultiEntry* d_slice_table, const TtsEntry* d_t
 // ---------------------------------------------------------------------------
 // NV input vectors per pass over W (linear with num_vecs > 1): vector v is x + v*cols, its result y + v*rows; every
 // (row, vector) pair accumulates in exactly the order of the single-vector kernel, so the results are bitwise the same.
-template <int R, bool HAS_BETA, int NV>
-__device__ __forceinline__ void gemv_rows_body(const float* __restrict__ W, const float* __restrict__ x,
+// WT = float: W is rows x cols fp32; a lane takes 4 consecutive columns per step (16-byte loads of W and x) when cols % 4 == 0.
+// WT = uint16_t, bf16 value storage: W is rows x cols bfloat16 (2 bytes per element), everything else the same -- fp32 x, products and
+// sums.  With cols % 8 == 0 a lane takes 8 consecutive columns per step: ONE 16-byte load of W per row (rows are 16-byte aligned)
+// against two float4 of x per vector; with cols % 4 == 0 four columns (8-byte loads of W).  bf16 -> fp32: `bits << 16` /
+// `bits & 0xffff0000`.  The lane-to-column assignment differs from the fp32 one (8 columns per lane instead of 4), so the bits differ
+// from an fp32 handle of R(W); every (row, vector) pair again accumulates in the order of the single-vector bf16 instantiation.
+// Otherwise, for both, element by element.
+// (WT comes FIRST in the body's parameter list: the LDS arrays of a kernel are laid out in the order of their mangled names, and with
+// WT last the `part` arrays of gemv_rows_multi_mixed_kernel's four bodies swapped places.)
+template <class WT, int R, bool HAS_BETA, int NV>
+__device__ __forceinline__ void gemv_rows_body(const WT* __restrict__ W, const float* __restrict__ x,
                                                const float* __restrict__ bias, float* __restrict__ y,
                                                int rows, int cols, float alpha, float beta, int block) {
+    static_assert(std::is_same_v<WT, float> || std::is_same_v<WT, uint16_t>, "fp32 or bf16 weights");
+    constexpr bool BF16 = std::is_same_v<WT, uint16_t>;
     __shared__ float part[4][R][NV];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int row0 = block * R;
@@ -2111,7 +1942,27 @@ __device__ __forceinline__ void gemv_rows_body(const float* __restrict__ W, cons
 #pragma unroll
         for (int v = 0; v < NV; ++v) acc[r][v] = 0.0f;
 
-    if ((cols & 3) == 0) {
+    if (BF16 && (cols & 7) == 0) {
+        if constexpr (BF16) {
+            const int n8 = cols >> 3, n4 = cols >> 2;
+            const float4* x4 = (const float4*)x;
+            for (int c = threadIdx.x; c < n8; c += 256) {
+                float4 xa[NV], xb[NV];
+#pragma unroll
+                for (int v = 0; v < NV; ++v) { xa[v] = x4[(size_t)v * n4 + 2 * c]; xb[v] = x4[(size_t)v * n4 + 2 * c + 1]; }
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int row = min(row0 + r, rows - 1);
+                    const uint4 q = ((const uint4*)(W + (size_t)row * cols))[c];
+                    const float a0 = i2f((int)(q.x << 16)), a1 = i2f((int)(q.x & 0xffff0000u)), a2 = i2f((int)(q.y << 16)), a3 = i2f((int)(q.y & 0xffff0000u));
+                    const float a4 = i2f((int)(q.z << 16)), a5 = i2f((int)(q.z & 0xffff0000u)), a6 = i2f((int)(q.w << 16)), a7 = i2f((int)(q.w & 0xffff0000u));
+#pragma unroll
+                    for (int v = 0; v < NV; ++v)
+                        acc[r][v] += (a0 * xa[v].x + a1 * xa[v].y + a2 * xa[v].z + a3 * xa[v].w) + (a4 * xb[v].x + a5 * xb[v].y + a6 * xb[v].z + a7 * xb[v].w);
+                }
+            }
+        }
+    } else if ((cols & 3) == 0) {   // 4 columns per lane: one 16-byte (fp32) or 8-byte (bf16) load of W against one float4 of x
         const int n4 = cols >> 2;
         const float4* x4 = (const float4*)x;
         for (int c = threadIdx.x; c < n4; c += 256) {
@@ -2121,12 +1972,19 @@ __device__ __forceinline__ void gemv_rows_body(const float* __restrict__ W, cons
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int row = min(row0 + r, rows - 1);
-                const float4 a = ((const float4*)(W + (size_t)row * cols))[c];
+                float a0, a1, a2, a3;
+                if constexpr (BF16) {
+                    const uint2 q = ((const uint2*)(W + (size_t)row * cols))[c];
+                    a0 = i2f((int)(q.x << 16)); a1 = i2f((int)(q.x & 0xffff0000u)); a2 = i2f((int)(q.y << 16)); a3 = i2f((int)(q.y & 0xffff0000u));
+                } else {
+                    const float4 a = ((const float4*)(W + (size_t)row * cols))[c];
+                    a0 = a.x; a1 = a.y; a2 = a.z; a3 = a.w;
+                }
 #pragma unroll
-                for (int v = 0; v < NV; ++v) acc[r][v] += a.x * xv[v].x + a.y * xv[v].y + a.z * xv[v].z + a.w * xv[v].w;
+                for (int v = 0; v < NV; ++v) acc[r][v] += a0 * xv[v].x + a1 * xv[v].y + a2 * xv[v].z + a3 * xv[v].w;
             }
         }
-    } else {   // rows are not 16-byte aligned: dword path
+    } else {   // rows are not 16-byte (bf16: 8-byte) aligned: element path
         for (int c = threadIdx.x; c < cols; c += 256) {
             float xv[NV];
 #pragma unroll
@@ -2134,7 +1992,9 @@ __device__ __forceinline__ void gemv_rows_body(const float* __restrict__ W, cons
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int row = min(row0 + r, rows - 1);
-                const float a = W[(size_t)row * cols + c];
+                float a;
+                if constexpr (BF16) a = i2f((int)((unsigned)W[(size_t)row * cols + c] << 16));
+                else a = W[(size_t)row * cols + c];
 #pragma unroll
                 for (int v = 0; v < NV; ++v) acc[r][v] += a * xv[v];
             }
@@ -2158,102 +2018,11 @@ __device__ __forceinline__ void gemv_rows_body(const float* __restrict__ W, cons
     }
 }
 
-template <int R, bool HAS_BETA, int NV>
-__global__ __launch_bounds__(256) void gemv_rows_kernel(const float* __restrict__ W, const float* __restrict__ x,
+template <int R, bool HAS_BETA, int NV, class WT>
+__global__ __launch_bounds__(256) void gemv_rows_kernel(const WT* __restrict__ W, const float* __restrict__ x,
                                                         const float* __restrict__ bias, float* __restrict__ y,
                                                         int rows, int cols, float alpha, float beta) {
-    gemv_rows_body<R, HAS_BETA, NV>(W, x, bias, y, rows, cols, alpha, beta, (int)blockIdx.x);
-}
-
-// bf16 value storage: W is rows x cols bfloat16 (2 bytes per element), everything else as above -- fp32 x, products and sums.  With
-// cols % 8 == 0 a lane takes 8 consecutive columns per step: ONE 16-byte load of W per row (rows are 16-byte aligned) against two
-// float4 of x per vector; with cols % 4 == 0 four columns (8-byte loads of W); otherwise element by element.  bf16 -> fp32: `bits << 16` / `bits & 0xffff0000`.  The lane-to-column
-// assignment differs from the fp32 body's (8 columns per lane instead of 4), so the bits differ from an fp32 handle of R(W); every
-// (row, vector) pair again accumulates in the order of this body's single-vector instantiation.
-template <int R, bool HAS_BETA, int NV>
-__device__ __forceinline__ void gemv_rows_bf16_body(const uint16_t* __restrict__ W, const float* __restrict__ x,
-                                                    const float* __restrict__ bias, float* __restrict__ y,
-                                                    int rows, int cols, float alpha, float beta, int block) {
-    __shared__ float part16[4][R][NV];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int row0 = block * R;
-    float acc[R][NV];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) acc[r][v] = 0.0f;
-
-    if ((cols & 7) == 0) {
-        const int n8 = cols >> 3, n4 = cols >> 2;
-        const float4* x4 = (const float4*)x;
-        for (int c = threadIdx.x; c < n8; c += 256) {
-            float4 xa[NV], xb[NV];
-#pragma unroll
-            for (int v = 0; v < NV; ++v) { xa[v] = x4[(size_t)v * n4 + 2 * c]; xb[v] = x4[(size_t)v * n4 + 2 * c + 1]; }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int row = min(row0 + r, rows - 1);
-                const uint4 q = ((const uint4*)(W + (size_t)row * cols))[c];
-                const float a0 = i2f((int)(q.x << 16)), a1 = i2f((int)(q.x & 0xffff0000u)), a2 = i2f((int)(q.y << 16)), a3 = i2f((int)(q.y & 0xffff0000u));
-                const float a4 = i2f((int)(q.z << 16)), a5 = i2f((int)(q.z & 0xffff0000u)), a6 = i2f((int)(q.w << 16)), a7 = i2f((int)(q.w & 0xffff0000u));
-#pragma unroll
-                for (int v = 0; v < NV; ++v)
-                    acc[r][v] += (a0 * xa[v].x + a1 * xa[v].y + a2 * xa[v].z + a3 * xa[v].w) + (a4 * xb[v].x + a5 * xb[v].y + a6 * xb[v].z + a7 * xb[v].w);
-            }
-        }
-    } else if ((cols & 3) == 0) {   // rows are 8-byte aligned: 4 columns per lane, one 8-byte load of W against one float4 of x
-        const int n4 = cols >> 2;
-        const float4* x4 = (const float4*)x;
-        for (int c = threadIdx.x; c < n4; c += 256) {
-            float4 xa[NV];
-#pragma unroll
-            for (int v = 0; v < NV; ++v) xa[v] = x4[(size_t)v * n4 + c];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int row = min(row0 + r, rows - 1);
-                const uint2 q = ((const uint2*)(W + (size_t)row * cols))[c];
-                const float a0 = i2f((int)(q.x << 16)), a1 = i2f((int)(q.x & 0xffff0000u)), a2 = i2f((int)(q.y << 16)), a3 = i2f((int)(q.y & 0xffff0000u));
-#pragma unroll
-                for (int v = 0; v < NV; ++v) acc[r][v] += a0 * xa[v].x + a1 * xa[v].y + a2 * xa[v].z + a3 * xa[v].w;
-            }
-        }
-    } else {   // element path
-        for (int c = threadIdx.x; c < cols; c += 256) {
-            float xv[NV];
-#pragma unroll
-            for (int v = 0; v < NV; ++v) xv[v] = x[(size_t)v * cols + c];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int row = min(row0 + r, rows - 1);
-                const float a = i2f((int)((unsigned)W[(size_t)row * cols + c] << 16));
-#pragma unroll
-                for (int v = 0; v < NV; ++v) acc[r][v] += a * xv[v];
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const float s = wave_sum(acc[r][v]);
-            if (lane == 0) part16[wv][r][v] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < R * NV) {
-        const int r = threadIdx.x / NV, v = threadIdx.x % NV;
-        const int row = row0 + r;
-        if (row < rows) {
-            const float s = (part16[0][r][v] + part16[1][r][v]) + (part16[2][r][v] + part16[3][r][v]);
-            y[(size_t)v * rows + row] = HAS_BETA ? alpha * s + beta * bias[row] : alpha * s;
-        }
-    }
-}
-
-template <int R, bool HAS_BETA, int NV>
-__global__ __launch_bounds__(256) void gemv_rows_bf16_kernel(const uint16_t* __restrict__ W, const float* __restrict__ x,
-                                                             const float* __restrict__ bias, float* __restrict__ y,
-                                                             int rows, int cols, float alpha, float beta) {
-    gemv_rows_bf16_body<R, HAS_BETA, NV>(W, x, bias, y, rows, cols, alpha, beta, (int)blockIdx.x);
+    gemv_rows_body<WT, R, HAS_BETA, NV>(W, x, bias, y, rows, cols, alpha, beta, (int)blockIdx.x);
 }
 
 // The dense handles of a batch call in one grid: block ranges per matrix (prefix.begin), largest matrix first so that the
@@ -2264,11 +2033,11 @@ __global__ __launch_bounds__(256) void gemv_rows_multi_kernel(const GemvEntry* _
     while (k + 1 < prefix.n && (long long)blockIdx.x >= prefix.begin[k + 1]) ++k;
     const GemvEntry e = table[k];
     const int block = (int)((long long)blockIdx.x - prefix.begin[k]);
-    if (e.beta != 0.0f) gemv_rows_body<4, true, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
-    else gemv_rows_body<4, false, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
+    if (e.beta != 0.0f) gemv_rows_body<float, 4, true, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
+    else gemv_rows_body<float, 4, false, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
 }
 
-// ... with bf16 entries among them (GemvEntry::bf16): the kernel that knows both bodies; a launch without one takes the kernel above
+// ... with bf16 entries among them (GemvEntry::bf16): the kernel that knows both weight types; a launch without one takes the kernel above
 __global__ __launch_bounds__(256) void gemv_rows_multi_mixed_kernel(const GemvEntry* __restrict__ table, MultiPrefix prefix, float alpha) {
     int k = 0;
 #pragma unroll 1
@@ -2276,11 +2045,11 @@ __global__ __launch_bounds__(256) void gemv_rows_multi_mixed_kernel(const GemvEn
     const GemvEntry e = table[k];
     const int block = (int)((long long)blockIdx.x - prefix.begin[k]);
     if (e.bf16) {
-        if (e.beta != 0.0f) gemv_rows_bf16_body<4, true, 1>((const uint16_t*)e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
-        else gemv_rows_bf16_body<4, false, 1>((const uint16_t*)e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
+        if (e.beta != 0.0f) gemv_rows_body<uint16_t, 4, true, 1>((const uint16_t*)e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
+        else gemv_rows_body<uint16_t, 4, false, 1>((const uint16_t*)e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
     } else {
-        if (e.beta != 0.0f) gemv_rows_body<4, true, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
-        else gemv_rows_body<4, false, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
+        if (e.beta != 0.0f) gemv_rows_body<float, 4, true, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, e.beta, block);
+        else gemv_rows_body<float, 4, false, 1>(e.W, e.x, e.bias, e.y, e.rows, e.cols, alpha, 0.0f, block);
     }
 }
 
@@ -2294,8 +2063,8 @@ static hipError_t launch_gemv_nv(int nv, const float* W, int32_t rows, int32_t c
     return with_nv<1, 2, 4, 8>(nv, [&](auto NV_) {
         constexpr int NV = NV_();
         return with_bools({bf16, beta != 0.0f}, [&](auto BF16, auto HAS_BETA) {
-            if constexpr (BF16()) return launch_gemv_rows<gemv_rows_bf16_kernel<4, HAS_BETA(), NV>>((const uint16_t*)W, rows, cols, x, bias, y, alpha, beta, stream);
-            else return launch_gemv_rows<gemv_rows_kernel<4, HAS_BETA(), NV>>(W, rows, cols, x, bias, y, alpha, beta, stream);
+            if constexpr (BF16()) return launch_gemv_rows<gemv_rows_kernel<4, HAS_BETA(), NV, uint16_t>>((const uint16_t*)W, rows, cols, x, bias, y, alpha, beta, stream);
+            else return launch_gemv_rows<gemv_rows_kernel<4, HAS_BETA(), NV, float>>(W, rows, cols, x, bias, y, alpha, beta, stream);
         });
     });
 }

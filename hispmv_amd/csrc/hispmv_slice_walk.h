@@ -1,13 +1,14 @@
 // hispmv_slice_walk.h -- what the satellite kernel files share: hispmv_transpose.hip, hispmv_value_grad.hip, hispmv_tts_transpose.hip,
 // hispmv_spmm.hip and hispmv_spmm_grad.hip (the last two through hispmv_wide_lanes.h as well, which sits on this file), and nobody else.
-// The bit and load helpers, the slice of a stream as it arrives and its
-// decode, the walk of a wavefront over the slices of its group (GroupWalk, local_rows, the column-number window), and the few host
-// helpers of their launches (the LDS limit, the geometry checks, the (USE_LDS, STRAYS, HALF) choice).  A change of the slice format is
-// made here once for all of them.  (What stays written out in the five files, and why: DESIGN.md 2.14.)
+// The buffer and vector-width helpers, the metas of a slice alone and the satellites' slice_values, the walk of a wavefront over the
+// slices of its group (GroupWalk, local_rows, the column-number window), and the few host helpers of their launches (the LDS limit, the
+// geometry checks, the (USE_LDS, STRAYS, HALF) choice).  (What stays written out in the five files, and why: DESIGN.md 2.14.)
 //
-// hispmv_kernels.hip does NOT include this file and keeps its own text of all of it: a shared body function has cost the step kernel
-// registers before, and nothing in here may move a forward kernel's instructions.  Everything sits in an unnamed namespace:
-// every including file gets its own copy, as it had when the text was written out in each of them.
+// The slice format's decode itself -- the bit casts, the stream loads, SliceRaw, request_slice, decode_metas -- is hispmv_slice_decode.h's,
+// which hispmv_kernels.hip includes as well: one text for all six kernel files.  hispmv_kernels.hip does NOT include this file: the walk
+// and the bodies of the forward kernels stay written out there, and nothing in here may move a forward kernel's
+// instructions.  Everything sits in an unnamed namespace: every including file gets its own copy, as it had when the text was written
+// out in each of them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,33 +17,13 @@
 
 #include "hispmv_format.h"
 #include "hispmv_kernels.h"
+#include "hispmv_slice_decode.h"
 
 namespace hispmv {
 
 namespace {
 
-// ---- bits and loads ---------------------------------------------------------------------------------------------------------------
-#define HISPMV_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ int f2i(float f) { return __builtin_bit_cast(int, f); }
-__device__ __forceinline__ float i2f(int i) { return __builtin_bit_cast(float, i); }
-__device__ __forceinline__ uint4 load_words(const uint4* p) {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v v = __builtin_nontemporal_load((const HISPMV_GLOBAL u4v*)p);
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ uint2 load_words2(const uint2* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    const u2v v = __builtin_nontemporal_load((const HISPMV_GLOBAL u2v*)p);
-    return uint2{v.x, v.y};
-}
-__device__ __forceinline__ int4 load_int4(const int4* p) {
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v v = *(const HISPMV_GLOBAL i4v*)p;
-    return int4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
+// ---- buffers and vector widths (the bit casts and the stream loads: hispmv_slice_decode.h) ---------------------------------------
 // a dword through a buffer descriptor: an offset past the descriptor's bytes (kNoAccess among them) reads 0
 constexpr unsigned kNoAccess = 0xffffffffu;
 __device__ __forceinline__ float buffer_float(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
@@ -89,34 +70,7 @@ __device__ __forceinline__ void store_grad(float* grad, long long n, int q, floa
     *p = r;
 }
 
-// ---- a slice as it arrives, and its decode ----------------------------------------------------------------------------------------
-// SliceRaw: values and metas (hispmv_format.h; the forward kernel's SliceRaw): per step 4 values and 4 metas per lane, or -- HALF -- one
-// 16-byte piece {v0 | v1 << 16, v2 | v3 << 16, m0 | m1 << 16, m2 | m3 << 16}.
-template <bool COMPACT, bool HALF = false> struct SliceRaw;
-template <> struct SliceRaw<true>  { uint4 v[kSliceSteps]; uint2 m[kSliceSteps]; };
-template <> struct SliceRaw<false> { uint4 v[kSliceSteps]; uint4 m[kSliceSteps]; };
-template <> struct SliceRaw<true, true> { uint4 q[kSliceSteps]; };
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void request_slice(SliceRaw<COMPACT, HALF>& s, const char* base, int lane) {
-    if constexpr (HALF) {
-        const uint4* pq = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.q[j] = load_words(pq + j * 64);
-    } else {
-        const uint4* pv = (const uint4*)base + lane;
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) s.v[j] = load_words(pv + j * 64);
-        if constexpr (COMPACT) {
-            const uint2* pm = (const uint2*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words2(pm + j * 64);
-        } else {
-            const uint4* pm = (const uint4*)(base + kSliceElems * 4) + lane;
-#pragma unroll
-            for (int j = 0; j < kSliceSteps; ++j) s.m[j] = load_words(pm + j * 64);
-        }
-    }
-}
+// ---- the metas of a slice alone, and the values of a whole one (SliceRaw, request_slice: hispmv_slice_decode.h) --------------------
 // SliceMetas: the metas alone (the gradients multiply no values).  They begin at byte 4096 of a compact (2 KiB) and of a wide (4 KiB)
 // slice; the 4 KiB of values before them are not requested.  HALF (bf16 storage): the compact metas of step j, lane l are dwords 2 and 3
 // of the 16-byte piece at (j * 64 + l) * 16; only those 8 bytes are requested, the bf16 values in dwords 0 and 1 are not.
@@ -153,25 +107,7 @@ __device__ __forceinline__ void slice_values(const SliceRaw<COMPACT, HALF>& s, f
         }
     }
 }
-// -> metas in wide form (rowEnd << 31 | window index or column), c[4*j + k] = element k of the lane in step j: of a whole slice ...
-template <bool COMPACT, bool HALF>
-__device__ __forceinline__ void decode_metas(const SliceRaw<COMPACT, HALF>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
-    if constexpr (COMPACT) {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) {
-            unsigned a, b;
-            if constexpr (HALF) { a = s.q[j].z; b = s.q[j].w; } else { a = s.m[j].x; b = s.m[j].y; }
-            c[4 * j + 0] = ((a & 0x8000u) << 16) | (a & 0x7fffu);
-            c[4 * j + 1] = (a & 0x80000000u) | ((a >> 16) & 0x7fffu);
-            c[4 * j + 2] = ((b & 0x8000u) << 16) | (b & 0x7fffu);
-            c[4 * j + 3] = (b & 0x80000000u) | ((b >> 16) & 0x7fffu);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kSliceSteps; ++j) { c[4 * j + 0] = s.m[j].x; c[4 * j + 1] = s.m[j].y; c[4 * j + 2] = s.m[j].z; c[4 * j + 3] = s.m[j].w; }
-    }
-}
-// ... and of its metas alone
+// -> metas in wide form, as decode_metas(SliceRaw) of hispmv_slice_decode.h gives them for a whole slice: of its metas alone
 template <bool COMPACT>
 __device__ __forceinline__ void decode_metas(const SliceMetas<COMPACT>& s, unsigned (&c)[kSliceSteps * kLaneElems]) {
     if constexpr (COMPACT) {

@@ -1,8 +1,8 @@
 // hispmv_value_grad.hip -- the kernels of the value gradient (hispmv_value_grad.h): grad[k] = alpha * sum_v gy[v, row_k] * x[v, col_k]
 // + beta * grad[k] for every entry k of the creation input, on the slice streams and dense layouts of loaded, updatable handles.
 // What it needs of the slice format (the meta request, decode_metas, store_grad, the buffer loads, the launch
-// checks) it shares with the other four satellite files: hispmv_slice_walk.h.  hispmv_kernels.hip takes no part in that and keeps its
-// own text, so that no forward kernel is touched from here.
+// checks) it shares with the other four satellite files: hispmv_slice_walk.h.  hispmv_kernels.hip shares only the slice decode under it
+// (hispmv_slice_decode.h) and keeps its own text of the rest, so that no forward kernel is touched from here.
 //
 // Roles, against the forward slice kernel (hispmv_kernels.hip: slices_group / batched_group) and the transposed one (slices_group_t):
 //   forward                                  transposed                                 value gradient

@@ -118,7 +118,7 @@ float hispmv_last_kernel_ms(hispmv_ctx* ctx);
 int hispmv_batch_graph_stats(hispmv_ctx* ctx, int64_t out[2]);
 /* How the LAST hispmv_spmv_device_batch call of this context was issued (diagnostics; bench.py names the kernels of its step from
  * it): out = {launches of the call, 1 if its slice groups and tiles ran as items of the step kernel's queue (one persistent
- * workgroup per CU, hispmv_kernels.hip: spmv_step_kernel, or spmv_step_half_kernel for a call with half groups under
+ * workgroup per CU, hispmv_kernels.hip: spmv_step_kernel, its HALF = 1 instantiation for a call with half groups under
  * hispmv_set_step_half), items of that queue, HIP streams the main launches were spread over}.
  * HISPMV_ESTATE before the first batch call. */
 int hispmv_batch_call_info(hispmv_ctx* ctx, int64_t out[4]);
@@ -128,8 +128,8 @@ int hispmv_batch_call_info(hispmv_ctx* ctx, int64_t out[4]);
  * runs as separate grids on two lanes, whatever else it holds.  ON: such a call qualifies for the step kernel under the same
  * conditions as a call of fp32 handles (HISPMV_STEP_KERNEL not 0, the call shares the chip, 1024- or 256-thread slice plans and
  * standard tile streams, no dense handle); it is planned from the parts' batch layouts and runs hispmv_kernels.hip:
- * spmv_step_half_kernel, whose slice items read half, compact and wide groups -- hispmv_batch_call_info then reports it like any step
- * call.  A call WITHOUT half groups takes spmv_step_kernel in either state.  HISPMV_STEP_KERNEL=0 still wins.
+ * spmv_step_kernel<., HALF = 1>, whose slice items read half, compact and wide groups -- hispmv_batch_call_info then reports it like
+ * any step call.  A call WITHOUT half groups takes spmv_step_kernel<., HALF = 0> in either state.  HISPMV_STEP_KERNEL=0 still wins.
  * A batch call issued after the setter runs under the new state: the state is part of the key of the cached batch plans, so a
  * plan built under the other state is not reused (and stays valid for work still in flight).
  * The result bits are those of the grids: every item runs the body the grids run, on the same slices in the same order. */

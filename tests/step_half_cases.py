@@ -80,7 +80,7 @@ def _neighbours():
 
 
 def case_hd_stray_slots():
-    """S.stray_slot_band() as bf16 (half groups WITH stray slots: spmv_step_half_kernel<true>) next to the small neighbours of case D: the
+    """S.stray_slot_band() as bf16 (half groups WITH stray slots: spmv_step_kernel<true, 1>) next to the small neighbours of case D: the
     9000-entry window-less part and the 147-group windowed part as bf16, the others fp32."""
     return mark([S.stray_slot_band()] + _neighbours(), {0, 2, 4}, {0: (True,), 4: (True,)})
 

@@ -1,4 +1,4 @@
-"""Batch calls with bf16 handles through the step kernel (hispmv_kernels.hip: spmv_step_half_kernel; opt-in: HISPMV_STEP_HALF=1 /
+"""Batch calls with bf16 handles through the step kernel (hispmv_kernels.hip: spmv_step_kernel<., HALF = 1>; opt-in: HISPMV_STEP_HALF=1 /
 hispmv_set_step_half), at SMALL shapes.
 
 Every case goes through the harness of tests/test_gpu_step_small.py (tests/step_small_harness.py) with HISPMV_STEP_HALF=1 added to the
@@ -82,7 +82,7 @@ def test_three_bodies_and_tiles_in_one_queue(torch_mod):
 
 
 def test_stray_slots_and_a_stray_split_next_to_half_groups(torch_mod):
-    """H-D: a bf16 part whose half groups have stray slots (spmv_step_half_kernel<true>: the stray fetch next to half slices) with
+    """H-D: a bf16 part whose half groups have stray slots (spmv_step_kernel<true, 1>: the stray fetch next to half slices) with
     neighbours of both storages; and a bf16 stray split -- a half windowed part, a wide stray part into a partial vector, merged in the tail."""
     for maker, label in ((H.case_hd_stray_slots, "case H-D (stray slots)"), (H.case_hd_stray_split, "case H-D (stray split)")):
         mats = maker()
@@ -99,7 +99,7 @@ def test_stray_slots_and_a_stray_split_next_to_half_groups(torch_mod):
 
 def test_few_items_and_alternating_kernels(torch_mod):
     """H-B: the smallest windowed bf16 input alone (32 items < CUs: the exit counter rearms against that grid size), a half call of more
-    items than CUs and an all-fp32 call (spmv_step_kernel as ever) in one context, then a-b-c-a-b-c on one stream without host
+    items than CUs and an all-fp32 call (spmv_step_kernel<., 0> as ever) in one context, then a-b-c-a-b-c on one stream without host
     synchronisation: each cached plan has its own sync words, and the two kernels alternate."""
     mats, one, big, fp32 = H.case_hb()
 

@@ -5,7 +5,7 @@ hispmv_spmv_device_batch call per step, issued four ways and timed alternately i
   fp32 / step    fp32 handles, the step kernel (the headline path)
   fp32 / grids   fp32 handles in a context created under HISPMV_STEP_KERNEL=0
   bf16 / grids   bf16 handles, the switch off: the route such a call takes by default
-  bf16 / step    bf16 handles after set_step_half(True): spmv_step_half_kernel over the half batch layouts
+  bf16 / step    bf16 handles after set_step_half(True): spmv_step_kernel<., HALF = 1> over the half batch layouts
 Every route is warmed up; then `--rounds` rounds (>= 9) of `--steps` steps (>= 20) per route, the routes alternating within a round,
 every step between two device events on one non-default stream.  A round's figure is the median of its steps; per route the median,
 min and max over the rounds are reported, next to the stream bytes of the route (values + metas of the layouts the route reads) and the
