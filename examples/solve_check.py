@@ -3,8 +3,11 @@
 SPD system for M right-hand sides in one call (solvers.cg_multi) and prints iterations and the true residual of every column.
 --gmres also solves a convection-diffusion system on the same grid (Peclet number 1000, strongly non-normal) with restarted GMRES
 (solvers.gmres, --restart M) and with BiCGSTAB under the same budget of products, and prints both outcomes.
+--block-jacobi BS also sets up a block-Jacobi preconditioner of block size BS (4, 8, 16, 32; solvers.block_jacobi) for the SPD system
+and for the convection-diffusion system and prints the iterations of CG and of GMRES without a preconditioner, with the inverse
+diagonal and with the blocks.
 
-    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]]
+    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]] [--block-jacobi BS]
 """
 from __future__ import annotations
 
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--rhs", type=int, default=0, help="also solve the SPD system for this many right-hand sides in one call")
     ap.add_argument("--gmres", action="store_true", help="also solve a convection-diffusion system with restarted GMRES and with BiCGSTAB")
     ap.add_argument("--restart", type=int, default=10, help="basis vectors of a GMRES cycle, 1 .. 64")
+    ap.add_argument("--block-jacobi", type=int, default=0, metavar="BS", help="also solve with a block-Jacobi preconditioner of this block size (4, 8, 16, 32)")
     args = ap.parse_args()
     import torch
     import pyhispmv
@@ -67,6 +71,11 @@ def main():
     if args.gmres:
         gr, gc, gv = convdiff_coo(args.grid)
         cd = h.create_sparse_handle(gr, gc, gv, n, n)
+    if args.block_jacobi:
+        h.set_transposable(True)             # the extraction walks slice streams: keep that format
+        bj_spd = h.create_sparse_handle(r, c, v, n, n)
+        gr, gc, gv = convdiff_coo(args.grid)
+        bj_cd = h.create_sparse_handle(gr, gc, gv, n, n)
     h.load_matrices()
 
     dev = torch.device("cuda", 0)
@@ -102,6 +111,21 @@ def main():
             print(f"{name:8s} {n} x {n}, convection-diffusion: {info['status']}, {info['iterations']} iterations, {info['products']} products, "
                   f"recursive residual {info['relres']:.3e}, true {true:.3e}")
             assert name != "GMRES" or (info["status"] == "CONVERGED" and true < 1000 * args.rtol)
+
+    if args.block_jacobi:          # the blocks follow the fast index of the grid: a block inverts bs coupled unknowns of a grid line at once
+        b = rng.uniform(-1, 1, n).astype(np.float32)
+        tb = torch.from_numpy(b).to(dev)
+        for name, idx, (cr, cc, cv), solve, kw in (("CG", bj_spd, (r, c, v), solvers.cg, dict(rtol=args.rtol)),
+                                                   ("GMRES", bj_cd, (gr, gc, gv), solvers.gmres, dict(restart=args.restart, rtol=10 * args.rtol, max_iters=20 * args.grid))):
+            pre = solvers.block_jacobi(h, idx, args.block_jacobi)
+            minv = torch.full((n,), 0.25, dtype=torch.float32, device=dev)          # both systems have 4 on the diagonal
+            print(f"{name} {n} x {n}, block-Jacobi {pre.block_size}: {pre.singular_blocks()} blocks could not be inverted")
+            for label, more in (("no preconditioner", {}), ("minv = 1 / diag", dict(minv=minv)), (f"blocks of {pre.block_size}", dict(precond=pre))):
+                x, info = solve(h, idx, tb, **kw, **more)
+                x64 = x.cpu().numpy().astype(np.float64)
+                true = np.linalg.norm(b - np.bincount(cr, weights=cv.astype(np.float64) * x64[cc], minlength=n)) / np.linalg.norm(b)
+                print(f"  {label:20s} {info['status']}, {info['iterations']} iterations, recursive residual {info['relres']:.3e}, true {true:.3e}")
+            assert info["status"] == "CONVERGED"
 
     b = rng.uniform(-1, 1, rows).astype(np.float32)
     x, info = solvers.cgls(h, ls, torch.from_numpy(b).to(dev), rtol=args.rtol)

@@ -41,6 +41,7 @@ HISPMV_KRYLOV_CGLS = 2
 KRYLOV_SOLVERS = {"cg": HISPMV_KRYLOV_CG, "bicgstab": HISPMV_KRYLOV_BICGSTAB, "cgls": HISPMV_KRYLOV_CGLS}
 KRYLOV_STATUS = ("CONVERGED", "MAX_ITERS", "BREAKDOWN", "IN_FLIGHT")
 HISPMV_GMRES_MAX_RESTART = 64
+BLOCK_JACOBI_SIZES = (4, 8, 16, 32)
 
 
 class MatrixInfo(C.Structure):
@@ -144,7 +145,17 @@ SIGNATURES = {
     "hispmv_gmres_info": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i64p]),
     "hispmv_dot_basis_device": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_int64, _p, _p, _p, C.c_int64, _p]),
     "hispmv_gmres_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
-    "hispmv_prep_vector_widths": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
+    "hispmv_prep_block_jacobi": (C.c_int, [C.c_int64, C.c_int64, _i64p]),
+    "hispmv_block_jacobi_info": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
+    "hispmv_block_jacobi_extract_device": (C.c_int, [_p, C.c_int, C.c_int64, _p, C.c_int64, _p]),
+    "hispmv_block_invert_device": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p]),
+    "hispmv_block_jacobi_setup_device": (C.c_int, [_p, C.c_int, C.c_int64, _p, C.c_int64, _p]),
+    "hispmv_block_jacobi_status": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, _i64p]),
+    "hispmv_block_jacobi_apply_device": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, _p, _p]),
+    "hispmv_cg_bj_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
+    "hispmv_gmres_bj_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p,
+                                         C.POINTER(KrylovResult)]),
+    "hispmv_prep_vector_widths":(C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),
     "hispmv_num_matrices": (C.c_int, [_p]),

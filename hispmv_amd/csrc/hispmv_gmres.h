@@ -69,7 +69,7 @@ struct GmresStep {
     float* V = nullptr;               // the basis, `stride` floats apart
     int64_t stride = 0;
     float* x = nullptr;
-    const float* minv = nullptr;
+    const float* minv = nullptr;      // the inverse diagonal; the block-Jacobi variant (bs > 0 below): the block area of the buffer
     float* z = nullptr;               // minv * v_j, the operand of the next product (with minv only)
     const double* parts_in = nullptr; // subtract-and-dot: the partials it sums
     double* parts_out = nullptr;      // pass 1: the partials of pass 2
@@ -82,9 +82,11 @@ hipError_t launch_gmres_multi_dot(const float* V, int64_t ld, int64_t k, const f
                                   hipStream_t s);
 // out[i] = the sum of part[i * gp .. + groups) in the fixed order, i < k (one workgroup)
 hipError_t launch_gmres_dot_finish(const double* part, int64_t gp, int64_t groups, int64_t k, double* out, hipStream_t s);
-hipError_t launch_gmres_open(const GmresStep& k, hipStream_t s);          // the stopping rule on (r, r); v_0 = r / beta
-hipError_t launch_gmres_sub(const GmresStep& k, hipStream_t s);           // w -= sum h_i v_i; the partials of the next pass
-hipError_t launch_gmres_rotate(const GmresStep& k, hipStream_t s);        // the Givens step and the stopping rule; v_{j+1} = w / hn
-hipError_t launch_gmres_close(const GmresStep& k, hipStream_t s);         // R y = g; x += minv * V y
+// The three kernels that precondition take bs: 0 = k.minv is an inverse diagonal, 4 / 8 / 16 / 32 = the block area of a block-Jacobi
+// buffer of that block size (hispmv_block_jacobi_device.h); everything else is the same text.
+hipError_t launch_gmres_open(const GmresStep& k, hipStream_t s, int bs = 0);          // the stopping rule on (r, r); v_0 = r / beta
+hipError_t launch_gmres_sub(const GmresStep& k, hipStream_t s);                       // w -= sum h_i v_i; the partials of the next pass
+hipError_t launch_gmres_rotate(const GmresStep& k, hipStream_t s, int bs = 0);        // the Givens step and the stopping rule; v_{j+1} = w / hn
+hipError_t launch_gmres_close(const GmresStep& k, hipStream_t s, int bs = 0);         // R y = g; x += minv * V y
 
 }  // namespace hispmv

@@ -6,6 +6,7 @@
 // the partials; only workgroup 0 writes the Givens data and the scalar block, and no kernel reads a word of these it writes.
 #include <hip/hip_runtime.h>
 
+#include "hispmv_block_jacobi_device.h"
 #include "hispmv_gmres.h"
 #include "hispmv_krylov_device.h"
 #include "hispmv_krylov_scalar.h"
@@ -101,6 +102,9 @@ __global__ __launch_bounds__(kKrylovThreads) void gmres_dot_finish_kernel(const 
 
 // The start of a cycle, behind r = b - A x (in basis slot 0) and the partials of (r, r).  first: the block from nothing, as
 // krylov_init_kernel builds it.  rr not finite: breakdown; rr <= rtol^2 bb: done; else v_0 = f32(1 / sqrt(rr)) r and g_res[0] = sqrt(rr).
+// BS (here and in the rotate and close kernels): 0 = k.minv is an inverse diagonal, the text these kernels had before they took a block
+// size; else the block size of a block-Jacobi buffer whose block area k.minv is (hispmv_block_jacobi_device.h).
+template <int BS>
 __global__ __launch_bounds__(kKrylovThreads) void gmres_open_kernel(GmresStep k) {
     __shared__ double sh[kKrylovThreads];
     double S[kKrylovState];
@@ -142,9 +146,13 @@ __global__ __launch_bounds__(kKrylovThreads) void gmres_open_kernel(GmresStep k)
         st4(k.V, i, m, r);
         if (k.minv) {
             float d[4];
-            ld4(k.minv, i, m, d);
+            if constexpr (BS == 0) {
+                ld4(k.minv, i, m, d);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] = d[e] * r[e];
+                for (int e = 0; e < 4; ++e) d[e] = d[e] * r[e];
+            } else {
+                block_jacobi_mul4<BS>(k.minv, i, m, r, d);
+            }
             st4(k.z, i, m, d);
         }
     });
@@ -204,6 +212,7 @@ __global__ __launch_bounds__(kKrylovThreads) void gmres_sub_kernel(GmresStep k) 
 // The Givens step of column j, by every thread from the same words: the earlier rotations on h, the new one from h_j and
 // hn = sqrt((w, w)), g_fin[j] and g_res[j + 1], the stopping rule on g_res[j + 1]^2; then v_{j+1} = f32(1 / hn) w in place and, with
 // minv, z = minv v_{j+1}.
+template <int BS>
 __global__ __launch_bounds__(kKrylovThreads) void gmres_rotate_kernel(GmresStep k) {
     __shared__ double sh[kKrylovThreads];
     __shared__ double cs[kGmresMaxRestart], ss[kGmresMaxRestart], hh[kGmresMaxBasis + 1];
@@ -262,9 +271,13 @@ __global__ __launch_bounds__(kKrylovThreads) void gmres_rotate_kernel(GmresStep 
         st4(w, i, m, v);
         if (k.minv) {
             float d[4];
-            ld4(k.minv, i, m, d);
+            if constexpr (BS == 0) {
+                ld4(k.minv, i, m, d);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] = d[e] * v[e];
+                for (int e = 0; e < 4; ++e) d[e] = d[e] * v[e];
+            } else {
+                block_jacobi_mul4<BS>(k.minv, i, m, v, d);
+            }
             st4(k.z, i, m, d);
         }
     });
@@ -272,6 +285,7 @@ __global__ __launch_bounds__(kKrylovThreads) void gmres_rotate_kernel(GmresStep 
 
 // The close of a cycle: acts once, and only on the cols completed columns -- also of a solve that froze inside the cycle.  Thread 0 of
 // every workgroup solves R y = g_fin by back substitution from the same words; u = sum f32(y_i) v_i; x += minv u (or u).
+template <int BS>
 __global__ __launch_bounds__(kKrylovThreads) void gmres_close_kernel(GmresStep k) {
     __shared__ double Rs[kGmresMaxRestart * kGmresMaxRestart];
     __shared__ double gs[kGmresMaxRestart], y[kGmresMaxRestart];
@@ -315,9 +329,15 @@ __global__ __launch_bounds__(kKrylovThreads) void gmres_close_kernel(GmresStep k
         }
         if (k.minv) {
             float d[4];
-            ld4(k.minv, i, m, d);
+            if constexpr (BS == 0) {
+                ld4(k.minv, i, m, d);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = d[e] * u[e];
+                for (int e = 0; e < 4; ++e) u[e] = d[e] * u[e];
+            } else {
+                block_jacobi_mul4<BS>(k.minv, i, m, u, d);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) u[e] = d[e];
+            }
         }
         ld4(k.x, i, m, x);
 #pragma unroll
@@ -343,9 +363,20 @@ hipError_t launch_gmres_dot_finish(const double* part, int64_t gp, int64_t group
     hipLaunchKernelGGL(kernel, dim3(grid_of(k.n)), dim3(kKrylovThreads), 0, s, k);                  \
     return hipGetLastError();
 
-hipError_t launch_gmres_open(const GmresStep& k, hipStream_t s) { GMRES_LAUNCH(gmres_open_kernel) }
+// the BS instantiation of one of the three kernels that precondition
+#define GMRES_LAUNCH_BS(kernel)                                                                  \
+    switch (bs) {                                                                                \
+        case 0: { GMRES_LAUNCH(kernel<0>) }                                                      \
+        case 4: { GMRES_LAUNCH(kernel<4>) }                                                      \
+        case 8: { GMRES_LAUNCH(kernel<8>) }                                                      \
+        case 16: { GMRES_LAUNCH(kernel<16>) }                                                    \
+        case 32: { GMRES_LAUNCH(kernel<32>) }                                                    \
+        default: return hipErrorInvalidValue;                                                    \
+    }
+
+hipError_t launch_gmres_open(const GmresStep& k, hipStream_t s, int bs) { GMRES_LAUNCH_BS(gmres_open_kernel) }
 hipError_t launch_gmres_sub(const GmresStep& k, hipStream_t s) { GMRES_LAUNCH(gmres_sub_kernel) }
-hipError_t launch_gmres_rotate(const GmresStep& k, hipStream_t s) { GMRES_LAUNCH(gmres_rotate_kernel) }
-hipError_t launch_gmres_close(const GmresStep& k, hipStream_t s) { GMRES_LAUNCH(gmres_close_kernel) }
+hipError_t launch_gmres_rotate(const GmresStep& k, hipStream_t s, int bs) { GMRES_LAUNCH_BS(gmres_rotate_kernel) }
+hipError_t launch_gmres_close(const GmresStep& k, hipStream_t s, int bs) { GMRES_LAUNCH_BS(gmres_close_kernel) }
 
 }  // namespace hispmv

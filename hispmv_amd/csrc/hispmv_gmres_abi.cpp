@@ -15,6 +15,7 @@ namespace {
 // enqueued behind every cycle the loop leaves, also behind the look that found the solve ended inside it.
 struct Gmres : KrylovSolve {
     int64_t n = 0, restart = 0;
+    int bs = 0;                       // 0: d_minv is NULL or an inverse diagonal; else the block size of the block-Jacobi buffer it is
     GmresLayout l;
     hispmv_krylov_result* result = nullptr;
     GmresStep base;
@@ -56,7 +57,7 @@ struct Gmres : KrylovSolve {
             LAUNCH_TRY(c, launch_krylov_dot, vec(0), vec(0), n, at<double>(l.off_rr), s);
             GmresStep k = step();
             k.first = it == 0;
-            LAUNCH_TRY(c, launch_gmres_open, k, s);
+            LAUNCH_TRY(c, launch_gmres_open, k, s, bs);
             for (int64_t j = 0; j < m && !stop; ++j) {
                 ++products;
                 if (const int rc = hispmv_spmv_device(c, idx, d_minv ? base.z : vec(j), nullptr, vec(j + 1), 1.0f, 0.0f, stream_arg)) return rc;
@@ -69,13 +70,13 @@ struct Gmres : KrylovSolve {
                 LAUNCH_TRY(c, launch_gmres_sub, k, s);
                 k = step();
                 k.j = (int)j;
-                LAUNCH_TRY(c, launch_gmres_rotate, k, s);
+                LAUNCH_TRY(c, launch_gmres_rotate, k, s, bs);
                 ++it;
                 if (check_every > 0 && it % check_every == 0)
                     if (const int rc = look(&stop)) return rc;
             }
             k = step();
-            LAUNCH_TRY(c, launch_gmres_close, k, s);
+            LAUNCH_TRY(c, launch_gmres_close, k, s, bs);
         }
         if (check_every == 0) {
             *result = hispmv_krylov_result{HISPMV_KRYLOV_IN_FLIGHT, 0, 0.0, products};
@@ -120,19 +121,24 @@ HISPMV_API int hispmv_dot_basis_device(hispmv_ctx* c, int64_t n, int64_t k, cons
     return HISPMV_OK;
 }
 
-HISPMV_API int hispmv_gmres_device(hispmv_ctx* c, int idx, const float* d_b, float* d_x, const float* d_minv, int64_t restart, double rtol, int64_t max_iters,
-                                   int64_t check_every, void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
+namespace {
+// bs > 0 (hispmv_gmres_bj_device): d_minv is the block-Jacobi buffer of that block size, 16-byte aligned, and may not be NULL
+int gmres_solve(hispmv_ctx* c, int idx, const float* d_b, float* d_x, const float* d_minv, int64_t bs, int64_t restart, double rtol, int64_t max_iters,
+                int64_t check_every, void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
     if (!c || !result) return HISPMV_EINVAL;
     Gmres v;
-    const std::string w("gmres_device");
+    const char* const name = bs != 0 ? "gmres_bj_device" : "gmres_device";
+    const std::string w(name);
     {
         std::lock_guard<std::mutex> g(c->mu);
         if (const int rc = krylov_check_scalars(c, w, rtol, max_iters, check_every)) return rc;
         if (restart < 1 || restart > kGmresMaxRestart) return fail(c, HISPMV_EINVAL, w + ": restart must be 1 .. " + std::to_string(kGmresMaxRestart));
         Matrix* mp = nullptr;
-        if (const int rc = find_handle(c, idx, "gmres_device", &mp)) return rc;
+        if (const int rc = find_handle(c, idx, name, &mp)) return rc;
         const Matrix& m = *mp;
         if (const int rc = krylov_check_square(c, w, m)) return rc;
+        if (bs != 0)
+            if (const int rc = krylov_check_blocks(c, w, d_minv, bs)) return rc;
         if (const int rc = krylov_check_operands(c, w, !d_b || !d_x, d_b, d_x, d_minv)) return rc;
         v.n = m.rows;
         v.l = gmres_layout(v.n, restart, d_minv != nullptr);
@@ -140,7 +146,7 @@ HISPMV_API int hispmv_gmres_device(hispmv_ctx* c, int idx, const float* d_b, flo
         if (const int rc = adopt_stream(c, stream, &v.s)) return rc;
     }
     v.c = c; v.idx = idx; v.max_iters = max_iters; v.check_every = check_every; v.work = (char*)d_work; v.stream_arg = stream;
-    v.d_b = d_b; v.d_x = d_x; v.d_minv = d_minv; v.result = result; v.restart = restart;
+    v.d_b = d_b; v.d_x = d_x; v.d_minv = d_minv; v.result = result; v.restart = restart; v.bs = (int)bs;
     const int64_t cycles = (max_iters + restart - 1) / restart;
     v.blocks.kernels = 2 * cycles + 3 * max_iters;          // open and close per cycle; subtract twice and rotate per step
     GmresStep& b = v.base;
@@ -152,4 +158,16 @@ HISPMV_API int hispmv_gmres_device(hispmv_ctx* c, int idx, const float* d_b, flo
     b.h1 = v.at<double>(l.off_h1); b.h = v.at<double>(l.off_h); b.R = v.at<double>(l.off_r);
     if (check_every > 0) HIP_TRY(c, hipHostMalloc((void**)&v.pinned, kGmresStateBytes, hipHostMallocDefault));
     return v.run();
+}
+}  // namespace
+
+HISPMV_API int hispmv_gmres_device(hispmv_ctx* c, int idx, const float* d_b, float* d_x, const float* d_minv, int64_t restart, double rtol, int64_t max_iters,
+                                   int64_t check_every, void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
+    return gmres_solve(c, idx, d_b, d_x, d_minv, 0, restart, rtol, max_iters, check_every, d_work, work_bytes, stream, result);
+}
+
+HISPMV_API int hispmv_gmres_bj_device(hispmv_ctx* c, int idx, const float* d_b, float* d_x, const void* d_pre, int64_t block_size, int64_t restart, double rtol,
+                                      int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
+    if (block_size == 0) return c ? fail(c, HISPMV_EINVAL, "gmres_bj_device: block_size must be 4, 8, 16 or 32") : HISPMV_EINVAL;
+    return gmres_solve(c, idx, d_b, d_x, (const float*)d_pre, block_size, restart, rtol, max_iters, check_every, d_work, work_bytes, stream, result);
 }

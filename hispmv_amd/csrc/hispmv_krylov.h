@@ -54,7 +54,7 @@ struct KrylovStep {
     int slot_rho = kSlotRho;        // where rho's partials lie (without minv, and in CGLS: kSlotRr, rho is rr)
     int slot_bb = kSlotB2;          // init: where (reference, reference) lies
     float* x = nullptr;
-    const float* minv = nullptr;
+    const float* minv = nullptr;    // the inverse diagonal; the block-Jacobi variants (bs > 0 below): the block area of the buffer
     float* r = nullptr;             // CGLS direction pass: s
     float* p = nullptr;
     const float* q = nullptr;       // BiCGSTAB: v
@@ -69,10 +69,12 @@ struct KrylovStep {
 hipError_t launch_krylov_dot(const float* a, const float* b, int64_t n, double* part, hipStream_t s);
 // *out = the sum of the groups partials in the fixed order (one workgroup)
 hipError_t launch_krylov_dot_finish(const double* part, int64_t groups, double* out, hipStream_t s);
-hipError_t launch_krylov_init(const KrylovStep& k, hipStream_t s);           // p = z = minv * r (or r), rhat = r; partials (r, r), (r, z)
+// The three kernels that precondition take bs: 0 = k.minv is an inverse diagonal (z = minv * r elementwise), 4 / 8 / 16 / 32 = it is the
+// block area of a block-Jacobi buffer of that block size (z = M^-1 r, hispmv_block_jacobi_device.h); everything else is the same text.
+hipError_t launch_krylov_init(const KrylovStep& k, hipStream_t s, int bs = 0);           // p = z = minv * r (or r), rhat = r; partials (r, r), (r, z)
 hipError_t launch_krylov_step_dot(const KrylovStep& k, hipStream_t s);       // the dot pass behind a product
-hipError_t launch_krylov_cg_update(const KrylovStep& k, hipStream_t s);      // x += alpha p, r -= alpha q; partials (r, r), (r, z)
-hipError_t launch_krylov_direction(const KrylovStep& k, hipStream_t s);      // p = z + beta p, and the stopping rule
+hipError_t launch_krylov_cg_update(const KrylovStep& k, hipStream_t s, int bs = 0);      // x += alpha p, r -= alpha q; partials (r, r), (r, z)
+hipError_t launch_krylov_direction(const KrylovStep& k, hipStream_t s, int bs = 0);      // p = z + beta p, and the stopping rule
 hipError_t launch_krylov_cgls_update(const KrylovStep& k, hipStream_t s);    // x += alpha p (n), r -= alpha q (n2)
 hipError_t launch_krylov_bicg_s(const KrylovStep& k, hipStream_t s);         // r = s = r - alpha v; partials (s, s)
 hipError_t launch_krylov_bicg_x(const KrylovStep& k, hipStream_t s);         // x += alpha p + omega s, r = s - omega t; partials (r, r), (rhat, r)

@@ -7,6 +7,7 @@
 // which hands the sums to the scalar rule of hispmv_krylov_scalar.h: the arithmetic of every scalar is written there.
 #include <hip/hip_runtime.h>
 
+#include "hispmv_block_jacobi_device.h"
 #include "hispmv_krylov.h"
 #include "hispmv_krylov_device.h"
 #include "hispmv_krylov_scalar.h"
@@ -37,6 +38,9 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_dot_finish_kernel(const
 }
 
 // The first kernel of a solve, behind the products that give src (the residual; CGLS: A^T of it): the scalar block from nothing.
+// BS (here and in the CG update and the direction kernel): 0 = k.minv is the inverse diagonal, the text these kernels had before they
+// took a block size; else the block size of a block-Jacobi buffer whose block area k.minv is (hispmv_block_jacobi_device.h).
+template <int BS>
 __global__ __launch_bounds__(kKrylovThreads) void krylov_init_kernel(KrylovStep k) {
     __shared__ double sh[kKrylovThreads];
     double S[kKrylovState];
@@ -50,10 +54,14 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_init_kernel(KrylovStep 
         float r[4], z[4];
         ld4(k.r, i, m, r);
         if (k.minv) {
-            float d[4];
-            ld4(k.minv, i, m, d);
+            if constexpr (BS == 0) {
+                float d[4];
+                ld4(k.minv, i, m, d);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = d[j] * r[j];
+                for (int j = 0; j < 4; ++j) z[j] = d[j] * r[j];
+            } else {
+                block_jacobi_mul4<BS>(k.minv, i, m, r, z);
+            }
             acc_rz += dot4(r, z, m);
         } else {
 #pragma unroll
@@ -108,6 +116,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_step_dot_kernel(KrylovS
 }
 
 // CG: alpha = rho / (p, q); x += alpha p; r -= alpha q; the partials of (r, r) and, with minv, of (r, minv r)
+template <int BS>
 __global__ __launch_bounds__(kKrylovThreads) void krylov_cg_update_kernel(KrylovStep k) {
     __shared__ double sh[kKrylovThreads];
     double S[kKrylovState];
@@ -138,11 +147,17 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_cg_update_kernel(Krylov
         st4(k.r, i, m, r);
         acc_rr += dot4(r, r, m);
         if (k.minv) {
-            float d[4], z[4];
-            ld4(k.minv, i, m, d);
+            if constexpr (BS == 0) {
+                float d[4], z[4];
+                ld4(k.minv, i, m, d);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = d[j] * r[j];
-            acc_rz += dot4(r, z, m);
+                for (int j = 0; j < 4; ++j) z[j] = d[j] * r[j];
+                acc_rz += dot4(r, z, m);
+            } else {
+                float z[4];
+                block_jacobi_mul4<BS>(k.minv, i, m, r, z);
+                acc_rz += dot4(r, z, m);
+            }
         }
     });
     const double rr = block_sum(acc_rr, sh);
@@ -154,6 +169,7 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_cg_update_kernel(Krylov
 }
 
 // CG and CGLS: the stopping rule on the new rr, then beta = rho' / rho; p = z + beta p with z = minv r (or r; CGLS: s)
+template <int BS>
 __global__ __launch_bounds__(kKrylovThreads) void krylov_direction_kernel(KrylovStep k) {
     __shared__ double sh[kKrylovThreads];
     double S[kKrylovState];
@@ -172,10 +188,17 @@ __global__ __launch_bounds__(kKrylovThreads) void krylov_direction_kernel(Krylov
         ld4(k.r, i, m, r);
         ld4(k.p, i, m, p);
         if (k.minv) {
-            float d[4];
-            ld4(k.minv, i, m, d);
+            if constexpr (BS == 0) {
+                float d[4];
+                ld4(k.minv, i, m, d);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) r[j] = d[j] * r[j];
+                for (int j = 0; j < 4; ++j) r[j] = d[j] * r[j];
+            } else {
+                float z[4];
+                block_jacobi_mul4<BS>(k.minv, i, m, r, z);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) r[j] = z[j];
+            }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -359,10 +382,21 @@ hipError_t launch_krylov_dot_finish(const double* part, int64_t groups, double* 
     hipLaunchKernelGGL(kernel, dim3(grid_of(n_)), dim3(kKrylovThreads), 0, s, k);                  \
     return hipGetLastError();
 
-hipError_t launch_krylov_init(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_init_kernel, k.n) }
+// the BS instantiation of one of the three kernels that precondition
+#define KRYLOV_LAUNCH_BS(kernel, n_)                                                                \
+    switch (bs) {                                                                                   \
+        case 0: { KRYLOV_LAUNCH(kernel<0>, n_) }                                                    \
+        case 4: { KRYLOV_LAUNCH(kernel<4>, n_) }                                                    \
+        case 8: { KRYLOV_LAUNCH(kernel<8>, n_) }                                                    \
+        case 16: { KRYLOV_LAUNCH(kernel<16>, n_) }                                                  \
+        case 32: { KRYLOV_LAUNCH(kernel<32>, n_) }                                                  \
+        default: return hipErrorInvalidValue;                                                       \
+    }
+
+hipError_t launch_krylov_init(const KrylovStep& k, hipStream_t s, int bs) { KRYLOV_LAUNCH_BS(krylov_init_kernel, k.n) }
 hipError_t launch_krylov_step_dot(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_step_dot_kernel, k.n) }
-hipError_t launch_krylov_cg_update(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_cg_update_kernel, k.n) }
-hipError_t launch_krylov_direction(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_direction_kernel, k.n) }
+hipError_t launch_krylov_cg_update(const KrylovStep& k, hipStream_t s, int bs) { KRYLOV_LAUNCH_BS(krylov_cg_update_kernel, k.n) }
+hipError_t launch_krylov_direction(const KrylovStep& k, hipStream_t s, int bs) { KRYLOV_LAUNCH_BS(krylov_direction_kernel, k.n) }
 hipError_t launch_krylov_cgls_update(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_cgls_update_kernel, (k.n > k.n2 ? k.n : k.n2)) }
 hipError_t launch_krylov_bicg_s(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_bicg_s_kernel, k.n) }
 hipError_t launch_krylov_bicg_x(const KrylovStep& k, hipStream_t s) { KRYLOV_LAUNCH(krylov_bicg_x_kernel, k.n) }

@@ -55,10 +55,12 @@ struct Solve : KrylovSolve {
         LAUNCH_TRY(c, launch_krylov_dot, sv, sv, cols, slot(kSlotBb), s);
         return HISPMV_OK;
     }
-    KRYLOV_LAUNCHER(init, launch_krylov_init)
+    // the three kernels that precondition: bs = 0, d_minv an inverse diagonal; bs > 0 (hispmv_cg_bj_device), the block area of a buffer
+    int bs = 0;
+    int init(const KrylovStep& k) { LAUNCH_TRY(c, launch_krylov_init, k, s, bs); return HISPMV_OK; }
+    int cg_update(const KrylovStep& k) { LAUNCH_TRY(c, launch_krylov_cg_update, k, s, bs); return HISPMV_OK; }
+    int direction(const KrylovStep& k) { LAUNCH_TRY(c, launch_krylov_direction, k, s, bs); return HISPMV_OK; }
     KRYLOV_LAUNCHER(step_dot, launch_krylov_step_dot)
-    KRYLOV_LAUNCHER(cg_update, launch_krylov_cg_update)
-    KRYLOV_LAUNCHER(direction, launch_krylov_direction)
     KRYLOV_LAUNCHER(cgls_update, launch_krylov_cgls_update)
     KRYLOV_LAUNCHER(bicg_s, launch_krylov_bicg_s)
     KRYLOV_LAUNCHER(bicg_x, launch_krylov_bicg_x)
@@ -74,28 +76,32 @@ struct Solve : KrylovSolve {
     void report_looked() { fill_result(pinned, false, products, result); }
 };
 
+// bs > 0 (hispmv_cg_bj_device): d_minv is the block-Jacobi buffer of that block size, 16-byte aligned, and may not be NULL
 int solve(hispmv_ctx* c, int idx, int solver, const float* d_b, float* d_x, const float* d_minv, double rtol, int64_t max_iters, int64_t check_every,
-          void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
+          void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result, int64_t bs = 0) {
     if (!c || !result) return HISPMV_EINVAL;
     Solve v;
-    const std::string w(kNames[solver]);
+    const char* const name = bs != 0 ? "cg_bj_device" : kNames[solver];
+    const std::string w(name);
     const bool cgls = solver == HISPMV_KRYLOV_CGLS;
     {
         std::lock_guard<std::mutex> g(c->mu);
         if (const int rc = krylov_check_scalars(c, w, rtol, max_iters, check_every)) return rc;
         Matrix* mp = nullptr;
-        if (const int rc = find_handle(c, idx, kNames[solver], &mp)) return rc;
+        if (const int rc = find_handle(c, idx, name, &mp)) return rc;
         const Matrix& m = *mp;
         if (!cgls)
             if (const int rc = krylov_check_square(c, w, m)) return rc;
         if (cgls && !m.companion && !transposable_handle(m)) return refuse_tile_stream(c, m, kNames[solver], "transposed product");
+        if (bs != 0)
+            if (const int rc = krylov_check_blocks(c, w, d_minv, bs)) return rc;
         if (const int rc = krylov_check_operands(c, w, !d_b || !d_x, d_b, d_x, d_minv)) return rc;
         if (const int rc = krylov_check_work(c, w, d_work, work_bytes, work_bytes_of(m, solver), "hispmv_krylov_info asks for")) return rc;
         if (const int rc = adopt_stream(c, stream, &v.s)) return rc;
         v.rows = m.rows; v.cols = m.cols; v.stride = stride_of(m);
     }
     v.c = c; v.idx = idx; v.solver = solver; v.max_iters = max_iters; v.check_every = check_every; v.work = (char*)d_work; v.stream_arg = stream;
-    v.d_b = d_b; v.d_x = d_x; v.d_minv = d_minv; v.result = result;
+    v.d_b = d_b; v.d_x = d_x; v.d_minv = d_minv; v.result = result; v.bs = (int)bs;
     v.blocks.kernels = 1 + max_iters * kKrylovLaunches[solver];
     v.base.n = v.cols; v.base.n2 = v.rows; v.base.x = d_x; v.base.parts = v.parts(); v.base.tol2 = rtol * rtol;
     v.base.slot_bb = cgls ? kSlotBb : kSlotB2;
@@ -141,6 +147,12 @@ HISPMV_API int hispmv_dot_device(hispmv_ctx* c, int64_t n, const float* d_a, con
 HISPMV_API int hispmv_cg_device(hispmv_ctx* c, int idx, const float* d_b, float* d_x, const float* d_minv, double rtol, int64_t max_iters, int64_t check_every,
                                 void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
     return solve(c, idx, HISPMV_KRYLOV_CG, d_b, d_x, d_minv, rtol, max_iters, check_every, d_work, work_bytes, stream, result);
+}
+
+HISPMV_API int hispmv_cg_bj_device(hispmv_ctx* c, int idx, const float* d_b, float* d_x, const void* d_pre, int64_t block_size, double rtol, int64_t max_iters,
+                                   int64_t check_every, void* d_work, int64_t work_bytes, void* stream, hispmv_krylov_result* result) {
+    if (block_size == 0) return c ? fail(c, HISPMV_EINVAL, "cg_bj_device: block_size must be 4, 8, 16 or 32") : HISPMV_EINVAL;
+    return solve(c, idx, HISPMV_KRYLOV_CG, d_b, d_x, (const float*)d_pre, rtol, max_iters, check_every, d_work, work_bytes, stream, result, block_size);
 }
 
 HISPMV_API int hispmv_bicgstab_device(hispmv_ctx* c, int idx, const float* d_b, float* d_x, double rtol, int64_t max_iters, int64_t check_every,

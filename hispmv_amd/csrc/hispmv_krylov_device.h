@@ -59,7 +59,7 @@ __device__ double block_sum(double v, double* sh) {
     return r;
 }
 // The sum of `groups` <= 1024 partials: thread t adds part[4t .. 4t + 3] ascending from +0, then the tree.
-__device__ double sum_partials(const double* part, int64_t groups, double* sh) {
+[[maybe_unused]] __device__ double sum_partials(const double* part, int64_t groups, double* sh) {
     double s = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

@@ -75,6 +75,12 @@ inline int krylov_check_operands(hispmv_ctx* c, const std::string& w, bool missi
     if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)opt) & 3) return fail(c, HISPMV_EINVAL, w + ": device pointers must be 4-byte aligned");
     return HISPMV_OK;
 }
+// the block-Jacobi buffer of hispmv_cg_bj_device and hispmv_gmres_bj_device in the place of d_minv
+inline int krylov_check_blocks(hispmv_ctx* c, const std::string& w, const void* d_pre, int64_t bs) {
+    if (bs != 4 && bs != 8 && bs != 16 && bs != 32) return fail(c, HISPMV_EINVAL, w + ": block_size must be 4, 8, 16 or 32");
+    if (!d_pre || ((uintptr_t)d_pre & 15)) return fail(c, HISPMV_EINVAL, w + ": the block-Jacobi buffer must be the 16-byte aligned one of hispmv_block_jacobi_setup_device");
+    return HISPMV_OK;
+}
 // asks = who wants `need` bytes: "hispmv_krylov_info asks for", "the 2 partials take"
 inline int krylov_check_work(hispmv_ctx* c, const std::string& w, const void* d_work, int64_t work_bytes, int64_t need, const std::string& asks) {
     if (work_bytes < need || (need > 0 && !d_work))

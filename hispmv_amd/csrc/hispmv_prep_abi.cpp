@@ -2,6 +2,7 @@
 // format / tiling choice and the tile-stream packer without a device, for tests on a CPU-only box.  Mirrors
 // HiSpmvHandle::getPreparedMtx (common/src/spmv-helper.cpp:800-802).  (hispmv_prep_from_coo_device is the one entry here that
 // touches the GPU.)
+#include "hispmv_block_jacobi.h"
 #include "hispmv_ctx.h"
 #include "hispmv_gmres.h"
 
@@ -378,5 +379,13 @@ HISPMV_API int hispmv_prep_gmres(int64_t n, int64_t restart, int with_minv, int6
     const GmresLayout l = gmres_layout(n, restart, with_minv != 0);
     out[0] = l.work_bytes; out[1] = l.off_v; out[2] = l.stride; out[3] = l.groups; out[4] = kGmresDotTile;
     out[5] = kGmresLaunchesInner; out[6] = kGmresLaunchesCycle; out[7] = restart + 1;
+    return HISPMV_OK;
+}
+
+// The layout rule of a block-Jacobi buffer (hispmv_block_jacobi.h: block_jacobi_layout), which every block-Jacobi entry follows.
+HISPMV_API int hispmv_prep_block_jacobi(int64_t n, int64_t bs, int64_t out[4]) {
+    if (!out || n < 0 || n > 0x7fffffffLL || !block_jacobi_size_ok(bs)) return HISPMV_EINVAL;
+    const BlockJacobiLayout l = block_jacobi_layout(n, bs);
+    out[0] = l.n_blocks; out[1] = l.pre_bytes; out[2] = l.off_flags; out[3] = l.block_floats;
     return HISPMV_OK;
 }

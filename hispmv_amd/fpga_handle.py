@@ -563,6 +563,70 @@ class FpgaHandle:
                                             int(max_iters), int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
         return self._krylov_result(res)
 
+    # -- block-Jacobi preconditioner (hispmv_block_jacobi_abi.cpp; hispmv_amd.solvers.block_jacobi wraps these) ------------------------
+    def block_jacobi_info(self, matrix_idx: int, block_size: int = 8) -> dict:
+        """{"accepted", "n_blocks", "pre_bytes", "setup_launches", "cg_work_bytes", "gmres_work_bytes", "gmres_step_bytes", "n"} of a
+        block-Jacobi preconditioner of block_size (4, 8, 16, 32) on a handle (hispmv_block_jacobi_info): the blocks and bytes of the
+        caller's buffer, the launches of a setup, the workspace of cg_bj_device and of gmres_bj_device with restart 1 plus what every
+        further step of restart adds; zeros for a handle that is not loaded, not square or a tile stream."""
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_block_jacobi_info(self._ctx, int(matrix_idx), int(block_size), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError("block_size must be 4, 8, 16 or 32")
+            raise IndexError("Matrix idx out of range")
+        keys = ("accepted", "n_blocks", "pre_bytes", "setup_launches", "cg_work_bytes", "gmres_work_bytes", "gmres_step_bytes", "n")
+        d = dict(zip(keys, (int(x) for x in out)))
+        d["accepted"] = bool(d["accepted"])
+        return d
+
+    def block_jacobi_extract_device(self, matrix_idx: int, block_size: int, d_pre: int, pre_bytes: int, stream: int = 0) -> None:
+        """The padded diagonal blocks of the loaded matrix, not inverted, into the block area of the buffer at d_pre
+        (hispmv_block_jacobi_extract_device; the layout is prep.block_jacobi's).  Asynchronous on `stream`.  A tile-stream handle
+        raises NotImplementedError; a handle that is not square, a bad block_size or a short, missing or misaligned buffer ValueError."""
+        self._check(lib.hispmv_block_jacobi_extract_device(self._ctx, int(matrix_idx), int(block_size), C.c_void_p(d_pre), int(pre_bytes), C.c_void_p(stream)))
+
+    def block_invert_device(self, d_pre: int, n_blocks: int, block_size: int, stream: int = 0) -> None:
+        """Inverts the n_blocks blocks of block_size x block_size floats at d_pre in place and writes their int32 flags behind them
+        (hispmv_block_invert_device): Gauss-Jordan with partial pivoting, bit for bit the rule of include/hispmv.h; a block that
+        cannot be inverted becomes the identity, flag 1.  Asynchronous on `stream`."""
+        self._check(lib.hispmv_block_invert_device(self._ctx, C.c_void_p(d_pre), int(n_blocks), int(block_size), C.c_void_p(stream)))
+
+    def block_jacobi_setup_device(self, matrix_idx: int, block_size: int, d_pre: int, pre_bytes: int, stream: int = 0) -> None:
+        """Extraction followed by inversion (hispmv_block_jacobi_setup_device); exceptions as block_jacobi_extract_device."""
+        self._check(lib.hispmv_block_jacobi_setup_device(self._ctx, int(matrix_idx), int(block_size), C.c_void_p(d_pre), int(pre_bytes), C.c_void_p(stream)))
+
+    def block_jacobi_status(self, d_pre: int, n: int, block_size: int, stream: int = 0) -> int:
+        """Waits for `stream` and returns the number of blocks of the buffer that were replaced by the identity (hispmv_block_jacobi_status)."""
+        out = C.c_int64(0)
+        self._check(lib.hispmv_block_jacobi_status(self._ctx, C.c_void_p(d_pre), int(n), int(block_size), C.c_void_p(stream), C.byref(out)))
+        return int(out.value)
+
+    def block_jacobi_apply_device(self, d_pre: int, n: int, block_size: int, d_r: int, d_z: int, stream: int = 0) -> None:
+        """d_z = M^-1 d_r over n float32 elements with the inverted blocks at d_pre (hispmv_block_jacobi_apply_device).  Asynchronous on
+        `stream`; d_r and d_z need 4-byte alignment only."""
+        self._check(lib.hispmv_block_jacobi_apply_device(self._ctx, C.c_void_p(d_pre), int(n), int(block_size), C.c_void_p(d_r), C.c_void_p(d_z),
+                                                         C.c_void_p(stream)))
+
+    def cg_bj_device(self, matrix_idx: int, d_b: int, d_x: int, d_pre: int, block_size: int, rtol: float = 1e-6, max_iters: int = 1000,
+                     check_every: int = 8, work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """cg_device with the block-Jacobi buffer (d_pre, block_size) in place of d_minv (hispmv_cg_bj_device); workspace, result and
+        exceptions as cg_device."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_cg_bj_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(d_pre), int(block_size), float(rtol),
+                                            int(max_iters), int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
+        return self._krylov_result(res)
+
+    def gmres_bj_device(self, matrix_idx: int, d_b: int, d_x: int, d_pre: int, block_size: int, restart: int = 30, rtol: float = 1e-6,
+                        max_iters: int = 1000, check_every: int = 8, work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """gmres_device with the block-Jacobi buffer (d_pre, block_size) in place of d_minv, as a right preconditioner
+        (hispmv_gmres_bj_device); the workspace is gmres_info(..., with_minv=True)'s; result and exceptions as gmres_device."""
+        res = _lib.KrylovResult()
+        self._check(lib.hispmv_gmres_bj_device(self._ctx, int(matrix_idx), C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(d_pre), int(block_size), int(restart),
+                                               float(rtol), int(max_iters), int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream),
+                                               C.byref(res)))
+        return self._krylov_result(res)
+
     def set_arena_bytes(self, nbytes: int) -> None:
         self._check(lib.hispmv_set_arena_bytes(self._ctx, int(nbytes)))
 

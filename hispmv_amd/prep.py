@@ -319,6 +319,16 @@ def gmres(n: int, restart: int, with_minv: bool = False) -> dict:
     return dict(zip(keys, (int(x) for x in out)))
 
 
+def block_jacobi(n: int, block_size: int) -> dict:
+    """The layout rule of a block-Jacobi buffer (hispmv_prep_block_jacobi), host-only: {"n_blocks", "pre_bytes", "flags_offset",
+    "block_floats"} for a system of n unknowns in blocks of block_size (4, 8, 16, 32) -- ceil(n / block_size) blocks of block_size^2
+    floats each, row-major, then one int32 flag per block at flags_offset, pre_bytes in all (a multiple of 16)."""
+    out = (C.c_int64 * 4)()
+    if lib.hispmv_prep_block_jacobi(int(n), int(block_size), out) != HISPMV_OK:
+        raise ValueError("hispmv_prep_block_jacobi: 0 <= n < 2^31 and block_size 4, 8, 16 or 32")
+    return dict(zip(("n_blocks", "pre_bytes", "flags_offset", "block_floats"), (int(x) for x in out)))
+
+
 VALUE_LAYOUT_FIELDS = ("bytes", "map_slots", "chunks", "written", "format", "tile_kind", "parts", "batch_layouts")
 
 

@@ -15,7 +15,11 @@ overwritten, before ``handle.krylov_status(info["work"].data_ptr(), 0)`` or ``ha
 Several right-hand sides: ``cg_multi`` and ``bicgstab_multi`` solve the columns of B [n, m] as m independent solves that share their
 launches (FpgaHandle.cg_multi_device / bicgstab_multi_device over spmm_device's products); same streams, same rule.
 
-Restarted GMRES: ``gmres`` (FpgaHandle.gmres_device) for square non-symmetric systems, one product per inner iteration."""
+Restarted GMRES: ``gmres`` (FpgaHandle.gmres_device) for square non-symmetric systems, one product per inner iteration.
+
+Block-Jacobi: ``block_jacobi(handle, idx, block_size)`` builds the inverted diagonal blocks of a loaded square handle on the device
+(FpgaHandle.block_jacobi_setup_device) and returns an object ``cg`` and ``gmres`` take as ``precond=`` in place of ``minv``; same
+streams, same rule."""
 from __future__ import annotations
 
 import torch
@@ -50,8 +54,63 @@ def _launch(handle, device, check_every: int, call):
     return info
 
 
-def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, check_every: int, work):
+class BlockJacobi:
+    """The block-Jacobi preconditioner of handle `idx`: the buffer tensor (``buffer``: the inverted diagonal blocks, then their flags;
+    prep.block_jacobi's layout) with ``block_size`` and ``n``.  Made by `block_jacobi`; pass it to `cg` / `gmres` as ``precond=``."""
+
+    def __init__(self, handle, idx: int, block_size: int, device):
+        info = handle.block_jacobi_info(idx, block_size)          # a bad block_size or index raises here
+        self.handle, self.idx, self.block_size = handle, idx, int(block_size)
+        self.n = handle.matrix_info(idx)["rows"]
+        # (a handle the setup refuses gets an empty buffer: the entry itself says why it refuses)
+        self.buffer = torch.empty(info["pre_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+        self.refresh()
+
+    def refresh(self) -> "BlockJacobi":
+        """A setup again on torch's current stream: after update_values_device the blocks of the new values."""
+        _launch(self.handle, self.buffer.device, 1,
+                lambda stream: self.handle.block_jacobi_setup_device(self.idx, self.block_size, self.buffer.data_ptr(), self.buffer.numel(), stream))
+        return self
+
+    def singular_blocks(self) -> int:
+        """Blocks that could not be inverted and were replaced by the identity (waits for the setup)."""
+        return _launch(self.handle, self.buffer.device, 0,
+                       lambda stream: self.handle.block_jacobi_status(self.buffer.data_ptr(), self.n, self.block_size, stream))
+
+    def apply(self, r):
+        """z = M^-1 r as a new tensor, on torch's current stream."""
+        r = _vector(r, "r", self.n)
+        z = torch.empty_like(r)
+        _launch(self.handle, r.device, 1,
+                lambda stream: self.handle.block_jacobi_apply_device(self.buffer.data_ptr(), self.n, self.block_size, r.data_ptr(), z.data_ptr(), stream))
+        return z
+
+
+def block_jacobi(handle, idx: int, block_size: int = 8, device=None) -> BlockJacobi:
+    """Sets up a block-Jacobi preconditioner for the loaded square handle `idx` on torch's current stream: the diagonal blocks of
+    block_size (4, 8, 16 or 32) are extracted from the loaded matrix and inverted on the device; a block that cannot be inverted is
+    replaced by the identity (`singular_blocks()` counts them).  Returns the object `cg` and `gmres` take as ``precond=``; after
+    update_values_device call its `refresh()`.  A tile-stream handle raises NotImplementedError, a handle that is not square ValueError."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return BlockJacobi(handle, idx, block_size, device)
+
+
+def _precond(precond, minv, n: int):
+    if precond is None:
+        return None
+    if minv is not None:
+        raise ValueError("give minv or precond, not both")
+    if not isinstance(precond, BlockJacobi):
+        raise TypeError("precond must be the object solvers.block_jacobi returns")
+    if precond.n != n:
+        raise ValueError(f"precond was set up for {precond.n} unknowns, the handle has {n}")
+    return precond
+
+
+def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, check_every: int, work, precond=None):
     m = handle.matrix_info(idx)
+    precond = _precond(precond, minv, m["rows"])
     b = _vector(b, "b", m["rows"])
     x = torch.zeros(m["cols"], dtype=torch.float32, device=b.device) if x0 is None else _vector(x0, "x0", m["cols"]).clone()
     if minv is not None:
@@ -63,6 +122,8 @@ def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, c
 
     def call(stream):
         kw = dict(rtol=rtol, max_iters=max_iters, check_every=check_every, work=work.data_ptr(), work_bytes=work.numel() * work.element_size(), stream=stream)
+        if solver == "cg" and precond is not None:
+            return handle.cg_bj_device(idx, b.data_ptr(), x.data_ptr(), precond.buffer.data_ptr(), precond.block_size, **kw)
         if solver == "cg":
             return handle.cg_device(idx, b.data_ptr(), x.data_ptr(), 0 if minv is None else minv.data_ptr(), **kw)
         if solver == "bicgstab":
@@ -73,12 +134,12 @@ def _solve(solver: str, handle, idx: int, b, x0, minv, rtol: float, max_iters, c
     return x, info
 
 
-def cg(handle, idx: int, b, x0=None, *, minv=None, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+def cg(handle, idx: int, b, x0=None, *, minv=None, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None, precond=None):
     """Solves A x = b for the symmetric positive definite handle `idx` by (diagonally preconditioned) CG on torch's current stream.
     b, x0 and minv (the inverse diagonal, optional) are float32 CUDA vectors; returns (x, info) with info = {"status", "iterations",
     "relres", "products", "work"}.  max_iters defaults to twice the dimension; check_every = 0 enqueues exactly max_iters iterations
-    and returns without waiting (status "IN_FLIGHT")."""
-    return _solve("cg", handle, idx, b, x0, minv, rtol, max_iters, check_every, work)
+    and returns without waiting (status "IN_FLIGHT").  precond: the object of `block_jacobi` in place of minv (both: ValueError)."""
+    return _solve("cg", handle, idx, b, x0, minv, rtol, max_iters, check_every, work, precond)
 
 
 def bicgstab(handle, idx: int, b, x0=None, *, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
@@ -98,12 +159,14 @@ def workspace_gmres(handle, idx: int, restart: int, with_minv: bool, device) -> 
     return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
 
 
-def gmres(handle, idx: int, b, x0=None, *, minv=None, restart: int = 30, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None):
+def gmres(handle, idx: int, b, x0=None, *, minv=None, restart: int = 30, rtol: float = 1e-6, max_iters=None, check_every: int = 8, work=None,
+          precond=None):
     """Solves A x = b for a square, non-symmetric handle by restarted GMRES(restart) on torch's current stream: one product per inner
     iteration, the basis orthogonalised by two passes of classical Gram-Schmidt in the library's fused kernels.  minv is an optional
     inverse diagonal used as a right preconditioner; max_iters counts inner iterations (default twice the dimension); result and
-    streams as `cg`."""
+    streams as `cg`.  precond: the object of `block_jacobi` in place of minv (both: ValueError)."""
     m = handle.matrix_info(idx)
+    precond = _precond(precond, minv, m["rows"])
     b = _vector(b, "b", m["rows"])
     x = torch.zeros(m["cols"], dtype=torch.float32, device=b.device) if x0 is None else _vector(x0, "x0", m["cols"]).clone()
     if minv is not None:
@@ -111,9 +174,13 @@ def gmres(handle, idx: int, b, x0=None, *, minv=None, restart: int = 30, rtol: f
     if max_iters is None:
         max_iters = 2 * max(m["rows"], m["cols"])
     if work is None:
-        work = workspace_gmres(handle, idx, restart, minv is not None, b.device)
+        work = workspace_gmres(handle, idx, restart, minv is not None or precond is not None, b.device)
 
     def call(stream):
+        if precond is not None:
+            return handle.gmres_bj_device(idx, b.data_ptr(), x.data_ptr(), precond.buffer.data_ptr(), precond.block_size, restart=restart, rtol=rtol,
+                                          max_iters=max_iters, check_every=check_every, work=work.data_ptr(),
+                                          work_bytes=work.numel() * work.element_size(), stream=stream)
         return handle.gmres_device(idx, b.data_ptr(), x.data_ptr(), 0 if minv is None else minv.data_ptr(), restart=restart, rtol=rtol,
                                    max_iters=max_iters, check_every=check_every, work=work.data_ptr(),
                                    work_bytes=work.numel() * work.element_size(), stream=stream)

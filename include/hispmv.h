@@ -762,6 +762,77 @@ int hispmv_gmres_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float
                         int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes, void* stream,
                         hispmv_krylov_result* result);
 
+/* ---- Block-Jacobi preconditioner for CG and GMRES -------------------------------------------------------------------------------------
+ * M = the block diagonal of a square handle in blocks of bs = 4, 8, 16 or 32: block k covers rows and columns k bs ..
+ * min(n, (k + 1) bs) - 1, n_blocks = ceil(n / bs).  The preconditioner is z = M^-1 r with the blocks inverted once.  It lives in a
+ * buffer of the CALLER's; nothing is kept in the handle or the context, and a companion (stored transpose) plays no part.
+ *
+ * THE BUFFER (hispmv_prep_block_jacobi: pre_bytes, 16-byte aligned): first n_blocks * bs * bs floats, block k row-major, the INVERSE
+ * of diagonal block k (a multiple of 16 bytes); then n_blocks int32 flags, 0 = inverted, 1 = replaced by the identity; the whole
+ * rounded up to 16 bytes.  The last block of an n that is no multiple of bs is padded before the inversion: 1 on the diagonal of
+ * its absent rows, 0 elsewhere in their rows and columns -- so its inverse is the inverse of the present part, padded the same way.
+ *
+ * EXTRACTION writes the padded diagonal blocks, not yet inverted.  Slice-stream handles (every group kind, column and band tiles,
+ * both parts of a stray split, fp32 and bf16 storage -- the rounded values, the system the solvers solve): a fill kernel, then one
+ * walk per part over the slice stream, which adds every stored value v at (row, col) with row / bs == col / bs and both below n
+ * into word (row / bs, row % bs, col % bs) with a hardware float atomic.  An entry stored once is one add onto +0: the same bits
+ * every run.  Two duplicates of one position give the same bits in either order.  THREE OR MORE duplicates of one position are summed
+ * in no fixed order.  A stored +-0 changes no value.  As for d_y of hispmv_spmv_device_t, the buffer must be ordinary device memory
+ * (hipMalloc, a torch tensor: coarse-grained); on fine-grained or host-pinned memory the adds are not guaranteed to land.  Dense
+ * handles (fp32 and bf16 W): one plain kernel reads the blocks of W, no atomics.  Tile-stream handles -> HISPMV_ENOTSUP with the
+ * message of the transposed entries' refusal; not square, a bad bs, a buffer that is NULL, short or not 16-byte aligned ->
+ * HISPMV_EINVAL; before hispmv_load_matrices -> HISPMV_ESTATE.  All before any launch.
+ *
+ * INVERSION, per block, in place: Gauss-Jordan with partial pivoting in fp32, unfused, one rounding per operation.  `used` = no row.
+ *   for k = 0 .. bs - 1:
+ *     p = the row not in `used` whose |a[p][k]| is largest, the magnitudes compared as their bit patterns without the sign (so a
+ *         NaN counts above Inf); the lowest such row on ties.  pv = a[p][k]; pv zero or not finite: the block is BAD.
+ *     inv = 1 / pv (one IEEE division).  The new pivot row: w[j] = a[p][j] * inv for j != k, w[k] = inv.
+ *     every other row i (used or not): f = a[i][k]; a[i][k] = +0; then for every j: t = f * w[j]; a[i][j] = a[i][j] - t.
+ *     a[p][:] = w; p joins `used`; sigma(k) = p.
+ *   The inverse: out[k][sigma(j)] = a[sigma(k)][j].  Any word of it not finite: the block is BAD.
+ * A BAD block is replaced by the identity and flagged 1, so a solve is never poisoned by a block that cannot be inverted.
+ *
+ * THE MULTIPLY z = M^-1 r: z_i = ((+0 + B[i][0] r_0) + B[i][1] r_1) + ... in fp32, every product rounded and then added, k ascending
+ * over the bs columns of row i's block B; r at or beyond n counts as +0, z at or beyond n is not stored.  It runs on the Krylov
+ * layer's chunk walk (1024 elements per workgroup step, a thread owns 4 consecutive rows) without LDS or barrier; d_r and d_z need
+ * 4-byte alignment only and may be the same vector.
+ *
+ * THE SOLVERS hispmv_cg_bj_device and hispmv_gmres_bj_device are hispmv_cg_device and hispmv_gmres_device with (d_pre, block_size)
+ * in place of d_minv: wherever those form minv * v elementwise, these form the multiply above on the same values (CG: z = M^-1 r, so
+ * M should be symmetric positive definite like A; GMRES: right preconditioning, A M^-1 u = b, x = M^-1 u).  Everything else is
+ * theirs: the workspace of the minv variants (hispmv_krylov_info; hispmv_gmres_info with with_minv = 1), the scalar rules, freeze,
+ * breakdown, check_every, hispmv_krylov_status, the stream rule, the launch counts.  d_pre must stay unchanged while a solve is in
+ * flight.  block_size outside {4, 8, 16, 32}, d_pre NULL or not 16-byte aligned -> HISPMV_EINVAL before any launch.
+ * Out of scope: preconditioned BiCGSTAB or CGLS, blocks for the multi-right-hand-side solvers, block sizes above 32, variable blocks,
+ * symmetrising the computed inverse, ILU / IC, tile-stream handles, a fixed summation order for three or more duplicates. */
+/* The layout rule on the host (no device needed): out = {n_blocks, pre_bytes, byte offset of the flags, floats of a block}.  n < 0,
+ * n >= 2^31 or bs outside {4, 8, 16, 32} -> HISPMV_EINVAL. */
+int hispmv_prep_block_jacobi(int64_t n, int64_t block_size, int64_t out[4]);
+/* out = {accepted, n_blocks, pre_bytes, launches of a setup (extraction and inversion), work_bytes of hispmv_cg_bj_device, work_bytes
+ * of hispmv_gmres_bj_device with restart 1, bytes each further step of restart adds, n}; zeros for a handle the extraction does not
+ * accept (not loaded, not square, a tile stream).  A bad index or block_size -> HISPMV_EINVAL. */
+int hispmv_block_jacobi_info(const hispmv_ctx* ctx, int matrix_idx, int64_t block_size, int64_t out[8]);
+/* The padded diagonal blocks of the loaded matrix, not inverted, into the block area of d_pre; the flags are not written.
+ * Asynchronous on `stream`. */
+int hispmv_block_jacobi_extract_device(hispmv_ctx* ctx, int matrix_idx, int64_t block_size, void* d_pre, int64_t pre_bytes, void* stream);
+/* Inverts the n_blocks blocks at d_pre in place and writes their flags behind them (the layout of n = n_blocks * block_size).
+ * Asynchronous on `stream`; needs no handle.  The result is bit for bit the rule above. */
+int hispmv_block_invert_device(hispmv_ctx* ctx, void* d_pre, int64_t n_blocks, int64_t block_size, void* stream);
+/* Extraction followed by inversion: d_pre is ready for the multiply and the solvers behind it on `stream`. */
+int hispmv_block_jacobi_setup_device(hispmv_ctx* ctx, int matrix_idx, int64_t block_size, void* d_pre, int64_t pre_bytes, void* stream);
+/* Synchronises `stream` and returns in *flagged the number of blocks replaced by the identity. */
+int hispmv_block_jacobi_status(hispmv_ctx* ctx, const void* d_pre, int64_t n, int64_t block_size, void* stream, int64_t* flagged);
+/* d_z = M^-1 d_r over n elements; asynchronous on `stream`. */
+int hispmv_block_jacobi_apply_device(hispmv_ctx* ctx, const void* d_pre, int64_t n, int64_t block_size, const float* d_r, float* d_z,
+                                     void* stream);
+int hispmv_cg_bj_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float* d_x, const void* d_pre, int64_t block_size, double rtol,
+                        int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes, void* stream,
+                        hispmv_krylov_result* result);
+int hispmv_gmres_bj_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, float* d_x, const void* d_pre, int64_t block_size,
+                           int64_t restart, double rtol, int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes,
+                           void* stream, hispmv_krylov_result* result);
+
 /* ---- getters (HiSpmvHandle getters, spmv-helper.cpp:752-810) ------------------------------------ */
 typedef struct hispmv_matrix_info {
     int32_t rows, cols;
