@@ -6,8 +6,10 @@ SPD system for M right-hand sides in one call (solvers.cg_multi) and prints iter
 --block-jacobi BS also sets up a block-Jacobi preconditioner of block size BS (4, 8, 16, 32; solvers.block_jacobi) for the SPD system
 and for the convection-diffusion system and prints the iterations of CG and of GMRES without a preconditioner, with the inverse
 diagonal and with the blocks.
+--eigsh K also computes K extreme eigenvalues (--which LA, SA or LM) of the grid's Laplacian plus a graded diagonal, which keeps its
+eigenvalues simple, with thick-restart Lanczos (solvers.eigsh) and prints the values, the fp64 true residuals and the products.
 
-    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]] [--block-jacobi BS]
+    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]] [--block-jacobi BS] [--eigsh K [--which SA]]
 """
 from __future__ import annotations
 
@@ -49,6 +51,8 @@ def main():
     ap.add_argument("--gmres", action="store_true", help="also solve a convection-diffusion system with restarted GMRES and with BiCGSTAB")
     ap.add_argument("--restart", type=int, default=10, help="basis vectors of a GMRES cycle, 1 .. 64")
     ap.add_argument("--block-jacobi", type=int, default=0, metavar="BS", help="also solve with a block-Jacobi preconditioner of this block size (4, 8, 16, 32)")
+    ap.add_argument("--eigsh", type=int, default=0, metavar="K", help="also compute this many extreme eigenvalues of a symmetric system")
+    ap.add_argument("--which", default="LA", choices=("LA", "SA", "LM"), help="which end of the spectrum --eigsh takes")
     args = ap.parse_args()
     import torch
     import pyhispmv
@@ -76,6 +80,11 @@ def main():
         bj_spd = h.create_sparse_handle(r, c, v, n, n)
         gr, gc, gv = convdiff_coo(args.grid)
         bj_cd = h.create_sparse_handle(gr, gc, gv, n, n)
+    if args.eigsh:          # a graded diagonal on the Laplacian: the plain grid operator has multiple eigenvalues, of which single-vector
+        er = np.concatenate([r, np.arange(n)])          # Lanczos finds one copy each
+        ec = np.concatenate([c, np.arange(n)])
+        ev = np.concatenate([v, np.linspace(0.0, 4.0, n).astype(np.float32)])
+        eig = h.create_sparse_handle(er, ec, ev, n, n)
     h.load_matrices()
 
     dev = torch.device("cuda", 0)
@@ -126,6 +135,16 @@ def main():
                 true = np.linalg.norm(b - np.bincount(cr, weights=cv.astype(np.float64) * x64[cc], minlength=n)) / np.linalg.norm(b)
                 print(f"  {label:20s} {info['status']}, {info['iterations']} iterations, recursive residual {info['relres']:.3e}, true {true:.3e}")
             assert info["status"] == "CONVERGED"
+
+    if args.eigsh:
+        vals, vecs, info = solvers.eigsh(h, eig, args.eigsh, which=args.which)
+        X = vecs.cpu().numpy().astype(np.float64)
+        print(f"eigsh {n} x {n}, k = {args.eigsh}, {args.which}: {info['status']}, {info['found']} pairs, {info['products']} products, {info['cycles']} cycles")
+        for j in range(info["found"]):
+            Ax = np.bincount(er, weights=ev.astype(np.float64) * X[ec, j], minlength=n)
+            true = np.linalg.norm(Ax - vals[j] * X[:, j]) / np.linalg.norm(X[:, j])
+            print(f"  value {j}: {vals[j]:.9g}, residual estimate {info['residuals'][j]:.3e}, true {true:.3e}")
+        assert info["status"] == "CONVERGED"
 
     b = rng.uniform(-1, 1, rows).astype(np.float32)
     x, info = solvers.cgls(h, ls, torch.from_numpy(b).to(dev), rtol=args.rtol)

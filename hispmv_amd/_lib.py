@@ -39,8 +39,10 @@ HISPMV_KRYLOV_CG = 0
 HISPMV_KRYLOV_BICGSTAB = 1
 HISPMV_KRYLOV_CGLS = 2
 KRYLOV_SOLVERS = {"cg": HISPMV_KRYLOV_CG, "bicgstab": HISPMV_KRYLOV_BICGSTAB, "cgls": HISPMV_KRYLOV_CGLS}
-KRYLOV_STATUS = ("CONVERGED", "MAX_ITERS", "BREAKDOWN", "IN_FLIGHT")
+KRYLOV_STATUS = ("CONVERGED", "MAX_ITERS", "BREAKDOWN", "IN_FLIGHT", "INVARIANT")
 HISPMV_GMRES_MAX_RESTART = 64
+HISPMV_LANCZOS_MAX_NCV = 64
+EIGSH_WHICH = {"LA": 0, "SA": 1, "LM": 2}
 BLOCK_JACOBI_SIZES = (4, 8, 16, 32)
 
 
@@ -62,7 +64,12 @@ class KrylovResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("relres", C.c_double), ("products", C.c_int64)]
 
 
+class EigshResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("found", C.c_int32), ("products", C.c_int64), ("cycles", C.c_int64), ("scale", C.c_double)]
+
+
 _p = C.c_void_p
+_f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
@@ -155,6 +162,14 @@ SIGNATURES = {
     "hispmv_cg_bj_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p, C.POINTER(KrylovResult)]),
     "hispmv_gmres_bj_device": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, _p, C.c_int64, _p,
                                          C.POINTER(KrylovResult)]),
+    "hispmv_prep_lanczos": (C.c_int, [C.c_int64, C.c_int64, _i64p]),
+    "hispmv_prep_ritz": (C.c_int, [_f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, _f64p, _f64p, _f64p, _i64p]),
+    "hispmv_lanczos_info": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
+    "hispmv_basis_rotate_device": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int64, _p, C.c_int64, _p, _p, C.c_int64, _p]),
+    "hispmv_lanczos_steps_device": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, C.c_int, _p, _p, C.c_int64, _p]),
+    "hispmv_lanczos_status": (C.c_int, [_p, _p, _p, _i64p]),
+    "hispmv_eigsh_device": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int64, _p, _p, C.c_int64, _f64p, _f64p, _p, C.c_int64, _p,
+                                      C.POINTER(EigshResult)]),
     "hispmv_prep_vector_widths":(C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),

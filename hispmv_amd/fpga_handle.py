@@ -563,6 +563,60 @@ class FpgaHandle:
                                             int(max_iters), int(check_every), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
         return self._krylov_result(res)
 
+    # -- thick-restart Lanczos (hispmv_lanczos_abi.cpp; hispmv_amd.solvers.eigsh wraps these) -----------------------------------------
+    def lanczos_info(self, matrix_idx: int, ncv: int = 20) -> dict:
+        """{"accepted", "work_bytes", "v_offset", "stride", "hc_offset", "yt_offset", "launches_per_step", "n"} of a Lanczos run with
+        ncv basis vectors on a handle (hispmv_lanczos_info): the workspace, where it keeps the basis, Hc (the betas lie right behind
+        its 64 columns of 66 doubles) and the coefficients of the last rotation; zeros for a handle that is not loaded or not square."""
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_lanczos_info(self._ctx, int(matrix_idx), int(ncv), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError(f"ncv must be 2 .. {_lib.HISPMV_LANCZOS_MAX_NCV}")
+            raise IndexError("Matrix idx out of range")
+        keys = ("accepted", "work_bytes", "v_offset", "stride", "hc_offset", "yt_offset", "launches_per_step", "n")
+        d = dict(zip(keys, (int(x) for x in out)))
+        d["accepted"] = bool(d["accepted"])
+        return d
+
+    def basis_rotate_device(self, n: int, m: int, k: int, d_V: int, d_Yt: int, d_out: int, ld_v=None, ld_out=None, stream: int = 0) -> None:
+        """out[c] = sum_{i < m} Yt[c, i] * V[i] for c < k <= 64 over float32 vectors of n elements, V_i = d_V + i * ld_v, m <= 65, Yt
+        float32 [k, m] in device memory (hispmv_basis_rotate_device): fp32, unfused, i ascending.  d_out may be d_V (in place, vector c
+        over slot c).  Asynchronous on `stream`."""
+        ld_v = int(n if ld_v is None else ld_v)
+        self._check(lib.hispmv_basis_rotate_device(self._ctx, int(n), int(m), int(k), C.c_void_p(d_V), ld_v, C.c_void_p(d_Yt), C.c_void_p(d_out),
+                                                   int(ld_v if ld_out is None else ld_out), C.c_void_p(stream)))
+
+    def lanczos_steps_device(self, matrix_idx: int, j0: int, j1: int, first: bool, d_v0: int, work: int, work_bytes: int, stream: int = 0) -> None:
+        """Enqueues the open (first: from the start vector d_v0) and the Lanczos steps j0 .. j1 - 1 on a square handle with no host look
+        (hispmv_lanczos_steps_device); lanczos_status reads the outcome.  Exceptions as gmres_device."""
+        self._check(lib.hispmv_lanczos_steps_device(self._ctx, int(matrix_idx), int(j0), int(j1), int(bool(first)), C.c_void_p(d_v0), C.c_void_p(work),
+                                                    int(work_bytes), C.c_void_p(stream)))
+
+    def lanczos_status(self, work: int, stream: int = 0) -> dict:
+        """Waits for `stream` and reads {"steps", "invariant", "breakdown", "products"} of the Lanczos run with workspace `work`."""
+        out = (C.c_int64 * 4)()
+        self._check(lib.hispmv_lanczos_status(self._ctx, C.c_void_p(work), C.c_void_p(stream), out))
+        return {"steps": int(out[0]), "invariant": bool(out[1]), "breakdown": bool(out[2]), "products": int(out[3])}
+
+    def eigsh_device(self, matrix_idx: int, k: int, d_v0: int, d_vecs: int, ld_vecs: int, ncv: int = 20, which: str = "LA", tol: float = 1e-5,
+                     max_products: int = 1000, work: int = 0, work_bytes: int = 0, stream: int = 0) -> dict:
+        """The k wanted eigenpairs of a symmetric handle by thick-restart Lanczos (hispmv_eigsh_device): d_v0 the start vector, d_vecs
+        takes the vectors ld_vecs floats apart.  Returns {"status", "found", "products", "cycles", "scale", "vals", "residuals"} with
+        the values and residual estimates as float64 arrays [found].  An unknown `which`, a bad k / ncv / tol / max_products or a short,
+        missing or misaligned workspace raises ValueError, a call before load_matrices AssertionError."""
+        if which not in _lib.EIGSH_WHICH:
+            raise ValueError('which must be "LA", "SA" or "LM"')
+        res = _lib.EigshResult()
+        vals = np.full(max(int(k), 1), np.nan, np.float64)
+        resid = np.full(max(int(k), 1), np.nan, np.float64)
+        self._check(lib.hispmv_eigsh_device(self._ctx, int(matrix_idx), int(k), int(ncv), _lib.EIGSH_WHICH[which], float(tol), int(max_products),
+                                            C.c_void_p(d_v0), C.c_void_p(d_vecs), int(ld_vecs), vals.ctypes.data_as(C.POINTER(C.c_double)),
+                                            resid.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(work), int(work_bytes), C.c_void_p(stream),
+                                            C.byref(res)))
+        return {"status": _lib.KRYLOV_STATUS[res.status], "found": int(res.found), "products": int(res.products), "cycles": int(res.cycles),
+                "scale": float(res.scale), "vals": vals[:res.found].copy(), "residuals": resid[:res.found].copy()}
+
     # -- block-Jacobi preconditioner (hispmv_block_jacobi_abi.cpp; hispmv_amd.solvers.block_jacobi wraps these) ------------------------
     def block_jacobi_info(self, matrix_idx: int, block_size: int = 8) -> dict:
         """{"accepted", "n_blocks", "pre_bytes", "setup_launches", "cg_work_bytes", "gmres_work_bytes", "gmres_step_bytes", "n"} of a

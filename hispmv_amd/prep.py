@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import lib, HISPMV_OK, VALUE_STORAGES
+from ._lib import lib, EIGSH_WHICH, HISPMV_OK, VALUE_STORAGES
 
 
 @dataclass
@@ -317,6 +317,38 @@ def gmres(n: int, restart: int, with_minv: bool = False) -> dict:
         raise ValueError("hispmv_prep_gmres: n >= 0 and 1 <= restart <= 64")
     keys = ("work_bytes", "v_offset", "stride", "groups", "dot_tile", "launches_per_iteration", "launches_per_cycle", "basis_vectors")
     return dict(zip(keys, (int(x) for x in out)))
+
+
+def lanczos(n: int, ncv: int) -> dict:
+    """The workspace rule of thick-restart Lanczos (hispmv_prep_lanczos), host-only: {"work_bytes", "v_offset", "stride", "groups",
+    "hc_offset", "yt_offset", "launches_per_step", "basis_vectors"} for a matrix of order n and ncv basis vectors -- the bytes a run
+    needs, where the basis lies and how many floats apart its vectors are, the partials of a dot product, where Hc lies (64 columns of
+    66 doubles, the 66 betas right behind them) and the fp32 coefficients of the last rotation, the launches of a step with its product,
+    and ncv + 1."""
+    out = (C.c_int64 * 8)()
+    if lib.hispmv_prep_lanczos(int(n), int(ncv), out) != HISPMV_OK:
+        raise ValueError("hispmv_prep_lanczos: n >= 0 and 2 <= ncv <= 64")
+    keys = ("work_bytes", "v_offset", "stride", "groups", "hc_offset", "yt_offset", "launches_per_step", "basis_vectors")
+    return dict(zip(keys, (int(x) for x in out)))
+
+
+def ritz(H, k: int, which: str, beta: float, tol: float) -> dict:
+    """The Ritz step of the eigensolver on the host (hispmv_prep_ritz): the eigenvalues of the symmetric float64 matrix H (m x m,
+    m <= 64) by cyclic Jacobi, ordered by `which` ("LA" largest first, "SA" smallest first, "LM" largest magnitude first).  Returns
+    {"theta" [m], "Yt" [m, m] (row c the eigenvector of theta[c]), "res" [m] = beta * |Yt[:, m - 1]|, "converged" (how many of the
+    first min(k, m) have res <= tol * max |theta|), "sweeps"}."""
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    if H.ndim != 2 or H.shape[0] != H.shape[1] or which not in EIGSH_WHICH:
+        raise ValueError('hispmv_prep_ritz: H must be square and which "LA", "SA" or "LM"')
+    m = H.shape[0]
+    theta, Yt, res = np.zeros(m, np.float64), np.zeros((m, m), np.float64), np.zeros(m, np.float64)
+    counts = (C.c_int64 * 2)()
+    dp = C.POINTER(C.c_double)
+    rc = lib.hispmv_prep_ritz(H.ctypes.data_as(dp), m, m, int(k), EIGSH_WHICH[which], float(beta), float(tol), theta.ctypes.data_as(dp), Yt.ctypes.data_as(dp),
+                              res.ctypes.data_as(dp), counts)
+    if rc != HISPMV_OK:
+        raise ValueError("hispmv_prep_ritz: 1 <= m <= 64, k >= 1 and tol >= 0")
+    return {"theta": theta, "Yt": Yt, "res": res, "converged": int(counts[0]), "sweeps": int(counts[1])}
 
 
 def block_jacobi(n: int, block_size: int) -> dict:

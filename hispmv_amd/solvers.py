@@ -19,7 +19,10 @@ Restarted GMRES: ``gmres`` (FpgaHandle.gmres_device) for square non-symmetric sy
 
 Block-Jacobi: ``block_jacobi(handle, idx, block_size)`` builds the inverted diagonal blocks of a loaded square handle on the device
 (FpgaHandle.block_jacobi_setup_device) and returns an object ``cg`` and ``gmres`` take as ``precond=`` in place of ``minv``; same
-streams, same rule."""
+streams, same rule.
+
+Eigenvalues: ``eigsh`` (FpgaHandle.eigsh_device) for a few extreme eigenpairs of a symmetric handle by thick-restart Lanczos; its
+driver looks at the device once per cycle, so it always returns with its result ready."""
 from __future__ import annotations
 
 import torch
@@ -187,6 +190,46 @@ def gmres(handle, idx: int, b, x0=None, *, minv=None, restart: int = 30, rtol: f
     info = _launch(handle, b.device, check_every, call)
     info["work"] = work          # check_every = 0: handle.krylov_status(info["work"].data_ptr(), stream) reads the outcome
     return x, info
+
+
+# ---- eigenvalues -------------------------------------------------------------------------------------------------------------------
+def workspace_eigsh(handle, idx: int, ncv: int, device) -> torch.Tensor:
+    """A workspace tensor for a Lanczos run with ncv basis vectors on handle `idx` (lanczos_info's work_bytes)."""
+    info = handle.lanczos_info(idx, ncv)
+    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+
+
+def eigsh(handle, idx: int, k: int = 6, *, which: str = "LA", ncv=None, tol: float = 1e-5, max_products=None, v0=None, seed: int = 0, work=None):
+    """The k algebraically largest ("LA"), smallest ("SA") or largest-magnitude ("LM") eigenvalues of the SYMMETRIC handle `idx` and
+    their eigenvectors, by thick-restart Lanczos on torch's current stream (FpgaHandle.eigsh_device; the caller owes the symmetry).
+    Returns (vals, vecs, info): vals a float64 numpy array [found], vecs a float32 CUDA tensor [n, found] (a transposed view of the
+    library's rows), info = {"status", "found", "products", "cycles", "residuals", "work"}; status is "CONVERGED", "MAX_ITERS",
+    "INVARIANT" (the Krylov space closed before k pairs converged: found may be below k) or "BREAKDOWN" (found 0).  ncv defaults to
+    min(max(2k + 1, 20), 64), max_products to max(10 n, 1000) capped at 2^30, v0 to torch.randn from a generator seeded with `seed`
+    (v0 is not written).  The driver looks at the device once per cycle, so the call waits for its result on any stream."""
+    m = handle.matrix_info(idx)
+    n = m["rows"]
+    if v0 is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        v0 = torch.randn(n, generator=gen, dtype=torch.float32).to(device)
+    v0 = _vector(v0, "v0", n)
+    k = int(k)
+    if ncv is None:
+        ncv = min(max(2 * k + 1, 20), 64)
+    if max_products is None:
+        max_products = min(max(10 * n, 1000), 1 << 30)
+    if work is None:
+        work = workspace_eigsh(handle, idx, ncv, v0.device)
+    stride = (n + 3) // 4 * 4
+    rows = torch.zeros(max(k, 1), stride, dtype=torch.float32, device=v0.device)
+    info = _launch(handle, v0.device, 1, lambda stream: handle.eigsh_device(
+        idx, k, v0.data_ptr(), rows.data_ptr(), stride, ncv=ncv, which=which, tol=tol, max_products=max_products, work=work.data_ptr(),
+        work_bytes=work.numel() * work.element_size(), stream=stream))
+    vals = info.pop("vals")
+    info.pop("scale")
+    info["work"] = work
+    return vals, rows[:info["found"], :n].t(), info
 
 
 # ---- several right-hand sides -------------------------------------------------------------------------------------------------------

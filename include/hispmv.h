@@ -833,6 +833,103 @@ int hispmv_gmres_bj_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, fl
                            int64_t restart, double rtol, int64_t max_iters, int64_t check_every, void* d_work, int64_t work_bytes,
                            void* stream, hispmv_krylov_result* result);
 
+/* ---- Lanczos / eigsh: a few eigenvalues of a symmetric handle ---------------------------------------------------------------------
+ * Thick-restart Lanczos with full reorthogonalisation for the k algebraically largest (LA), algebraically smallest (SA) or largest in
+ * magnitude (LM) eigenvalues of a square handle, and their eigenvectors.  The library cannot check symmetry, as with hispmv_cg_device:
+ * the caller owes it.  A step is a GMRES inner iteration without the Givens rotation -- the product of hispmv_spmv_device written
+ * straight into the basis, the multi-dot kernel, the subtract-and-dot kernel twice (hispmv_gmres_device's, unchanged) -- and one kernel
+ * that normalises and records.  The restart is one tall-skinny in-place rotation of the basis.  The host looks ONCE PER CYCLE, behind
+ * the last step it has enqueued: there is no check_every.  The grid, the chunk order and every dot product are hispmv_dot_device's
+ * for n; vectors are fp32, unfused, one rounding per operation; sums and scalars are fp64 with IEEE / and sqrt; a scalar is rounded
+ * ONCE to fp32 before it meets a vector.  ONE run per handle in flight; the whole state lies in the caller's workspace.
+ *
+ * OPEN: slot 0 of the basis = v0; vv = (v0, v0).  vv zero or not finite: BREAKDOWN (slot 0 keeps the copy).  Otherwise
+ *   V_0 = f32(1 / sqrt(vv)) * v0.  The scalar block is built from nothing.
+ * STEP j (V_0 .. V_j orthonormal): w = A V_j into slot j + 1 (alpha 1, beta 0, no bias).  CGS2 exactly as GMRES's inner step:
+ *   h1_i = (V_i, w), i <= j; w = w - f32(h1_i) * V_i for i ascending; h2_i = (V_i, w); the same subtraction with h2; h_i = h1_i + h2_i;
+ *   a h1_i or h2_i that is not finite sets breakdown in the kernel that sums it.  Then the normalise-and-record kernel: ww = (w, w);
+ *   not finite: BREAKDOWN.  Otherwise products += 1, steps = j + 1, Hc[j][i] = h_i for i <= j, beta_j = sqrt(ww), and
+ *   THE INVARIANT SUBSPACE RULE: t = +0, t = t + h_i * h_i for i ascending; if ww <= tiny^2 * (ww + t), tiny = 2^-12
+ *   (HISPMV_LANCZOS_TINY_LOG2), w is rounding noise: it is not normalised, the word `invariant` is set and the state freezes (the word
+ *   `done` of the other solvers: every later kernel of the cycle copies the block and writes no vector; the products still run and are
+ *   ignored).  An all-zero matrix gives 0 <= 0: invariant with eigenvalue 0, not a breakdown.  Otherwise V_{j+1} = f32(1 / beta_j) * w.
+ *   `products` counts the steps that reached this kernel unfrozen, so a run that freezes reports the products it used.
+ * HOST LOOK, once per cycle: the scalar block, Hc and the betas come to pinned memory, the stream is synchronised.  m = steps.  The
+ *   projected matrix H (m x m) holds the kept Ritz values on its leading diagonal after a restart (zero elsewhere); every column j the
+ *   device computed in this cycle is mirrored into its row, H[i][j] = H[j][i] = Hc[j][i], i <= j.  With full CGS2 the arrowhead column
+ *   at index keep comes out of the dots by itself.
+ * RITZ STEP (hispmv_prep_ritz, fp64): cyclic Jacobi on H; theta its eigenvalues, Y orthonormal.  Order by `which`: LA descending, SA
+ *   ascending, LM descending in |theta|, ties in Jacobi's order.  res_i = beta_{m-1} * |Y[m-1][i]|; scale = max |theta_i| over all m;
+ *   pair i is converged when res_i <= tol * scale.
+ * STOP: CONVERGED when the first min(k, m) pairs in order are converged and m >= k; else INVARIANT (HISPMV_KRYLOV_INVARIANT) when the
+ *   subspace is invariant -- found = min(k, m) pairs are returned with their honest residuals; else MAX_ITERS when products >=
+ *   max_products at the look (found = min(k, m) pairs are returned as they stand).  BREAKDOWN returns found = 0 and leaves d_vecs
+ *   untouched.
+ * RESTART otherwise: keep = min(k + (ncv - k) / 2, ncv - 1); V[:, c] = sum_i f32(Y[i][order c]) * V[:, i] for c < keep -- fp32, the
+ *   product rounded, then added, i ascending from 0.0f --; slot keep takes slot m, the normalised residual vector; H = diag(theta in
+ *   order, keep of them); the next cycle runs steps keep .. ncv - 1.
+ * FINISH: the same rotation with the `found` wanted columns, out of place, into d_vecs (vector c at d_vecs + c * ld_vecs).  The vectors
+ *   are not renormalised: their norm is 1 to a few fp32 ulps times sqrt(m).  vals_out[i] = theta_i and res_out[i] = res_i for
+ *   i < found; the entries behind are not written.
+ *
+ * WORKSPACE (hispmv_lanczos_info: work_bytes, 16-byte aligned; the rule is hispmv_prep_lanczos's): three 128-byte scalar blocks in the
+ * 512 bytes the other solvers open with -- breakdown, done and products keep their slots, slot 13 holds steps and slot 14
+ * `invariant`; the three kernels of a step that write the block pass it 0 -> 1 -> 2 -> 0, so a kernel never writes the block it
+ * reads and every step, hence every call, leaves the state in block 0 --, then h1 and h (66 doubles each), Hc (64 columns of 66 doubles, column j at
+ * hc_offset + 528 j), the 66 betas right behind Hc, Yt (64 x 65 floats: the coefficients of the last rotation, row c = output c), the
+ * partials, and the ncv + 1 basis vectors (ceil(n / 4) * 4 floats apart).  Only workgroup 0 writes Hc, the betas and the block.
+ * ACCEPTED: every square handle hispmv_spmv_device accepts -- slice streams, tile streams, dense, fp32 or bf16 storage (a bf16 handle
+ * has the eigenvalues of its rounded values).  HISPMV_EINVAL before any launch, outputs untouched: a handle that is not square, k < 1,
+ * ncv outside k + 1 .. HISPMV_LANCZOS_MAX_NCV, tol < 0, max_products < 1 or > 2^30, an unknown `which`, a NULL pointer or one not 4-byte
+ * aligned, a workspace that is NULL, short or not 16-byte aligned; a call before load_matrices -> HISPMV_ESTATE.
+ * Out of scope: multiple or tightly clustered eigenvalues beyond one copy (single-vector Lanczos finds ONE eigenvector of a multiple
+ * eigenvalue), a random restart after an invariant subspace, shift-invert, generalised problems, singular values, non-symmetric
+ * Arnoldi, ncv > 64, locking and deflation, fp64 vectors, several start vectors, sharding over devices, HIP-graph capture. */
+#define HISPMV_LANCZOS_MAX_NCV 64
+#define HISPMV_LANCZOS_TINY_LOG2 (-12)
+#define HISPMV_KRYLOV_INVARIANT 4
+#define HISPMV_EIGSH_LA 0
+#define HISPMV_EIGSH_SA 1
+#define HISPMV_EIGSH_LM 2
+typedef struct hispmv_eigsh_result {
+    int32_t status;         /* HISPMV_KRYLOV_CONVERGED, _MAX_ITERS, _BREAKDOWN, _INVARIANT */
+    int32_t found;          /* pairs returned */
+    int64_t products;
+    int64_t cycles;         /* host looks */
+    double scale;           /* max |theta| of the last look: what tol is relative to */
+} hispmv_eigsh_result;
+/* The workspace rule on the host (no device needed): out = {work_bytes, byte offset of the basis V, floats between two basis vectors,
+ * groups, byte offset of Hc, byte offset of Yt, launches per step (5, the product included), basis vectors held (ncv + 1)}.  n < 0 or
+ * ncv outside 2 .. 64 -> HISPMV_EINVAL. */
+int hispmv_prep_lanczos(int64_t n, int64_t ncv, int64_t out[8]);
+/* The Ritz step on the host and nothing else (no device needed): H is symmetric m x m, row-major with ld doubles between rows (the
+ * upper triangle is read), 1 <= m <= 64.  theta_out[m] and res_out[m] in the order of `which`; Yt_out[m * m], row c the eigenvector of
+ * theta_out[c]; counts_out = {converged among the first min(k, m), Jacobi sweeps}.  Bad arguments -> HISPMV_EINVAL. */
+int hispmv_prep_ritz(const double* H, int64_t ld, int64_t m, int64_t k, int which, double beta, double tol, double* theta_out, double* Yt_out,
+                     double* res_out, int64_t counts_out[2]);
+/* out = {accepted, work_bytes, byte offset of V, vector stride in floats, byte offset of Hc, byte offset of Yt, launches per step, n};
+ * zeros for a handle that is not loaded or not square.  A bad index, ncv outside 2 .. 64 -> HISPMV_EINVAL. */
+int hispmv_lanczos_info(const hispmv_ctx* ctx, int matrix_idx, int64_t ncv, int64_t out[8]);
+/* d_out[c * ld_out + e] = sum_{i < m} d_Yt[c * m + i] * d_V[i * ld_v + e], c < k <= 64, e < n, 1 <= m <= 65: fp32, the product rounded
+ * and then added, i ascending, starting from 0.0f.  d_out may be d_V itself (ld_out == ld_v): vector c then lands over slot c, and the
+ * slots at or above k are untouched.  Any other overlap is undefined.  Pointers 4-byte aligned, pads never read or written.
+ * Asynchronous on `stream`. */
+int hispmv_basis_rotate_device(hispmv_ctx* ctx, int64_t n, int64_t m, int64_t k, const float* d_V, int64_t ld_v, const float* d_Yt,
+                               float* d_out, int64_t ld_out, void* stream);
+/* Enqueues the open (first != 0: j0 must be 0, d_v0 the start vector) and the steps j0 .. j1 - 1, 0 <= j0 < j1 <= 64, with no host
+ * look.  The workspace is that of hispmv_prep_lanczos(n, max(j1, 2)): j1 + 1 basis vectors, and never less than the smallest layout
+ * the rule knows.  Asynchronous on `stream`. */
+int hispmv_lanczos_steps_device(hispmv_ctx* ctx, int matrix_idx, int64_t j0, int64_t j1, int first, const float* d_v0, void* d_work,
+                                int64_t work_bytes, void* stream);
+/* Synchronises `stream` and reads out = {steps, invariant, breakdown, products} out of the workspace of a run on it. */
+int hispmv_lanczos_status(hispmv_ctx* ctx, const void* d_work, void* stream, int64_t out[4]);
+/* The driver above.  d_v0[n] is the start vector (not written); d_vecs takes `found` vectors, ld_vecs >= n floats apart; vals_out and
+ * res_out are host doubles [k].  The call returns with *result filled and the stream synchronised.  It allocates and frees its
+ * pinned buffer itself, like a hispmv_cg_device call with check_every > 0. */
+int hispmv_eigsh_device(hispmv_ctx* ctx, int matrix_idx, int64_t k, int64_t ncv, int which, double tol, int64_t max_products,
+                        const float* d_v0, float* d_vecs, int64_t ld_vecs, double* vals_out, double* res_out, void* d_work,
+                        int64_t work_bytes, void* stream, hispmv_eigsh_result* result);
+
 /* ---- getters (HiSpmvHandle getters, spmv-helper.cpp:752-810) ------------------------------------ */
 typedef struct hispmv_matrix_info {
     int32_t rows, cols;
