@@ -88,6 +88,43 @@ def invert(blocks):
     return inv, flags
 
 
+def invert_many(blocks):
+    """`invert` with every step taken on all blocks at once, for the tens of thousands of blocks of a large system: the same float32
+    operations in the same order per block, so the same bits (tests/test_block_jacobi_plans_host.py compares the two).  A block found
+    BAD goes on being computed with and is replaced at the end."""
+    a = np.array(blocks, f32)
+    nb, bs = a.shape[0], a.shape[1]
+    if nb == 0:
+        return a, np.zeros(0, np.int32)
+    b = np.arange(nb)
+    used = np.zeros((nb, bs), bool)
+    sigma = np.zeros((nb, bs), np.int64)
+    bad = np.zeros(nb, bool)
+    with np.errstate(all="ignore"):
+        for k in range(bs):
+            key = (np.ascontiguousarray(a[:, :, k]).view(np.uint32) & 0x7FFFFFFF).astype(np.int64)
+            key[used] = -1
+            p = key.argmax(axis=1)          # the first of the largest: the lowest row on ties
+            best = key[b, p]
+            bad |= (best == 0) | (best >= 0x7F800000)
+            inv = f32(1.0) / a[b, p, k]
+            w = a[b, p, :] * inv[:, None]
+            w[:, k] = inv
+            f = a[:, :, k].copy()
+            a[:, :, k] = 0
+            t = f[:, :, None] * w[:, None, :]          # rounded to float32, then subtracted
+            a = a - t
+            a[b, p, :] = w
+            used[b, p] = True
+            sigma[:, k] = p
+        rows = np.take_along_axis(a, sigma[:, :, None], axis=1)          # rows[., k, j] = a[., sigma[k], j]
+        out = np.zeros_like(a)
+        np.put_along_axis(out, np.broadcast_to(sigma[:, None, :], a.shape), rows, axis=2)          # out[., k, sigma[j]] = rows[., k, j]
+    bad |= ~np.isfinite(out).all(axis=(1, 2))
+    out[bad] = np.eye(bs, dtype=f32)
+    return out, bad.astype(np.int32)
+
+
 # ---- the multiply --------------------------------------------------------------------------------------------------------------------
 class BlockInverse:
     """M^-1 over the inverted blocks [n_blocks, bs, bs] for n unknowns: ``self * r`` is the multiply of include/hispmv.h."""
