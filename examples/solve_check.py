@@ -8,8 +8,11 @@ and for the convection-diffusion system and prints the iterations of CG and of G
 diagonal and with the blocks.
 --eigsh K also computes K extreme eigenvalues (--which LA, SA or LM) of the grid's Laplacian plus a graded diagonal, which keeps its
 eigenvalues simple, with thick-restart Lanczos (solvers.eigsh) and prints the values, the fp64 true residuals and the products.
+--svds K also computes the K largest singular values of the least-squares matrix with thick-restart Golub-Kahan (solvers.svds) and
+prints the values, the fp64 true residuals |A v - s u| and |A^T u - s v|, and the products; the condition number CGLS then meets is
+not among them: that needs the smallest singular value, which svds does not compute.
 
-    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]] [--block-jacobi BS] [--eigsh K [--which SA]]
+    python examples/solve_check.py [--grid 64] [--rtol 1e-6] [--rhs M] [--gmres [--restart 10]] [--block-jacobi BS] [--eigsh K [--which SA]] [--svds K]
 """
 from __future__ import annotations
 
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--block-jacobi", type=int, default=0, metavar="BS", help="also solve with a block-Jacobi preconditioner of this block size (4, 8, 16, 32)")
     ap.add_argument("--eigsh", type=int, default=0, metavar="K", help="also compute this many extreme eigenvalues of a symmetric system")
     ap.add_argument("--which", default="LA", choices=("LA", "SA", "LM"), help="which end of the spectrum --eigsh takes")
+    ap.add_argument("--svds", type=int, default=0, metavar="K", help="also compute this many of the largest singular values of the least-squares matrix")
     args = ap.parse_args()
     import torch
     import pyhispmv
@@ -144,6 +148,17 @@ def main():
             Ax = np.bincount(er, weights=ev.astype(np.float64) * X[ec, j], minlength=n)
             true = np.linalg.norm(Ax - vals[j] * X[:, j]) / np.linalg.norm(X[:, j])
             print(f"  value {j}: {vals[j]:.9g}, residual estimate {info['residuals'][j]:.3e}, true {true:.3e}")
+        assert info["status"] == "CONVERGED"
+
+    if args.svds:          # the stored transpose of `ls` gives both products a fixed order: the run repeats bit for bit
+        s, u, vt, info = solvers.svds(h, ls, args.svds)
+        U, Vt = u.cpu().numpy().astype(np.float64), vt.cpu().numpy().astype(np.float64)
+        print(f"svds  {rows} x {cols}, k = {args.svds}: {info['status']}, {info['found']} triplets, {info['products']} products, {info['cycles']} cycles")
+        for j in range(info["found"]):
+            Av = np.bincount(lr, weights=lv.astype(np.float64) * Vt[j, lc], minlength=rows)
+            Atu = np.bincount(lc, weights=lv.astype(np.float64) * U[lr, j], minlength=cols)
+            print(f"  value {j}: {s[j]:.9g}, residual estimate {info['residuals'][j]:.3e}, true |A v - s u| {np.linalg.norm(Av - s[j] * U[:, j]):.3e}, "
+                  f"|A^T u - s v| {np.linalg.norm(Atu - s[j] * Vt[j]):.3e}")
         assert info["status"] == "CONVERGED"
 
     b = rng.uniform(-1, 1, rows).astype(np.float32)

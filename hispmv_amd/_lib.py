@@ -42,6 +42,7 @@ KRYLOV_SOLVERS = {"cg": HISPMV_KRYLOV_CG, "bicgstab": HISPMV_KRYLOV_BICGSTAB, "c
 KRYLOV_STATUS = ("CONVERGED", "MAX_ITERS", "BREAKDOWN", "IN_FLIGHT", "INVARIANT")
 HISPMV_GMRES_MAX_RESTART = 64
 HISPMV_LANCZOS_MAX_NCV = 64
+HISPMV_GK_MAX_NCV = 64
 EIGSH_WHICH = {"LA": 0, "SA": 1, "LM": 2}
 BLOCK_JACOBI_SIZES = (4, 8, 16, 32)
 
@@ -170,6 +171,13 @@ SIGNATURES = {
     "hispmv_lanczos_status": (C.c_int, [_p, _p, _p, _i64p]),
     "hispmv_eigsh_device": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int64, _p, _p, C.c_int64, _f64p, _f64p, _p, C.c_int64, _p,
                                       C.POINTER(EigshResult)]),
+    "hispmv_prep_gk": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _i64p]),
+    "hispmv_prep_bsvd": (C.c_int, [_f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p, _i64p]),
+    "hispmv_gk_info": (C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
+    "hispmv_gk_steps_device": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, _p, _p, C.c_int64, _p]),
+    "hispmv_gk_status": (C.c_int, [_p, _p, _p, _i64p]),
+    "hispmv_svds_device": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int64, _p, C.c_int, _p, C.c_int64, _p, C.c_int64, _f64p, _f64p, _p,
+                                     C.c_int64, _p, C.POINTER(EigshResult)]),
     "hispmv_prep_vector_widths":(C.c_int, [_p, C.c_int, C.c_int64, _i64p]),
     "hispmv_time_device": (C.c_float, [_p, C.c_int, _p, _p, _p, C.c_float, C.c_float, C.c_int]),
     "hispmv_get_matrix_info": (C.c_int, [_p, C.c_int, C.POINTER(MatrixInfo)]),

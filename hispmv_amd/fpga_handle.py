@@ -617,6 +617,55 @@ class FpgaHandle:
         return {"status": _lib.KRYLOV_STATUS[res.status], "found": int(res.found), "products": int(res.products), "cycles": int(res.cycles),
                 "scale": float(res.scale), "vals": vals[:res.found].copy(), "residuals": resid[:res.found].copy()}
 
+    # -- thick-restart Golub-Kahan (hispmv_gk_abi.cpp; hispmv_amd.solvers.svds wraps these) --------------------------------------------
+    def gk_info(self, matrix_idx: int, ncv: int = 20) -> dict:
+        """{"accepted", "work_bytes", "v_offset", "v_stride", "u_offset", "u_stride", "gc_offset", "yt_offset"} of a Golub-Kahan run with
+        ncv basis vectors on a handle (hispmv_gk_info): the workspace, where it keeps V and U, Gc (the alphas and the betas lie right
+        behind its 64 columns of 66 doubles) and the coefficients of the last rotation; zeros for a handle that is not loaded or that
+        spmv_device_t refuses."""
+        out = (C.c_int64 * 8)()
+        rc = lib.hispmv_gk_info(self._ctx, int(matrix_idx), int(ncv), out)
+        if rc != _lib.HISPMV_OK:
+            if 0 <= int(matrix_idx) < self.num_matrices():
+                raise ValueError(f"ncv must be 2 .. {_lib.HISPMV_GK_MAX_NCV}")
+            raise IndexError("Matrix idx out of range")
+        keys = ("accepted", "work_bytes", "v_offset", "v_stride", "u_offset", "u_stride", "gc_offset", "yt_offset")
+        d = dict(zip(keys, (int(x) for x in out)))
+        d["accepted"] = bool(d["accepted"])
+        return d
+
+    def gk_steps_device(self, matrix_idx: int, ncv: int, j0: int, j1: int, first: bool, d_v0: int, work: int, work_bytes: int, stream: int = 0) -> None:
+        """Enqueues the open (first: from the start vector d_v0, cols floats) and the Golub-Kahan steps j0 .. j1 - 1 <= ncv - 1 of a run
+        whose workspace is gk_info(matrix_idx, ncv)'s, with no host look (hispmv_gk_steps_device); gk_status reads the outcome.
+        Exceptions as svds_device."""
+        self._check(lib.hispmv_gk_steps_device(self._ctx, int(matrix_idx), int(ncv), int(j0), int(j1), int(bool(first)), C.c_void_p(d_v0),
+                                               C.c_void_p(work), int(work_bytes), C.c_void_p(stream)))
+
+    def gk_status(self, work: int, stream: int = 0) -> dict:
+        """Waits for `stream` and reads {"steps", "invariant", "closed_u", "breakdown", "products"} of the Golub-Kahan run with
+        workspace `work`."""
+        out = (C.c_int64 * 5)()
+        self._check(lib.hispmv_gk_status(self._ctx, C.c_void_p(work), C.c_void_p(stream), out))
+        return {"steps": int(out[0]), "invariant": bool(out[1]), "closed_u": bool(out[2]), "breakdown": bool(out[3]), "products": int(out[4])}
+
+    def svds_device(self, matrix_idx: int, k: int, d_v0: int, d_u: int, ld_u: int, d_v: int, ld_v: int, ncv: int = 20, tol: float = 1e-5,
+                    max_products: int = 1000, work: int = 0, work_bytes: int = 0, stream: int = 0, vectors: bool = True) -> dict:
+        """The k largest singular values of a handle of any shape by thick-restart Golub-Kahan (hispmv_svds_device): d_v0 the start
+        vector (cols floats), d_u takes the left vectors ld_u floats apart, d_v the right vectors ld_v floats apart (vectors=False:
+        neither is looked at).  Returns {"status", "found", "products", "cycles", "scale", "s", "residuals"} with the values and
+        residual estimates as float64 arrays [found].  A bad k / ncv / tol / max_products, a NULL or misaligned pointer or a short,
+        missing or misaligned workspace raises ValueError, a call before load_matrices AssertionError, a handle spmv_device_t refuses
+        its NotImplementedError."""
+        res = _lib.EigshResult()
+        s = np.full(max(int(k), 1), np.nan, np.float64)
+        resid = np.full(max(int(k), 1), np.nan, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(lib.hispmv_svds_device(self._ctx, int(matrix_idx), int(k), int(ncv), float(tol), int(max_products), C.c_void_p(d_v0),
+                                           int(bool(vectors)), C.c_void_p(d_u), int(ld_u), C.c_void_p(d_v), int(ld_v), s.ctypes.data_as(dp),
+                                           resid.ctypes.data_as(dp), C.c_void_p(work), int(work_bytes), C.c_void_p(stream), C.byref(res)))
+        return {"status": _lib.KRYLOV_STATUS[res.status], "found": int(res.found), "products": int(res.products), "cycles": int(res.cycles),
+                "scale": float(res.scale), "s": s[:res.found].copy(), "residuals": resid[:res.found].copy()}
+
     # -- block-Jacobi preconditioner (hispmv_block_jacobi_abi.cpp; hispmv_amd.solvers.block_jacobi wraps these) ------------------------
     def block_jacobi_info(self, matrix_idx: int, block_size: int = 8) -> dict:
         """{"accepted", "n_blocks", "pre_bytes", "setup_launches", "cg_work_bytes", "gmres_work_bytes", "gmres_step_bytes", "n"} of a

@@ -351,6 +351,38 @@ def ritz(H, k: int, which: str, beta: float, tol: float) -> dict:
     return {"theta": theta, "Yt": Yt, "res": res, "converged": int(counts[0]), "sweeps": int(counts[1])}
 
 
+def gk(rows: int, cols: int, ncv: int) -> dict:
+    """The workspace rule of thick-restart Golub-Kahan (hispmv_prep_gk), host-only: {"work_bytes", "v_offset", "v_stride", "u_offset",
+    "u_stride", "gc_offset", "yt_offset", "part_offset"} for a rows x cols matrix and ncv basis vectors -- the bytes a run needs, where
+    V (ncv + 1 vectors of cols floats) and U (ncv vectors of rows floats) lie and how many floats apart their vectors are, where Gc lies
+    (64 columns of 66 doubles, the 66 alphas and the 66 betas right behind them), the fp32 coefficients of the last rotation, and the
+    partials: 132 arrays between part_offset and v_offset, each as long as the larger of the two sides' grids rounded up to 2."""
+    out = (C.c_int64 * 8)()
+    if lib.hispmv_prep_gk(int(rows), int(cols), int(ncv), out) != HISPMV_OK:
+        raise ValueError("hispmv_prep_gk: rows >= 0, cols >= 0 and 2 <= ncv <= 64")
+    keys = ("work_bytes", "v_offset", "v_stride", "u_offset", "u_stride", "gc_offset", "yt_offset", "part_offset")
+    return dict(zip(keys, (int(x) for x in out)))
+
+
+def bsvd(B, k: int, beta: float, tol: float) -> dict:
+    """The small SVD of the singular-value solver on the host (hispmv_prep_bsvd): B = P diag(s) Q^T for the float64 matrix B
+    (m x m or m x (m + 1), m <= 64) by one-sided Jacobi, s descending.  Returns {"s" [m], "Pt" [m, m] (row c the left vector of s[c]),
+    "Qt" [m, cols] (row c its right vector), "res" [m] = beta * |Pt[:, m - 1]|, "converged" (how many of the first min(k, m) have
+    res <= tol * s[0]), "sweeps"}."""
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    if B.ndim != 2:
+        raise ValueError("hispmv_prep_bsvd: B must be a matrix")
+    m, cols = B.shape
+    s, Pt, Qt, res = np.zeros(max(m, 1), np.float64), np.zeros((max(m, 1), max(m, 1)), np.float64), np.zeros((max(m, 1), max(cols, 1)), np.float64), np.zeros(max(m, 1), np.float64)
+    counts = (C.c_int64 * 2)()
+    dp = C.POINTER(C.c_double)
+    rc = lib.hispmv_prep_bsvd(B.ctypes.data_as(dp), cols, m, cols, int(k), float(beta), float(tol), s.ctypes.data_as(dp), Pt.ctypes.data_as(dp),
+                              Qt.ctypes.data_as(dp), res.ctypes.data_as(dp), counts)
+    if rc != HISPMV_OK:
+        raise ValueError("hispmv_prep_bsvd: 1 <= m <= 64, m <= cols <= m + 1, k >= 1, beta >= 0 and tol >= 0")
+    return {"s": s, "Pt": Pt, "Qt": Qt, "res": res, "converged": int(counts[0]), "sweeps": int(counts[1])}
+
+
 def block_jacobi(n: int, block_size: int) -> dict:
     """The layout rule of a block-Jacobi buffer (hispmv_prep_block_jacobi), host-only: {"n_blocks", "pre_bytes", "flags_offset",
     "block_floats"} for a system of n unknowns in blocks of block_size (4, 8, 16, 32) -- ceil(n / block_size) blocks of block_size^2

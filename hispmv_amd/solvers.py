@@ -22,7 +22,11 @@ Block-Jacobi: ``block_jacobi(handle, idx, block_size)`` builds the inverted diag
 streams, same rule.
 
 Eigenvalues: ``eigsh`` (FpgaHandle.eigsh_device) for a few extreme eigenpairs of a symmetric handle by thick-restart Lanczos; its
-driver looks at the device once per cycle, so it always returns with its result ready."""
+driver looks at the device once per cycle, so it always returns with its result ready.
+
+Singular values: ``svds`` (FpgaHandle.svds_device) for the k largest singular values of a handle of any shape, with their vectors, by
+thick-restart Golub-Kahan bidiagonalisation over spmv_device and spmv_device_t; ``spectral_norm`` is its k = 1.  Same streams as
+``eigsh``."""
 from __future__ import annotations
 
 import torch
@@ -230,6 +234,55 @@ def eigsh(handle, idx: int, k: int = 6, *, which: str = "LA", ncv=None, tol: flo
     info.pop("scale")
     info["work"] = work
     return vals, rows[:info["found"], :n].t(), info
+
+
+# ---- singular values ---------------------------------------------------------------------------------------------------------------
+def workspace_svds(handle, idx: int, ncv: int, device) -> torch.Tensor:
+    """A workspace tensor for a Golub-Kahan run with ncv basis vectors on handle `idx` (gk_info's work_bytes)."""
+    info = handle.gk_info(idx, ncv)
+    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+
+
+def svds(handle, idx: int, k: int = 6, *, ncv=None, tol: float = 1e-5, max_products=None, v0=None, seed: int = 0, work=None,
+         return_vectors: bool = True):
+    """The k largest singular values of handle `idx`, of any shape rows x cols, with their singular vectors, by thick-restart
+    Golub-Kahan bidiagonalisation on torch's current stream (FpgaHandle.svds_device); the handle must be one spmv_device_t accepts.
+    Returns (s, u, vt, info): s a float64 numpy array [found], descending; u a float32 CUDA tensor [rows, found] and vt [found, cols]
+    (views of the library's rows; None with return_vectors=False, which skips the two finishing rotations); info = {"status", "found",
+    "products", "cycles", "residuals", "scale", "work"}; status as `eigsh`'s.  products counts forward and transposed products together.
+    ncv defaults to min(max(2k + 1, 20), 64), max_products to max(20 max(rows, cols), 2000) capped at 2^30, v0 (cols elements, not
+    written) to torch.randn from a generator seeded with `seed`.  The call waits for its result on any stream."""
+    m = handle.matrix_info(idx)
+    rows, cols = m["rows"], m["cols"]
+    if v0 is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        v0 = torch.randn(cols, generator=gen, dtype=torch.float32).to(device)
+    v0 = _vector(v0, "v0", cols)
+    k = int(k)
+    if ncv is None:
+        ncv = min(max(2 * k + 1, 20), 64)
+    if max_products is None:
+        max_products = min(max(20 * max(rows, cols), 2000), 1 << 30)
+    if work is None:
+        work = workspace_svds(handle, idx, ncv, v0.device)
+    ld_u, ld_v = (rows + 3) // 4 * 4, (cols + 3) // 4 * 4
+    u = torch.zeros(max(k, 1), ld_u, dtype=torch.float32, device=v0.device) if return_vectors else None
+    v = torch.zeros(max(k, 1), ld_v, dtype=torch.float32, device=v0.device) if return_vectors else None
+    info = _launch(handle, v0.device, 1, lambda stream: handle.svds_device(
+        idx, k, v0.data_ptr(), u.data_ptr() if return_vectors else 0, ld_u, v.data_ptr() if return_vectors else 0, ld_v, ncv=ncv, tol=tol,
+        max_products=max_products, work=work.data_ptr(), work_bytes=work.numel() * work.element_size(), stream=stream, vectors=return_vectors))
+    s = info.pop("s")
+    info["work"] = work
+    if not return_vectors:
+        return s, None, None, info
+    return s, u[:info["found"], :rows].t(), v[:info["found"], :cols], info
+
+
+def spectral_norm(handle, idx: int, tol: float = 1e-4) -> float:
+    """The largest singular value of handle `idx`: svds(k=1) without the vectors.  A run that finds nothing (the all-zero matrix) gives 0."""
+    s = svds(handle, idx, 1, tol=tol, return_vectors=False)[0]
+    return float(s[0]) if len(s) else 0.0
 
 
 # ---- several right-hand sides -------------------------------------------------------------------------------------------------------

@@ -19,7 +19,7 @@ there, at the price of two host waits per pass.  Inside ``with torch.cuda.stream
 real stream and nothing waits (examples/train_sparse_layer.py).  Without ``values`` the layer adds no wait, as before: on the default
 stream the caller synchronises between torch's operations and the layer.  One exception: a non-contiguous ``x`` or ``bias`` is copied
 inside the forward pass, on torch's current stream, where no caller can stand between the copy and the launch; on the default stream
-the forward pass waits for that copy itself.
+the forward pass waits for that copy itself, and for the launch that reads it before the copy is released.
 
 ``spmm=True`` routes the forward product and grad_x through the wide-batch entries (FpgaHandle.spmm_device / spmm_device_t) on
 feature-major copies of the activations; ``wide_grad=True`` on top of it takes grad_values through the wide-batch value gradient
@@ -64,6 +64,8 @@ def _function(torch):
                 current.synchronize()
             handle.linear_device(idx, x.data_ptr(), x.shape[0], b.data_ptr() if b is not None else 0, y.data_ptr(), 1.0,
                                  1.0 if b is not None else 0.0, stream)
+            if copied and stream == 0:        # ... and the copies die with this frame: torch's allocator hands their memory to the next kernel
+                handle.synchronize()          # on the default stream, which must not happen while the context's stream still reads them
             ctx.cols = x.shape[1]
             return y
 

@@ -883,7 +883,7 @@ int hispmv_gmres_bj_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, fl
  * ncv outside k + 1 .. HISPMV_LANCZOS_MAX_NCV, tol < 0, max_products < 1 or > 2^30, an unknown `which`, a NULL pointer or one not 4-byte
  * aligned, a workspace that is NULL, short or not 16-byte aligned; a call before load_matrices -> HISPMV_ESTATE.
  * Out of scope: multiple or tightly clustered eigenvalues beyond one copy (single-vector Lanczos finds ONE eigenvector of a multiple
- * eigenvalue), a random restart after an invariant subspace, shift-invert, generalised problems, singular values, non-symmetric
+ * eigenvalue), a random restart after an invariant subspace, shift-invert, generalised problems, singular values (those are hispmv_svds_device's, below), non-symmetric
  * Arnoldi, ncv > 64, locking and deflation, fp64 vectors, several start vectors, sharding over devices, HIP-graph capture. */
 #define HISPMV_LANCZOS_MAX_NCV 64
 #define HISPMV_LANCZOS_TINY_LOG2 (-12)
@@ -929,6 +929,103 @@ int hispmv_lanczos_status(hispmv_ctx* ctx, const void* d_work, void* stream, int
 int hispmv_eigsh_device(hispmv_ctx* ctx, int matrix_idx, int64_t k, int64_t ncv, int which, double tol, int64_t max_products,
                         const float* d_v0, float* d_vecs, int64_t ld_vecs, double* vals_out, double* res_out, void* d_work,
                         int64_t work_bytes, void* stream, hispmv_eigsh_result* result);
+
+/* ---- Golub-Kahan / svds: a few singular values of a handle of any shape ----------------------------------------------------------------
+ * Thick-restart Golub-Kahan bidiagonalisation with full reorthogonalisation on both sides for the k LARGEST singular values of a
+ * rows x cols handle, with their left and right singular vectors.  A step is two Lanczos steps on two bases of different lengths: V
+ * holds ncv + 1 vectors of cols floats, U holds ncv vectors of rows floats, each with its own stride ceil(n / 4) * 4 and its own dot
+ * grid, hispmv_dot_device's for that length.  The forward product is hispmv_spmv_device's, the transposed one hispmv_spmv_device_t's,
+ * each written straight into the other basis; the multi-dot kernel and the subtract-and-dot kernel are hispmv_gmres_device's, unchanged,
+ * the open is Lanczos's, the restart and the finish are hispmv_basis_rotate_device's kernel; one new kernel normalises and records, for
+ * either side.  The host looks ONCE PER CYCLE.  All arithmetic follows the rules of "Lanczos / eigsh": vectors fp32, unfused, one
+ * rounding per operation; sums and scalars fp64 with IEEE / and sqrt; a scalar is rounded ONCE to fp32 before it meets a vector.  ONE run
+ * per handle in flight; the whole state lies in the caller's workspace.
+ *
+ * OPEN: Lanczos's, on V slot 0 with v0 (cols floats): vv = (v0, v0) zero or not finite: BREAKDOWN; else V_0 = f32(1 / sqrt(vv)) * v0.
+ * STEP j, U side (V_0 .. V_j and U_0 .. U_{j-1} orthonormal): u = A V_j into U slot j (alpha 1, beta 0, no bias).  CGS2 against
+ *   U_0 .. U_{j-1} exactly as Lanczos's against its basis: g1_i = (U_i, u); u = u - f32(g1_i) * U_i, i ascending; g2_i = (U_i, u); the same
+ *   subtraction; g_i = g1_i + g2_i; a sum that is not finite sets breakdown in the kernel that sums it.  At j = 0 there is nothing to
+ *   subtract: (u, u) comes from the dot kernel's partials alone.  Then the record kernel: uu = (u, u); not finite: BREAKDOWN.  Otherwise
+ *   Gc[j][i] = g_i for i < j, and THE CLOSED-SPACE RULE: t = +0, t = t + g_i * g_i for i ascending; if uu <= tiny^2 * (uu + t), tiny =
+ *   2^-12 as in Lanczos, A V_j lies in span U: steps = j, products += 1 (the product that found this out is work the answer uses: its
+ *   coefficients are the last column of B'), the words `invariant`, `closed_u` and `done` are set, U slot j is not normalised, alpha_j is
+ *   not written, and the state freezes.  Otherwise alpha_j = sqrt(uu) and U_j = f32(1 / alpha_j) * u.  (0 <= 0 holds: A v0 = 0 closes
+ *   at step 0 with steps = 0.)
+ * STEP j, V side: w = A^T U_j into V slot j + 1.  CGS2 against V_0 .. V_j, coefficients h_i, i <= j.  The record kernel: ww = (w, w);
+ *   not finite: BREAKDOWN.  Otherwise beta_j = sqrt(ww), steps = j + 1, products += 2 (this step's two products: `products` counts
+ *   unfrozen work only), and Lanczos's invariant rule on ww and the h_i: if it holds, `invariant` and `done` are set and w is not
+ *   normalised; otherwise V_{j+1} = f32(1 / beta_j) * w.  The V-side coefficients serve the orthogonalisation and the rule only.
+ *   The products of a frozen run still land in their slots (U slot j', V slot j' + 1 of the later steps) and are ignored.
+ * HOST LOOK, once per cycle: the scalar block, Gc, the alphas and the betas come to pinned memory, the stream is synchronised.  m =
+ *   steps.  The projected matrix B (m x m, upper) holds the kept singular values on its leading diagonal after a restart; every column
+ *   j the device computed in this cycle is B[i][j] = Gc[j][i] for i < j and B[j][j] = alpha_j.  The arrow column at index keep comes out
+ *   of the U-side dots by itself: (U_i, A V_keep) = beta * P[m-1][i].  hispmv_prep_bsvd gives B = P diag(s) Q^T, s descending;
+ *   res_i = beta_{m-1} * |P[m-1][i]|; scale = s_0; pair i is converged when res_i <= tol * scale.
+ *   After closed_u: A V_{m+1} = U_m B' and A^T U_m = V_{m+1} B'^T hold exactly with B' = [B | g] (m x (m + 1), g_i = Gc[m][i]); the SVD
+ *   of B' gives singular values of A with residual estimates 0, the right vectors over m + 1 basis vectors.  m = 0 returns found = 0
+ *   with status INVARIANT: the all-zero matrix and A v0 = 0 both end this way.
+ * STOP (eigsh's rule): CONVERGED when the first min(k, m) pairs are converged and m >= k; else INVARIANT when the state froze by either
+ *   rule, found = min(k, m) pairs with their honest residuals; else MAX_ITERS when products >= max_products at the look.  BREAKDOWN
+ *   returns found = 0 and leaves the outputs untouched.
+ * RESTART otherwise: keep = min(k + (ncv - k) / 2, ncv - 1); U[:, c] = sum_i f32(P[i][c]) * U_i and V[:, c] = sum_i f32(Q[i][c]) * V_i for
+ *   c < keep, i < m: two in-place rotations with the arithmetic of hispmv_basis_rotate_device; V slot keep takes V slot m; B =
+ *   diag(s_0 .. s_{keep-1}); the next cycle runs steps keep .. ncv - 1.
+ * FINISH: the same rotations with the `found` wanted columns, out of place, into d_u (vector c at d_u + c * ld_u, rows floats) and d_v
+ *   (d_v + c * ld_v, cols floats), not renormalised.  s_out[i] and res_out[i] for i < found; the entries behind are not written.
+ *
+ * THE SMALL SVD (hispmv_prep_bsvd, fp64): one-sided (Hestenes) Jacobi on G = B^T: rotations from the right over the column pairs
+ *   (p, q), p < q, row-cyclic, make the columns orthogonal; a pair rotates when |g_p . g_q| > 8 eps |g_p| |g_q|; at most 64 sweeps.
+ *   s = the column norms, Q = the normalised columns, P = the accumulated rotations; descending, ties in Jacobi's order.  A zero column
+ *   has its place in Q filled by the first unit vector that two Gram-Schmidt passes against the columns before it leave longer than 1/2.
+ *
+ * WORKSPACE (hispmv_gk_info: work_bytes, 16-byte aligned; the rule is hispmv_prep_gk's): three 128-byte scalar blocks in the 512 bytes
+ * the other solvers open with -- breakdown, done and products keep their slots, slot 13 holds steps, slot 14 `invariant`, slot 15
+ * `closed_u` --, then g1 and g (66 doubles each, the two sides in turn), Gc (64 columns of 66 doubles, column j at gc_offset + 528 j),
+ * the 66 alphas and then the 66 betas right behind Gc, Yt (64 x 65 floats, the two rotations of a look in turn), the partials (sized by
+ * the larger of krylov_groups(rows) and krylov_groups(cols)), V, then U.  THE BLOCKS: a kernel reads the block the kernel before it
+ * wrote; every kernel of a step but the last writes block 1 or 2, whichever it does not read; the last, the V side's record kernel,
+ * writes block 0.  So no kernel writes the block it reads, and every step, hence every call, leaves the state in block 0.  A step is
+ * 10 launches beside what the two products launch themselves.  Only workgroup 0 writes Gc, the alphas, the betas and the block.
+ * ACCEPTED: every handle both hispmv_spmv_device and hispmv_spmv_device_t accept -- slice streams, dense, fp32 or bf16 storage (a bf16
+ * handle has the singular values of its rounded values), tile streams under _KEEP_FORMAT, _COMPANION handles.  A handle
+ * hispmv_spmv_device_t refuses is refused with that entry's message and status before any launch.  HISPMV_EINVAL before any launch,
+ * outputs untouched: k < 1, k > min(rows, cols), ncv outside k + 1 .. HISPMV_GK_MAX_NCV, tol < 0, max_products outside 2 .. 2^30, a NULL
+ * pointer or one not 4-byte aligned, a workspace that is NULL, short or not 16-byte aligned; a call before load_matrices ->
+ * HISPMV_ESTATE.
+ * DETERMINISM: on a _COMPANION handle both products have a fixed order, so the whole run is bit for bit tests/gk_model.py's.  On every
+ * other handle the transposed product meets its sums in y through atomics -- the dense transposed kernel too, whenever it splits the
+ * rows over several workgroups --: the run is correct, its bits are not promised.
+ * Out of scope: the smallest singular values (which = "SM", harmonic Ritz), multiple singular values beyond one copy, shift-invert,
+ * ncv > 64, fp64 vectors, the multi-vector layout, sharding over devices, HIP-graph capture, lsqr / lsmr on the same recurrence. */
+#define HISPMV_GK_MAX_NCV 64
+/* The workspace rule on the host (no device needed): out = {work_bytes, byte offset of V, floats between two V vectors, byte offset of
+ * U, floats between two U vectors, byte offset of Gc, byte offset of Yt, byte offset of the partials (132 arrays of gp doubles up to
+ * V, gp = the larger grid rounded up to 2)}.  rows or cols < 0, ncv outside 2 .. 64 -> HISPMV_EINVAL. */
+int hispmv_prep_gk(int64_t rows, int64_t cols, int64_t ncv, int64_t out[8]);
+/* The small SVD on the host and nothing else (no device needed): B is rows_b x cols_b, row-major with ld doubles between rows,
+ * 1 <= rows_b <= 64, rows_b <= cols_b <= rows_b + 1.  s_out[rows_b] descending; Pt_out[rows_b * rows_b], row c the left vector of
+ * s_out[c]; Qt_out[rows_b * cols_b], row c its right vector; res_out[c] = beta * |Pt_out[c][rows_b - 1]|; counts_out = {converged among
+ * the first min(k, rows_b): res <= tol * s_out[0], Jacobi sweeps}.  Bad arguments (beta or tol negative or NaN too) -> HISPMV_EINVAL. */
+int hispmv_prep_bsvd(const double* B, int64_t ld, int64_t rows_b, int64_t cols_b, int64_t k, double beta, double tol, double* s_out,
+                     double* Pt_out, double* Qt_out, double* res_out, int64_t counts_out[2]);
+/* out = {accepted, work_bytes, byte offset of V, V stride in floats, byte offset of U, U stride in floats, byte offset of Gc, byte
+ * offset of Yt}; zeros for a handle that is not loaded or that the transposed product refuses.  A bad index, ncv outside 2 .. 64 ->
+ * HISPMV_EINVAL. */
+int hispmv_gk_info(const hispmv_ctx* ctx, int matrix_idx, int64_t ncv, int64_t out[8]);
+/* Enqueues the open (first != 0: j0 must be 0, d_v0 the start vector of cols floats) and the steps j0 .. j1 - 1, 0 <= j0 < j1 <= ncv,
+ * with no host look.  The workspace is that of the rule for ncv (2 .. 64), which is an argument because U lies behind the ncv + 1
+ * vectors of V: the calls of one run give the same ncv.  Asynchronous on `stream`. */
+int hispmv_gk_steps_device(hispmv_ctx* ctx, int matrix_idx, int64_t ncv, int64_t j0, int64_t j1, int first, const float* d_v0,
+                           void* d_work, int64_t work_bytes, void* stream);
+/* Synchronises `stream` and reads out = {steps, invariant, closed_u, breakdown, products} out of the workspace of a run on it. */
+int hispmv_gk_status(hispmv_ctx* ctx, const void* d_work, void* stream, int64_t out[5]);
+/* The driver above.  d_v0[cols] is the start vector (not written).  vectors != 0: d_u takes `found` left vectors ld_u >= rows floats
+ * apart, d_v the right vectors ld_v >= cols floats apart; vectors == 0: the two finishing rotations are skipped and d_u, d_v are not
+ * looked at.  s_out and res_out are host doubles [k].  *result is hispmv_eigsh_result, `scale` = s_0 of the last look.  The call
+ * returns with *result filled and the stream synchronised; it allocates and frees its pinned buffer itself. */
+int hispmv_svds_device(hispmv_ctx* ctx, int matrix_idx, int64_t k, int64_t ncv, double tol, int64_t max_products, const float* d_v0,
+                       int vectors, float* d_u, int64_t ld_u, float* d_v, int64_t ld_v, double* s_out, double* res_out, void* d_work,
+                       int64_t work_bytes, void* stream, hispmv_eigsh_result* result);
 
 /* ---- getters (HiSpmvHandle getters, spmv-helper.cpp:752-810) ------------------------------------ */
 typedef struct hispmv_matrix_info {
