@@ -1,8 +1,9 @@
-// hispmv_lanczos.hip -- the kernels thick-restart Lanczos adds to hispmv_gmres.hip's (hispmv_lanczos.h; include/hispmv.h: "Lanczos /
-// eigsh").  lanczos_open and lanczos_norm run on the Krylov grid with its chunk order and its fixed-order fp64 sums: fp32 vectors,
-// unfused (-ffp-contract=off), scalars fp64 and rounded once to fp32 before they meet a vector; every workgroup finishes the sums it
-// needs itself, only workgroup 0 writes Hc, the betas and the scalar block.  basis_rotate is the restart: a tall-skinny product
-// V[:, :k] <- V[:, :m] Y that may run in place, lanes along the elements.
+// hispmv_lanczos.hip -- the kernels the thick-restart solvers, Lanczos and Golub-Kahan, add to hispmv_gmres.hip's (hispmv_lanczos.h;
+// include/hispmv.h: "Lanczos / eigsh", "Golub-Kahan / svds").  lanczos_open and basis_record run on the Krylov grid of their basis's
+// length with its chunk order and its fixed-order fp64 sums: fp32 vectors, unfused (-ffp-contract=off), scalars fp64 and rounded once
+// to fp32 before they meet a vector; every workgroup finishes the sums it needs itself, only workgroup 0 writes Hc, the alphas, the
+// betas and the scalar block.  basis_rotate is the restart: a tall-skinny product V[:, :k] <- V[:, :m] Y that may run in place, lanes
+// along the elements.
 #include <hip/hip_runtime.h>
 
 #include "hispmv_krylov_device.h"
@@ -14,7 +15,7 @@ namespace {
 
 // The block from nothing behind the partials of (v0, v0): a sum that is zero or not finite is a breakdown, and slot 0 then holds the
 // plain copy of v0; otherwise V_0 = f32(1 / sqrt((v0, v0))) * v0.
-__global__ __launch_bounds__(kKrylovThreads) void lanczos_open_kernel(LanczosStep k) {
+__global__ __launch_bounds__(kKrylovThreads) void lanczos_open_kernel(RecordStep k) {
     __shared__ double sh[kKrylovThreads];
     double S[kKrylovState];
 #pragma unroll
@@ -36,43 +37,58 @@ __global__ __launch_bounds__(kKrylovThreads) void lanczos_open_kernel(LanczosSte
     });
 }
 
-// The end of step j, behind pass 2 of the subtract-and-dot kernel: ww = (w, w) from its partials, not finite: breakdown.  Column j of
-// Hc and beta_j = sqrt(ww) by workgroup 0; the invariant subspace rule ww <= tiny^2 * (ww + sum h_i^2) by every thread from the same
-// words; otherwise V_{j+1} = f32(1 / beta_j) * w in place.
-__global__ __launch_bounds__(kKrylovThreads) void lanczos_norm_kernel(LanczosStep k) {
+// The end of one step's work on a basis, behind pass 2 of the subtract-and-dot kernel (Golub-Kahan's U side, j = 0: behind the dot
+// kernel): ww = (w, w) from its partials, not finite: breakdown.  The rule ww <= tiny^2 * (ww + sum h_i^2) by every thread from the
+// same words.  What RULE decides (hispmv_lanczos.h: RecordRule): where w lies and how many coefficients the step has -- U side: slot j
+// and j of them, otherwise slot j + 1 and j + 1; what workgroup 0 records -- column j of Hc (not the V side), alpha_j = sqrt(ww) on the
+// U side unless the rule holds, beta_j = sqrt(ww) otherwise; and the block's words -- U side: only where the rule holds, which there
+// closes the space: steps = j, one more product, invariant and closed_u; otherwise steps = j + 1, one more product (the V side: two),
+// and the rule is the invariant subspace rule.  Where the rule does not hold w = f32(1 / sqrt(ww)) * w in place.
+template <RecordRule RULE>
+__global__ __launch_bounds__(kKrylovThreads) void basis_record_kernel(RecordStep k) {
+    constexpr bool U = RULE == kRecordGkU;
     __shared__ double sh[kKrylovThreads];
-    __shared__ double hh[kLanczosMaxNcv];
+    __shared__ double hh[kLanczosMaxNcv + 1];
     double S[kKrylovState];
     load_state(k.s_in, S);
     if (frozen(S)) {
         store_state(k.s_out, S);
         return;
     }
-    const int j = k.j, t = threadIdx.x;
-    if (t <= j) hh[t] = k.h[t];
+    const int j = k.j, t = threadIdx.x, cnt = U ? j : j + 1;
+    if (t < cnt) hh[t] = k.h[t];
     const double ww = sum_partials(k.part, groups_of(k.n), sh);          // its barriers publish hh
     if (!finite_d(ww)) {
         S[kKsBreakdown] = 1.0;
         store_state(k.s_out, S);
         return;
     }
-    const double beta = sqrt(ww);
+    const double nrm = sqrt(ww);
     double hsq = 0.0;
-    for (int i = 0; i <= j; ++i) {
+    for (int i = 0; i < cnt; ++i) {
         const double sq = hh[i] * hh[i];
         hsq = hsq + sq;
     }
-    const bool invariant = ww <= kLanczosTiny2 * (ww + hsq);
+    const bool closed = ww <= kLanczosTiny2 * (ww + hsq);
     if (blockIdx.x == 0) {
-        if (t <= j) k.Hc[(int64_t)j * kLanczosHcLd + t] = hh[t];
-        if (t == 0) k.beta[j] = beta;
+        if (RULE != kRecordGkV && t < cnt) k.Hc[(int64_t)j * kLanczosHcLd + t] = hh[t];
+        if (U) {
+            if (t == 0 && !closed) k.alpha[j] = nrm;
+        } else if (t == 0) {
+            k.beta[j] = nrm;
+        }
     }
-    S[kKsProducts] += 1.0; S[kKsRr] = ww; S[kLsSteps] = (double)(j + 1);
-    if (invariant) { S[kLsInvariant] = 1.0; S[kKsDone] = 1.0; }
+    S[kKsRr] = ww;
+    if (U) {
+        if (closed) { S[kKsProducts] += 1.0; S[kLsSteps] = (double)j; S[kLsClosedU] = 1.0; }
+    } else {
+        S[kKsProducts] += RULE == kRecordGkV ? 2.0 : 1.0; S[kLsSteps] = (double)(j + 1);
+    }
+    if (closed) { S[kLsInvariant] = 1.0; S[kKsDone] = 1.0; }
     store_state(k.s_out, S);
-    if (invariant) return;
-    const float inv32 = (float)(1.0 / beta);
-    float* w = k.V + (int64_t)(j + 1) * k.stride;
+    if (closed) return;
+    const float inv32 = (float)(1.0 / nrm);
+    float* w = k.V + (int64_t)(U ? j : j + 1) * k.stride;
     for_chunks(k.n, [&](int64_t i, int m) {
         float v[4];
         ld4(w, i, m, v);
@@ -165,12 +181,13 @@ __global__ __launch_bounds__(kRotateThreads) void basis_rotate_kernel(const floa
 
 }  // namespace
 
-hipError_t launch_lanczos_open(const LanczosStep& k, hipStream_t s) {
+hipError_t launch_lanczos_open(const RecordStep& k, hipStream_t s) {
     hipLaunchKernelGGL(lanczos_open_kernel, dim3(grid_of(k.n)), dim3(kKrylovThreads), 0, s, k);
     return hipGetLastError();
 }
-hipError_t launch_lanczos_norm(const LanczosStep& k, hipStream_t s) {
-    hipLaunchKernelGGL(lanczos_norm_kernel, dim3(grid_of(k.n)), dim3(kKrylovThreads), 0, s, k);
+hipError_t launch_basis_record(const RecordStep& k, RecordRule rule, hipStream_t s) {
+    void (*const kernels[])(RecordStep) = {basis_record_kernel<kRecordLanczos>, basis_record_kernel<kRecordGkU>, basis_record_kernel<kRecordGkV>};
+    hipLaunchKernelGGL(kernels[rule], dim3(grid_of(k.n)), dim3(kKrylovThreads), 0, s, k);
     return hipGetLastError();
 }
 

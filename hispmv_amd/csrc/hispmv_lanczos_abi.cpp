@@ -1,22 +1,20 @@
 // hispmv_lanczos_abi.cpp -- the thick-restart Lanczos entries of the C ABI (include/hispmv.h: hispmv_prep_lanczos, hispmv_prep_ritz,
-// hispmv_lanczos_info, hispmv_basis_rotate_device, hispmv_lanczos_steps_device, hispmv_lanczos_status, hispmv_eigsh_device) over the
-// launchers of hispmv_lanczos.h and the two GMRES launchers a step shares.  The products go through hispmv_spmv_device like any
-// caller's, the checks are hispmv_krylov_solve.h's, and the whole state of a run lies in the caller's workspace in the layout of
-// lanczos_layout.  The host half -- the Ritz values of the projected matrix, their order, the stopping rule -- is hispmv_prep_ritz,
+// hispmv_lanczos_info, hispmv_basis_rotate_device, hispmv_lanczos_steps_device, hispmv_lanczos_status, hispmv_eigsh_device) as a
+// backend of hispmv_thick_restart.h: a step's launches on one basis, the checks and the driver loop are its, shared with Golub-Kahan.
+// The products go through hispmv_spmv_device like any caller's, and the whole state of a run lies in the caller's workspace in the
+// layout of lanczos_layout.  The host half -- the Ritz values of the projected matrix, their order, the stopping rule -- is hispmv_prep_ritz,
 // which needs no device.
 #include <algorithm>
 #include <numeric>
 #include <vector>
 
-#include "hispmv_krylov_solve.h"
-#include "hispmv_lanczos.h"
+#include "hispmv_thick_restart.h"
 
 using namespace hispmv;
 
 namespace {
 
 constexpr int kM = kLanczosMaxNcv;
-constexpr int64_t kStateBytes = kKrylovState * 8;
 
 // Cyclic Jacobi in Rutishauser's form on the symmetric a (m x m, row-major, destroyed): d = the eigenvalues, column c of v (row-major)
 // the eigenvector of d[c].  Returns the sweeps it took.
@@ -97,71 +95,53 @@ double ritz(const double* H, int64_t ld, int m, int k, int which, double beta, d
     return scale;
 }
 
-// The order of launches of a run.  A step: the product into slot j + 1, the multi-dot pass over slots 0 .. j, the subtract-and-dot
-// kernel twice, the normalise-and-record kernel.  The three kernels of a step that write the scalar block pass it round three blocks,
-// 0 -> 1 -> 2 -> 0: every kernel reads one block and writes another, and every step -- so every call -- leaves the state in block 0,
-// which the open kernel writes, the multi-dot kernel and the next step read, and hispmv_lanczos_status reports.
-struct Lanczos : KrylovSolve {
+// The order of launches of a run.  A step: the product into slot j + 1, the orthogonalisation against slots 0 .. j (the multi-dot pass,
+// the subtract-and-dot kernel twice), the record kernel.  The backend of thick_restart_run: the projected matrix is H, the look Hc
+// with the betas behind it.
+struct Lanczos : ThickRestart {
+    static constexpr int64_t kLookDoubles = (int64_t)(kM + 1) * kLanczosHcLd;
+    static constexpr int kRotations = 1, kLd = kM;
     int64_t n = 0;
-    LanczosLayout l;
-    int cur = 0;
+    int which = 0;
+    float* d_vecs = nullptr;
+    int64_t ld_vecs = 0;
+    std::vector<double> P, Yt, vals, res;          // of the driver only: H (kM x kM), the Ritz step's results
 
-    template <class P> P* at(int64_t off) const { return (P*)(work + off); }
-    double* state(int64_t which) const { return at<double>(which * kStateBytes); }
     float* vec(int64_t i) const { return at<float>(l.off_v) + i * l.stride; }
-    template <class K> void turn(K& k) {
-        k.s_in = state(cur);
-        cur = (cur + 1) % 3;
-        k.s_out = state(cur);
-    }
-    LanczosStep lstep() {
-        LanczosStep k;
-        k.n = n; k.V = vec(0); k.stride = l.stride; k.Hc = at<double>(l.off_hc); k.beta = at<double>(l.off_beta); k.h = at<double>(l.off_h);
-        turn(k);
-        return k;
-    }
-    GmresStep gstep(int64_t j, bool second) {
-        GmresStep k;
-        k.n = n; k.j = (int)j; k.second = second; k.gp = l.gp; k.V = vec(0); k.stride = l.stride;
-        k.parts_in = at<double>(second ? l.off_pb : l.off_pa); k.parts_out = at<double>(l.off_pb); k.part_ww = at<double>(l.off_ww);
-        k.h1 = at<double>(l.off_h1); k.h = at<double>(l.off_h);
-        turn(k);
-        return k;
-    }
-    int open(const float* d_v0) {
-        LAUNCH_TRY(c, launch_krylov_dot, d_v0, d_v0, n, at<double>(l.off_vv), s);
-        LanczosStep k = lstep();
-        k.s_out = state(cur = 0);          // from nothing, into block 0
-        k.v0 = d_v0; k.part = at<double>(l.off_vv);
-        LAUNCH_TRY(c, launch_lanczos_open, k, s);
-        return HISPMV_OK;
-    }
+    int open(const float* d_v0) { return ThickRestart::open(d_v0, n, vec(0), l.stride); }
     int steps(int64_t j0, int64_t j1) {
         for (int64_t j = j0; j < j1; ++j) {
             if (const int rc = hispmv_spmv_device(c, idx, vec(j), nullptr, vec(j + 1), 1.0f, 0.0f, stream_arg)) return rc;
-            LAUNCH_TRY(c, launch_gmres_multi_dot, vec(0), l.stride, j + 1, vec(j + 1), n, at<double>(l.off_pa), l.gp, state(cur), s);
-            LAUNCH_TRY(c, launch_gmres_sub, gstep(j, false), s);
-            LAUNCH_TRY(c, launch_gmres_sub, gstep(j, true), s);
-            LanczosStep k = lstep();
-            k.j = (int)j; k.part = at<double>(l.off_ww);
-            LAUNCH_TRY(c, launch_lanczos_norm, k, s);
+            if (const int rc = orthogonalise(n, vec(0), l.stride, j)) return rc;
+            if (const int rc = record(n, vec(0), l.stride, j, kRecordLanczos, nullptr, true)) return rc;
         }
         return HISPMV_OK;
     }
+    bool verdict(const double* S, int n_cv, int* m, bool* invariant, hispmv_eigsh_result*) const {
+        *m = (int)S[kLsSteps];
+        *invariant = S[kLsInvariant] != 0.0;
+        return S[kKsBreakdown] == 0.0 && *m >= 1 && *m <= n_cv;
+    }
+    void project(const double* Hc, int j0, int m) {
+        for (int j = j0; j < m; ++j)
+            for (int i = 0; i <= j; ++i) P[(size_t)i * kM + j] = P[(size_t)j * kM + i] = Hc[(int64_t)j * kLanczosHcLd + i];
+    }
+    double decompose(const double* Hc, int m, int k, double tol, int64_t counts[2]) {
+        const double* betas = Hc + (int64_t)kM * kLanczosHcLd;
+        return ritz(P.data(), kM, m, k, which, betas[m - 1], tol, vals.data(), Yt.data(), res.data(), counts);
+    }
+    int finish(float* y32, int m, int found) { return rotate(y32, Yt.data(), n, vec(0), l.stride, m, found, d_vecs, ld_vecs, nullptr, nullptr); }
+    int restart(float* y32, int m, int keep) { return rotate(y32, Yt.data(), n, vec(0), l.stride, m, keep, vec(0), l.stride, vec(m), vec(keep)); }
 };
 
-// what the three entries that take a handle and a workspace check alike; fills v
+// the checks of the two entries that take a handle and a workspace; fills v
 int lanczos_enter(hispmv_ctx* c, const char* name, int idx, int64_t basis_ncv, const void* d_work, int64_t work_bytes, void* stream, Lanczos& v) {
-    const std::string w(name);
-    Matrix* mp = nullptr;
-    if (const int rc = find_handle(c, idx, name, &mp)) return rc;
-    if (const int rc = krylov_check_square(c, w, *mp)) return rc;
-    v.n = mp->rows;
-    v.l = lanczos_layout(v.n, basis_ncv);
-    if (const int rc = krylov_check_work(c, w, d_work, work_bytes, v.l.work_bytes, "hispmv_lanczos_info asks for")) return rc;
-    if (const int rc = adopt_stream(c, stream, &v.s)) return rc;
-    v.c = c; v.idx = idx; v.work = (char*)d_work; v.stream_arg = stream;
-    return HISPMV_OK;
+    return thick_restart_enter(c, name, idx, d_work, work_bytes, "hispmv_lanczos_info asks for", stream, v, [&](const Matrix& m) {
+        if (const int rc = krylov_check_square(c, name, m)) return rc;
+        v.n = m.rows;
+        v.l = lanczos_layout(v.n, basis_ncv);
+        return HISPMV_OK;
+    });
 }
 
 }  // namespace
@@ -231,15 +211,8 @@ HISPMV_API int hispmv_lanczos_steps_device(hispmv_ctx* c, int idx, int64_t j0, i
 
 HISPMV_API int hispmv_lanczos_status(hispmv_ctx* c, const void* d_work, void* stream, int64_t out[4]) {
     if (!c || !out) return HISPMV_EINVAL;
-    hipStream_t s;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (!d_work || ((uintptr_t)d_work & 15)) return fail(c, HISPMV_EINVAL, "lanczos_status: the workspace must be the 16-byte aligned one of the run");
-        if (const int rc = adopt_stream(c, stream, &s)) return rc;
-    }
     double S[kKrylovState];
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipMemcpy(S, d_work, kStateBytes, hipMemcpyDeviceToHost));          // block 0: where every call leaves the state
+    if (const int rc = thick_restart_status(c, "lanczos_status", d_work, stream, S)) return rc;
     out[0] = (int64_t)S[kLsSteps]; out[1] = S[kLsInvariant] != 0.0; out[2] = S[kKsBreakdown] != 0.0; out[3] = (int64_t)S[kKsProducts];
     return HISPMV_OK;
 }
@@ -263,55 +236,7 @@ HISPMV_API int hispmv_eigsh_device(hispmv_ctx* c, int idx, int64_t k, int64_t nc
         if (const int rc = lanczos_enter(c, "eigsh_device", idx, ncv, d_work, work_bytes, stream, v)) return rc;
         if (k > 1 && ld_vecs < v.n) return fail(c, HISPMV_EINVAL, w + ": ld_vecs must be at least n");
     }
-    // pinned: the scalar block, Hc and the betas as the workspace holds them, then the fp32 coefficients of a rotation
-    const int64_t hc_doubles = (int64_t)(kM + 1) * kLanczosHcLd;
-    HIP_TRY(c, hipHostMalloc((void**)&v.pinned, (size_t)((kKrylovState + hc_doubles) * 8 + kRotateMaxOut * kRotateMaxIn * 4), hipHostMallocDefault));
-    const double* S = v.pinned;
-    const double *Hc = v.pinned + kKrylovState, *betas = Hc + (int64_t)kM * kLanczosHcLd;
-    float* y32 = (float*)(v.pinned + kKrylovState + hc_doubles);
-    std::vector<double> H((size_t)kM * kM, 0.0), Yt((size_t)kM * kM), theta(kM), res(kM);
-    const int n_cv = (int)ncv, kk = (int)k;
-    int64_t cycles = 0, counts[2] = {0, 0};
-    *result = hispmv_eigsh_result{HISPMV_KRYLOV_BREAKDOWN, 0, 0, 0, 0.0};
-    if (const int rc = v.open(d_v0)) return rc;
-    // the coefficients of `cols` Ritz vectors over m basis vectors into the workspace, then the rotation into out
-    auto rotate = [&](int m, int cols, float* out, int64_t ld_out, const float* xsrc, float* xdst) -> int {
-        for (int col = 0; col < cols; ++col)
-            for (int i = 0; i < m; ++i) y32[col * m + i] = (float)Yt[(size_t)col * m + i];
-        HIP_TRY(c, hipMemcpyAsync(v.at<float>(v.l.off_yt), y32, (size_t)cols * m * 4, hipMemcpyHostToDevice, v.s));
-        LAUNCH_TRY(c, launch_basis_rotate, v.vec(0), v.l.stride, m, cols, v.at<float>(v.l.off_yt), out, ld_out, v.n, xsrc, xdst, v.s);
-        return HISPMV_OK;
-    };
-    for (int j0 = 0;;) {
-        if (const int rc = v.steps(j0, n_cv)) return rc;
-        ++cycles;
-        HIP_TRY(c, hipMemcpyAsync(v.pinned, v.state(0), kStateBytes, hipMemcpyDeviceToHost, v.s));
-        HIP_TRY(c, hipMemcpyAsync(v.pinned + kKrylovState, v.at<double>(v.l.off_hc), (size_t)hc_doubles * 8, hipMemcpyDeviceToHost, v.s));
-        HIP_TRY(c, hipStreamSynchronize(v.s));
-        result->products = (int64_t)S[kKsProducts];
-        result->cycles = cycles;
-        const int m = (int)S[kLsSteps];
-        if (S[kKsBreakdown] != 0.0 || m < 1 || m > n_cv) return HISPMV_OK;          // BREAKDOWN: d_vecs untouched
-        for (int j = j0; j < m; ++j)
-            for (int i = 0; i <= j; ++i) H[(size_t)i * kM + j] = H[(size_t)j * kM + i] = Hc[(int64_t)j * kLanczosHcLd + i];
-        result->scale = ritz(H.data(), kM, m, kk, which, betas[m - 1], tol, theta.data(), Yt.data(), res.data(), counts);
-        const int found = std::min(kk, m);
-        const bool invariant = S[kLsInvariant] != 0.0;
-        int status = -1;
-        if (counts[0] == found && m >= kk) status = HISPMV_KRYLOV_CONVERGED;
-        else if (invariant) status = HISPMV_KRYLOV_INVARIANT;
-        else if (result->products >= max_products) status = HISPMV_KRYLOV_MAX_ITERS;
-        if (status >= 0) {
-            for (int i = 0; i < found; ++i) { vals_out[i] = theta[i]; res_out[i] = res[i]; }
-            if (const int rc = rotate(m, found, d_vecs, ld_vecs, nullptr, nullptr)) return rc;
-            HIP_TRY(c, hipStreamSynchronize(v.s));
-            result->status = status; result->found = found;
-            return HISPMV_OK;
-        }
-        const int keep = std::min(kk + (n_cv - kk) / 2, n_cv - 1);
-        if (const int rc = rotate(m, keep, v.vec(0), v.l.stride, v.vec(m), v.vec(keep))) return rc;
-        std::fill(H.begin(), H.end(), 0.0);
-        for (int i = 0; i < keep; ++i) H[(size_t)i * kM + i] = theta[i];
-        j0 = keep;
-    }
+    v.which = which; v.d_vecs = d_vecs; v.ld_vecs = ld_vecs;
+    v.P.assign((size_t)kM * kM, 0.0); v.Yt.resize((size_t)kM * kM); v.vals.resize(kM); v.res.resize(kM);
+    return thick_restart_run(v, k, ncv, tol, max_products, d_v0, vals_out, res_out, result);
 }

@@ -568,13 +568,16 @@ class FpgaHandle:
         """{"accepted", "work_bytes", "v_offset", "stride", "hc_offset", "yt_offset", "launches_per_step", "n"} of a Lanczos run with
         ncv basis vectors on a handle (hispmv_lanczos_info): the workspace, where it keeps the basis, Hc (the betas lie right behind
         its 64 columns of 66 doubles) and the coefficients of the last rotation; zeros for a handle that is not loaded or not square."""
+        return self._basis_info(lib.hispmv_lanczos_info, matrix_idx, ncv, _lib.HISPMV_LANCZOS_MAX_NCV,
+                                ("accepted", "work_bytes", "v_offset", "stride", "hc_offset", "yt_offset", "launches_per_step", "n"))
+
+    def _basis_info(self, entry, matrix_idx: int, ncv: int, max_ncv: int, keys) -> dict:
+        """The eight words of lanczos_info and gk_info under `keys`."""
         out = (C.c_int64 * 8)()
-        rc = lib.hispmv_lanczos_info(self._ctx, int(matrix_idx), int(ncv), out)
-        if rc != _lib.HISPMV_OK:
+        if entry(self._ctx, int(matrix_idx), int(ncv), out) != _lib.HISPMV_OK:
             if 0 <= int(matrix_idx) < self.num_matrices():
-                raise ValueError(f"ncv must be 2 .. {_lib.HISPMV_LANCZOS_MAX_NCV}")
+                raise ValueError(f"ncv must be 2 .. {max_ncv}")
             raise IndexError("Matrix idx out of range")
-        keys = ("accepted", "work_bytes", "v_offset", "stride", "hc_offset", "yt_offset", "launches_per_step", "n")
         d = dict(zip(keys, (int(x) for x in out)))
         d["accepted"] = bool(d["accepted"])
         return d
@@ -623,16 +626,8 @@ class FpgaHandle:
         ncv basis vectors on a handle (hispmv_gk_info): the workspace, where it keeps V and U, Gc (the alphas and the betas lie right
         behind its 64 columns of 66 doubles) and the coefficients of the last rotation; zeros for a handle that is not loaded or that
         spmv_device_t refuses."""
-        out = (C.c_int64 * 8)()
-        rc = lib.hispmv_gk_info(self._ctx, int(matrix_idx), int(ncv), out)
-        if rc != _lib.HISPMV_OK:
-            if 0 <= int(matrix_idx) < self.num_matrices():
-                raise ValueError(f"ncv must be 2 .. {_lib.HISPMV_GK_MAX_NCV}")
-            raise IndexError("Matrix idx out of range")
-        keys = ("accepted", "work_bytes", "v_offset", "v_stride", "u_offset", "u_stride", "gc_offset", "yt_offset")
-        d = dict(zip(keys, (int(x) for x in out)))
-        d["accepted"] = bool(d["accepted"])
-        return d
+        return self._basis_info(lib.hispmv_gk_info, matrix_idx, ncv, _lib.HISPMV_GK_MAX_NCV,
+                                ("accepted", "work_bytes", "v_offset", "v_stride", "u_offset", "u_stride", "gc_offset", "yt_offset"))
 
     def gk_steps_device(self, matrix_idx: int, ncv: int, j0: int, j1: int, first: bool, d_v0: int, work: int, work_bytes: int, stream: int = 0) -> None:
         """Enqueues the open (first: from the start vector d_v0, cols floats) and the Golub-Kahan steps j0 .. j1 - 1 <= ncv - 1 of a run

@@ -197,10 +197,25 @@ def gmres(handle, idx: int, b, x0=None, *, minv=None, restart: int = 30, rtol: f
 
 
 # ---- eigenvalues -------------------------------------------------------------------------------------------------------------------
+def _workspace(info: dict, device) -> torch.Tensor:
+    """The workspace tensor an *_info dict asks for; empty for a handle the solver refuses, whose call then says why."""
+    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+
+
+def _start(v0, n: int, seed: int, k, ncv):
+    """(v0, k, ncv) of eigsh and svds with their defaults: v0 = torch.randn from a CPU generator seeded with `seed`, moved to the
+    current device; ncv = min(max(2k + 1, 20), 64)."""
+    if v0 is None:
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        v0 = torch.randn(n, generator=gen, dtype=torch.float32).to(torch.device("cuda", torch.cuda.current_device()))
+    v0 = _vector(v0, "v0", n)
+    k = int(k)
+    return v0, k, min(max(2 * k + 1, 20), 64) if ncv is None else ncv
+
+
 def workspace_eigsh(handle, idx: int, ncv: int, device) -> torch.Tensor:
     """A workspace tensor for a Lanczos run with ncv basis vectors on handle `idx` (lanczos_info's work_bytes)."""
-    info = handle.lanczos_info(idx, ncv)
-    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+    return _workspace(handle.lanczos_info(idx, ncv), device)
 
 
 def eigsh(handle, idx: int, k: int = 6, *, which: str = "LA", ncv=None, tol: float = 1e-5, max_products=None, v0=None, seed: int = 0, work=None):
@@ -213,14 +228,7 @@ def eigsh(handle, idx: int, k: int = 6, *, which: str = "LA", ncv=None, tol: flo
     (v0 is not written).  The driver looks at the device once per cycle, so the call waits for its result on any stream."""
     m = handle.matrix_info(idx)
     n = m["rows"]
-    if v0 is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-        gen = torch.Generator(device="cpu").manual_seed(int(seed))
-        v0 = torch.randn(n, generator=gen, dtype=torch.float32).to(device)
-    v0 = _vector(v0, "v0", n)
-    k = int(k)
-    if ncv is None:
-        ncv = min(max(2 * k + 1, 20), 64)
+    v0, k, ncv = _start(v0, n, seed, k, ncv)
     if max_products is None:
         max_products = min(max(10 * n, 1000), 1 << 30)
     if work is None:
@@ -239,8 +247,7 @@ def eigsh(handle, idx: int, k: int = 6, *, which: str = "LA", ncv=None, tol: flo
 # ---- singular values ---------------------------------------------------------------------------------------------------------------
 def workspace_svds(handle, idx: int, ncv: int, device) -> torch.Tensor:
     """A workspace tensor for a Golub-Kahan run with ncv basis vectors on handle `idx` (gk_info's work_bytes)."""
-    info = handle.gk_info(idx, ncv)
-    return torch.empty(info["work_bytes"] if info["accepted"] else 0, dtype=torch.uint8, device=device)
+    return _workspace(handle.gk_info(idx, ncv), device)
 
 
 def svds(handle, idx: int, k: int = 6, *, ncv=None, tol: float = 1e-5, max_products=None, v0=None, seed: int = 0, work=None,
@@ -254,14 +261,7 @@ def svds(handle, idx: int, k: int = 6, *, ncv=None, tol: float = 1e-5, max_produ
     written) to torch.randn from a generator seeded with `seed`.  The call waits for its result on any stream."""
     m = handle.matrix_info(idx)
     rows, cols = m["rows"], m["cols"]
-    if v0 is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-        gen = torch.Generator(device="cpu").manual_seed(int(seed))
-        v0 = torch.randn(cols, generator=gen, dtype=torch.float32).to(device)
-    v0 = _vector(v0, "v0", cols)
-    k = int(k)
-    if ncv is None:
-        ncv = min(max(2 * k + 1, 20), 64)
+    v0, k, ncv = _start(v0, cols, seed, k, ncv)
     if max_products is None:
         max_products = min(max(20 * max(rows, cols), 2000), 1 << 30)
     if work is None:

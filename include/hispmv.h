@@ -874,7 +874,9 @@ int hispmv_gmres_bj_device(hispmv_ctx* ctx, int matrix_idx, const float* d_b, fl
  *
  * WORKSPACE (hispmv_lanczos_info: work_bytes, 16-byte aligned; the rule is hispmv_prep_lanczos's): three 128-byte scalar blocks in the
  * 512 bytes the other solvers open with -- breakdown, done and products keep their slots, slot 13 holds steps and slot 14
- * `invariant`; the three kernels of a step that write the block pass it 0 -> 1 -> 2 -> 0, so a kernel never writes the block it
+ * `invariant`; the kernels of a step that write the block pass it on by the one rule of the thick-restart solvers (every kernel but the
+ * step's last writes block 1 or 2, whichever it does not read, the last writes block 0), which for Lanczos's three kernels gives
+ * 0 -> 1 -> 2 -> 0, so a kernel never writes the block it
  * reads and every step, hence every call, leaves the state in block 0 --, then h1 and h (66 doubles each), Hc (64 columns of 66 doubles, column j at
  * hc_offset + 528 j), the 66 betas right behind Hc, Yt (64 x 65 floats: the coefficients of the last rotation, row c = output c), the
  * partials, and the ncv + 1 basis vectors (ceil(n / 4) * 4 floats apart).  Only workgroup 0 writes Hc, the betas and the block.

@@ -25,7 +25,7 @@ def test_prep_lanczos_is_the_rule_of_the_header(n, ncv):
     assert [p[k] for k in keys] == [int(v) for v in out]
     stride, groups = (n + 3) // 4 * 4, prep.krylov_groups(n)
     assert (p["stride"], p["groups"], p["basis_vectors"], p["launches_per_step"]) == (stride, groups, ncv + 1, 5)
-    # the regions in order: three scalar blocks in 512 bytes (a step passes the state 0 -> 1 -> 2 -> 0), h1 and h (66 doubles each),
+    # the regions in order: three scalar blocks in 512 bytes (a step passes the state 0 -> 1 -> 2 -> 0: what the one block rule gives for three kernels), h1 and h (66 doubles each),
     # Hc (64 columns of 66 doubles), the betas (66 doubles), Yt (64 x 65 floats), two single partial arrays and two of 65 sums, the basis -- each 16-byte aligned
     gp = max(groups + groups % 2, 2)
     regions = [512, 66 * 8, 66 * 8, 64 * 66 * 8, 66 * 8, 64 * 65 * 4, gp * 8, gp * 8, 65 * gp * 8, 65 * gp * 8]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 r"""Are the kernels of two builds the same instructions?  Reads the device assembly of one kernel file from two builds -- .s files of
-`make -C hispmv_amd/csrc asm-all`: kernels.s, transpose.s, value_grad.s, tts_transpose.s, spmm.s, spmm_grad.s -- and
+`make -C hispmv_amd/csrc asm-all`: kernels.s, transpose.s, value_grad.s, tts_transpose.s, spmm.s, spmm_grad.s, krylov.s, krylov_multi.s, gmres.s, lanczos.s,
+block_jacobi.s -- and
 compares, per kernel symbol, the function text and the .amdhsa_kernel descriptor block -- comments, .loc / .file lines and blank lines
 stripped, label numbers (.LBB<n>_, .Ltmp<n>, .Lfunc_*<n>) normalised.  Per symbol, not with diff: the order in which the
 instantiations are emitted follows the host code.  Exit status 1 if a kernel changed, appeared or went.
