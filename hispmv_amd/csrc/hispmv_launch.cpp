@@ -261,14 +261,12 @@ int launch_transposed(hispmv_ctx* c, Matrix& m, int64_t vecs, const float* d_x, 
         const int nv = transposed_width(m, vecs - k);
         const float* xk = d_x + k * m.rows;
         float* yk = d_y + k * m.cols;
-        // (a pass of several vectors reports under the one-vector launcher's name)
         if (m.dense) {
-            LAUNCH_TRY_AS(c, "launch_gemv_t", nv == 1 ? launch_gemv_t(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, xk, yk, alpha, s)
-                                                   : launch_gemv_t_nv(m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, nv, xk, yk, alpha, s));
+            LAUNCH_TRY(c, launch_gemv_t, m.d_dense, m.rows, m.cols, m.value_storage == HISPMV_VALUES_BF16, nv, xk, yk, alpha, s);
         } else if (m.format == 1) {
             LAUNCH_TRY(c, launch_tts_t, m.parts[0].tdev, nv, xk, yk, alpha, s);      // an accepted tile stream: one launch, no carries, no fix-up
         } else {
-            for (auto& p : m.parts) LAUNCH_TRY_AS(c, "launch_spmv_t", nv == 1 ? launch_spmv_t(p.dev, xk, yk, alpha, s) : launch_spmv_t_nv(p.dev, nv, xk, yk, alpha, s));
+            for (auto& p : m.parts) LAUNCH_TRY(c, launch_spmv_t, p.dev, nv, xk, yk, alpha, s);
         }
         k += nv;
     }

@@ -39,148 +39,39 @@ __global__ __launch_bounds__(256) void transpose_prologue_kernel(const float* bi
     }
 }
 
-// The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B).
+// The work of one workgroup on group `group` of a slice stream, for a group stored COMPACT (6 B per element), HALF (4 B) or wide (8 B),
+// on NV vectors in one pass over the stream (NV > 1: hispmv_linear_device_t; the roles batched_group has against slices_group in the
+// forward file).  Vector v reads x + v * rows and adds into y + v * cols.  A slice's words are decoded ONCE -- metas c, values v, local
+// rows lr stay in registers -- and the NV vectors then go through the element loop one after the other.
 // STRAYS: the plan has stray areas behind the window (m.has_strays); whether THIS group uses them is bit 2 of its group word.
-// LDS as in the forward launch: [window: lds_floats (the wavefronts' stray areas are its last floats)][ytile_floats per wavefront].
-template <bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
+// LDS, slice_lds_bytes(m, NV) in all: [NV accumulator windows of lds_floats each (the wavefronts' stray areas are a window's last
+// floats): window v at xs + v * lds_floats][ONE x tile of ytile_floats per wavefront]; with NV = 1 that is the forward launch's.
+// x is reached through a buffer descriptor over `rows` floats, one per vector: a row past the end (the open row behind the last slice)
+// reads as 0 and not as the next vector's x[0].
+// Where the tile is filled differs, and each order is the one its kernels were measured with:
+//   NV == 1  descriptor ahead of the walk; the whole tile and the open row are loaded BEFORE the next slice is requested
+//   NV > 1   descriptor after the request; the first 64 floats of a vector's tile and its open row (t_head, t_open) are requested one
+//            vector ahead, before the current vector's elements are multiplied
+// `if constexpr (NV == 1) break;` at the end of a loop over the vectors: with one vector there is no loop for the compiler to hoist out
+// of, and the instructions stay where the one-vector text had them (2.30).
+template <int NV, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
 __device__ __forceinline__ void slices_group_t(
     const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const float* __restrict__ x, float* y,
     float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows, long long group, int4 g) {
     extern __shared__ float xs[];
     constexpr int kE = kSliceSteps * kLaneElems;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
-    // x is reached through a buffer descriptor over `rows` floats: a row past the end (the open row behind the last slice) reads as 0
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
-    float* const xtile = xs + (USE_LDS ? lds_floats : 0) + wave * ytile_floats;
-    // the forward kernel's walk; the first request leaves before the window is zeroed
-    auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
-    const bool in_lds = wk.in_lds, strays = wk.strays;
-    const int win_floats = wk.win_floats;
-    float* const stray_area = xs + win_floats + wave * kStraySlots;
-    // the columns of every slice's strays live behind the headers (hispmv_load.cpp: upload_slice_layout), 64 per slice, 0xffffffff = none
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
-
-    SliceRaw<COMPACT, HALF> w;
-    int4 h = int4{0, 0, 0, 0};
-    if (wk.live()) {
-        h = load_int4(hdr + wk.cur());
-        request_slice<COMPACT, HALF>(w, wk.slice(), lane);
-    }
-    if (USE_LDS) {
-        for (int i = (int)threadIdx.x; i < lds_floats; i += (int)blockDim.x) xs[i] = 0.0f;
-        __syncthreads();
-    }
-
-    while (wk.live()) {
-        const int row_first = __builtin_amdgcn_readfirstlane(h.x);      // first row that ends in this slice
-        const int n_rows = __builtin_amdgcn_readfirstlane(h.z);         // rows that end in it; its elements lie in rows row_first .. row_first + n_rows
-        const long long cur = wk.cur();
-        unsigned c[kE];
-        float v[kE];
-        decode_metas<COMPACT, HALF>(w, c);
-        slice_values<COMPACT, HALF>(w, v);
-        // x of the slice's rows -> this wavefront's tile, coalesced; the open last row has no place in a full tile and is kept in a register
-        for (int i = lane; i <= n_rows && i < ytile_floats; i += 64)
-            xtile[i] = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + i) << 2, 0, 0));
-        const float x_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
-        unsigned sc = kNoAccess;
-        if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(cur * kStraySlots + lane) << 2, 0, 0);
-        int lr[kE];
-        local_rows(c, lr);
-        // the next slice of this wavefront, into the registers the copies above have left
-        wk.advance();
-        if (wk.live()) {
-            h = load_int4(hdr + wk.cur());
-            request_slice<COMPACT, HALF>(w, wk.slice(), lane);
-        }
-        __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order: the tile is complete for every lane)
-#pragma unroll
-        for (int i = 0; i < kE; ++i) {
-            const int li = lr[i] < ytile_floats ? lr[i] : ytile_floats - 1;
-            const float xt = xtile[li];
-            const float xr = lr[i] < ytile_floats ? xt : x_open;
-            if ((f2i(v[i]) & 0x7fffffff) == 0) continue;          // a +-0 slot adds nothing, whatever x holds
-            const float p = v[i] * xr;
-            if constexpr (COMPACT) {
-                const int idx = (int)(c[i] & 0x7fffu);
-                if (STRAYS && strays && idx >= win_floats) lds_add(stray_area + ((idx - win_floats) & (kStraySlots - 1)), p);
-                else lds_add(xs + idx, p);
-            } else {
-                const unsigned ci = c[i] & ~kRowEndBit;
-                if (USE_LDS && in_lds && !(ci & kGlobalColBit)) {
-                    if (ci < (unsigned)win_floats) lds_add(xs + ci, p);
-                } else {
-                    const unsigned col = ci & ~kGlobalColBit;
-                    if (col < (unsigned)cols) y_add(y, col, alpha * p);
-                }
-            }
-        }
-        if (STRAYS && strays) {       // the slice's strays leave for their columns; the area is zero again for the wavefront's next slice
-            __builtin_amdgcn_wave_barrier();
-            const float a = stray_area[lane];
-            stray_area[lane] = 0.0f;
-            if (sc != kNoAccess && sc < (unsigned)cols) y_add(y, sc, alpha * a);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (USE_LDS) {
-        __syncthreads();
-        // the flush: per fragment {col_start, len, lds_off} one wave-instruction per 64 consecutive floats of y
-        const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
-        for (int f = wave; f < nf; f += n_waves) {
-            const int4 fr = load_int4(frags + f0 + f);
-            const int col0 = __builtin_amdgcn_readfirstlane(fr.x), len = __builtin_amdgcn_readfirstlane(fr.y), off = __builtin_amdgcn_readfirstlane(fr.z);
-            for (int i = lane; i < len; i += 64)
-                if (col0 + i < cols && off + i < win_floats) y_add(y, (unsigned)(col0 + i), alpha * xs[off + i]);
-        }
-    }
-}
-
-// HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
-template <bool USE_LDS, bool STRAYS, bool HALF>
-__global__ __launch_bounds__(1024) void spmv_slices_t_kernel(
-    const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
-    const float* __restrict__ x, float* y, float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows) {
-    const long long group = (long long)blockIdx.x;
-    if constexpr (USE_LDS) {
-        const int4 g = load_int4(groups + group);
-        const int gw = __builtin_amdgcn_readfirstlane(g.w);
-        if constexpr (HALF) {
-            if (gw & kGroupHalf) {
-                slices_group_t<true, true, STRAYS, true>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
-                return;
-            }
-        }
-        // (a compact group that is not half does not exist in a bf16 handle today; should a packer ever make one, it is decoded as what
-        // its group word says it is)
-        if (gw & kGroupCompact)
-            slices_group_t<true, true, STRAYS, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
-        else
-            slices_group_t<true, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
-    } else {
-        slices_group_t<false, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, int4{0, 0, 0, 0});
-    }
-}
-
-// NV vectors through one pass over the stream (hispmv_linear_device_t): slices_group_t with the roles batched_group has against
-// slices_group in the forward file.  Vector v reads x + v * rows and adds into y + v * cols.  A slice's words are decoded ONCE -- metas
-// c, values v, local rows lr stay in registers -- and the NV vectors then go through the body one after the other.
-// LDS: [NV accumulator windows of lds_floats each, stray areas included: window v at xs + v * lds_floats][ONE x tile per wavefront],
-// slice_lds_bytes(m, NV) in all.  Every vector has its own buffer descriptor over its `rows` floats of x, so the open row behind the
-// last slice reads 0 and not the next vector's x[0].  The first 64 floats of the next vector's tile and its open row are requested
-// before the current vector's elements are multiplied.
-template <int NV, bool USE_LDS, bool COMPACT, bool STRAYS, bool HALF>
-__device__ __forceinline__ void slices_group_t_nv(
-    const char* __restrict__ stream, const int4* __restrict__ hdr, const int4* __restrict__ frags, const float* __restrict__ x, float* y,
-    float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows, long long group, int4 g) {
-    extern __shared__ float xs[];
-    constexpr int kE = kSliceSteps * kLaneElems;
-    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
+    __amdgpu_buffer_rsrc_t rx;
+    if constexpr (NV == 1) rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
     float* const xtile = xs + (USE_LDS ? lds_floats * NV : 0) + wave * ytile_floats;
+    // the forward kernel's walk; the first request leaves before the windows are zeroed
     auto wk = GroupWalk<USE_LDS, COMPACT, STRAYS, HALF>::at(stream, n_slices, group_slices, lds_floats, group, g, wave, n_waves);
     const bool in_lds = wk.in_lds, strays = wk.strays;
     const int win_floats = wk.win_floats;
-    const int stray_at = win_floats + wave * kStraySlots;          // this wavefront's stray area inside every vector's window
+    // this wavefront's stray area: a pointer for one vector, formed here; an offset into every vector's window for NV > 1
+    float* const stray_one = xs + win_floats + wave * kStraySlots;
+    const int stray_at = win_floats + wave * kStraySlots;
+    // the columns of every slice's strays live behind the headers (hispmv_load.cpp: upload_slice_layout), 64 per slice, 0xffffffff = none
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hdr + n_slices), 0, strays ? (int)(n_slices * (kStraySlots * 4)) : 0, 0x00020000);
 
     SliceRaw<COMPACT, HALF> w;
@@ -195,38 +86,50 @@ __device__ __forceinline__ void slices_group_t_nv(
     }
 
     while (wk.live()) {
-        const int row_first = __builtin_amdgcn_readfirstlane(h.x);
-        const int n_rows = __builtin_amdgcn_readfirstlane(h.z);
+        const int row_first = __builtin_amdgcn_readfirstlane(h.x);      // first row that ends in this slice
+        const int n_rows = __builtin_amdgcn_readfirstlane(h.z);         // rows that end in it; its elements lie in rows row_first .. row_first + n_rows
         const long long cur = wk.cur();
         unsigned c[kE];
         float v[kE];
         decode_metas<COMPACT, HALF>(w, c);
         slice_values<COMPACT, HALF>(w, v);
+        // x of the slice's rows -> this wavefront's tile, coalesced; the open last row has no place in a full tile and is kept in a register
+        float x_open, t_head, t_open;
+        if constexpr (NV == 1) {
+            for (int i = lane; i <= n_rows && i < ytile_floats; i += 64)
+                xtile[i] = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + i) << 2, 0, 0));
+            x_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+        }
         unsigned sc = kNoAccess;
         if (strays) sc = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(cur * kStraySlots + lane) << 2, 0, 0);
         int lr[kE];
         local_rows(c, lr);
+        // the next slice of this wavefront, into the registers the copies above have left
         wk.advance();
         if (wk.live()) {
             h = load_int4(hdr + wk.cur());
             request_slice<COMPACT, HALF>(w, wk.slice(), lane);
         }
-        // vector 0: the head of its tile (rows row_first + lane; past the end of x the descriptor gives 0) and its open row
-        __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
-        float t_head = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + lane) << 2, 0, 0));
-        float t_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+        if constexpr (NV > 1) {       // vector 0: the head of its tile (rows row_first + lane) and its open row
+            rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, rows * 4, 0x00020000);
+            t_head = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + lane) << 2, 0, 0));
+            t_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+        }
 #pragma unroll 1
         for (int vv = 0; vv < NV; ++vv) {
             float* const win = xs + vv * lds_floats;
             float* const yv = y + (size_t)vv * (size_t)cols;
-            if (lane <= n_rows && lane < ytile_floats) xtile[lane] = t_head;
-            for (int i = lane + 64; i <= n_rows && i < ytile_floats; i += 64)
-                xtile[i] = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + i) << 2, 0, 0));
-            const float x_open = t_open;
-            if (vv + 1 < NV) {
-                rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)(vv + 1) * (size_t)rows), 0, rows * 4, 0x00020000);
-                t_head = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + lane) << 2, 0, 0));
-                t_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+            float* const stray_area = NV == 1 ? stray_one : win + stray_at;
+            if constexpr (NV > 1) {
+                if (lane <= n_rows && lane < ytile_floats) xtile[lane] = t_head;
+                for (int i = lane + 64; i <= n_rows && i < ytile_floats; i += 64)
+                    xtile[i] = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + i) << 2, 0, 0));
+                x_open = t_open;
+                if (vv + 1 < NV) {
+                    rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)(vv + 1) * (size_t)rows), 0, rows * 4, 0x00020000);
+                    t_head = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + lane) << 2, 0, 0));
+                    t_open = i2f((int)__builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(row_first + n_rows) << 2, 0, 0));
+                }
             }
             __builtin_amdgcn_wave_barrier();      // (LDS operations of one wavefront execute in order: the tile is complete for every lane)
 #pragma unroll
@@ -238,7 +141,7 @@ __device__ __forceinline__ void slices_group_t_nv(
                 const float p = v[i] * xr;
                 if constexpr (COMPACT) {
                     const int idx = (int)(c[i] & 0x7fffu);
-                    if (STRAYS && strays && idx >= win_floats) lds_add(win + stray_at + ((idx - win_floats) & (kStraySlots - 1)), p);
+                    if (STRAYS && strays && idx >= win_floats) lds_add(stray_area + ((idx - win_floats) & (kStraySlots - 1)), p);
                     else lds_add(win + idx, p);
                 } else {
                     const unsigned ci = c[i] & ~kRowEndBit;
@@ -250,17 +153,19 @@ __device__ __forceinline__ void slices_group_t_nv(
                     }
                 }
             }
-            if (STRAYS && strays) {       // this vector's strays of the slice leave for their columns; its area is zero again
+            if (STRAYS && strays) {       // this vector's strays of the slice leave for their columns; its area is zero again for the wavefront's next slice
                 __builtin_amdgcn_wave_barrier();
-                const float a = win[stray_at + lane];
-                win[stray_at + lane] = 0.0f;
+                const float a = stray_area[lane];
+                stray_area[lane] = 0.0f;
                 if (sc != kNoAccess && sc < (unsigned)cols) y_add(yv, sc, alpha * a);
             }
             __builtin_amdgcn_wave_barrier();      // the tile is read: the next vector (or slice) may fill it
+            if constexpr (NV == 1) break;
         }
     }
     if (USE_LDS) {
         __syncthreads();
+        // the flush: per fragment {col_start, len, lds_off} one wave-instruction per 64 consecutive floats of y, vector after vector
         const int f0 = __builtin_amdgcn_readfirstlane(g.x), nf = in_lds ? __builtin_amdgcn_readfirstlane(g.y) : 0;
         for (int f = wave; f < nf; f += n_waves) {
             const int4 fr = load_int4(frags + f0 + f);
@@ -273,8 +178,9 @@ __device__ __forceinline__ void slices_group_t_nv(
     }
 }
 
+// HALF: the handle stores bf16 values and has half groups; the group word of every group decides which body decodes it.
 template <int NV, bool USE_LDS, bool STRAYS, bool HALF>
-__global__ __launch_bounds__(1024) void spmv_slices_t_nv_kernel(
+__global__ __launch_bounds__(1024) void spmv_slices_t_kernel(
     const char* __restrict__ words, const int4* __restrict__ hdr, const int4* __restrict__ groups, const int4* __restrict__ frags,
     const float* __restrict__ x, float* y, float alpha, long long n_slices, int group_slices, int lds_floats, int ytile_floats, int cols, int rows) {
     const long long group = (long long)blockIdx.x;
@@ -283,74 +189,18 @@ __global__ __launch_bounds__(1024) void spmv_slices_t_nv_kernel(
         const int gw = __builtin_amdgcn_readfirstlane(g.w);
         if constexpr (HALF) {
             if (gw & kGroupHalf) {
-                slices_group_t_nv<NV, true, true, STRAYS, true>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+                slices_group_t<NV, true, true, STRAYS, true>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
                 return;
             }
         }
+        // (a compact group that is not half does not exist in a bf16 handle today; should a packer ever make one, it is decoded as what
+        // its group word says it is)
         if (gw & kGroupCompact)
-            slices_group_t_nv<NV, true, true, STRAYS, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+            slices_group_t<NV, true, true, STRAYS, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
         else
-            slices_group_t_nv<NV, true, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
+            slices_group_t<NV, true, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, g);
     } else {
-        slices_group_t_nv<NV, false, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, int4{0, 0, 0, 0});
-    }
-}
-
-// Dense: a workgroup of 256 threads takes rows [r0, r1) x kGemvTCols columns.  A thread owns 4 consecutive columns (one 16-byte load of
-// fp32 W per row, 8 bytes of bf16 W) and sums over the rows in registers, x[row] wave-uniform; the sums cross the LDS so that every
-// wave-instruction of the output covers 64 consecutive floats of y.  VEC: cols % 4 == 0 and W aligned; otherwise element loads (odd
-// cols, where a row of W starts at any 4-byte -- bf16: 2-byte -- boundary).
-template <bool BF16, bool VEC>
-__global__ __launch_bounds__(256) void gemv_t_kernel(const void* __restrict__ Wv, int rows, int cols, const float* __restrict__ x, float* y,
-                                                    float alpha, int rows_per_block, int atomic) {
-    __shared__ float out[kGemvTCols];
-    const int tid = (int)threadIdx.x;
-    const int cb = (int)blockIdx.x * kGemvTCols;
-    const int c0 = cb + tid * 4;
-    const int r0 = (int)blockIdx.y * rows_per_block;
-    const int r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    if (c0 < cols) {
-#pragma unroll 4
-        for (int r = r0; r < r1; ++r) {
-            const float xr = x[r];
-            const size_t at = (size_t)r * (size_t)cols + (size_t)c0;
-            float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
-            if constexpr (BF16) {
-                const uint16_t* W = (const uint16_t*)Wv;
-                if constexpr (VEC) {
-                    const uint2 q = *(const uint2*)(W + at);
-                    w0 = i2f((int)(q.x << 16)); w1 = i2f((int)(q.x & 0xffff0000u)); w2 = i2f((int)(q.y << 16)); w3 = i2f((int)(q.y & 0xffff0000u));
-                } else {
-                    w0 = i2f((int)((unsigned)W[at] << 16));
-                    if (c0 + 1 < cols) w1 = i2f((int)((unsigned)W[at + 1] << 16));
-                    if (c0 + 2 < cols) w2 = i2f((int)((unsigned)W[at + 2] << 16));
-                    if (c0 + 3 < cols) w3 = i2f((int)((unsigned)W[at + 3] << 16));
-                }
-            } else {
-                const float* W = (const float*)Wv;
-                if constexpr (VEC) {
-                    const float4 q = *(const float4*)(W + at);
-                    w0 = q.x; w1 = q.y; w2 = q.z; w3 = q.w;
-                } else {
-                    w0 = W[at];
-                    if (c0 + 1 < cols) w1 = W[at + 1];
-                    if (c0 + 2 < cols) w2 = W[at + 2];
-                    if (c0 + 3 < cols) w3 = W[at + 3];
-                }
-            }
-            a0 += w0 * xr; a1 += w1 * xr; a2 += w2 * xr; a3 += w3 * xr;
-        }
-    }
-    out[tid * 4 + 0] = a0; out[tid * 4 + 1] = a1; out[tid * 4 + 2] = a2; out[tid * 4 + 3] = a3;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int col = cb + tid + 256 * k;
-        if (col >= cols) continue;
-        const float s = alpha * out[tid + 256 * k];
-        if (atomic) y_add(y, (unsigned)col, s);
-        else y[col] = y[col] + s;            // one row block: this thread is the only writer of the column
+        slices_group_t<NV, false, false, false, false>(words, hdr, frags, x, y, alpha, n_slices, group_slices, lds_floats, ytile_floats, cols, rows, group, int4{0, 0, 0, 0});
     }
 }
 
@@ -383,12 +233,17 @@ __device__ __forceinline__ float4 gemv_t_load_w(const void* __restrict__ Wv, siz
     return w;
 }
 
-// gemv_t_kernel for NV vectors per pass over W (hispmv_linear_device_t): vector v reads x + v * rows and adds into y + v * cols.  A
-// thread owns 4 columns x NV sums, x[v * rows + r] is wave-uniform, W is read once; the LDS transposition holds NV x kGemvTCols floats.
-// Per vector the sum of a column is the one gemv_t_kernel forms (same row blocks, same order inside a block).
+// Dense: a workgroup of 256 threads takes rows [r0, r1) x kGemvTCols columns.  A thread owns 4 consecutive columns (one 16-byte load of
+// fp32 W per row, 8 bytes of bf16 W) and sums over the rows in registers, x[row] wave-uniform; the sums cross the LDS so that every
+// wave-instruction of the output covers 64 consecutive floats of y.  VEC: cols % 4 == 0 and W aligned; otherwise element loads (odd
+// cols, where a row of W starts at any 4-byte -- bf16: 2-byte -- boundary).
+// NV vectors per pass over W (NV > 1: hispmv_linear_device_t): vector v reads x + v * rows and adds into y + v * cols.  A thread owns
+// 4 columns x NV sums, x[v * rows + r] is wave-uniform, W is read once; the LDS transposition holds NV x kGemvTCols floats.  Per vector
+// the sum of a column is the one a pass of one vector forms (same row blocks, same order inside a block).
+// (`if constexpr (NV == 1) break;`: as in slices_group_t)
 template <bool BF16, bool VEC, int NV>
-__global__ __launch_bounds__(256) void gemv_t_nv_kernel(const void* __restrict__ Wv, int rows, int cols, const float* __restrict__ x, float* y,
-                                                       float alpha, int rows_per_block, int atomic) {
+__global__ __launch_bounds__(256) void gemv_t_kernel(const void* __restrict__ Wv, int rows, int cols, const float* __restrict__ x, float* y,
+                                                    float alpha, int rows_per_block, int atomic) {
     __shared__ float out[NV][kGemvTCols];
     const int tid = (int)threadIdx.x;
     const int cb = (int)blockIdx.x * kGemvTCols;
@@ -397,15 +252,18 @@ __global__ __launch_bounds__(256) void gemv_t_nv_kernel(const void* __restrict__
     const int r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
     float4 a[NV];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) a[v] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int v = 0; v < NV; ++v) { a[v] = float4{0.0f, 0.0f, 0.0f, 0.0f}; if constexpr (NV == 1) break; }
     if (c0 < cols) {
 #pragma unroll 4
         for (int r = r0; r < r1; ++r) {
+            float x_first;
+            if constexpr (NV == 1) x_first = x[r];          // one vector: x[r] is requested ahead of W, the order its kernels were measured with
             const float4 w = gemv_t_load_w<BF16, VEC>(Wv, (size_t)r * (size_t)cols + (size_t)c0, c0, cols);
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
-                const float xr = x[(size_t)v * (size_t)rows + (size_t)r];
+                const float xr = NV == 1 ? x_first : x[(size_t)v * (size_t)rows + (size_t)r];
                 a[v].x += w.x * xr; a[v].y += w.y * xr; a[v].z += w.z * xr; a[v].w += w.w * xr;
+                if constexpr (NV == 1) break;
             }
         }
     }
@@ -426,23 +284,22 @@ __global__ __launch_bounds__(256) void gemv_t_nv_kernel(const void* __restrict__
     }
 }
 
-// the kernel of a pass of NV vectors (1: the single-vector kernel)
-template <int NV, bool USE_LDS, bool STRAYS, bool HALF>
-constexpr auto slices_t_kernel() {
-    if constexpr (NV == 1) return spmv_slices_t_kernel<USE_LDS, STRAYS, HALF>;
-    else return spmv_slices_t_nv_kernel<NV, USE_LDS, STRAYS, HALF>;
-}
-
 template <int NV>
 hipError_t launch_slices_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
     return with_slice_flags(m, [&](auto USE_LDS, auto STRAYS, auto HALF) {
-        constexpr auto kernel = slices_t_kernel<NV, USE_LDS(), STRAYS(), HALF()>();
+        constexpr auto kernel = spmv_slices_t_kernel<NV, USE_LDS(), STRAYS(), HALF()>;
         const hipError_t e = raise_lds_limit<kernel>();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3((unsigned)m.n_groups), dim3((unsigned)m.block_threads), slice_lds_bytes(m, NV), stream, (const char*)m.words, m.hdr,
                            m.groups, m.frags, x, y, alpha, (long long)m.n_slices, m.group_slices, m.lds_floats, m.ytile_floats, m.cols, m.rows);
         return hipGetLastError();
     });
+}
+
+// the dense kernel of a pass of NV vectors, by weight type and by whether W takes vector loads
+template <int NV>
+auto gemv_t_kernel_of(bool bf16, bool vec) {
+    return bf16 ? (vec ? gemv_t_kernel<true, true, NV> : gemv_t_kernel<true, false, NV>) : (vec ? gemv_t_kernel<false, true, NV> : gemv_t_kernel<false, false, NV>);
 }
 
 }  // namespace
@@ -459,13 +316,6 @@ hipError_t launch_transpose_prologue(const float* bias, float* y, int32_t n, flo
     return hipGetLastError();
 }
 
-hipError_t launch_spmv_t(const SpmvDeviceMatrix& m, const float* x, float* y, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
-    if (!slice_geometry_ok(m, slice_lds_bytes(m))) return hipErrorInvalidValue;
-    return launch_slices_t<1>(m, x, y, alpha, stream);
-}
-
 // Plan classes of the multi-vector pass; spmv_t_width is where a class that a measurement shows no faster than single calls is narrowed.
 int spmv_t_width(const SpmvDeviceMatrix& m, int64_t vecs) {
     for (int nv = kMaxBatch; nv >= 2; nv >>= 1) {
@@ -476,12 +326,16 @@ int spmv_t_width(const SpmvDeviceMatrix& m, int64_t vecs) {
     return 1;
 }
 
-hipError_t launch_spmv_t_nv(const SpmvDeviceMatrix& m, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
+hipError_t launch_spmv_t(const SpmvDeviceMatrix& m, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
     (void)hipGetLastError();
-    if (nv != 2 && nv != 4) return hipErrorInvalidValue;
+    if (nv != 1 && nv != 2 && nv != 4) return hipErrorInvalidValue;
     if (m.n_slices <= 0 || m.n_groups <= 0) return hipSuccess;
-    if (!slice_geometry_ok(m, slice_lds_bytes(m, nv)) || spmv_t_width(m, nv) != nv) return hipErrorInvalidValue;
-    return nv == 4 ? launch_slices_t<4>(m, x, y, alpha, stream) : launch_slices_t<2>(m, x, y, alpha, stream);
+    if (!slice_geometry_ok(m, slice_lds_bytes(m, nv)) || (nv > 1 && spmv_t_width(m, nv) != nv)) return hipErrorInvalidValue;
+    switch (nv) {
+        case 4: return launch_slices_t<4>(m, x, y, alpha, stream);
+        case 2: return launch_slices_t<2>(m, x, y, alpha, stream);
+        default: return launch_slices_t<1>(m, x, y, alpha, stream);
+    }
 }
 
 // Row blocks per column block: enough workgroups to fill the chip twice over (1024 in all) while a block keeps at least 16 rows,
@@ -496,53 +350,21 @@ int gemv_t_row_blocks(int32_t rows, int32_t cols) {
     return (int)(((int64_t)rows + per - 1) / per);
 }
 
-hipError_t launch_gemv_t(const void* W, int32_t rows, int32_t cols, bool bf16, const float* x, float* y, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
-    const int nb = gemv_t_row_blocks(rows, cols);
-    if (nb <= 0) return hipSuccess;
-    const int per = (rows + nb - 1) / nb;
-    const dim3 grid((unsigned)(((int64_t)cols + kGemvTCols - 1) / kGemvTCols), (unsigned)nb);
-    const bool vec = (cols & 3) == 0 && ((uintptr_t)W & (bf16 ? 7 : 15)) == 0;
-    const int atomic = nb > 1 ? 1 : 0;
-    if (bf16) {
-        if (vec) hipLaunchKernelGGL((gemv_t_kernel<true, true>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-        else hipLaunchKernelGGL((gemv_t_kernel<true, false>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-    } else {
-        if (vec) hipLaunchKernelGGL((gemv_t_kernel<false, true>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-        else hipLaunchKernelGGL((gemv_t_kernel<false, false>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-    }
-    return hipGetLastError();
-}
-
 int gemv_t_width(int64_t vecs) { return vecs >= 8 ? 8 : vecs >= 4 ? 4 : vecs >= 2 ? 2 : 1; }
 
-template <int NV>
-static hipError_t launch_gemv_t_width(const void* W, int32_t rows, int32_t cols, bool bf16, const float* x, float* y, float alpha, hipStream_t stream) {
+hipError_t launch_gemv_t(const void* W, int32_t rows, int32_t cols, bool bf16, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (nv != 1 && nv != 2 && nv != 4 && nv != 8) return hipErrorInvalidValue;
+    if (nv > 1 && ((int64_t)rows * nv >= (1 << 30) || (int64_t)cols * nv >= (1 << 30))) return hipErrorInvalidValue;
     const int nb = gemv_t_row_blocks(rows, cols);
     if (nb <= 0) return hipSuccess;
     const int per = (rows + nb - 1) / nb;
     const dim3 grid((unsigned)(((int64_t)cols + kGemvTCols - 1) / kGemvTCols), (unsigned)nb);
     const bool vec = (cols & 3) == 0 && ((uintptr_t)W & (bf16 ? 7 : 15)) == 0;
     const int atomic = nb > 1 ? 1 : 0;
-    if (bf16) {
-        if (vec) hipLaunchKernelGGL((gemv_t_nv_kernel<true, true, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-        else hipLaunchKernelGGL((gemv_t_nv_kernel<true, false, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-    } else {
-        if (vec) hipLaunchKernelGGL((gemv_t_nv_kernel<false, true, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-        else hipLaunchKernelGGL((gemv_t_nv_kernel<false, false, NV>), grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
-    }
+    const auto kernel = nv == 8 ? gemv_t_kernel_of<8>(bf16, vec) : nv == 4 ? gemv_t_kernel_of<4>(bf16, vec) : nv == 2 ? gemv_t_kernel_of<2>(bf16, vec) : gemv_t_kernel_of<1>(bf16, vec);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, W, (int)rows, (int)cols, x, y, alpha, per, atomic);
     return hipGetLastError();
-}
-
-hipError_t launch_gemv_t_nv(const void* W, int32_t rows, int32_t cols, bool bf16, int nv, const float* x, float* y, float alpha, hipStream_t stream) {
-    (void)hipGetLastError();
-    if ((int64_t)rows * nv >= (1 << 30) || (int64_t)cols * nv >= (1 << 30)) return hipErrorInvalidValue;
-    switch (nv) {
-        case 2: return launch_gemv_t_width<2>(W, rows, cols, bf16, x, y, alpha, stream);
-        case 4: return launch_gemv_t_width<4>(W, rows, cols, bf16, x, y, alpha, stream);
-        case 8: return launch_gemv_t_width<8>(W, rows, cols, bf16, x, y, alpha, stream);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 }  // namespace hispmv

@@ -9,7 +9,8 @@ Per matrix, timed with HIP events around `--reps` back-to-back launches on one s
 Matrices (generators of hispmv_amd/matrices.py): a windowed band (the crankseg_2 stand-in, all groups compact), the same band with
 2 % of its entries re-drawn at random columns (stray slots or a stray split, as the loader decides), a scattered matrix whose
 plan has no window (the analytics stand-in, created with set_transposable on: every element adds to y directly), and the
-1024 x 8192 layer of model_test_layers as a dense handle.
+1024 x 8192 layer of model_test_layers as a dense handle -- with fp32 and with bf16 values, whole and less its last column (odd cols:
+the element-load kernels).
 Next to the times: what transpose_info reports, the arena bytes (c) costs, and the simple floor of (b): stream bytes / 5.6 TB/s
 (what the step kernel reaches) + atomic bytes / 1.3 TB/s (the chip-wide rate of float atomic adds).
 Prints one JSON line and writes it to --out.
@@ -131,10 +132,16 @@ def main() -> None:
         kind, (r, c, v), rows, cols, _b = M.model_test_layers()[2]
         W = np.zeros((rows, cols), np.float32)
         W[r, c] = v
-        i = h.create_dense_handle(W.reshape(-1), rows, cols)
-        before = h.arena_bytes_used()
-        j = h.create_dense_handle(np.ascontiguousarray(W.T).reshape(-1), cols, rows)
-        todo.append((f"dense layer {rows} x {cols}", i, j, h.arena_bytes_used() - before))
+        # the four dense kernels of (b): fp32 and bf16 W, vector loads (cols % 4 == 0) and element loads (the layer less its last column)
+        for storage in ("fp32", "bf16"):
+            for Wd in (W, np.ascontiguousarray(W[:, :-1])):
+                h.set_value_storage(storage)
+                i = h.create_dense_handle(Wd.reshape(-1), *Wd.shape)
+                before = h.arena_bytes_used()
+                j = h.create_dense_handle(np.ascontiguousarray(Wd.T).reshape(-1), *Wd.shape[::-1])
+                tag = "" if storage == "fp32" else " bf16"
+                todo.append((f"dense layer {Wd.shape[0]} x {Wd.shape[1]}{tag}", i, j, h.arena_bytes_used() - before))
+        h.set_value_storage("fp32")
         del W
         h.load_matrices()
         out = [measure(torch, h, name, i, j, nbytes, a.rounds, a.reps) for name, i, j, nbytes in todo]
